@@ -20,8 +20,10 @@ processes (a child `python -m torch.distributed.run`, before this process touche
 request i -> rank i mod N, each rank's segments decoded through the continuous-batching scheduler; the whole job is one step
 (strong scaling).  `--decode beam`, `--dtype f32`, `--bigvgan-only`, `--concurrency R` select the other BASELINE configs.
 
-The default N=1 line also carries, under "extra", figures the driver would otherwise never see: the config-5 BigVGAN
-microbench, the served-default 3-beam request, the fp32 (parity-mode) request and the decode step per batch size.
+A plain run sets up, warms up, times `--steps` steps and prints the line.  `--full` adds what takes runs of its own: the
+roofline of the dominant decode kernel and of the other stages, the CPU baseline and, on the default N=1 line, under "extra",
+the config-5 BigVGAN microbench, the served-default 3-beam request, the fp32 (parity-mode) request, the prompt side and the decode
+step per batch size.  `--dump-outputs DIR` writes what the last timed step returned (dump_outputs).
 
 Prints ONE JSON line (rank 0).
 """
@@ -90,13 +92,18 @@ def parse(argv=None):
                     "sample: BASELINE configs[2] -- top-p sampling without beams (top_p 0.8, top_k 30, temperature 0.8), both segments together")
     ap.add_argument("--emo-alpha", type=float, default=None, help="BASELINE configs[2]: a separate emotion prompt (5 s, 249 w2v-bert frames) merged with this "
                     "alpha (0.7) in the conditioning encoders (merge_emovec, model_v2.py:742-747)")
-    ap.add_argument("--bigvgan-only", action="store_true", help="BASELINE configs[4]: 1000-frame random mel -> waveform microbench (20 warm-up + 100 timed)")
+    ap.add_argument("--bigvgan-only", action="store_true", help="BASELINE configs[4]: 1000-frame random mel -> waveform microbench (--warmup + --steps forwards; "
+                    "the config-5 figure of --full: 20 + 100)")
     ap.add_argument("--no-prompt-side", action="store_true", help="mixed64: feed synthetic per-prompt features instead of running the prompt-side models "
                     "(w2v-bert, codec, CAM++, mel) on a distinct 5 s recording per request")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-load-warmup", action="store_true", help="skip the short synthetic request the loader runs before the first real one (server lifespan does the same)")
     ap.add_argument("--no-roofline", action="store_true")
     ap.add_argument("--no-extra", action="store_true", help="skip the extra figures of the default line (config 5, beam, fp32, step per batch size)")
+    ap.add_argument("--full", action="store_true", help="after the timed steps, also measure the rooflines, the CPU baseline and the extra "
+                    "figures of the default line (each of them its own runs; --no-roofline / --no-cpu-baseline / --no-extra leave one out)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="write what the last timed step returned to DIR/<name>.npy "
+                    "(float32, at most 64 MB in all)")
     return ap.parse_args(argv)
 
 
@@ -118,28 +125,30 @@ def launch_ranks(args):
 
 
 # ================================================================================================ stage microbenches
-def bigvgan_microbench(WR, dev, model=None):
-    """BASELINE configs[4] / SURVEY 8(d) config 5: mel ~ N(-4, 2) clipped to [-11.5, 2], fp32 [1, 80, 1000] -> [1, 1, 256000]."""
+def bigvgan_microbench(WR, dev, model=None, steps=100, warmup=20):
+    """BASELINE configs[4] / SURVEY 8(d) config 5: mel ~ N(-4, 2) clipped to [-11.5, 2], fp32 [1, 80, 1000] -> [1, 1, 256000].
+    Returns the result line and the waveform of the last timed forward."""
     from voice_tts_amd.bigvgan import BigVGAN
 
     m = model if model is not None else BigVGAN(WR.BIGVGAN_CFG, max_frames=1024, device=dev).load_state_dict(WR.make_bigvgan_weights(WR.BIGVGAN_CFG, seed=1234))
     F = 1000
     mel = (torch.randn(1, 80, F, generator=torch.Generator().manual_seed(6)) * 2 - 4).clamp(-11.5, 2).to(dev)
-    for _ in range(20):
+    for _ in range(warmup):
         m(mel)
     e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
     e0.record()
-    for _ in range(100):
-        m(mel)
+    for _ in range(steps):
+        wav = m(mel)
     e1.record()
     torch.cuda.synchronize()
-    ms = e0.elapsed_time(e1) / 100
+    ms = e0.elapsed_time(e1) / steps
     fl = m.flops(1, F)
     alg_bytes = 732.8e6  # SURVEY 8(d): weights once + stage-boundary activations once + mel + wav, per 1000 frames
-    return {"metric": "bigvgan_ms_per_1000_frames", "value": round(ms, 3), "unit": "ms", "n_gpus": 1, "steps": 100, "warmup": 20,
-            "higher_is_better": False, "dtype": "f32", "data": "synthetic", "audio_seconds_per_second": round(256 * F / 22050 / (ms * 1e-3), 1),
+    return {"metric": "bigvgan_ms_per_1000_frames", "value": round(ms, 3), "unit": "ms", "n_gpus": 1, "steps": steps, "warmup": warmup,
+            "ms_per_step": round(ms, 3), "higher_is_better": False, "dtype": "f32", "data": "synthetic",
+            "audio_seconds_per_second": round(256 * F / 22050 / (ms * 1e-3), 1),
             "config": {"workload": "BigVGAN-only: 1000-frame random mel -> 256000 samples (11.61 s)"},
-            "roofline": dict(conv_roofline(fl / ms / 1e9), flops=fl, hbm_GBps_algorithmic=round(alg_bytes / (ms * 1e-3) / 1e9, 1), hbm_peak_GBps=PEAK_HBM)}
+            "roofline": dict(conv_roofline(fl / ms / 1e9), flops=fl, hbm_GBps_algorithmic=round(alg_bytes / (ms * 1e-3) / 1e9, 1), hbm_peak_GBps=PEAK_HBM)}, wav
 
 
 def decode_step_by_batch(hp, P, batches, n_steps=256):
@@ -199,6 +208,34 @@ def prompt_wav(seconds=5.0, sr=24000, seed=0):
     return b.getvalue()
 
 
+DUMP_BYTES = 64_000_000
+# Every request starts from this state of the default generators (the s2mel CFM noise is drawn from them): each step computes
+# the same outputs, whatever the number of steps before it, so that --dump-outputs of runs with different --steps compare.
+STEP_SEED = 1234
+
+
+def dump_outputs(path, arrays, budget=DUMP_BYTES):
+    """--dump-outputs: each (name, array) to path/<name>.npy as float32, at most `budget` bytes in all.  When they do not all fit
+    (mixed64: ~260 MB of PCM), a fixed, seeded choice of them is written.  Returns the names written."""
+    os.makedirs(path, exist_ok=True)
+    arrays = [(n, np.ascontiguousarray(a, dtype=np.float32)) for n, a in arrays]
+    order = range(len(arrays))
+    if sum(a.nbytes + 128 for _, a in arrays) > budget:  # 128: the .npy header
+        order = np.random.RandomState(0).permutation(len(arrays))
+    keep = set()
+    for i in order:
+        size = arrays[i][1].nbytes + 128
+        if size <= budget:
+            keep.add(i)
+            budget -= size
+    written = []
+    for i, (name, a) in enumerate(arrays):
+        if i in keep:
+            np.save(os.path.join(path, name + ".npy"), a)
+            written.append(name)
+    return written
+
+
 # ================================================================================================ the request
 class Workload:
     """Synthetic inputs of one rank, resident in HBM before the timed region, and the request loop over the HotPath."""
@@ -212,6 +249,7 @@ class Workload:
         self.g = torch.Generator().manual_seed(100 + rank)
         self.stage_ms = {"gpt_gen": 0.0, "gpt_forward": 0.0, "s2mel": 0.0, "bigvgan": 0.0}
         self.prompt_enc = None  # mixed64 / extra.prompt_side: the prompt-side models at production size (build_prompt_encoder)
+        self.outputs = [] if args.dump_outputs else None  # --dump-outputs: (codes, PCM) of each segment of the current step
 
     def prompt_from_audio(self, wav_bytes):
         """What a request with a NEW speaker prompt pays before its first segment (infer_v2.py:508-545), on the device."""
@@ -252,6 +290,8 @@ class Workload:
         wav = hp.vocode(mel).to(torch.int16).cpu()  # wav.cpu() per segment, int16 truncation (infer_v2.py:744,781)
         td = tick()
         assert lat.shape == (len(codes), self.D) and wav.shape[-1] == frames * 256
+        if self.outputs is not None:
+            self.outputs.append((codes, wav))
         acc["gpt_forward"] += (tb - ta) * 1e3
         acc["s2mel"] += (tc - tb) * 1e3
         acc["bigvgan"] += (td - tc) * 1e3
@@ -273,6 +313,9 @@ def make_hotpath(args, dev, dtype, max_batch, max_seq, max_frames, share=None):
 def run_request(wl, hp, pr, texts, n_codes, mode, R=1, acc=None):
     """One /tts request (or R of them sharing the decode slots).  mode: greedy | beam."""
     acc = wl.stage_ms if acc is None else acc
+    torch.manual_seed(STEP_SEED)
+    if wl.outputs is not None:
+        wl.outputs.clear()
     tick = lambda: (torch.cuda.synchronize(), time.perf_counter())[1]
     t0 = tick()
     cl = wl.conds(pr)
@@ -307,6 +350,9 @@ def run_mixed(wl, hp, reqs, prompts, texts, acc):
     """configs[3] on one rank: every request's prompt-side stages (all prompts distinct: the speaker cache never hits), its
     conditioning, all segments through the scheduler, then the post stages."""
     tick = lambda: (torch.cuda.synchronize(), time.perf_counter())[1]
+    torch.manual_seed(STEP_SEED)
+    if wl.outputs is not None:
+        wl.outputs.clear()
     if wl.prompt_enc is not None:
         tp = tick()
         prompts = [wl.prompt_from_audio(w) for w in prompts]  # `prompts` arrive as WAV byte strings
@@ -351,7 +397,9 @@ def main():
     from voice_tts_amd.pipeline import audio_seconds
 
     if args.bigvgan_only:
-        out = bigvgan_microbench(WR, dev)
+        out, wav = bigvgan_microbench(WR, dev, steps=args.steps, warmup=args.warmup)
+        if args.dump_outputs:
+            dump_outputs(args.dump_outputs, [(f"rank{rank}_wav" if world > 1 else "wav", wav.float().cpu().numpy().reshape(-1))], DUMP_BYTES // world)
         if rank == 0:
             print(json.dumps(out), flush=True)
         return
@@ -469,11 +517,18 @@ def main():
     ms_per_step = elapsed / args.steps * 1e3
     value = total_audio / elapsed
     stage_ms = wl.stage_ms
+    if args.dump_outputs:  # per segment of the last timed step: its mel codes and its int16 PCM (what infer() hands back)
+        pre = f"rank{rank}_" if world > 1 else ""
+        arrays = []
+        for k, (codes, wav) in enumerate(wl.outputs):
+            arrays += [(f"{pre}seg{k:03d}_codes", torch.as_tensor(codes).cpu().numpy()), (f"{pre}seg{k:03d}_pcm", wav.numpy().reshape(-1))]
+        names = dump_outputs(args.dump_outputs, arrays, DUMP_BYTES // world)
+        log(f"dumped {len(names)} of {len(arrays)} outputs to {args.dump_outputs}")
 
     # ---- roofline of the dominant kernel: the decode-step FC GEMV (largest weight stream per launch), timed live with
     # events on the launch stream, cycling the 24 layers (314 MB bf16 > Infinity Cache)
     roofline = None
-    if rank == 0 and not args.no_roofline:
+    if rank == 0 and args.full and not args.no_roofline:
         B = min(n_seg, hp.gpt.max_batch) if not mixed and R == 1 and args.decode == "greedy" else hp.gpt.max_batch
         es = 2 if args.dtype == "bf16" else 4
         L = WR.GPT_CFG["layers"]
@@ -531,7 +586,7 @@ def main():
     # ---- the other stages against their rooflines (fp32 MFMA peak): BigVGAN from its timed stage, the DiT attention kernel
     # timed live with events on the launch stream (report the binding fraction per family)
     stage_roof = None
-    if rank == 0 and not args.no_roofline and not mixed:
+    if rank == 0 and args.full and not args.no_roofline and not mixed:
         bv_tf = hp.bigvgan.flops(1, frames) * n_seg * R / (stage_ms["bigvgan"] / args.steps * 1e-3) / 1e12
         stage_roof = {"bigvgan": dict(conv_roofline(bv_tf), flops_per_segment=hp.bigvgan.flops(1, frames))}
         if use_s2mel:
@@ -558,11 +613,11 @@ def main():
 
     # ---- extra figures of the default line (driver-visible): config 5, the served 3-beam default, fp32 parity mode, step per B
     extra = None
-    default_line = world == 1 and not mixed and R == 1 and args.decode == "greedy" and args.dtype == "bf16" and not args.no_extra and args.emo_alpha is None
+    default_line = world == 1 and not mixed and R == 1 and args.decode == "greedy" and args.dtype == "bf16" and args.full and not args.no_extra and args.emo_alpha is None
     if rank == 0 and default_line:
         extra = {}
         log("extra: BigVGAN config-5 microbench")
-        mb = bigvgan_microbench(WR, dev, hp.bigvgan)
+        mb, _ = bigvgan_microbench(WR, dev, hp.bigvgan)
         extra["bigvgan_config5"] = {"ms_per_1000_frames": mb["value"], "audio_seconds_per_second": mb["audio_seconds_per_second"],
                                     "TFLOPs": mb["roofline"]["achieved"], "frac": mb["roofline"]["frac"], "peak": mb["roofline"]["peak"],
                                     "frac_fp32_mfma_peak": mb["roofline"]["frac_of_fp32_mfma_peak"]}
@@ -624,7 +679,7 @@ def main():
 
     # ---- CPU baseline: the oracle (port of the reference's CPU path) on a bounded sample
     cpu = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline and not mixed:
+    if rank == 0 and world == 1 and args.full and not args.no_cpu_baseline and not mixed:
         from oracle import gpt as OG
         from oracle import vocoder as OV
 

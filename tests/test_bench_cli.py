@@ -1,5 +1,5 @@
 """bench.py host logic that needs no GPU: `--gpus N` outside torchrun starts its own ranks (a child torch.distributed.run on
-127.0.0.1, before anything touches a GPU), the argument surface, and the mixed64 request list."""
+127.0.0.1, before anything touches a GPU), the argument surface, the mixed64 request list and the --dump-outputs writer."""
 import os
 import sys
 
@@ -40,3 +40,34 @@ def test_defaults_and_modes():
     reqs = sharding.mixed_requests()
     mine = [sharding.my_requests(len(reqs), r, 8) for r in range(8)]
     assert sorted(i for m in mine for i in m) == list(range(64)) and all(len(m) == 8 for m in mine)  # request i -> rank i mod 8
+
+
+def test_plain_run_leaves_the_side_measurements_to_full():
+    import bench
+
+    a = bench.parse([])
+    assert (a.full, a.dump_outputs) == (False, None)
+    a = bench.parse(["--full", "--dump-outputs", "out", "--no-extra"])
+    assert (a.full, a.dump_outputs, a.no_extra) == (True, "out", True)
+
+
+def test_dump_outputs_float32_within_budget(tmp_path):
+    import numpy as np
+
+    import bench
+
+    codes = np.arange(1100, dtype=np.int32)
+    pcm = (np.arange(-3000, 3000) * 5).astype(np.int16)
+    names = bench.dump_outputs(str(tmp_path / "a"), [("seg000_codes", codes), ("seg000_pcm", pcm)])
+    assert names == ["seg000_codes", "seg000_pcm"]
+    for n, ref in zip(names, (codes, pcm)):
+        got = np.load(tmp_path / "a" / f"{n}.npy")
+        assert got.dtype == np.float32 and np.array_equal(got, ref.astype(np.float32))  # exact: ints below 2**24
+
+    # more than the budget: a fixed, seeded choice that fits, the same on every run
+    arrays = [(f"x{i:02d}", np.full(1000 * (i + 1), i, np.float32)) for i in range(20)]
+    budget = 60_000
+    picks = [bench.dump_outputs(str(tmp_path / d), arrays, budget) for d in ("b", "c")]
+    assert picks[0] == picks[1] and 0 < len(picks[0]) < len(arrays)
+    assert sum(os.path.getsize(tmp_path / "b" / f"{n}.npy") for n in picks[0]) <= budget
+    assert sorted(os.listdir(tmp_path / "b")) == [f"{n}.npy" for n in picks[0]]

@@ -8,9 +8,9 @@ TAG=${1:-r02}
 cd /tmp && export TMPDIR=/tmp && cd $GRAFT_REPO_ROOT
 O=gpurun_out/$TAG
 mkdir -p $O
-python bench.py --steps 3 --warmup 1 > $O/bench.json 2> $O/bench.err
+python bench.py --steps 3 --warmup 1 --full > $O/bench.json 2> $O/bench.err
 echo "[profile] bench done"
-rocprofv3 --kernel-trace --stats --output-format csv -d $O/prof -- python bench.py --steps 1 --warmup 1 --no-cpu-baseline --no-extra > $O/bench_under_rocprof.json 2> $O/prof.err
+rocprofv3 --kernel-trace --stats --output-format csv -d $O/prof -- python bench.py --steps 1 --warmup 1 --full --no-cpu-baseline --no-extra > $O/bench_under_rocprof.json 2> $O/prof.err
 find $O/prof -name "*kernel_trace.csv" -delete
 cp $(find $O/prof -name "*kernel_stats.csv" | head -1) $O/bench_kernel_stats.csv
 echo "[profile] kernel stats done"

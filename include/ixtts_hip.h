@@ -117,6 +117,15 @@ long ixtts_gemm_x6_rows_padded(long rows);
 int ixtts_gemm_x6_split(const float* a_dev, long lda, void* planes_dev, long rows, int K, void* stream);
 int ixtts_gemm_x6_f32(const void* a_planes_dev, long rows_total, long row0, const void* packed_dev, const float* bias_dev, float* c_dev, long ldc,
                       int M, int N, int K, int accumulate, int tile, void* stream);
+/* ixtts_gemm_x6_pair_f32: the same GEMM with a pair epilogue, over weights packed with their two halves interleaved in 32-row blocks
+ * (rows 64q .. 64q + 31 = rows 32q .. of the first half, 64q + 32 .. 64q + 63 = the same rows of the second; bias_dev [N] likewise):
+ * C[M][N/2] = f(a, b), a / b = the two halves' results + bias; epilogue 1 = silu(a) * b (SwiGLU), 2 = tanh(a + g_a) * sigmoid(b + g_b)
+ * with (g_a | g_b) = gate_dev[min(r / rows_per_batch, nbatch - 1) * gate_ld + (0 .. N)) for output row r (the WaveNet gate).  taps > 1:
+ * K = taps x K_a over planes of K_a columns, k block j of the weights reading the planes' rows shifted down by j (a k-tap Conv1d over a
+ * row buffer in one GEMM; rows row0 .. row0 + M + taps - 1 of rows_total are read).  N a multiple of 64; tile 0 / 2 / 3 as above. */
+int ixtts_gemm_x6_pair_f32(const void* a_planes_dev, long rows_total, long row0, int taps, const void* packed_dev, const float* bias_dev,
+                           const float* gate_dev, long gate_ld, long rows_per_batch, int nbatch, float* c_dev, long ldc, int M, int N, int K,
+                           int epilogue, int tile, void* stream);
 
 /* ------------------------------------------------------------------------------------
  * Seam 2 -- BigVGAN-v2 generator

@@ -77,6 +77,11 @@ __global__ __launch_bounds__(256) void gemm_x6_split_kernel(const float* __restr
   }
 }
 
+// Epilogues.  The pair forms read the weights packed with their two halves interleaved in 32-row blocks (block 2q = rows
+// [32q, 32q + 32) of the first half, block 2q + 1 the same rows of the second), so one wave's two 32-column accumulator blocks hold
+// matching columns a, b of the two halves and the tile writes N / 2 columns: output column 32q + l31.
+enum { EPI_PLAIN = 0, EPI_SWIGLU = 1, EPI_GATE = 2 };  // C (+)= acc + bias  |  silu(a) * b  |  tanh(a + g_a) * sigmoid(b + g_b)
+
 struct GemmX6Params {
   const uint4* Ap;   // activation planes [K/16][6][Mpad], this GEMM's rows start at unit `arow0`
   long Mpad;
@@ -86,6 +91,11 @@ struct GemmX6Params {
   float* C;
   long ldc;
   int M, N, Npad, K, accumulate, m_tiles, n_tiles;
+  int tap_steps;     // 16-deep steps per tap: step s reads k-group s % tap_steps of the planes, rows shifted down by s / tap_steps
+  int epi;           // EPI_*: what the tile writes
+  const float* gate; // EPI_GATE: per-batch gate biases, row r takes gate[min(r / rows_per_batch, nbatch - 1) * gate_ld + ...]
+  long gate_ld, rows_per_batch;
+  int nbatch;
   unsigned long long* dbg;  // DBG == 3: per-step phase stamps of workgroup 0, wave 0 (developer timing)
 };
 
@@ -131,12 +141,13 @@ __global__ __launch_bounds__(256, (NST * (MT + NT) * 6 * 64 * 16 <= 80 * 1024) ?
   const uint4* asrc = p.Ap + p.arow0 + m0 + lane;
   const uint4* wsrc = p.Wp + n0 + lane;
   auto issue = [&](int s, uint4* st) {
+    const int tap = s / p.tap_steps, sa = s - tap * p.tap_steps;  // A: k-group sa of the planes, rows shifted down by `tap`
 #pragma unroll
     for (int q = 0; q < NDMA; ++q) {
       const int e = q * 4 + wave;  // piece id among the step's 6 (MT + NT)
       if (e < 6 * MT) {
         const int run = e / MT, piece = e % MT;
-        __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(asrc + ((long)s * 6 + run) * p.Mpad + piece * 64),
+        __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(asrc + ((long)sa * 6 + run) * p.Mpad + tap + piece * 64),
                                          (__attribute__((address_space(3))) void*)(st + run * BM + piece * 64), 16, 0, 0);
       } else {
         const int e2 = e - 6 * MT, run = e2 / NT, piece = e2 % NT;
@@ -247,7 +258,35 @@ __global__ __launch_bounds__(256, (NST * (MT + NT) * 6 * 64 * 16 <= 80 * 1024) ?
   }
 
   wg_stamp(2);
-  // ---- epilogue: + bias (+ what C held): register r of a lane = row (r & 3) + 8 (r >> 2) + 4 lh of the 32 x 32 tile, column l31
+  // ---- epilogue: register r of a lane = row (r & 3) + 8 (r >> 2) + 4 lh of the 32 x 32 tile, column l31
+  if (p.epi != EPI_PLAIN) {
+    static_assert(NT == 2, "pair epilogues: the wave's two 32-column blocks are the two halves");
+    const int oc = (n0 + wn * 64) / 2 + l31;  // output column
+    const int nh = p.N >> 1;
+    if (oc < nh) {
+      const float ba = p.bias != nullptr ? p.bias[n0 + wn * 64 + l31] : 0.f, bb = p.bias != nullptr ? p.bias[n0 + wn * 64 + 32 + l31] : 0.f;
+#pragma unroll
+      for (int i = 0; i < MT; ++i) {
+        const int rbase = m0 + wm * (32 * MT) + i * 32 + 4 * lh;
+#pragma unroll
+        for (int r = 0; r < 16; ++r) {
+          const int row = rbase + (r & 3) + 8 * (r >> 2);
+          if (row < p.M) {
+            float a = acc[i][0][r] + ba, b = acc[i][1][r] + bb, v;
+            if (p.epi == EPI_SWIGLU) {
+              v = a / (1.0f + expf(-a)) * b;  // swiglu_kernel's arithmetic
+            } else {
+              const float* g = p.gate + (long)min((long)row / p.rows_per_batch, (long)p.nbatch - 1) * p.gate_ld;
+              a += g[oc];
+              b += g[nh + oc];
+              v = tanhf(a) * (1.0f / (1.0f + expf(-b)));  // wn_gate_rows_kernel's arithmetic
+            }
+            p.C[(long)row * p.ldc + oc] = v;
+          }
+        }
+      }
+    }
+  } else
 #pragma unroll
   for (int j = 0; j < NT; ++j) {
     const int col = n0 + wn * (32 * NT) + j * 32 + l31;
@@ -282,7 +321,9 @@ static int launch_gemm_x6(GemmX6Params p, hipStream_t st) {
   p.m_tiles = ceil_div(p.M, BM);
   p.n_tiles = ceil_div(p.N, BN);
   IX_ARG((long)p.n_tiles * BN <= p.Npad, "gemm_x6: packed weights padded to %d features, the %d-wide tile needs %d", p.Npad, BN, p.n_tiles * BN);
-  IX_ARG(p.arow0 + (long)p.m_tiles * BM <= p.Mpad, "gemm_x6: activation planes hold %ld rows, the %d-row tiles reach row %ld", p.Mpad, BM, p.arow0 + (long)p.m_tiles * BM);
+  const int taps = (p.K >> 4) / p.tap_steps;  // the last tap reads taps - 1 rows below the tile
+  IX_ARG(p.arow0 + (long)p.m_tiles * BM + taps - 1 <= p.Mpad, "gemm_x6: activation planes hold %ld rows, the %d-row tiles reach row %ld", p.Mpad, BM,
+         p.arow0 + (long)p.m_tiles * BM + taps - 1);
   auto kern = gemm_x6_kernel<MT, NT, NST, DBG>;
   static bool done = false;
   if (!done) {
@@ -326,19 +367,9 @@ extern "C" int ixtts_gemm_x6_split(const float* a_dev, long lda, void* planes_de
   return IXTTS_OK;
 }
 
-extern "C" int ixtts_gemm_x6_f32(const void* a_planes_dev, long rows_total, long row0, const void* packed_dev, const float* bias_dev, float* c_dev,
-                                 long ldc, int M, int N, int K, int accumulate, int tile, void* stream) {
-  IX_ARG(a_planes_dev && packed_dev && c_dev && M > 0 && N > 0 && K > 0 && K % 64 == 0, "gemm_x6: bad argument (K must be a multiple of 64: the split pass works on 64-wide k blocks)");
-  IX_ARG(ldc >= N && row0 >= 0 && row0 + M <= rows_total, "gemm_x6: rows [%ld, %ld) of %ld, ldc %ld", row0, row0 + M, rows_total, ldc);
-  GemmX6Params p;
-  p.Ap = reinterpret_cast<const uint4*>(a_planes_dev); p.Mpad = ixtts_gemm_x6_rows_padded(rows_total); p.arow0 = row0;
-  p.Wp = reinterpret_cast<const uint4*>(packed_dev); p.bias = bias_dev; p.C = c_dev; p.ldc = ldc;
-  p.M = M; p.N = N; p.Npad = (N + 255) / 256 * 256; p.K = K; p.accumulate = accumulate ? 1 : 0; p.m_tiles = p.n_tiles = 0;
-  p.dbg = (tile == 32 || tile == 33) ? reinterpret_cast<unsigned long long*>(const_cast<float*>(bias_dev)) : nullptr;  // developer stamps travel in the bias slot
-  if (p.dbg) p.bias = nullptr;
-  hipStream_t st = (hipStream_t)stream;
+static int run_gemm_x6(GemmX6Params p, int tile, hipStream_t st) {
   if (tile == 0) {  // by fill of the 256 CUs: the wider tile while it still gives most CUs work (operand bytes per MFMA fall with the tile)
-    const long t42 = (long)ceil_div(M, 256) * ceil_div(N, 128);
+    const long t42 = (long)ceil_div(p.M, 256) * ceil_div(p.N, 128);
     tile = t42 >= 140 ? 2 : 3;
   }
   switch (tile) {
@@ -356,4 +387,37 @@ extern "C" int ixtts_gemm_x6_f32(const void* a_planes_dev, long rows_total, long
   }
   set_error("gemm_x6: tile %d (0 auto; 2 / 3: 256x128 / 128x128, two workgroups per CU; 4 / 5: the same, one per CU with a 4-stage ring)", tile);
   return IXTTS_ERR_ARG;
+}
+
+extern "C" int ixtts_gemm_x6_f32(const void* a_planes_dev, long rows_total, long row0, const void* packed_dev, const float* bias_dev, float* c_dev,
+                                 long ldc, int M, int N, int K, int accumulate, int tile, void* stream) {
+  IX_ARG(a_planes_dev && packed_dev && c_dev && M > 0 && N > 0 && K > 0 && K % 64 == 0, "gemm_x6: bad argument (K must be a multiple of 64: the split pass works on 64-wide k blocks)");
+  IX_ARG(ldc >= N && row0 >= 0 && row0 + M <= rows_total, "gemm_x6: rows [%ld, %ld) of %ld, ldc %ld", row0, row0 + M, rows_total, ldc);
+  GemmX6Params p;
+  p.Ap = reinterpret_cast<const uint4*>(a_planes_dev); p.Mpad = ixtts_gemm_x6_rows_padded(rows_total); p.arow0 = row0;
+  p.Wp = reinterpret_cast<const uint4*>(packed_dev); p.bias = bias_dev; p.C = c_dev; p.ldc = ldc;
+  p.M = M; p.N = N; p.Npad = (N + 255) / 256 * 256; p.K = K; p.accumulate = accumulate ? 1 : 0; p.m_tiles = p.n_tiles = 0;
+  p.tap_steps = K >> 4; p.epi = EPI_PLAIN; p.gate = nullptr; p.gate_ld = 0; p.rows_per_batch = 1; p.nbatch = 1;
+  p.dbg = (tile == 32 || tile == 33) ? reinterpret_cast<unsigned long long*>(const_cast<float*>(bias_dev)) : nullptr;  // developer stamps travel in the bias slot
+  if (p.dbg) p.bias = nullptr;
+  return run_gemm_x6(p, tile, (hipStream_t)stream);
+}
+
+extern "C" int ixtts_gemm_x6_pair_f32(const void* a_planes_dev, long rows_total, long row0, int taps, const void* packed_dev, const float* bias_dev,
+                                      const float* gate_dev, long gate_ld, long rows_per_batch, int nbatch, float* c_dev, long ldc, int M, int N, int K,
+                                      int epilogue, int tile, void* stream) {
+  IX_ARG(a_planes_dev && packed_dev && c_dev && M > 0 && N > 0 && taps > 0 && K > 0, "gemm_x6_pair: bad argument");
+  IX_ARG(K % taps == 0 && (K / taps) % 64 == 0 && N % 64 == 0, "gemm_x6_pair: K %d = %d taps of a multiple of 64, N %d a multiple of 64", K, taps, N);
+  IX_ARG(epilogue == EPI_SWIGLU || (epilogue == EPI_GATE && gate_dev && rows_per_batch > 0 && nbatch > 0 && gate_ld >= N / 2),
+         "gemm_x6_pair: epilogue %d (1 swiglu; 2 gate, with gate biases)", epilogue);
+  IX_ARG(ldc >= N / 2 && row0 >= 0 && row0 + M + taps - 1 <= rows_total, "gemm_x6_pair: rows [%ld, %ld) + %d taps of %ld, ldc %ld", row0, row0 + M, taps,
+         rows_total, ldc);
+  IX_ARG(tile == 0 || tile == 2 || tile == 3, "gemm_x6_pair: tile %d (0 auto, 2, 3)", tile);
+  GemmX6Params p;
+  p.Ap = reinterpret_cast<const uint4*>(a_planes_dev); p.Mpad = ixtts_gemm_x6_rows_padded(rows_total); p.arow0 = row0;
+  p.Wp = reinterpret_cast<const uint4*>(packed_dev); p.bias = bias_dev; p.C = c_dev; p.ldc = ldc;
+  p.M = M; p.N = N; p.Npad = (N + 255) / 256 * 256; p.K = K; p.accumulate = 0; p.m_tiles = p.n_tiles = 0;
+  p.tap_steps = (K / taps) >> 4; p.epi = epilogue; p.gate = gate_dev; p.gate_ld = gate_ld; p.rows_per_batch = rows_per_batch; p.nbatch = nbatch;
+  p.dbg = nullptr;
+  return run_gemm_x6(p, tile, (hipStream_t)stream);
 }

@@ -83,3 +83,40 @@ def linear(x, pl, out=None, accumulate=False, bias=True, tile=0, row0=0, rows=No
                                           M, N, K, 1 if accumulate else 0, int(tile), _lib.current_stream_ptr())
     _lib.check(rc, "ixtts_gemm_x6_f32")
     return out
+
+
+SWIGLU, GATE = 1, 2  # pair epilogues of `pair_linear` (csrc/gemm_x6.hip EPI_*)
+
+
+def interleave_halves(a, b):
+    """Rows of a and b [F, ...] -> [2F, ...] interleaved in 32-row blocks (a[32q:32q+32], b[32q:32q+32], ...): the packing the pair
+    epilogues read, so one 64-column block of the GEMM holds matching columns of both halves.  F a multiple of 32."""
+    F = a.shape[0]
+    assert b.shape == a.shape and F % 32 == 0, (tuple(a.shape), tuple(b.shape))
+    return torch.stack([a.reshape(F // 32, 32, *a.shape[1:]), b.reshape(F // 32, 32, *b.shape[1:])], 1).reshape(2 * F, *a.shape[1:]).contiguous()
+
+
+def pair_linear(x, pl, epilogue, taps=1, out=None, gate=None, gate_off=0, rows_per_batch=1, row0=0, rows=None, tile=0):
+    """out[M, N/2] = f(a, b) over a GEMM whose packed weights hold two halves interleaved (`interleave_halves`): SWIGLU silu(a) * b,
+    GATE tanh(a + g_a) * sigmoid(b + g_b) with (g_a | g_b) = gate[batch of the row, gate_off : gate_off + N] and rows_per_batch rows per
+    batch entry.  taps > 1: the weights are [N, taps * K_a] over planes of K_a columns, tap j reading the planes' rows shifted down by
+    j (one GEMM for a k-tap Conv1d over a padded row buffer); M defaults to the rows the last tap still covers."""
+    if not isinstance(x, Planes):
+        x = split(x)
+    assert pl.K == taps * x.K and pl.N % 64 == 0, (pl.K, taps, x.K, pl.N)
+    M = (x.rows - row0 - (taps - 1)) if rows is None else int(rows)
+    if out is None:
+        out = torch.empty(M, pl.N // 2, dtype=torch.float32, device=pl.packed.device)
+    assert out.shape[-1] == pl.N // 2 and out.stride(-1) == 1 and out.numel() >= M * (pl.N // 2)
+    ldc = int(out.stride(-2)) if out.dim() >= 2 else pl.N // 2
+    gp, gld, nb = None, 0, 1
+    if epilogue == GATE:
+        assert gate.is_contiguous() and gate.dim() == 2 and gate_off + pl.N <= gate.shape[1]
+        gp, gld, nb = gate.data_ptr() + 4 * int(gate_off), int(gate.shape[1]), int(gate.shape[0])
+    b = pl.bias
+    with torch.cuda.device(pl.packed.device):
+        rc = _lib.lib().ixtts_gemm_x6_pair_f32(x.buf.data_ptr(), x.rows, int(row0), int(taps), pl.packed.data_ptr(), b.data_ptr() if b is not None else None,
+                                               gp, gld, int(rows_per_batch), nb, out.data_ptr(), ldc, M, pl.N, pl.K, int(epilogue), int(tile),
+                                               _lib.current_stream_ptr())
+    _lib.check(rc, "ixtts_gemm_x6_pair_f32")
+    return out

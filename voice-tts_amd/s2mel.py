@@ -20,6 +20,7 @@ import os
 import torch
 import torch.nn.functional as F
 
+from . import gemm as G
 from .convs import conv1d  # GEMM forms: no MIOpen in the request path (convs.py)
 
 from .weights import fold_weight_norm
@@ -358,6 +359,19 @@ class S2Mel:
                 self.wn_out_bias = self.wn_out_bias + rb
         sw = W["cfm.estimator.skip_linear.weight"]  # input = [x_res (H) | x (C)]
         self.skipl_res, self.skipl_x = sw[:, :H].contiguous(), sw[:, H:].contiguous()
+        # split-product GEMMs with fused epilogues (csrc/gemm_x6.hip) on the device, packed once here: [w1; w3] with the SwiGLU in its
+        # epilogue, and each WaveNet in_layer's k taps as ONE GEMM (K = k x Hw over row-shifted windows of one split) with the gate in
+        # its epilogue -- the two halves interleaved in 32-row blocks (gemm.interleave_halves).  The CPU leg keeps torch's GEMMs.
+        self.x6_w13, self.x6_wn = None, None
+        if self.device.type == "cuda" and H % 64 == 0:
+            inter = self.w13[0].shape[0] // 2
+            self.x6_w13 = [G.PackedLinear(G.interleave_halves(w[:inter], w[inter:])) for w in self.w13]
+            self.x6_wn = [G.PackedLinear(G.interleave_halves(torch.cat(tp, 1)[:Hw], torch.cat(tp, 1)[Hw:]), G.interleave_halves(b[:Hw], b[Hw:]))
+                          for tp, b in zip(self.wn_taps, self.wn_bin)]
+
+    def _x6(self, packs):
+        """Whether the device GEMMs with fused epilogues are taken (`IXTTS_S2MEL_GEMM=library`: torch's library GEMMs, for A/B)."""
+        return packs is not None and os.environ.get("IXTTS_S2MEL_GEMM", "x6") != "library"
 
     # ------------------------------------------------------------------ small pieces
     def gpt_layer(self, latent):
@@ -433,6 +447,7 @@ class S2Mel:
         # (weight | bias) of every AdaLN, one contiguous [B, 2H] slab per norm
         wb_all = F.linear(c, self.proj_w, self.proj_b).view(B, 2 * L + 1, 2 * H).transpose(0, 1).contiguous()
         x = x.reshape(B * T, H)
+        x6 = x.is_cuda and self._x6(self.x6_w13)
         skips = []
         for i in range(L):
             p = f"cfm.estimator.transformer.layers.{i}."
@@ -443,8 +458,9 @@ class S2Mel:
             y = self._attention(F.linear(a.view(B * T, H), W[p + "attention.wqkv.weight"]), B, T, mask)
             # residuals accumulate in place where the input is private (layer inputs 1..L/2 are also the saved U-ViT skips)
             h = torch.addmm(x, y, W[p + "attention.wo.weight"].t()) if 0 < i <= L // 2 else x.addmm_(y, W[p + "attention.wo.weight"].t())
-            f = adaln_rmsnorm(h.view(B, T, H), wb_all[2 * i + 1], W[p + "ffn_norm.norm.weight"])
-            x = h.addmm_(swiglu(F.linear(f.view(B * T, H), self.w13[i])), W[p + "feed_forward.w2.weight"].t())
+            f = adaln_rmsnorm(h.view(B, T, H), wb_all[2 * i + 1], W[p + "ffn_norm.norm.weight"]).view(B * T, H)
+            u = G.pair_linear(f, self.x6_w13[i], G.SWIGLU) if x6 else swiglu(F.linear(f, self.w13[i]))
+            x = h.addmm_(u, W[p + "feed_forward.w2.weight"].t())
             if i < L // 2:
                 skips.append(x)
         return adaln_rmsnorm(x.view(B, T, H), wb_all[2 * L], W["cfm.estimator.transformer.norm.norm.weight"])
@@ -532,12 +548,16 @@ class S2Mel:
         M = B * Tp - tot
         centre = P2[left:left + M]  # the input row under output row r
         out = torch.empty(B * Tp, Hw, device=h.device, dtype=h.dtype)
+        x6 = self._x6(self.x6_wn)
         for i in range(nl):
             reflect_halo_rows(P, T_, left, right)
-            acc = torch.addmm(self.wn_bin[i], P2[:M], self.wn_taps[i][0].t())
-            for j in range(1, k):
-                acc.addmm_(P2[j:j + M], self.wn_taps[i][j].t())
-            acts = wn_gate_rows(acc, g, i * 2 * Hw, Hw, Tp)
+            if x6:  # the k taps + bias + gate: one GEMM over one split of the padded rows
+                acts = G.pair_linear(G.split(P2), self.x6_wn[i], G.GATE, taps=k, gate=g, gate_off=i * 2 * Hw, rows_per_batch=Tp)
+            else:
+                acc = torch.addmm(self.wn_bin[i], P2[:M], self.wn_taps[i][0].t())
+                for j in range(1, k):
+                    acc.addmm_(P2[j:j + M], self.wn_taps[i][j].t())
+                acts = wn_gate_rows(acc, g, i * 2 * Hw, Hw, Tp)
             if i < nl - 1:
                 centre.addmm_(acts, self.wn_r1[i].t())
             if i == 0:

@@ -67,6 +67,18 @@ int ixtts_attn_full_f32(const float* q_dev, const float* k_dev, const float* v_d
                         int head_dim, long stride_b, long stride_t, long stride_h, long ostride_b, long ostride_t,
                         long ostride_h, float scale, void* workspace_dev, size_t workspace_bytes, void* stream);
 
+/* ixtts_attn_full_varlen_f32: the same attention (x3 arithmetic) over n PACKED sequences of unequal length: sequence s owns rows
+ * [seq_off[s], seq_off[s+1]) of q, k, v, out (element (row, h, d) at base[row*stride_t + h*stride_h + d]), and its queries see its
+ * own keys only.  table_dev (int32, device) = [seq_off (nseq + 1) | tile_off (nseq + 1) | n_work (sequence, 128-query block) pairs]:
+ * tile_off the prefix sums of ceil(T_s / 64) (total_tiles = tile_off[nseq]), every (s, block) with block < ceil(T_s / 128) listed
+ * once, every T_s >= 1.  workspace_dev: ixtts_attn_full_varlen_workspace_bytes(nseq, H, total_tiles) bytes (the K / V planes; the
+ * key range is never split).  IXTTS_ATTN_FULL is not read: callers wanting the fp32-MFMA kernel call the entry above per sequence.
+ */
+size_t ixtts_attn_full_varlen_workspace_bytes(int nseq, int H, int total_tiles);
+int ixtts_attn_full_varlen_f32(const float* q_dev, const float* k_dev, const float* v_dev, float* out_dev, const int* table_dev, int nseq,
+                               int total_tiles, int n_work, int H, int head_dim, long stride_t, long stride_h, long ostride_t, long ostride_h,
+                               float scale, void* workspace_dev, size_t workspace_bytes, void* stream);
+
 /* Row N1 helpers -- the element/row chains between the DiT's GEMMs, one fp32 pass each (csrc/dit_ops.hip).
  *
  * ixtts_adaln_rmsnorm_f32  replaces AdaptiveLayerNorm.forward over RMSNorm (gpt_fast/model.py:18-37,362-372):
@@ -95,6 +107,23 @@ int ixtts_wn_gate_f32(const float* a_dev, const float* g_dev, float* out_dev, in
 int ixtts_wn_gate_rows_f32(const float* a_dev, const float* g_dev, float* out_dev, long rows, int C, long rows_per_batch, int B, long g_stride,
                            int g_offset, void* stream);
 int ixtts_reflect_halo_rows_f32(float* p_dev, int B, int T, int C, int left, int right, void* stream);
+
+/* The same row ops over n PACKED sequences of unequal length: seq_off_dev (int32, device) [nseq + 1] ascending row offsets, sequence s
+ * owning rows [seq_off[s], seq_off[s+1]), rows = seq_off[nseq] (the gate: rows past seq_off[nseq] take the last sequence's biases).
+ * ixtts_adaln_rmsnorm_varlen_f32 / ixtts_ln_modulate_varlen_f32: row r takes row s of wb / shift_scale [nseq, 2H].
+ * ixtts_rope_qk_varlen_f32: positions restart at 0 in each sequence (cos_sin covers the longest one).
+ * ixtts_wn_gate_rows_varlen_f32: row r takes the gate biases g[s * g_stride + g_offset ...] of its sequence.
+ * ixtts_reflect_halo_rows_varlen_f32: sequence s = left halo | T_s interior | right halo rows, T_s > max(left, right) (a shorter
+ *     sequence is left untouched; the caller refuses it).
+ */
+int ixtts_adaln_rmsnorm_varlen_f32(const float* x_dev, const float* wb_dev, const float* g_dev, float* out_dev, const int* seq_off_dev, int nseq,
+                                   long rows, int H, float eps, void* stream);
+int ixtts_ln_modulate_varlen_f32(const float* x_dev, const float* shift_scale_dev, float* out_dev, const int* seq_off_dev, int nseq, long rows, int H,
+                                 float eps, void* stream);
+int ixtts_rope_qk_varlen_f32(float* qkv_dev, const float* cos_sin_dev, const int* seq_off_dev, int nseq, long rows, int H, int head_dim, void* stream);
+int ixtts_wn_gate_rows_varlen_f32(const float* a_dev, const float* g_dev, float* out_dev, long rows, int C, const int* seq_off_dev, int nseq,
+                                  long g_stride, int g_offset, void* stream);
+int ixtts_reflect_halo_rows_varlen_f32(float* p_dev, const int* seq_off_dev, int nseq, int C, int left, int right, void* stream);
 
 /* Row N1 -- the linear layers of the s2mel DiT / WaveNet: C[M][N] (+)= A[M][K] . W[N][K]^T + bias, fp32 in and out
  * replaces: `nn.Linear` / 1x1 and k-tap Conv1d of indextts/s2mel/modules/gpt_fast/model.py:242-326 (wqkv, wo, w1 | w3, w2),
@@ -126,6 +155,12 @@ int ixtts_gemm_x6_f32(const void* a_planes_dev, long rows_total, long row0, cons
 int ixtts_gemm_x6_pair_f32(const void* a_planes_dev, long rows_total, long row0, int taps, const void* packed_dev, const float* bias_dev,
                            const float* gate_dev, long gate_ld, long rows_per_batch, int nbatch, float* c_dev, long ldc, int M, int N, int K,
                            int epilogue, int tile, void* stream);
+/* ixtts_gemm_x6_pair_gate_varlen_f32: the gate epilogue (2) over a row buffer of n packed sequences: output row r takes the gate biases
+ * gate_dev[s * gate_ld + ...] of the s with seq_off[s] <= r < seq_off[s+1] (seq_off_dev: int32 device table [nseq + 1], the padded
+ * offsets -- each sequence with its own halo rows; rows past seq_off[nseq] take the last sequence's). */
+int ixtts_gemm_x6_pair_gate_varlen_f32(const void* a_planes_dev, long rows_total, long row0, int taps, const void* packed_dev, const float* bias_dev,
+                                       const float* gate_dev, long gate_ld, const int* seq_off_dev, int nseq, float* c_dev, long ldc, int M, int N,
+                                       int K, int tile, void* stream);
 
 /* ------------------------------------------------------------------------------------
  * Seam 2 -- BigVGAN-v2 generator

@@ -23,11 +23,16 @@ struct AttnFullArgs {
   float scale;
   float* ws_o;   // KSPLIT > 1: un-normalised partial outputs [split][B][H][T][64]
   float* ws_ml;  //             and their (running max in log2 units, sum) [split][B][H][T][2]
+  // packed (ragged) sequences, attn_full_x3 only (B = 1, T unused): vl_tab = [seq_off n+1 | tile_off n+1 | (seq, 128-query block) pairs]
+  const int* vl_tab;
+  int vl_n, vl_tiles;  // sequences, key tiles of all of them (tile_off[n])
 };
 
 // bytes of K / V planes the x3 build keeps per call: [B*H][tiles][2 (K, V)][3 planes][512 units] x 16 B
 size_t attn_full_x3_plane_bytes(int B, int H, int T);
 // split pass + attention (+ partials for the caller's merge when a.ws_o is set); planes = attn_full_x3_plane_bytes() of scratch
 int launch_attn_full_x3(const AttnFullArgs& a, void* planes, bool split, hipStream_t st);
+// the same over packed sequences: queries of sequence s see the keys of sequence s only; n_work (sequence, query block) items
+int launch_attn_full_x3_varlen(const AttnFullArgs& a, void* planes, int n_work, hipStream_t st);
 
 }  // namespace ixtts

@@ -235,6 +235,7 @@ extern "C" int ixtts_attn_full_f32(const float* q_dev, const float* k_dev, const
   a.osb = ostride_b; a.ost = ostride_t; a.osh = ostride_h;
   a.B = B; a.H = H; a.T = T; a.scale = scale;
   a.ws_o = a.ws_ml = nullptr;
+  a.vl_tab = nullptr; a.vl_n = a.vl_tiles = 0;
   hipStream_t st = (hipStream_t)stream;
   const int qblocks = ceil_div(T, AF_WAVES * AF_QW);
   // split the keys when the un-split grid cannot give every SIMD two waves and the caller brought the workspace
@@ -267,4 +268,30 @@ extern "C" int ixtts_attn_full_f32(const float* q_dev, const float* k_dev, const
   }
   IX_HIP(hipGetLastError());
   return IXTTS_OK;
+}
+
+extern "C" size_t ixtts_attn_full_varlen_workspace_bytes(int nseq, int H, int total_tiles) {
+  if (nseq <= 0 || H <= 0 || total_tiles <= 0) return 0;
+  return (size_t)H * total_tiles * 2 * 3 * 8 * 64 * 16;  // K / V planes only: this entry never splits the key range
+}
+
+extern "C" int ixtts_attn_full_varlen_f32(const float* q_dev, const float* k_dev, const float* v_dev, float* out_dev, const int* table_dev, int nseq,
+                                          int total_tiles, int n_work, int H, int head_dim, long stride_t, long stride_h, long ostride_t, long ostride_h,
+                                          float scale, void* workspace_dev, size_t workspace_bytes, void* stream) {
+  using namespace ixtts;
+  IX_ARG(q_dev && k_dev && v_dev && out_dev && table_dev, "attn_full_varlen: null pointer");
+  IX_ARG(head_dim == AF_D, "attn_full_varlen: head_dim %d (only 64 is built)", head_dim);
+  IX_ARG(nseq > 0 && total_tiles >= nseq && n_work >= nseq && H > 0 && H <= 65535, "attn_full_varlen: bad shape nseq=%d tiles=%d work=%d H=%d", nseq, total_tiles,
+         n_work, H);
+  IX_ARG(stride_t % 4 == 0 && stride_h % 4 == 0, "attn_full_varlen: strides must keep 16-byte row alignment");
+  IX_ARG(workspace_dev && workspace_bytes >= ixtts_attn_full_varlen_workspace_bytes(nseq, H, total_tiles), "attn_full_varlen: workspace of %zu bytes, %zu needed",
+         workspace_bytes, ixtts_attn_full_varlen_workspace_bytes(nseq, H, total_tiles));
+  AttnFullArgs a;
+  a.q = q_dev; a.k = k_dev; a.v = v_dev; a.o = out_dev;
+  a.sb = 0; a.st = stride_t; a.sh = stride_h;
+  a.osb = 0; a.ost = ostride_t; a.osh = ostride_h;
+  a.B = 1; a.H = H; a.T = 0; a.scale = scale;
+  a.ws_o = a.ws_ml = nullptr;
+  a.vl_tab = table_dev; a.vl_n = nseq; a.vl_tiles = total_tiles;
+  return launch_attn_full_x3_varlen(a, workspace_dev, n_work, (hipStream_t)stream);
 }

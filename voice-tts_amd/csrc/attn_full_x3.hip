@@ -36,12 +36,27 @@ size_t attn_full_x3_plane_bytes(int B, int H, int T) {
 //   K block  [plane][oct 8][key 64]: unit = d 8*oct .. 8*oct+7 of one key (the A operand of S^T for lane (key, kh = oct & 1))
 //   V block  [plane][unit 8 = (j, u, kh)][d 64]: element e = key 32j + 16u + 8(e>>2) + 4kh + (e&3) of one d
 // Keys at or beyond T are written as zeros (their scores are masked in the attention kernel).
+// VL (packed sequences): blockIdx.x is a tile of all sequences' tiles; sequence s's tiles sit at tile_off[s] of head h's run
+template <bool VL>
 __global__ __launch_bounds__(256) void attn_kv_planes_kernel(AttnFullArgs a, uint4* __restrict__ planes) {
-  const int tile = blockIdx.x, bh = blockIdx.y, b = bh / a.H, h = bh % a.H;
-  const int n_tiles = (a.T + AF_KT - 1) / AF_KT;
-  const float* kb = a.k + b * a.sb + h * a.sh;
-  const float* vb = a.v + b * a.sb + h * a.sh;
-  uint4* kdst = planes + ((size_t)bh * n_tiles + tile) * 2 * AX_TILE_UNITS;
+  int tile = blockIdx.x, T = a.T;
+  const float *kb, *vb;
+  uint4* kdst;
+  if constexpr (VL) {
+    const int h = blockIdx.y, s = seq_of_row(a.vl_tab + a.vl_n + 1, a.vl_n, tile);
+    const int r0 = a.vl_tab[s];
+    T = a.vl_tab[s + 1] - r0;
+    kdst = planes + ((size_t)h * a.vl_tiles + tile) * 2 * AX_TILE_UNITS;
+    tile -= a.vl_tab[a.vl_n + 1 + s];
+    kb = a.k + (long)r0 * a.st + h * a.sh;
+    vb = a.v + (long)r0 * a.st + h * a.sh;
+  } else {
+    const int bh = blockIdx.y, b = bh / a.H, h = bh % a.H;
+    const int n_tiles = (a.T + AF_KT - 1) / AF_KT;
+    kb = a.k + b * a.sb + h * a.sh;
+    vb = a.v + b * a.sb + h * a.sh;
+    kdst = planes + ((size_t)bh * n_tiles + tile) * 2 * AX_TILE_UNITS;
+  }
   uint4* vdst = kdst + AX_TILE_UNITS;
   const int t0 = tile * AF_KT;
 #pragma unroll
@@ -50,9 +65,9 @@ __global__ __launch_bounds__(256) void attn_kv_planes_kernel(AttnFullArgs a, uin
     const int key = uid >> 3, oct = uid & 7;
     const int t = t0 + key;
     float v[8];
-    const float4* src = reinterpret_cast<const float4*>(kb + (long)min(t, a.T - 1) * a.st + 8 * oct);
+    const float4* src = reinterpret_cast<const float4*>(kb + (long)min(t, T - 1) * a.st + 8 * oct);
     const float4 x0 = src[0], x1 = src[1];
-    const bool live = t < a.T;
+    const bool live = t < T;
     v[0] = live ? x0.x : 0.f; v[1] = live ? x0.y : 0.f; v[2] = live ? x0.z : 0.f; v[3] = live ? x0.w : 0.f;
     v[4] = live ? x1.x : 0.f; v[5] = live ? x1.y : 0.f; v[6] = live ? x1.z : 0.f; v[7] = live ? x1.w : 0.f;
     uint4 ph, pm, pl;
@@ -69,8 +84,8 @@ __global__ __launch_bounds__(256) void attn_kv_planes_kernel(AttnFullArgs a, uin
 #pragma unroll
     for (int e = 0; e < 8; ++e) {
       const int t = t0 + 32 * j + 16 * u + 8 * (e >> 2) + 4 * kh + (e & 3);
-      const float x = vb[(long)min(t, a.T - 1) * a.st + d];
-      v[e] = t < a.T ? x : 0.f;
+      const float x = vb[(long)min(t, T - 1) * a.st + d];
+      v[e] = t < T ? x : 0.f;
     }
     uint4 ph, pm, pl;
     split8_bf16x3(v, ph, pm, pl);
@@ -80,21 +95,42 @@ __global__ __launch_bounds__(256) void attn_kv_planes_kernel(AttnFullArgs a, uin
   }
 }
 
-template <int KSPLIT>
+// VL (packed sequences, KSPLIT 1): blockIdx.x is a work item (sequence s, 128-query block), blockIdx.y the head; the queries and keys
+// are those of sequence s, its key tiles start at tile_off[s] of the head's run of planes
+template <int KSPLIT, bool VL = false>
 __global__ __launch_bounds__(AX_WAVES * 64, 3) void attn_full_x3_kernel(AttnFullArgs a, const uint4* __restrict__ planes) {
   __shared__ uint4 Ks[AX_TILE_UNITS];  // [plane][oct][key]
   __shared__ uint4 Vs[AX_TILE_UNITS];  // [plane][unit][d]
-  const int bh = blockIdx.y, b = bh / a.H, h = bh % a.H;
+  static_assert(!VL || KSPLIT == 1, "packed sequences: no key-range split");
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const int l31 = lane & 31, lh = lane >> 5;
-  const int q0 = blockIdx.x * (AX_WAVES * AF_QW) + wave * AF_QW;
-  const float* qb = a.q + b * a.sb + h * a.sh;
+  int T, q0;
+  const float* qb;
+  const uint4* pb;
+  float* ob;  // output row 0 of this (sequence, head)
+  if constexpr (VL) {
+    const int h = blockIdx.y;
+    const int* w = a.vl_tab + 2 * (a.vl_n + 1) + 2 * blockIdx.x;
+    const int s = w[0], r0 = a.vl_tab[s];
+    T = a.vl_tab[s + 1] - r0;
+    q0 = w[1] * (AX_WAVES * AF_QW) + wave * AF_QW;
+    qb = a.q + (long)r0 * a.st + h * a.sh;
+    pb = planes + ((size_t)h * a.vl_tiles + a.vl_tab[a.vl_n + 1 + s]) * 2 * AX_TILE_UNITS;
+    ob = a.o + (long)r0 * a.ost + h * a.osh;
+  } else {
+    const int bh = blockIdx.y, b = bh / a.H, h = bh % a.H;
+    T = a.T;
+    q0 = blockIdx.x * (AX_WAVES * AF_QW) + wave * AF_QW;
+    qb = a.q + b * a.sb + h * a.sh;
+    pb = planes + (size_t)bh * ((T + AF_KT - 1) / AF_KT) * 2 * AX_TILE_UNITS;
+    ob = a.o + b * a.osb + h * a.osh;
+  }
 
   // Q^T as the B operand of S^T = K Q^T: for step s the lane holds d = 16s + 8lh .. +7 of query l31, pre-scaled into the log2
   // domain (softmax weights are one v_exp_f32 each), split once
   uint4 qp[4][3];
   {
-    const int qi = min(q0 + l31, a.T - 1);
+    const int qi = min(q0 + l31, T - 1);
     const float* qrow = qb + (long)qi * a.st + 8 * lh;
     const float qs = a.scale * 1.4426950408889634f;
 #pragma unroll
@@ -111,11 +147,10 @@ __global__ __launch_bounds__(AX_WAVES * 64, 3) void attn_full_x3_kernel(AttnFull
     for (int r = 0; r < 16; ++r) ot[j][r] = 0.f;
   float m_run = -INFINITY, l_run = 0.f;
 
-  const int n_tiles = (a.T + AF_KT - 1) / AF_KT;
+  const int n_tiles = (T + AF_KT - 1) / AF_KT;
   const int tiles_per = (n_tiles + KSPLIT - 1) / KSPLIT;
   const int tile_lo = KSPLIT > 1 ? blockIdx.z * tiles_per : 0;
   const int tile_hi = KSPLIT > 1 ? min(n_tiles, tile_lo + tiles_per) : n_tiles;
-  const uint4* pb = planes + (size_t)bh * n_tiles * 2 * AX_TILE_UNITS;
   // a tile block is 1536 contiguous units: six 16-byte LDS-DMA copies per thread
   auto issue_tile = [&](const uint4* __restrict__ src, uint4* __restrict__ dst) {
 #pragma unroll
@@ -174,13 +209,13 @@ __global__ __launch_bounds__(AX_WAVES * 64, 3) void attn_full_x3_kernel(AttnFull
       mfma6x2(st[0], st[1], ka[0], ka[1], qp[s]);
     }
     // ---- online softmax for this lane's query; keys beyond T are masked (only the last tile has any)
-    if (t0 + AF_KT > a.T) {
+    if (t0 + AF_KT > T) {
 #pragma unroll
       for (int j = 0; j < 2; ++j)
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
           const int key = t0 + j * 32 + (r & 3) + 8 * (r >> 2) + 4 * lh;
-          if (key >= a.T) st[j][r] = -INFINITY;
+          if (key >= T) st[j][r] = -INFINITY;
         }
     }
     float tmax = -INFINITY;
@@ -235,16 +270,16 @@ __global__ __launch_bounds__(AX_WAVES * 64, 3) void attn_full_x3_kernel(AttnFull
   }
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
   const int qi = q0 + l31;
-  if (qi < a.T) {
+  if (qi < T) {
     if constexpr (KSPLIT == 1) {
       const float inv = 1.0f / l_run;
-      float* op = a.o + b * a.osb + (long)qi * a.ost + h * a.osh;
+      float* op = ob + (long)qi * a.ost;
 #pragma unroll
       for (int j = 0; j < 2; ++j)
 #pragma unroll
         for (int r = 0; r < 16; ++r) op[j * 32 + (r & 3) + 8 * (r >> 2) + 4 * lh] = ot[j][r] * inv;
     } else {
-      const long row = ((long)blockIdx.z * a.B * a.H + bh) * a.T + qi;
+      const long row = ((long)blockIdx.z * a.B * a.H + blockIdx.y) * T + qi;
       float* op = a.ws_o + row * AF_D;
 #pragma unroll
       for (int j = 0; j < 2; ++j)
@@ -259,9 +294,19 @@ int launch_attn_full_x3(const AttnFullArgs& a, void* planes, bool split, hipStre
   const int n_tiles = ceil_div(a.T, AF_KT);
   const int qblocks = ceil_div(a.T, AX_WAVES * AF_QW);
   uint4* pl = reinterpret_cast<uint4*>(planes);
-  hipLaunchKernelGGL(attn_kv_planes_kernel, dim3(n_tiles, a.B * a.H), dim3(256), 0, st, a, pl);
+  hipLaunchKernelGGL(attn_kv_planes_kernel<false>, dim3(n_tiles, a.B * a.H), dim3(256), 0, st, a, pl);
   if (split) hipLaunchKernelGGL(attn_full_x3_kernel<AX_KSPLIT>, dim3(qblocks, a.B * a.H, AX_KSPLIT), dim3(AX_WAVES * 64), 0, st, a, (const uint4*)pl);
   else hipLaunchKernelGGL(attn_full_x3_kernel<1>, dim3(qblocks, a.B * a.H), dim3(AX_WAVES * 64), 0, st, a, (const uint4*)pl);
+  IX_HIP(hipGetLastError());
+  return IXTTS_OK;
+}
+
+// Packed sequences: one split pass over every sequence's key tiles, then one attention grid of (sequence, query block) work items x
+// heads, so short sequences leave no idle workgroups.  No key-range split: the grid holds every sequence's query blocks.
+int launch_attn_full_x3_varlen(const AttnFullArgs& a, void* planes, int n_work, hipStream_t st) {
+  uint4* pl = reinterpret_cast<uint4*>(planes);
+  hipLaunchKernelGGL(attn_kv_planes_kernel<true>, dim3(a.vl_tiles, a.H), dim3(256), 0, st, a, pl);
+  hipLaunchKernelGGL((attn_full_x3_kernel<1, true>), dim3(n_work, a.H), dim3(AX_WAVES * 64), 0, st, a, (const uint4*)pl);
   IX_HIP(hipGetLastError());
   return IXTTS_OK;
 }

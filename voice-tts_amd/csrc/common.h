@@ -47,6 +47,18 @@ typedef __hip_bfloat16 bf16;
 __device__ __forceinline__ float bf16_bits_to_f32(unsigned short b) {
   return __uint_as_float(((unsigned int)b) << 16);
 }
+// Packed (ragged) sequences: off[0 .. n] ascending, sequence s owns rows [off[s], off[s+1]).  Returns the s with
+// off[s] <= row < off[s+1], clamped to [0, n-1] (rows past off[n] belong to the last sequence).
+__device__ __forceinline__ int seq_of_row(const int* __restrict__ off, int n, long row) {
+  int lo = 0, hi = n - 1;
+  while (lo < hi) {
+    const int mid = (lo + hi + 1) >> 1;
+    if ((long)off[mid] <= row) lo = mid;
+    else hi = mid - 1;
+  }
+  return lo;
+}
+
 __device__ __forceinline__ float lo_bf16(unsigned int w) { return __uint_as_float(w << 16); }
 __device__ __forceinline__ float hi_bf16(unsigned int w) { return __uint_as_float(w & 0xffff0000u); }
 

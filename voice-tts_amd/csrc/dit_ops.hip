@@ -17,7 +17,7 @@ constexpr int ROW_NV = 8;  // float4 per lane: rows up to 64 * 8 * 4 = 2048 floa
 template <bool CENTER>
 __global__ __launch_bounds__(256) void row_norm_mod_kernel(const float* __restrict__ x, const float* __restrict__ mw, const float* __restrict__ mb,
                                                            const float* __restrict__ g, float* __restrict__ out, long rows, int T, int H, long mstride,
-                                                           float eps, float wadd) {
+                                                           float eps, float wadd, const int* __restrict__ seq_off = nullptr, int nseq = 0) {
   const long row = (long)blockIdx.x * 4 + (threadIdx.x >> 6);
   if (row >= rows) return;
   const int lane = threadIdx.x & 63;
@@ -46,7 +46,7 @@ __global__ __launch_bounds__(256) void row_norm_mod_kernel(const float* __restri
     }
   }
   const float rstd = 1.0f / sqrtf(wave_sum(q) / (float)H + eps);
-  const long bidx = row / T;  // modulation vectors are per batch entry
+  const long bidx = seq_off ? seq_of_row(seq_off, nseq, row) : row / T;  // modulation vectors are per batch entry (or packed sequence)
   const float4* w4 = reinterpret_cast<const float4*>(mw + bidx * mstride);
   const float4* b4 = reinterpret_cast<const float4*>(mb + bidx * mstride);
   const float4* g4 = reinterpret_cast<const float4*>(g);
@@ -67,14 +67,16 @@ __global__ __launch_bounds__(256) void row_norm_mod_kernel(const float* __restri
 }
 
 // qkv [rows][3H]; q = cols [0,H), k = cols [H,2H); pair i of head h sits at h*hd + 2i, +1; table [T][hd/2] (cos, sin)
-__global__ __launch_bounds__(256) void rope_qk_kernel(float* __restrict__ qkv, const float2* __restrict__ tab, long rows, int T, int H, int hd) {
+// seq_off: packed sequences (positions restart at 0 at each off[s]) instead of B sequences of T rows
+__global__ __launch_bounds__(256) void rope_qk_kernel(float* __restrict__ qkv, const float2* __restrict__ tab, long rows, int T, int H, int hd,
+                                                      const int* __restrict__ seq_off = nullptr, int nseq = 0) {
   const int per_row = (2 * H) >> 2;  // float4 (two pairs) of the q and k thirds
   const long idx = (long)blockIdx.x * 256 + threadIdx.x;
   if (idx >= rows * per_row) return;
   const long row = idx / per_row;
   const int c4 = (int)(idx % per_row);
   const int col = c4 * 4;  // within [0, 2H)
-  const int t = (int)(row % T);
+  const int t = seq_off ? (int)(row - seq_off[seq_of_row(seq_off, nseq, row)]) : (int)(row % T);
   const int p = (col % hd) >> 1;  // first of the two pairs
   float4* ptr = reinterpret_cast<float4*>(qkv + row * 3 * H + col);
   const float4 v = *ptr;
@@ -111,13 +113,13 @@ __global__ __launch_bounds__(256) void wn_gate_kernel(const float* __restrict__ 
 
 // Row layout of the same gate: a [rows][2C], out [rows][C]; row r belongs to batch entry min(r / rows_per_batch, B-1)
 __global__ __launch_bounds__(256) void wn_gate_rows_kernel(const float* __restrict__ a, const float* __restrict__ gvec, float* __restrict__ out, long rows, int C,
-                                                           long rows_per_batch, int B, long gstride, int goff) {
+                                                           long rows_per_batch, int B, long gstride, int goff, const int* __restrict__ seq_off = nullptr) {
   const long idx = (long)blockIdx.x * 256 + threadIdx.x;  // one float4 of one output row
   const int C4 = C >> 2;
   if (idx >= rows * C4) return;
   const long r = idx / C4;
   const int c = (int)(idx % C4) * 4;
-  const int b = (int)min(r / rows_per_batch, (long)B - 1);
+  const int b = seq_off ? seq_of_row(seq_off, B, r) : (int)min(r / rows_per_batch, (long)B - 1);
   const float4 xa = *reinterpret_cast<const float4*>(a + r * 2 * C + c);
   const float4 xb = *reinterpret_cast<const float4*>(a + r * 2 * C + C + c);
   const float4 ga = *reinterpret_cast<const float4*>(gvec + b * gstride + goff + c);
@@ -141,6 +143,23 @@ __global__ __launch_bounds__(256) void reflect_halo_rows_kernel(float* __restric
   const int h = (int)((idx % per_b) / C4);
   const int c = (int)(idx % C4) * 4;
   float* base = p + (long)b * (left + T + right) * C;
+  const int dst = h < left ? left - 1 - h : left + T + (h - left);
+  const int src = h < left ? left + h + 1 : left + T - 2 - (h - left);
+  *reinterpret_cast<float4*>(base + (long)dst * C + c) = *reinterpret_cast<const float4*>(base + (long)src * C + c);
+}
+
+// The same over packed sequences of unequal length: sequence s owns rows [off[s], off[s+1]) = left halo | T_s interior | right halo
+__global__ __launch_bounds__(256) void reflect_halo_rows_varlen_kernel(float* __restrict__ p, const int* __restrict__ off, int n, int C, int left, int right) {
+  const int C4 = C >> 2;
+  const long idx = (long)blockIdx.x * 256 + threadIdx.x;
+  const long per_b = (long)(left + right) * C4;
+  if (idx >= per_b * n) return;
+  const int b = (int)(idx / per_b);
+  const int h = (int)((idx % per_b) / C4);
+  const int c = (int)(idx % C4) * 4;
+  const int o0 = off[b], T = off[b + 1] - o0 - left - right;
+  if (T <= left || T <= right) return;  // refused on the host; never read outside the sequence
+  float* base = p + (long)o0 * C;
   const int dst = h < left ? left - 1 - h : left + T + (h - left);
   const int src = h < left ? left + h + 1 : left + T - 2 - (h - left);
   *reinterpret_cast<float4*>(base + (long)dst * C + c) = *reinterpret_cast<const float4*>(base + (long)src * C + c);
@@ -219,6 +238,62 @@ extern "C" int ixtts_reflect_halo_rows_f32(float* p_dev, int B, int T, int C, in
   const long n = (long)B * (left + right) * (C / 4);
   if (n == 0) return IXTTS_OK;
   hipLaunchKernelGGL(reflect_halo_rows_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, p_dev, B, T, C, left, right);
+  IX_HIP(hipGetLastError());
+  return IXTTS_OK;
+}
+
+// ---- packed (ragged) sequences: seq_off_dev [nseq + 1] int32 row offsets on the device, rows = seq_off[nseq]
+
+extern "C" int ixtts_adaln_rmsnorm_varlen_f32(const float* x_dev, const float* wb_dev, const float* g_dev, float* out_dev, const int* seq_off_dev, int nseq,
+                                              long rows, int H, float eps, void* stream) {
+  IX_ARG(x_dev && wb_dev && g_dev && out_dev && seq_off_dev, "adaln_rmsnorm_varlen: null pointer");
+  IX_ARG(nseq > 0 && rows > 0 && H > 0 && H % 4 == 0 && H <= 64 * ROW_NV * 4, "adaln_rmsnorm_varlen: bad shape nseq=%d rows=%ld H=%d", nseq, rows, H);
+  hipLaunchKernelGGL(row_norm_mod_kernel<false>, dim3((unsigned)((rows + 3) / 4)), dim3(256), 0, (hipStream_t)stream, x_dev, wb_dev, wb_dev + H, g_dev, out_dev,
+                     rows, 1, H, (long)2 * H, eps, 0.0f, seq_off_dev, nseq);
+  IX_HIP(hipGetLastError());
+  return IXTTS_OK;
+}
+
+extern "C" int ixtts_ln_modulate_varlen_f32(const float* x_dev, const float* shift_scale_dev, float* out_dev, const int* seq_off_dev, int nseq, long rows, int H,
+                                            float eps, void* stream) {
+  IX_ARG(x_dev && shift_scale_dev && out_dev && seq_off_dev, "ln_modulate_varlen: null pointer");
+  IX_ARG(nseq > 0 && rows > 0 && H > 0 && H % 4 == 0 && H <= 64 * ROW_NV * 4, "ln_modulate_varlen: bad shape nseq=%d rows=%ld H=%d", nseq, rows, H);
+  hipLaunchKernelGGL(row_norm_mod_kernel<true>, dim3((unsigned)((rows + 3) / 4)), dim3(256), 0, (hipStream_t)stream, x_dev, shift_scale_dev + H, shift_scale_dev,
+                     (const float*)nullptr, out_dev, rows, 1, H, (long)2 * H, eps, 1.0f, seq_off_dev, nseq);
+  IX_HIP(hipGetLastError());
+  return IXTTS_OK;
+}
+
+extern "C" int ixtts_rope_qk_varlen_f32(float* qkv_dev, const float* cos_sin_dev, const int* seq_off_dev, int nseq, long rows, int H, int head_dim, void* stream) {
+  IX_ARG(qkv_dev && cos_sin_dev && seq_off_dev, "rope_qk_varlen: null pointer");
+  IX_ARG(nseq > 0 && rows > 0 && H > 0 && head_dim > 0 && head_dim % 4 == 0 && H % head_dim == 0, "rope_qk_varlen: bad shape nseq=%d rows=%ld H=%d hd=%d", nseq,
+         rows, H, head_dim);
+  const long n = rows * (2 * H / 4);
+  hipLaunchKernelGGL(rope_qk_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, qkv_dev, reinterpret_cast<const float2*>(cos_sin_dev),
+                     rows, 1, H, head_dim, seq_off_dev, nseq);
+  IX_HIP(hipGetLastError());
+  return IXTTS_OK;
+}
+
+extern "C" int ixtts_wn_gate_rows_varlen_f32(const float* a_dev, const float* g_dev, float* out_dev, long rows, int C, const int* seq_off_dev, int nseq,
+                                             long g_stride, int g_offset, void* stream) {
+  IX_ARG(a_dev && g_dev && out_dev && seq_off_dev, "wn_gate_rows_varlen: null pointer");
+  IX_ARG(rows > 0 && C > 0 && C % 4 == 0 && nseq > 0 && g_offset >= 0 && g_offset % 4 == 0 && g_stride % 4 == 0,
+         "wn_gate_rows_varlen: bad shape rows=%ld C=%d nseq=%d", rows, C, nseq);
+  const long n = rows * (C / 4);
+  hipLaunchKernelGGL(wn_gate_rows_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, a_dev, g_dev, out_dev, rows, C, (long)1, nseq,
+                     g_stride, g_offset, seq_off_dev);
+  IX_HIP(hipGetLastError());
+  return IXTTS_OK;
+}
+
+extern "C" int ixtts_reflect_halo_rows_varlen_f32(float* p_dev, const int* seq_off_dev, int nseq, int C, int left, int right, void* stream) {
+  IX_ARG(p_dev && seq_off_dev, "reflect_halo_rows_varlen: null pointer");
+  IX_ARG(nseq > 0 && C > 0 && C % 4 == 0 && left >= 0 && right >= 0, "reflect_halo_rows_varlen: bad shape nseq=%d C=%d left=%d right=%d", nseq, C, left, right);
+  const long n = (long)nseq * (left + right) * (C / 4);
+  if (n == 0) return IXTTS_OK;
+  hipLaunchKernelGGL(reflect_halo_rows_varlen_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, p_dev, seq_off_dev, nseq, C, left,
+                     right);
   IX_HIP(hipGetLastError());
   return IXTTS_OK;
 }

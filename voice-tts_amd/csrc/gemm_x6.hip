@@ -96,6 +96,7 @@ struct GemmX6Params {
   const float* gate; // EPI_GATE: per-batch gate biases, row r takes gate[min(r / rows_per_batch, nbatch - 1) * gate_ld + ...]
   long gate_ld, rows_per_batch;
   int nbatch;
+  const int* gate_seq_off;  // EPI_GATE over packed sequences: row r takes the gate of the s with off[s] <= r < off[s+1] (nbatch = n), or null
   unsigned long long* dbg;  // DBG == 3: per-step phase stamps of workgroup 0, wave 0 (developer timing)
 };
 
@@ -276,7 +277,8 @@ __global__ __launch_bounds__(256, (NST * (MT + NT) * 6 * 64 * 16 <= 80 * 1024) ?
             if (p.epi == EPI_SWIGLU) {
               v = a / (1.0f + expf(-a)) * b;  // swiglu_kernel's arithmetic
             } else {
-              const float* g = p.gate + (long)min((long)row / p.rows_per_batch, (long)p.nbatch - 1) * p.gate_ld;
+              const long gb = p.gate_seq_off ? (long)seq_of_row(p.gate_seq_off, p.nbatch, row) : min((long)row / p.rows_per_batch, (long)p.nbatch - 1);
+              const float* g = p.gate + gb * p.gate_ld;
               a += g[oc];
               b += g[nh + oc];
               v = tanhf(a) * (1.0f / (1.0f + expf(-b)));  // wn_gate_rows_kernel's arithmetic
@@ -397,7 +399,7 @@ extern "C" int ixtts_gemm_x6_f32(const void* a_planes_dev, long rows_total, long
   p.Ap = reinterpret_cast<const uint4*>(a_planes_dev); p.Mpad = ixtts_gemm_x6_rows_padded(rows_total); p.arow0 = row0;
   p.Wp = reinterpret_cast<const uint4*>(packed_dev); p.bias = bias_dev; p.C = c_dev; p.ldc = ldc;
   p.M = M; p.N = N; p.Npad = (N + 255) / 256 * 256; p.K = K; p.accumulate = accumulate ? 1 : 0; p.m_tiles = p.n_tiles = 0;
-  p.tap_steps = K >> 4; p.epi = EPI_PLAIN; p.gate = nullptr; p.gate_ld = 0; p.rows_per_batch = 1; p.nbatch = 1;
+  p.tap_steps = K >> 4; p.epi = EPI_PLAIN; p.gate = nullptr; p.gate_ld = 0; p.rows_per_batch = 1; p.nbatch = 1; p.gate_seq_off = nullptr;
   p.dbg = (tile == 32 || tile == 33) ? reinterpret_cast<unsigned long long*>(const_cast<float*>(bias_dev)) : nullptr;  // developer stamps travel in the bias slot
   if (p.dbg) p.bias = nullptr;
   return run_gemm_x6(p, tile, (hipStream_t)stream);
@@ -418,6 +420,26 @@ extern "C" int ixtts_gemm_x6_pair_f32(const void* a_planes_dev, long rows_total,
   p.Wp = reinterpret_cast<const uint4*>(packed_dev); p.bias = bias_dev; p.C = c_dev; p.ldc = ldc;
   p.M = M; p.N = N; p.Npad = (N + 255) / 256 * 256; p.K = K; p.accumulate = 0; p.m_tiles = p.n_tiles = 0;
   p.tap_steps = (K / taps) >> 4; p.epi = epilogue; p.gate = gate_dev; p.gate_ld = gate_ld; p.rows_per_batch = rows_per_batch; p.nbatch = nbatch;
+  p.gate_seq_off = nullptr;
+  p.dbg = nullptr;
+  return run_gemm_x6(p, tile, (hipStream_t)stream);
+}
+
+extern "C" int ixtts_gemm_x6_pair_gate_varlen_f32(const void* a_planes_dev, long rows_total, long row0, int taps, const void* packed_dev, const float* bias_dev,
+                                                  const float* gate_dev, long gate_ld, const int* seq_off_dev, int nseq, float* c_dev, long ldc, int M, int N,
+                                                  int K, int tile, void* stream) {
+  IX_ARG(seq_off_dev && nseq > 0, "gemm_x6_pair_gate_varlen: null offsets table or nseq %d", nseq);
+  IX_ARG(a_planes_dev && packed_dev && c_dev && gate_dev && M > 0 && N > 0 && taps > 0 && K > 0 && gate_ld >= N / 2, "gemm_x6_pair_gate_varlen: bad argument");
+  IX_ARG(K % taps == 0 && (K / taps) % 64 == 0 && N % 64 == 0, "gemm_x6_pair_gate_varlen: K %d = %d taps of a multiple of 64, N %d a multiple of 64", K, taps, N);
+  IX_ARG(ldc >= N / 2 && row0 >= 0 && row0 + M + taps - 1 <= rows_total, "gemm_x6_pair_gate_varlen: rows [%ld, %ld) + %d taps of %ld, ldc %ld", row0, row0 + M,
+         taps, rows_total, ldc);
+  IX_ARG(tile == 0 || tile == 2 || tile == 3, "gemm_x6_pair_gate_varlen: tile %d (0 auto, 2, 3)", tile);
+  GemmX6Params p;
+  p.Ap = reinterpret_cast<const uint4*>(a_planes_dev); p.Mpad = ixtts_gemm_x6_rows_padded(rows_total); p.arow0 = row0;
+  p.Wp = reinterpret_cast<const uint4*>(packed_dev); p.bias = bias_dev; p.C = c_dev; p.ldc = ldc;
+  p.M = M; p.N = N; p.Npad = (N + 255) / 256 * 256; p.K = K; p.accumulate = 0; p.m_tiles = p.n_tiles = 0;
+  p.tap_steps = (K / taps) >> 4; p.epi = EPI_GATE; p.gate = gate_dev; p.gate_ld = gate_ld; p.rows_per_batch = 1; p.nbatch = nseq;
+  p.gate_seq_off = seq_off_dev;
   p.dbg = nullptr;
   return run_gemm_x6(p, tile, (hipStream_t)stream);
 }

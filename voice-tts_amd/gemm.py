@@ -96,11 +96,13 @@ def interleave_halves(a, b):
     return torch.stack([a.reshape(F // 32, 32, *a.shape[1:]), b.reshape(F // 32, 32, *b.shape[1:])], 1).reshape(2 * F, *a.shape[1:]).contiguous()
 
 
-def pair_linear(x, pl, epilogue, taps=1, out=None, gate=None, gate_off=0, rows_per_batch=1, row0=0, rows=None, tile=0):
+def pair_linear(x, pl, epilogue, taps=1, out=None, gate=None, gate_off=0, rows_per_batch=1, row0=0, rows=None, tile=0, seq_off=None):
     """out[M, N/2] = f(a, b) over a GEMM whose packed weights hold two halves interleaved (`interleave_halves`): SWIGLU silu(a) * b,
     GATE tanh(a + g_a) * sigmoid(b + g_b) with (g_a | g_b) = gate[batch of the row, gate_off : gate_off + N] and rows_per_batch rows per
-    batch entry.  taps > 1: the weights are [N, taps * K_a] over planes of K_a columns, tap j reading the planes' rows shifted down by
-    j (one GEMM for a k-tap Conv1d over a padded row buffer); M defaults to the rows the last tap still covers."""
+    batch entry -- or, with `seq_off` (GATE only: an object with `.tab`, an int32 device tensor starting with the n + 1 row offsets of
+    packed sequences, and `.n`), the gate row of the row's own sequence.  taps > 1: the weights are [N, taps * K_a] over planes of K_a
+    columns, tap j reading the planes' rows shifted down by j (one GEMM for a k-tap Conv1d over a padded row buffer); M defaults to the
+    rows the last tap still covers."""
     if not isinstance(x, Planes):
         x = split(x)
     assert pl.K == taps * x.K and pl.N % 64 == 0, (pl.K, taps, x.K, pl.N)
@@ -114,6 +116,14 @@ def pair_linear(x, pl, epilogue, taps=1, out=None, gate=None, gate_off=0, rows_p
         assert gate.is_contiguous() and gate.dim() == 2 and gate_off + pl.N <= gate.shape[1]
         gp, gld, nb = gate.data_ptr() + 4 * int(gate_off), int(gate.shape[1]), int(gate.shape[0])
     b = pl.bias
+    if seq_off is not None:
+        assert epilogue == GATE and seq_off.tab.is_cuda and gate.shape[0] >= seq_off.n
+        with torch.cuda.device(pl.packed.device):
+            rc = _lib.lib().ixtts_gemm_x6_pair_gate_varlen_f32(x.buf.data_ptr(), x.rows, int(row0), int(taps), pl.packed.data_ptr(),
+                                                               b.data_ptr() if b is not None else None, gp, gld, seq_off.tab.data_ptr(), int(seq_off.n),
+                                                               out.data_ptr(), ldc, M, pl.N, pl.K, int(tile), _lib.current_stream_ptr())
+        _lib.check(rc, "ixtts_gemm_x6_pair_gate_varlen_f32")
+        return out
     with torch.cuda.device(pl.packed.device):
         rc = _lib.lib().ixtts_gemm_x6_pair_f32(x.buf.data_ptr(), x.rows, int(row0), int(taps), pl.packed.data_ptr(), b.data_ptr() if b is not None else None,
                                                gp, gld, int(rows_per_batch), nb, out.data_ptr(), ldc, M, pl.N, pl.K, int(epilogue), int(tile),

@@ -32,6 +32,12 @@ from .weights import BIGVGAN_CFG, GPT_CFG, load_bigvgan_checkpoint, load_gpt_che
 logger = logging.getLogger("indextts.infer_v2")
 
 
+def s2mel_batching():
+    """IXTTS_S2MEL_BATCH=1: the CFM solves of several segments as ONE packed solve (S2Mel.solve_many).  Off by default: at the
+    headline's 2 x 1100 codes the packed solve is 2.6 % slower than two per-segment solves (profiles/r05_notes.md)."""
+    return os.environ.get("IXTTS_S2MEL_BATCH", "0") == "1"
+
+
 def _same_prompt(a, b):
     """The reference's cache test `cache_spk_audio_prompt != spk_audio_prompt` (infer_v2.py:508,566) for every prompt form:
     equal paths / bytes hit the cache even when they are distinct objects; arrays and tensors compare by content."""
@@ -602,13 +608,12 @@ class IndexTTS2:
                 todo, lambda seg, ids: plans[seg.request]["codes"].__setitem__(seg.index, ids), do_sample=top_k != 1, **sampler)
         torch.cuda.synchronize(self.device)
         t_decode = time.perf_counter() - start
-        out = []
+        # per request: codes -> latents (a code outside the codebook fails its request only, before anything is packed)
         for ri, plan in enumerate(plans):
             if ri in failed:
-                out.append(failed[ri])
                 continue
             try:
-                wavs = []
+                plan["items"] = []
                 for ids, seg in zip(plan["codes"], plan["segments"]):
                     row = torch.from_numpy(np.asarray(ids).astype(np.int64)).to(self.device)
                     stops = (row == self.stop_mel_token).nonzero(as_tuple=False)
@@ -621,12 +626,42 @@ class IndexTTS2:
                     t = torch.cat((tt.new_tensor([self.gpt_cfg["start_text_token"]]), tt, tt.new_tensor([self.gpt_cfg["stop_text_token"]]))).long()
                     prefix = torch.cat((plan["cl"], self.text_embedding[t] + self.text_pos_embedding[: t.numel()]), 0)
                     latent = self.gpt.latent(prefix, codes[0]).unsqueeze(0)
-                    lens = torch.tensor([n], dtype=torch.long, device=self.device)
                     spk = plan["spk"]
-                    if self.s2mel is not None:
-                        mel = self.s2mel(latent, codes, lens, spk["prompt_condition"], spk["ref_mel"], spk["style"], n_timesteps=25, inference_cfg_rate=0.7)
-                    else:
-                        mel = self._stage("s2mel", None)(latent, codes, lens, spk)
+                    plan["items"].append((latent, codes, spk["prompt_condition"], spk["ref_mel"], spk["style"]))
+            except Exception as e:  # this request only
+                failed[ri] = e
+        # s2mel, IXTTS_S2MEL_BATCH=1: every surviving segment of every request in one packed solve (S2Mel.solve_many) -- an exception
+        # raised inside it is returned for every request of the batch; default, or an injected s2mel stage: segment after segment
+        live = [ri for ri in range(len(plans)) if ri not in failed]
+        if self.s2mel is not None and s2mel_batching():
+            try:
+                mels = iter(self.s2mel.solve_many([it for ri in live for it in plans[ri]["items"]], n_timesteps=25, inference_cfg_rate=0.7))
+                for ri in live:
+                    plans[ri]["mels"] = [next(mels) for _ in plans[ri]["items"]]
+            except Exception as e:
+                for ri in live:
+                    failed[ri] = e
+        else:
+            for ri in live:
+                try:
+                    plans[ri]["mels"] = []
+                    for latent, codes, pc, rm, st in plans[ri]["items"]:
+                        lens = torch.tensor([codes.shape[1]], dtype=torch.long, device=self.device)
+                        if self.s2mel is not None:
+                            mel = self.s2mel(latent, codes, lens, pc, rm, st, n_timesteps=25, inference_cfg_rate=0.7)
+                        else:
+                            mel = self._stage("s2mel", None)(latent, codes, lens, plans[ri]["spk"])
+                        plans[ri]["mels"].append(mel)
+                except Exception as e:  # this request only
+                    failed[ri] = e
+        out = []
+        for ri, plan in enumerate(plans):
+            if ri in failed:
+                out.append(failed[ri])
+                continue
+            try:
+                wavs = []
+                for mel in plan["mels"]:
                     wav = torch.clamp(32767 * self.bigvgan(mel.float()).squeeze().unsqueeze(0), -32767.0, 32767.0)
                     wavs.append(wav.cpu())
                 if not wavs:
@@ -769,6 +804,9 @@ class IndexTTS2:
                 typical_mass=float(generation_kwargs.get("typical_mass", 0.9)) if generation_kwargs.get("typical_sampling") else 0.0)
             torch.cuda.synchronize(self.device)
             gpt_gen_time += time.perf_counter() - m0
+        # several segments, whole audio at the end, IXTTS_S2MEL_BATCH=1: their CFM solves run as ONE packed solve (S2Mel.solve_many;
+        # default: segment after segment, as the reference); streaming keeps the per-segment order for its first-chunk latency
+        packed = [] if (not stream_return and len(segments) > 1 and self.s2mel is not None and s2mel_batching()) else None
         for seg_index, sent_ids in enumerate(segments):
             text_tokens = torch.as_tensor(sent_ids, dtype=torch.int32, device=self.device).reshape(-1)
             m0 = time.perf_counter()
@@ -812,6 +850,9 @@ class IndexTTS2:
 
             m0 = time.perf_counter()
             self._check_codes(codes)
+            if packed is not None:  # every segment's CFM in one solve after the loop
+                packed.append((latent, codes, spk["prompt_condition"], spk["ref_mel"], spk["style"]))
+                continue
             if self.s2mel is not None:  # infer_v2.py:713-731
                 mel = self.s2mel(latent, codes, code_lens, spk["prompt_condition"], spk["ref_mel"], spk["style"],
                                  n_timesteps=25, inference_cfg_rate=0.7)
@@ -831,6 +872,17 @@ class IndexTTS2:
                 if silence is None:
                     silence = self.interval_silence(wavs, sampling_rate=sampling_rate, interval_silence=interval_silence)
                 yield silence
+        if packed:
+            m0 = time.perf_counter()
+            mels = self.s2mel.solve_many(packed, n_timesteps=25, inference_cfg_rate=0.7)
+            torch.cuda.synchronize(self.device)
+            s2mel_time += time.perf_counter() - m0
+            for mel in mels:
+                m0 = time.perf_counter()
+                wav = self.bigvgan(mel.float()).squeeze().unsqueeze(0)
+                torch.cuda.synchronize(self.device)
+                bigvgan_time += time.perf_counter() - m0
+                wavs.append(torch.clamp(32767 * wav, -32767.0, 32767.0).cpu())
         end_time = time.perf_counter()
         if not wavs:
             return

@@ -191,6 +191,15 @@ class HotPath:
         return self.s2mel_model(latent.reshape(1, codes.shape[1], -1), codes, lens, prompt_condition, ref_mel, style,
                                 n_timesteps=n_timesteps, inference_cfg_rate=inference_cfg_rate, noise=noise)
 
+    def s2mel_many(self, segments, n_timesteps=25, inference_cfg_rate=0.7, noises=None):
+        """`s2mel` for several segments in ONE packed CFM solve (S2Mel.solve_many): segments are (latent [n,D], codes [n],
+        prompt_condition, ref_mel, style) tuples; returns one mel [1,80,floor(1.72 n)] per segment."""
+        items = []
+        for latent, codes, prompt_condition, ref_mel, style in segments:
+            codes = torch.as_tensor(np.asarray(codes), dtype=torch.long, device=self.device).reshape(1, -1)
+            items.append((latent.reshape(1, codes.shape[1], -1), codes, prompt_condition, ref_mel, style))
+        return self.s2mel_model.solve_many(items, n_timesteps=n_timesteps, inference_cfg_rate=inference_cfg_rate, noises=noises)
+
     # ------------------------------------------------------------------ V0-V5
     def vocode(self, mel):
         """bigvgan(mel.float()) then the PCM clamp of infer_v2.py:735-744: returns fp32 [1, T] scaled to +-32767."""

@@ -240,6 +240,159 @@ def reflect_halo_rows(p, T, left, right):
     return p
 
 
+# ---------------------------------------------------------------------------------- packed (ragged) sequences
+# n sequences of unequal length back to back as rows; sequence s owns rows [off[s], off[s+1]).  The GPU forms are the *_varlen HIP
+# entries (csrc/dit_ops.hip, attn_full_x3.hip, gemm_x6.hip) reading a small int32 offsets table uploaded once per solve; the CPU forms
+# are the same arithmetic through row -> sequence index gathers.
+class RowPack:
+    """Host description of a pack: `lens` (>= 1 each), `off` (n + 1 prefix sums).  `tab` int32 on `device` = [off | tile_off | (seq,
+    128-query block) pairs] (the attention's table; its first n + 1 entries are the offsets every row op reads); CPU: `seq` / `pos`,
+    each row's sequence and its position in it."""
+
+    def __init__(self, lens, device):
+        self.lens = [int(t) for t in lens]
+        assert self.lens and min(self.lens) >= 1, self.lens
+        self.n = len(self.lens)
+        self.off = [0]
+        for t in self.lens:
+            self.off.append(self.off[-1] + t)
+        self.rows = self.off[-1]
+        self.device = torch.device(device)
+        tiles = [0]
+        for t in self.lens:
+            tiles.append(tiles[-1] + (t + 63) // 64)
+        self.tiles = tiles[-1]
+        work = [(s, q) for s, t in enumerate(self.lens) for q in range((t + 127) // 128)]
+        self.n_work = len(work)
+        host = torch.tensor(self.off + tiles + [v for w in work for v in w], dtype=torch.int32)
+        self.tab = host.to(self.device)
+        if self.device.type != "cuda":
+            self.seq = torch.repeat_interleave(torch.arange(self.n), torch.tensor(self.lens))
+            self.pos = torch.arange(self.rows) - torch.tensor(self.off[:-1])[self.seq]
+
+    def span(self, s):
+        return self.off[s], self.off[s + 1]
+
+
+def adaln_rmsnorm_packed(x, wb, g, pk, eps=1e-5):
+    """`adaln_rmsnorm` over a pack: x [rows, H], wb [n, 2H]; row r takes the (weight | bias) row of its own sequence."""
+    rows, H = x.shape
+    if x.is_cuda:
+        import ctypes as C
+
+        x, wb = x.contiguous(), wb.contiguous()
+        out = torch.empty_like(x)
+        with torch.cuda.device(x.device):
+            _hip_call("ixtts_adaln_rmsnorm_varlen_f32", x.data_ptr(), wb.data_ptr(), g.data_ptr(), out.data_ptr(), pk.tab.data_ptr(), pk.n, rows, H, C.c_float(eps))
+        return out
+    wbr = wb[pk.seq]
+    return torch.addcmul(wbr[:, H:], wbr[:, :H], F.rms_norm(x, (H,), g, eps))
+
+
+def ln_modulate_packed(x, ss, pk, eps=1e-6):
+    """`ln_modulate` over a pack: x [rows, H], ss [n, 2H] (shift | scale) per sequence."""
+    rows, H = x.shape
+    if x.is_cuda:
+        import ctypes as C
+
+        x, ss = x.contiguous(), ss.contiguous()
+        out = torch.empty_like(x)
+        with torch.cuda.device(x.device):
+            _hip_call("ixtts_ln_modulate_varlen_f32", x.data_ptr(), ss.data_ptr(), out.data_ptr(), pk.tab.data_ptr(), pk.n, rows, H, C.c_float(eps))
+        return out
+    ssr = ss[pk.seq]
+    return F.layer_norm(x, (H,), None, None, eps) * (1 + ssr[:, H:]) + ssr[:, :H]
+
+
+def rope_qk_packed(qkv, fc, pk, head_dim):
+    """RoPE on the q and k thirds of a packed wqkv output qkv [rows, 3H], positions restarting at 0 in each sequence; fc complex
+    [>= max len, head_dim / 2].  Device: in place (returns qkv).  CPU: returns a rotated copy."""
+    rows, H3 = qkv.shape
+    H = H3 // 3
+    if qkv.is_cuda:
+        assert qkv.is_contiguous() and fc.shape[0] >= max(pk.lens)
+        with torch.cuda.device(qkv.device):
+            _hip_call("ixtts_rope_qk_varlen_f32", qkv.data_ptr(), torch.view_as_real(fc).data_ptr(), pk.tab.data_ptr(), pk.n, rows, H, head_dim)
+        return qkv
+    f = fc[pk.pos][:, None, :]  # [rows, 1, hd/2]
+    out = qkv.clone()
+    for j in range(2):
+        xc = torch.view_as_complex(qkv[:, j * H:(j + 1) * H].reshape(rows, H // head_dim, head_dim // 2, 2).contiguous())
+        out[:, j * H:(j + 1) * H] = torch.view_as_real(xc * f).reshape(rows, H)
+    return out
+
+
+def attn_full_packed(q, k, v, pk, scale=None):
+    """softmax(scale q k^T) v per sequence of a pack: q, k, v [rows, h, 64] strided views (d contiguous, one row stride) of device fp32
+    rows; queries of sequence s see the keys of sequence s only (csrc/attn_full_x3.hip, varlen entry).  Returns [rows, h, 64]."""
+    import ctypes as C
+
+    from . import _lib
+
+    rows, Hh, d = q.shape
+    assert d == 64 and q.is_cuda and q.dtype == torch.float32 and k.shape == q.shape and v.shape == q.shape and rows == pk.rows
+    for t in (q, k, v):
+        assert t.stride(2) == 1 and t.stride() == q.stride() and t.stride(0) % 4 == 0 and t.data_ptr() % 16 == 0
+    out = torch.empty(rows, Hh, d, device=q.device, dtype=torch.float32)
+    sc = float(scale if scale is not None else 1.0 / math.sqrt(d))
+    L = _lib.lib()
+    nws = L.ixtts_attn_full_varlen_workspace_bytes(pk.n, Hh, pk.tiles)
+    ws = torch.empty(nws, device=q.device, dtype=torch.uint8)
+    with torch.cuda.device(q.device):
+        rc = L.ixtts_attn_full_varlen_f32(q.data_ptr(), k.data_ptr(), v.data_ptr(), out.data_ptr(), pk.tab.data_ptr(), pk.n, pk.tiles, pk.n_work, Hh, d,
+                                          q.stride(0), q.stride(1), out.stride(0), out.stride(1), C.c_float(sc), ws.data_ptr(), nws, _lib.current_stream_ptr())
+    _lib.check(rc, "ixtts_attn_full_varlen_f32")
+    return out
+
+
+def wn_gate_rows_packed(a, g, off, C_, poff):
+    """`wn_gate_rows` over the WaveNet's padded pack: row r takes the gate biases of the sequence s with poff[s] <= r < poff[s+1]
+    (rows past the end: the last sequence).  poff: a RowPack of the padded lengths."""
+    rows = a.shape[0]
+    if a.is_cuda:
+        a, g = a.contiguous(), g.contiguous()
+        out = torch.empty(rows, C_, device=a.device, dtype=a.dtype)
+        with torch.cuda.device(a.device):
+            _hip_call("ixtts_wn_gate_rows_varlen_f32", a.data_ptr(), g.data_ptr(), out.data_ptr(), rows, C_, poff.tab.data_ptr(), poff.n, g.shape[1], off)
+        return out
+    b = torch.cat([poff.seq, poff.seq.new_full((max(0, rows - poff.rows),), poff.n - 1)])[:rows]
+    x = a + g[b, off:off + 2 * C_]
+    return torch.tanh(x[:, :C_]) * torch.sigmoid(x[:, C_:])
+
+
+def _reflect_src(T, left, right):
+    """Row sources of one sequence's halo under `_pad_reflect` (zero-extension included): (dst rows, src rows or -1 for zero)."""
+    idx = _pad_reflect(torch.arange(1, T + 1, dtype=torch.float64)[None, None], left, right)[0, 0].long() - 1
+    dst = list(range(left)) + list(range(left + T, left + T + right))
+    return dst, [int(idx[i]) + left if int(idx[i]) >= 0 else -1 for i in dst]
+
+
+def reflect_halo_rows_packed(p, poff, left, right):
+    """Refresh, in place, the reflect halo of every sequence of the padded pack p [rows, C] (sequence s = left halo | interior |
+    right halo over rows [poff[s], poff[s+1]))."""
+    if p.is_cuda:
+        assert p.is_contiguous() and min(poff.lens) - left - right > max(left, right)
+        with torch.cuda.device(p.device):
+            _hip_call("ixtts_reflect_halo_rows_varlen_f32", p.data_ptr(), poff.tab.data_ptr(), poff.n, p.shape[1], left, right)
+        return p
+    if not hasattr(poff, "halo"):
+        dst, src, zero = [], [], []
+        for s, L in enumerate(poff.lens):
+            o = poff.off[s]
+            for d_, s_ in zip(*_reflect_src(L - left - right, left, right)):
+                (dst.append(o + d_), src.append(o + s_)) if s_ >= 0 else zero.append(o + d_)
+        poff.halo = (torch.tensor(dst, dtype=torch.long), torch.tensor(src, dtype=torch.long), torch.tensor(zero, dtype=torch.long))
+    dst, src, zero = poff.halo
+    p[dst] = p[src]
+    if zero.numel():
+        p[zero] = 0
+    return p
+
+
+# Frames (sum of segment lengths, prompt frames included) per packed CFM solve (`S2Mel.solve_many`; IXTTS_S2MEL_BATCH_FRAMES): peak
+# activations are ~0.1 MB per frame at production width (DESIGN.md 4.2b), so a pack of this size holds ~1.6 GB
+S2MEL_BATCH_FRAMES = 16384
+
 TUNED_GEMMS = os.path.join(os.path.dirname(os.path.abspath(__file__)), "tunable", "gfx950_s2mel.csv")
 
 
@@ -678,3 +831,214 @@ class S2Mel:
         lens = torch.tensor([cat.shape[1]], device=cat.device, dtype=torch.long)
         mel = self.cfm_inference(cat, lens, ref_mel, style, n_timesteps, inference_cfg_rate, noise)
         return mel[:, :, ref_mel.shape[-1]:]
+
+    # ------------------------------------------------------------------ many segments through ONE CFM solve (packed rows)
+    def _attention_packed(self, qkv, pk):
+        """`_attention` over a pack (qkv [rows, 3H] -> [rows, H]): one varlen HIP attention on the device; per sequence on slices where
+        its limits are not met (head_dim != 64, IXTTS_ATTN_FULL=f32) -- the single-sequence path, same result."""
+        H, nh, hd = self.cfg["hidden_dim"], self.cfg["num_heads"], self.head_dim
+        if qkv.is_cuda and hd == 64 and os.environ.get("IXTTS_ATTN_FULL", "x3") != "f32":
+            rope_qk_packed(qkv, self._rope_cache(max(pk.lens)), pk, hd)
+            v4 = qkv.view(pk.rows, 3, nh, hd)
+            return attn_full_packed(v4[:, 0], v4[:, 1], v4[:, 2], pk).view(pk.rows, H)
+        out = torch.empty(pk.rows, H, device=qkv.device, dtype=qkv.dtype)
+        if qkv.is_cuda:
+            for s in range(pk.n):
+                a, b = pk.span(s)
+                out[a:b] = self._attention(qkv[a:b], 1, b - a, None)
+            return out
+        qk = rope_qk_packed(qkv, self._rope_cache(max(pk.lens)), pk, hd)  # the torch form of the device pass
+        for s in range(pk.n):
+            a, b = pk.span(s)
+            q, k, v = (qk[a:b, :H], qk[a:b, H:2 * H], qkv[a:b, 2 * H:])
+            y = F.scaled_dot_product_attention(*(z.reshape(1, b - a, nh, hd).transpose(1, 2) for z in (q, k, v)), dropout_p=0.0)
+            out[a:b] = y.transpose(1, 2).reshape(b - a, H)
+        return out
+
+    def _transformer_packed(self, x, c, pk):
+        """`_transformer` over a pack: x [rows, H], c [n, H] (one timestep embedding per sequence)."""
+        W, cfg = self.W, self.cfg
+        H, L = cfg["hidden_dim"], cfg["depth"]
+        wb_all = F.linear(c, self.proj_w, self.proj_b).view(pk.n, 2 * L + 1, 2 * H).transpose(0, 1).contiguous()
+        x6 = x.is_cuda and self._x6(self.x6_w13)
+        skips = []
+        for i in range(L):
+            p = f"cfm.estimator.transformer.layers.{i}."
+            if i > L // 2:
+                wa, wb_ = self.skip_w[i]
+                x = F.linear(skips.pop(), wb_, W[p + "skip_in_linear.bias"]).addmm_(x, wa.t())
+            a = adaln_rmsnorm_packed(x, wb_all[2 * i], W[p + "attention_norm.norm.weight"], pk)
+            y = self._attention_packed(F.linear(a, W[p + "attention.wqkv.weight"]), pk)
+            h = torch.addmm(x, y, W[p + "attention.wo.weight"].t()) if 0 < i <= L // 2 else x.addmm_(y, W[p + "attention.wo.weight"].t())
+            f = adaln_rmsnorm_packed(h, wb_all[2 * i + 1], W[p + "ffn_norm.norm.weight"], pk)
+            u = G.pair_linear(f, self.x6_w13[i], G.SWIGLU) if x6 else swiglu(F.linear(f, self.w13[i]))
+            x = h.addmm_(u, W[p + "feed_forward.w2.weight"].t())
+            if i < L // 2:
+                skips.append(x)
+        return adaln_rmsnorm_packed(x, wb_all[2 * L], W["cfm.estimator.transformer.norm.norm.weight"], pk)
+
+    def _wavenet_packed(self, h, g, hp):
+        """`_wavenet_rows` over a pack: h [rows, Hw] (sequences of `hp`), g [n, Hw].  Every sequence sits in one row buffer followed by
+        its own k - 1 halo rows (`hp.padded`: the padded offsets), so each tap is still ONE GEMM over all of them.  Returns the skip sum
+        [rows, Hw] WITHOUT `wn_out_bias`."""
+        W, cfg = self.W, self.cfg
+        Hw, nl, k = cfg["wavenet_hidden"], cfg["wavenet_layers"], cfg["wavenet_kernel"]
+        assert cfg["wavenet_dilation_rate"] == 1
+        p = "cfm.estimator.wavenet."
+        g = F.linear(g, W[p + "cond_layer.conv.conv.weight"][:, :, 0], W[p + "cond_layer.conv.conv.bias"])
+        tot = k - 1
+        right = tot // 2
+        left = tot - right
+        pp, interior = hp.padded, hp.interior
+        P2 = torch.empty(pp.rows, Hw, device=h.device, dtype=h.dtype)
+        P2[interior] = h
+        M = pp.rows - tot
+        centre = P2[left:left + M]
+        out = torch.empty(pp.rows, Hw, device=h.device, dtype=h.dtype)
+        x6 = h.is_cuda and self._x6(self.x6_wn)
+        for i in range(nl):
+            reflect_halo_rows_packed(P2, pp, left, right)
+            if x6:
+                acts = G.pair_linear(G.split(P2), self.x6_wn[i], G.GATE, taps=k, gate=g, gate_off=i * 2 * Hw, seq_off=pp)
+            else:
+                acc = torch.addmm(self.wn_bin[i], P2[:M], self.wn_taps[i][0].t())
+                for j in range(1, k):
+                    acc.addmm_(P2[j:j + M], self.wn_taps[i][j].t())
+                acts = wn_gate_rows_packed(acc, g, i * 2 * Hw, Hw, pp)
+            if i < nl - 1:
+                centre.addmm_(acts, self.wn_r1[i].t())
+            if i == 0:
+                torch.mm(acts, self.wn_r2[i].t(), out=out[:M])
+            else:
+                out[:M].addmm_(acts, self.wn_r2[i].t())
+        return out[interior - left]
+
+    def _halo(self):
+        cfg = self.cfg
+        return sum((cfg["wavenet_kernel"] - 1) * cfg["wavenet_dilation_rate"] ** i for i in range(cfg["wavenet_layers"])) // 2 + 1
+
+    def packable(self, T, Tp, device=None):
+        """Whether a segment of T frames (Tp of them prompt) can join a packed solve on `device`: on the GPU its WaveNet rows must take
+        the row-GEMM form there (more than 2 k frames past the halo, dilation 1) -- a shorter one is solved on its own, as `__call__`."""
+        dev = self.device if device is None else torch.device(device)
+        if dev.type != "cuda":
+            return True
+        cfg = self.cfg
+        Th = T - max(0, Tp - self._halo())
+        return cfg["wavenet_dilation_rate"] == 1 and Th > 2 * cfg["wavenet_kernel"]
+
+    def _cfm_packed(self, segs, n_timesteps, inference_cfg_rate):
+        """The Euler solve of `cfm_inference` for several segments at once.  segs: dicts mu [1,T,content], prompt [1,80,Tp'], style
+        [1,sd], z [1,80,T].  Sequences (rows of every GEMM and row kernel): all conditional ones, then, with CFG, all null ones; x
+        (shared by the two branches) is packed once.  Returns x [1,80,T] per segment."""
+        W, cfg = self.W, self.cfg
+        e = "cfm.estimator."
+        dev = segs[0]["mu"].device
+        C_, H = cfg["in_channels"], cfg["hidden_dim"]
+        n = len(segs)
+        lens = [s["mu"].shape[1] for s in segs]
+        Tps = [min(s["prompt"].shape[-1], T) for s, T in zip(segs, lens)]
+        R = sum(lens)
+        cfg_on = inference_cfg_rate > 0
+        nb = 2 if cfg_on else 1
+        pk = RowPack(lens * nb, dev)
+        xo = pk.off[:n + 1]
+        # x rows [R, C]: the noise with the prompt frames zeroed; the velocities of frames >= Tp are the only ones used
+        x = torch.cat([s["z"][0].t() for s in segs], 0).contiguous()
+        keep = torch.cat([torch.arange(xo[i] + Tps[i], xo[i + 1]) for i in range(n)]).to(dev)
+        pmask = torch.ones(R, 1, device=dev)
+        for i in range(n):
+            pmask[xo[i]:xo[i] + Tps[i]] = 0
+        x.mul_(pmask)
+        # dit_prepare: the (x, t)-independent part of the merge linear, per row
+        prompt_rows = torch.zeros(R, C_, device=dev)
+        for i, s in enumerate(segs):
+            prompt_rows[xo[i]:xo[i] + Tps[i]] = s["prompt"][0, :, :Tps[i]].t()
+        mu = torch.cat([s["mu"][0] for s in segs], 0)
+        style = torch.cat([s["style"].expand(T, -1) for s, T in zip(segs, lens)], 0)
+        rest = torch.cat([prompt_rows, _lin(mu, W, e + "cond_projection"), style], -1)
+        if cfg_on:
+            rest = torch.cat([rest, torch.cat([torch.zeros_like(prompt_rows), _lin(torch.zeros_like(mu), W, e + "cond_projection"), torch.zeros_like(style)], -1)], 0)
+        base = F.linear(rest, self.merge_rest, W[e + "cond_x_merge_linear.bias"])
+        # the WaveNet head: frames [lo, T) of each sequence (lo = Tp - halo), each followed by its k - 1 halo rows
+        halo, k = self._halo(), cfg["wavenet_kernel"]
+        los = [max(0, Tp - halo) for Tp in Tps] * nb
+        head_lens = [L - lo for L, lo in zip(pk.lens, los)]
+        hp = RowPack(head_lens, dev)
+        hp.padded = RowPack([t + k - 1 for t in head_lens], dev)
+        right = (k - 1) // 2
+        left = k - 1 - right
+        hidx = torch.cat([torch.arange(pk.off[s] + los[s], pk.off[s + 1]) for s in range(pk.n)])
+        hp.interior = torch.cat([torch.arange(hp.padded.off[s] + left, hp.padded.off[s] + left + head_lens[s]) for s in range(pk.n)]).to(dev)
+        hrows = hidx.to(dev)  # transformer row of each head row
+        hx = (hidx - torch.tensor(pk.off[:-1]).repeat_interleave(torch.tensor(head_lens)) +
+              torch.tensor(xo[:-1] * nb).repeat_interleave(torch.tensor(head_lens))).to(dev)  # x row of each head row
+        # velocity rows of frames >= Tp: cond half and null half of the head rows
+        hsel = torch.cat([torch.arange(hp.off[s] + Tps[s % n] - los[s], hp.off[s + 1]) for s in range(pk.n)]).to(dev)
+        nkeep = keep.numel()
+        t_span = torch.linspace(0, 1, n_timesteps + 1, device=dev)
+        t = t_span[0]
+        for step in range(1, len(t_span)):
+            dt = t_span[step] - t_span[step - 1]
+            tt = t.expand(pk.n)
+            t1 = self._t_embed(tt, e + "t_embedder")
+            x_in = (base.view(nb, R, H) + F.linear(x, self.merge_x)).view(nb * R, H)
+            x_res = self._transformer_packed(x_in, t1, pk)
+            x_res = x_res.index_select(0, hrows)
+            xt = x.index_select(0, hx)
+            x_res = F.linear(x_res, self.skipl_res, W[e + "skip_linear.bias"]) + F.linear(xt, self.skipl_x)
+            h = _lin(x_res, W, e + "conv1")
+            t2 = self._t_embed(tt, e + "t_embedder2")
+            h = self._wavenet_packed(h, t2, hp) + F.linear(x_res, W[e + "res_projection.weight"], W[e + "res_projection.bias"] + self.wn_out_bias)
+            ss = _lin(F.silu(t1), W, e + "final_layer.adaLN_modulation.1")
+            h = ln_modulate_packed(h, ss, hp)
+            h = _lin(h, W, e + "final_layer.linear")
+            d = F.linear(h.index_select(0, hsel), W[e + "conv2.weight"][:, :, 0], W[e + "conv2.bias"])
+            dphi = (1.0 + inference_cfg_rate) * d[:nkeep] - inference_cfg_rate * d[nkeep:] if cfg_on else d
+            x.index_add_(0, keep, dt * dphi)
+            t = t + dt
+            x.mul_(pmask)  # the prompt frames back to zero (flow_matching.py:112)
+        return [x[xo[i]:xo[i + 1]].t()[None] for i in range(n)]
+
+    @torch.no_grad()
+    def solve_many(self, items, n_timesteps=25, inference_cfg_rate=0.7, noises=None):
+        """`__call__` for several segments: items are (latent, codes, prompt_condition, ref_mel, style) as `__call__` takes them (code
+        lengths = codes.shape[1]); returns one mel [1, 80, frames_i] per item, each equal to its own `__call__` up to fp32
+        reassociation.  The length regulator runs per item; the CFM solves of all items run as ONE Euler loop over packed rows
+        (`_cfm_packed`), at most IXTTS_S2MEL_BATCH_FRAMES frames per pack (larger requests: several packs, grouped by length).  With
+        noises None each item's noise is drawn as n successive `__call__`s would draw it (item order, default generator)."""
+        segs = []
+        for i, (latent, codes, prompt_condition, ref_mel, style) in enumerate(items):
+            code_lens = torch.tensor([codes.shape[-1]], device=codes.device)
+            S = self.vq2emb(codes) + self.gpt_layer(latent)
+            cond = self.length_regulator(S, (code_lens * 1.72).long())
+            mu = torch.cat([prompt_condition, cond], dim=1)
+            T = mu.shape[1]
+            z = torch.randn(1, self.cfg["in_channels"], T, device=mu.device) if noises is None or noises[i] is None else \
+                noises[i].to(mu.device, torch.float32)
+            segs.append(dict(mu=mu, prompt=ref_mel, style=style, z=z, Tp=ref_mel.shape[-1]))
+        xs = [None] * len(segs)
+        budget = max(1, int(os.environ.get("IXTTS_S2MEL_BATCH_FRAMES", str(S2MEL_BATCH_FRAMES))))
+        order = sorted(range(len(segs)), key=lambda i: segs[i]["mu"].shape[1])
+        groups, cur, used = [], [], 0
+        for i in order:
+            T = segs[i]["mu"].shape[1]
+            if not self.packable(T, segs[i]["Tp"], segs[i]["mu"].device):
+                groups.append([i])
+                continue
+            if cur and used + T > budget:
+                groups.append(cur)
+                cur, used = [], 0
+            cur.append(i)
+            used += T
+        if cur:
+            groups.append(cur)
+        for grp in groups:
+            if len(grp) == 1 and not self.packable(segs[grp[0]]["mu"].shape[1], segs[grp[0]]["Tp"], segs[grp[0]]["mu"].device):
+                s = segs[grp[0]]
+                lens = torch.tensor([s["mu"].shape[1]], device=s["mu"].device, dtype=torch.long)
+                xs[grp[0]] = self.cfm_inference(s["mu"], lens, s["prompt"], s["style"], n_timesteps, inference_cfg_rate, s["z"])
+                continue
+            for i, x in zip(grp, self._cfm_packed([segs[i] for i in grp], n_timesteps, inference_cfg_rate)):
+                xs[i] = x
+        return [x[:, :, s["Tp"]:] for x, s in zip(xs, segs)]

@@ -335,6 +335,74 @@ int ixtts_gpt_max_batch(void);
 
 int ixtts_gpt_destroy(ixtts_gpt* h);
 
+/* ------------------------------------------------------------------------------------
+ * Text emotion model -- Qwen3 causal-LM decode, one sequence
+ * replaces: `QwenEmotion.model.generate(...)` (indextts/infer_v2.py:795-906), the arithmetic of
+ *   transformers/models/qwen3/modeling_qwen3.py (embed -> L x {RMSNorm, q|k|v, q_norm/k_norm, RoPE, GQA attention,
+ *   o_proj + residual, RMSNorm, SiLU(gate) * up, down + residual} -> norm -> lm_head).
+ * Weights are f16 (the reference loads torch_dtype="float16") or f32 (parity mode); accumulation, the residual stream,
+ * norm statistics and the KV cache are fp32.  Token selection runs on the device: greedy = argmax (lowest id on a tie);
+ * sampling = temperature -> top-k -> top-p (HF warper order), 1 <= top_k <= IXTTS_QWEN_TOPK_MAX, draws from the
+ * counter-based stream (seed, 0, generated count).
+ * Usage: create -> set_tensor (HF names) for every tensor -> finalize -> prefill(prompt ids) -> generate, or step + read.
+ */
+#define IXTTS_DTYPE_F16 2
+#define IXTTS_QWEN_TOPK_MAX 64
+#define IXTTS_QWEN_MAX_EOS 8
+
+typedef struct ixtts_qwen_cfg {
+  int hidden_size;         /* 1024 (multiple of 512) */
+  int layers;              /* 28 */
+  int heads;               /* 16 query heads */
+  int kv_heads;            /* 8 (heads / kv_heads in {1, 2, 4}) */
+  int head_dim;            /* 128 (the only value built) */
+  int intermediate_size;   /* 3072 (multiple of 512) */
+  int vocab_size;          /* 151936 */
+  float rms_norm_eps;      /* 1e-6 */
+  float rope_theta;        /* 1e6 */
+  int tie_word_embeddings; /* lm_head = embed_tokens when lm_head.weight is not given */
+  int max_seq;             /* KV-cache positions (prompt + generated) */
+  int weight_dtype;        /* IXTTS_DTYPE_F32 | IXTTS_DTYPE_F16 */
+  int n_eos;               /* 1..IXTTS_QWEN_MAX_EOS */
+  int eos_ids[IXTTS_QWEN_MAX_EOS];
+} ixtts_qwen_cfg;
+
+typedef struct ixtts_qwen_sampling {
+  int do_sample;     /* 0: argmax */
+  float temperature; /* > 0 */
+  int top_k;         /* 1..IXTTS_QWEN_TOPK_MAX when do_sample */
+  float top_p;       /* (0, 1] */
+  uint64_t seed;
+} ixtts_qwen_sampling;
+
+typedef struct ixtts_qwen ixtts_qwen;
+
+int ixtts_qwen_create(ixtts_qwen** out, const ixtts_qwen_cfg* cfg);
+/* `name` as in the HF state dict (model.embed_tokens.weight, model.layers.N.self_attn.q_proj.weight, ..., lm_head.weight);
+ * data_host fp32, converted to the engine's weight dtype.  Synchronous. */
+int ixtts_qwen_set_tensor(ixtts_qwen* h, const char* name, const float* data_host, const int64_t* shape, int ndim);
+int ixtts_qwen_finalize(ixtts_qwen* h);
+/* Resets the sequence to the prompt ids_host[0..n) and runs its first n-1 positions through the layers (1 <= n < max_seq),
+ * 4 positions per pass over the weights, the remainder one by one. */
+int ixtts_qwen_prefill(ixtts_qwen* h, const int32_t* ids_host, int n, void* stream);
+/* n_steps decode steps (each: one position through the model, logits, one token).  A finished sequence (EOS drawn, or
+ * the cache full) stays put: further steps change nothing. */
+int ixtts_qwen_step(ixtts_qwen* h, int n_steps, const ixtts_qwen_sampling* sc, void* stream);
+/* Generated ids so far (EOS included when drawn); *finished: 0 running, 1 EOS, 2 cache full.  Synchronises.  Returns
+ * IXTTS_ERR_STATE when a step met non-finite logits (the sequence stopped there without a token). */
+int ixtts_qwen_read(ixtts_qwen* h, int32_t* ids_host, int cap, int* n_ids, int* finished, void* stream);
+/* Steps until EOS, a full cache or max_new tokens, then reads as ixtts_qwen_read.  Synchronous. */
+int ixtts_qwen_generate(ixtts_qwen* h, int max_new, const ixtts_qwen_sampling* sc, int32_t* ids_host, int cap, int* n_ids,
+                        int* finished, void* stream);
+/* Tests: the fp32 logits [vocab_size] of the last decode step; the ids and probabilities its token selection kept
+ * (descending); n draws from those probabilities with stream counters 0..n-1 (the sequence does not move). */
+int ixtts_qwen_read_logits(ixtts_qwen* h, float* logits_host, void* stream);
+int ixtts_qwen_read_kept(ixtts_qwen* h, int32_t* ids_host, float* probs_host, int cap, int* n_kept, void* stream);
+int ixtts_qwen_draw(ixtts_qwen* h, uint64_t seed, int n, int32_t* ids_host, void* stream);
+/* HBM bytes of one decode step at context S (weights + K/V rows). */
+double ixtts_qwen_step_bytes(const ixtts_qwen* h, int S);
+int ixtts_qwen_destroy(ixtts_qwen* h);
+
 #ifdef __cplusplus
 }
 #endif

@@ -39,6 +39,23 @@ class SamplerCfg(C.Structure):
     ]
 
 
+QWEN_TOPK_MAX = 64  # IXTTS_QWEN_TOPK_MAX
+QWEN_MAX_EOS = 8
+
+
+class QwenCfg(C.Structure):
+    _fields_ = [
+        ("hidden_size", C.c_int), ("layers", C.c_int), ("heads", C.c_int), ("kv_heads", C.c_int), ("head_dim", C.c_int),
+        ("intermediate_size", C.c_int), ("vocab_size", C.c_int), ("rms_norm_eps", C.c_float), ("rope_theta", C.c_float),
+        ("tie_word_embeddings", C.c_int), ("max_seq", C.c_int), ("weight_dtype", C.c_int), ("n_eos", C.c_int),
+        ("eos_ids", C.c_int * QWEN_MAX_EOS),
+    ]
+
+
+class QwenSampling(C.Structure):
+    _fields_ = [("do_sample", C.c_int), ("temperature", C.c_float), ("top_k", C.c_int), ("top_p", C.c_float), ("seed", C.c_uint64)]
+
+
 # every symbol include/ixtts_hip.h declares: name -> (restype, argtypes)
 _P = C.c_void_p
 SYMBOLS = {
@@ -106,6 +123,18 @@ SYMBOLS = {
     "ixtts_gpt_step_bytes": (C.c_double, [_P, C.c_int, C.c_int]),
     "ixtts_gpt_max_batch": (C.c_int, []),
     "ixtts_gpt_destroy": (C.c_int, [_P]),
+    "ixtts_qwen_create": (C.c_int, [C.POINTER(_P), C.POINTER(QwenCfg)]),
+    "ixtts_qwen_set_tensor": (C.c_int, [_P, C.c_char_p, _P, C.POINTER(C.c_int64), C.c_int]),
+    "ixtts_qwen_finalize": (C.c_int, [_P]),
+    "ixtts_qwen_prefill": (C.c_int, [_P, _P, C.c_int, _P]),
+    "ixtts_qwen_step": (C.c_int, [_P, C.c_int, C.POINTER(QwenSampling), _P]),
+    "ixtts_qwen_read": (C.c_int, [_P, _P, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int), _P]),
+    "ixtts_qwen_generate": (C.c_int, [_P, C.c_int, C.POINTER(QwenSampling), _P, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int), _P]),
+    "ixtts_qwen_read_logits": (C.c_int, [_P, _P, _P]),
+    "ixtts_qwen_read_kept": (C.c_int, [_P, _P, _P, C.c_int, C.POINTER(C.c_int), _P]),
+    "ixtts_qwen_draw": (C.c_int, [_P, C.c_uint64, C.c_int, _P, _P]),
+    "ixtts_qwen_step_bytes": (C.c_double, [_P, C.c_int]),
+    "ixtts_qwen_destroy": (C.c_int, [_P]),
 }
 
 _lib = None

@@ -135,7 +135,8 @@ class IndexTTS2:
                  use_cuda_kernel=None, use_deepspeed=False, *, glue=None, gpt_state_dict=None, bigvgan_state_dict=None,
                  s2mel_state_dict=None, gpt_cfg=None, bigvgan_cfg=None, cond_cfg=None, s2mel_cfg=None, tokenizer=None,
                  max_seq=2048, max_frames=4096, w2v_bert=None, w2v_stats=None, semantic_codec_state_dict=None, codec_cfg=None,
-                 campplus_state_dict=None, emo_matrix=None, spk_matrix=None, emo_num=None, weight_broadcast=None):
+                 campplus_state_dict=None, emo_matrix=None, spk_matrix=None, emo_num=None, weight_broadcast=None, qwen_emo=None,
+                 qwen_emo_dtype="f16"):
         if device is None:
             if not torch.cuda.is_available():
                 raise RuntimeError("the HIP hot path needs a GPU (no CPU fallback); pass device='cuda:N'")
@@ -290,6 +291,16 @@ class IndexTTS2:
                 logger.info(f"bpe model loaded from: {bpe}")
             except ImportError as e:
                 self.missing_glue.append(f"text normalizer (WeTextProcessing not importable: {e})")
+        # text emotion model (infer_v2.py:82): a given QwenEmotion or directory, else model_dir/<qwen_emo_path> when it exists.
+        # Every worker reads it itself (also under weight_broadcast).  fp16 weights as the reference loads them.
+        self.qwen_emo_dir = os.path.join(model_dir, cfg["qwen_emo_path"]) if cfg.get("qwen_emo_path") else None
+        if qwen_emo is None and self.qwen_emo_dir and os.path.isdir(self.qwen_emo_dir):
+            qwen_emo = self.qwen_emo_dir
+        if qwen_emo is not None and not hasattr(qwen_emo, "inference"):
+            from .qwen_emotion import QwenEmotion
+
+            qwen_emo = QwenEmotion(qwen_emo, dtype=qwen_emo_dtype, device=self.device)
+        self.qwen_emo = qwen_emo
         # prompt caches (infer_v2.py:190-197)
         self.cache_spk_audio_prompt = None
         self.cache_spk = None
@@ -686,8 +697,21 @@ class IndexTTS2:
         glue = self.glue
         speaker_fn = self._stage("speaker", self.prompt.speaker if self.prompt else None)
         emotion_fn = self._stage("emotion", self.prompt.emotion if self.prompt else None)
+        qwen_time = 0.0
         if use_emo_text:
-            raise NotImplementedError("use_emo_text needs the Qwen emotion model (infer_v2.py:481-488), out of scope")
+            # infer_v2.py:475-488: the emotion reference clip gives way, the text (or `text`) becomes the emotion vector
+            if self.qwen_emo is None:
+                raise NotImplementedError(
+                    f"use_emo_text needs the Qwen emotion model: no directory at model_dir/qwen_emo_path "
+                    f"({self.qwen_emo_dir or 'config.yaml names no qwen_emo_path'}); pass qwen_emo=... or provide it")
+            emo_audio_prompt = None
+            if emo_text is None:
+                emo_text = text
+            q0 = time.perf_counter()
+            emo_dict = self.qwen_emo.inference(emo_text)
+            qwen_time = time.perf_counter() - q0
+            logger.info(f"detected emotion vectors from text: {emo_dict}")
+            emo_vector = list(emo_dict.values())
         if emo_vector is not None:
             emo_audio_prompt = None
             scale = max(0.0, min(1.0, emo_alpha))
@@ -733,6 +757,7 @@ class IndexTTS2:
 
         wavs = []
         gpt_gen_time = gpt_forward_time = s2mel_time = bigvgan_time = 0.0
+        gpt_gen_time += qwen_time  # the emotion decode counts as generation time (the reference books it under the total only)
         has_warned = False
         silence = None
         req_emovec = req_cond32 = None

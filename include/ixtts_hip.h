@@ -303,7 +303,7 @@ int ixtts_gpt_beam_force(ixtts_gpt* h, const int32_t* picks_host, int n, void* s
  * `_beam_search` over num_beams sequences.  Here the segments of a request (or of several requests) decode TOGETHER: group g
  * owns slots g*num_beams .. g*num_beams+num_beams-1 and its own scorer state (beam scores, hypotheses, done flag, forced
  * draws), the weights are read once per step for all groups.  An engine of up to 4 slots holds one group (the calls above ==
- * group 0); a wide engine (max_batch 5..16, bf16) holds floor(max_batch / num_beams) of them.  A group's tokens do not depend
+ * group 0); a wide engine (max_batch 5..16, either weight type) holds floor(max_batch / num_beams) of them.  A group's tokens do not depend
  * on which other groups step with it.  Usage per segment: ixtts_gpt_prefill(h, g*num_beams, ...) ->
  * ixtts_gpt_beam_begin_group(h, g, num_beams, rng_stream) (rng_stream selects the group's random stream: 0 is the stream
  * ixtts_gpt_beam_begin uses, so segment i decoded with rng_stream i draws the same numbers in any group) -> repeated

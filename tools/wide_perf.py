@@ -1,5 +1,7 @@
 """Decode step per batch size on the register GEMVs (max_batch 4) and on the wide MFMA engine (max_batch 16): us per step,
-us per sequence, fraction of the HBM roofline.  Run on the GPU box: python tools/wide_perf.py [P] [steps]"""
+us per sequence, fraction of the HBM roofline.  Run on the GPU box: python tools/wide_perf.py [P] [steps] [--dtype bf16|f32]
+(f32: the parity mode -- the register engine at B = 1, 2, 4 and the wide fp32 engine at B = 5, 8, 16)"""
+import argparse
 import json
 import os
 import sys
@@ -10,14 +12,19 @@ import torch
 import voice_tts_amd.weights as WR
 from voice_tts_amd.gpt_engine import GptEngine
 
-P = int(sys.argv[1]) if len(sys.argv) > 1 else 137
-N = int(sys.argv[2]) if len(sys.argv) > 2 else 512
+ap = argparse.ArgumentParser()
+ap.add_argument("P", nargs="?", type=int, default=137)
+ap.add_argument("steps", nargs="?", type=int, default=512)
+ap.add_argument("--dtype", choices=("bf16", "f32"), default="bf16")
+args = ap.parse_args()
+P, N, DT = args.P, args.steps, args.dtype
+WIDE_B = (1, 2, 4, 8, 12, 16) if DT == "bf16" else (5, 8, 16)  # (IXTTS_WIDE=1, small batches on the MFMA GEMVs, is a bf16 A/B switch)
 dev = torch.device("cuda:0")
 W = WR.make_gpt_weights(WR.GPT_CFG, seed=1234)
 emb = (torch.randn(P - 1, 1280, generator=torch.Generator().manual_seed(1)) * 0.5).to(dev)
 out = {}
-for name, mb, batches in (("register", 4, (1, 2, 4)), ("wide", 16, (1, 2, 4, 8, 12, 16))):
-    eng = GptEngine(WR.GPT_CFG, dtype="bf16", max_seq=P + N + 96, max_batch=mb, device=dev).load_state_dict(W)
+for name, mb, batches in (("register", 4, (1, 2, 4)), ("wide", 16, WIDE_B)):
+    eng = GptEngine(WR.GPT_CFG, dtype=DT, max_seq=P + N + 96, max_batch=mb, device=dev).load_state_dict(W)
     for B in batches:
         for b in range(B):
             eng.prefill(b, emb, 0)
@@ -33,4 +40,4 @@ for name, mb, batches in (("register", 4, (1, 2, 4)), ("wide", 16, (1, 2, 4, 8, 
         print(name, B, out[f"{name}_B{B}"], flush=True)
     del eng
     torch.cuda.empty_cache()
-print(json.dumps(out))
+print(json.dumps({"dtype": DT, "P": P, "steps": N, **out}))

@@ -298,33 +298,44 @@ static void launch_sampler(ixtts_gpt* h, int n_active, hipStream_t st) {
 
 
 // ------------------------------------------------------------------------------------ wide engines (gpt_wide.h)
-// max_batch > 4: bf16 only.  Rows per workgroup (RP0 + RP1) make one workgroup per CU at model_dim 1280: 15 / 5 / 16 + 4 / 5 / 16 + 16.
-template <int K, int INP, int EPI, int NW, int RP0, int RP1>
+// max_batch > 4, either weight type.  Rows per workgroup (RP0 + RP1) make one workgroup per CU at model_dim 1280:
+//   bf16 (v_mfma_f32_16x16x32_bf16): 15 / 5 / 16 + 4 / 5 / 16 + 16 for QKV / out-proj / FC / MLP-out / head, 4 waves each;
+//   fp32 (v_mfma_f32_16x16x4_f32):   15 / 5 / 16 + 4 / 5 (8 waves, K walked in 4 phases) / 16 + 16 -- the same split: a row is
+//   twice the bytes, so a workgroup streams twice as much, but 256 workgroups of equal size still balance over 256 CUs and a
+//   finer split would only add rounds.
+template <typename WT, typename KVT, int K, int INP, int EPI, int NW, int RP0, int RP1>
 static int launch_wide(const void* wt, const void* xin, const float* bias, void* out, int N, int B, int slot0, int out_stride, ixtts_gpt* h,
                        void* kc, void* vc, const float* ln_w, const float* ln_b, hipStream_t st) {
   constexpr int NT = RP1 > 0 ? 2 : 1;
-  hipLaunchKernelGGL((gemv_wide_kernel<K, NT, INP, EPI, bf16, NW, RP0, RP1>), dim3(ceil_div(N, RP0 + RP1)), dim3(64 * NW), 0, st,
-                     reinterpret_cast<const bf16*>(wt), xin, bias, out, N, B, slot0, out_stride, h->smax, kc, vc, (const int*)h->cur_len, h->H, ln_w, ln_b);
+  if constexpr (std::is_same<WT, float>::value) {
+    hipLaunchKernelGGL((gemv_wide_f32_kernel<K, NT, INP, EPI, KVT, NW, RP0, RP1>), dim3(ceil_div(N, RP0 + RP1)), dim3(64 * NW), 0, st,
+                       reinterpret_cast<const float*>(wt), xin, bias, out, N, B, slot0, out_stride, h->smax, kc, vc, (const int*)h->cur_len, h->H, ln_w, ln_b);
+  } else {
+    hipLaunchKernelGGL((gemv_wide_kernel<K, NT, INP, EPI, KVT, NW, RP0, RP1>), dim3(ceil_div(N, RP0 + RP1)), dim3(64 * NW), 0, st,
+                       reinterpret_cast<const bf16*>(wt), xin, bias, out, N, B, slot0, out_stride, h->smax, kc, vc, (const int*)h->cur_len, h->H, ln_w, ln_b);
+  }
   return IXTTS_OK;
 }
 
-template <int D>
+template <typename WT, int D>
 static int wide_which(ixtts_gpt* h, int which, int l, int B, int slot0, hipStream_t st) {
+  using KVT = WT;  // the K/V cache has the weights' type
+  constexpr int NW_PR = std::is_same<WT, float>::value ? 8 : 4;  // fp32 MLP-out: K = 4 D of fp32 activations does not fit 4 waves' registers
   const LayerOff& o = h->lo[std::min(l, h->L - 1)];
-  const size_t lstride = (size_t)h->slots * D * h->smax * sizeof(bf16);
+  const size_t lstride = (size_t)h->slots * D * h->smax * sizeof(KVT);
   switch (which) {
     case 0:
-      return launch_wide<D, WIN_LN, EPI_QKV, 4, 15, 0>(A_PTR(o.wqkv), h->h, A_F32(o.bqkv), h->q, 3 * D, B, slot0, D, h, (uint8_t*)h->kc + l * lstride,
-                                                 (uint8_t*)h->vc + l * lstride, nullptr, nullptr, st);
+      return launch_wide<WT, KVT, D, WIN_LN, EPI_QKV, 4, 15, 0>(A_PTR(o.wqkv), h->h, A_F32(o.bqkv), h->q, 3 * D, B, slot0, D, h, (uint8_t*)h->kc + l * lstride,
+                                                         (uint8_t*)h->vc + l * lstride, nullptr, nullptr, st);
     case 1:
-      return launch_wide<D, WIN_PLAIN, EPI_RESID, 4, 5, 0>(A_PTR(o.wo), h->att, A_F32(o.bo), h->h, D, B, slot0, D, h, nullptr, nullptr, nullptr, nullptr, st);
+      return launch_wide<WT, KVT, D, WIN_PLAIN, EPI_RESID, 4, 5, 0>(A_PTR(o.wo), h->att, A_F32(o.bo), h->h, D, B, slot0, D, h, nullptr, nullptr, nullptr, nullptr, st);
     case 2:
-      return launch_wide<D, WIN_LN, EPI_GELU, 4, 16, 4>(A_PTR(o.wfc), h->h, A_F32(o.bfc), h->ff, 4 * D, B, slot0, 4 * D, h, nullptr, nullptr, nullptr, nullptr, st);
+      return launch_wide<WT, KVT, D, WIN_LN, EPI_GELU, 4, 16, 4>(A_PTR(o.wfc), h->h, A_F32(o.bfc), h->ff, 4 * D, B, slot0, 4 * D, h, nullptr, nullptr, nullptr, nullptr, st);
     case 3:
-      return launch_wide<4 * D, WIN_FF, EPI_RESID, 4, 5, 0>(A_PTR(o.wpr), h->ff, A_F32(o.bpr), h->h, D, B, slot0, D, h, nullptr, nullptr, nullptr, nullptr, st);
+      return launch_wide<WT, KVT, 4 * D, WIN_FF, EPI_RESID, NW_PR, 5, 0>(A_PTR(o.wpr), h->ff, A_F32(o.bpr), h->h, D, B, slot0, D, h, nullptr, nullptr, nullptr, nullptr, st);
     case 4:
-      return launch_wide<D, WIN_LN2, EPI_LOGITS, 4, 16, 16>(A_PTR(h->whead), h->h, A_F32(h->bhead), h->logits, h->V, B, slot0, h->V, h, nullptr, nullptr,
-                                                    A_F32(h->lnf_w), A_F32(h->lnf_b), st);
+      return launch_wide<WT, KVT, D, WIN_LN2, EPI_LOGITS, 4, 16, 16>(A_PTR(h->whead), h->h, A_F32(h->bhead), h->logits, h->V, B, slot0, h->V, h, nullptr, nullptr,
+                                                            A_F32(h->lnf_w), A_F32(h->lnf_b), st);
   }
   set_error("wide_which: %d", which);
   return IXTTS_ERR_ARG;
@@ -332,32 +343,41 @@ static int wide_which(ixtts_gpt* h, int which, int l, int B, int slot0, hipStrea
 
 // sampler / prefill leave the token's embedding in h->h; one workgroup per (head, slot) sweeps the whole context (the split-S
 // partials would have to be re-read by every out-proj workgroup: 21 KB per sequence)
-template <int D>
+template <typename WT, int D>
 static int forward_layers_wide(ixtts_gpt* h, int B, int slot0, hipStream_t st) {
-  const size_t lstride = (size_t)h->slots * D * h->smax * sizeof(bf16);
+  using KVT = WT;
+  const size_t lstride = (size_t)h->slots * D * h->smax * sizeof(KVT);
   h->hc = h->h;
   for (int l = 0; l < h->L; ++l) {
-    IX_TRY(wide_which<D>(h, 0, l, B, slot0, st));
-    hipLaunchKernelGGL((attn_decode_kernel<bf16, 8, 4>), dim3(h->H, 1, B), dim3(512), 0, st, h->q, (const void*)((uint8_t*)h->kc + l * lstride),
+    IX_TRY((wide_which<WT, D>(h, 0, l, B, slot0, st)));
+    hipLaunchKernelGGL((attn_decode_kernel<KVT, 8, 4>), dim3(h->H, 1, B), dim3(512), 0, st, h->q, (const void*)((uint8_t*)h->kc + l * lstride),
                        (const void*)((uint8_t*)h->vc + l * lstride), h->cur_len, h->valid_from, h->smax, h->H, slot0, D, h->att, 1 IXTTS_TRACE_ARG);
-    IX_TRY(wide_which<D>(h, 1, l, B, slot0, st));
-    IX_TRY(wide_which<D>(h, 2, l, B, slot0, st));
-    IX_TRY(wide_which<D>(h, 3, l, B, slot0, st));
+    IX_TRY((wide_which<WT, D>(h, 1, l, B, slot0, st)));
+    IX_TRY((wide_which<WT, D>(h, 2, l, B, slot0, st)));
+    IX_TRY((wide_which<WT, D>(h, 3, l, B, slot0, st)));
   }
   IX_HIP(hipGetLastError());
   return IXTTS_OK;
 }
 
+// dispatch a wide launch on (weight dtype, D)
+#define DISPATCH_WIDE(FN, h, ...)                                                                      \
+  do {                                                                                                 \
+    if ((h)->cfg.weight_dtype == IXTTS_DTYPE_F32)                                                      \
+      return (h)->D == 1280 ? FN<float, 1280>(__VA_ARGS__) : FN<float, 128>(__VA_ARGS__);              \
+    return (h)->D == 1280 ? FN<bf16, 1280>(__VA_ARGS__) : FN<bf16, 128>(__VA_ARGS__);                  \
+  } while (0)
+
 static int do_forward_layers(ixtts_gpt* h, int B, int slot0, hipStream_t st) {
-  if (h->wide) return h->D == 1280 ? forward_layers_wide<1280>(h, B, slot0, st) : forward_layers_wide<128>(h, B, slot0, st);
+  if (h->wide) DISPATCH_WIDE(forward_layers_wide, h, h, B, slot0, st);
   DISPATCH(forward_layers, h, B, h, slot0, st);
 }
 static int do_head(ixtts_gpt* h, int B, int slot0, float* norm_out, hipStream_t st) {
-  if (h->wide) return h->D == 1280 ? wide_which<1280>(h, 4, 0, B, slot0, st) : wide_which<128>(h, 4, 0, B, slot0, st);
+  if (h->wide) DISPATCH_WIDE(wide_which, h, h, 4, 0, B, slot0, st);
   DISPATCH(gemv_head, h, B, h, slot0, norm_out, st);
 }
 static int do_gemv_which(ixtts_gpt* h, int which, int l, int B, hipStream_t st) {
-  if (h->wide) return h->D == 1280 ? wide_which<1280>(h, which, l, B, 0, st) : wide_which<128>(h, which, l, B, 0, st);
+  if (h->wide) DISPATCH_WIDE(wide_which, h, h, which, l, B, 0, st);
   switch (which) {
     case 0: DISPATCH(gemv_qkv, h, B, h, l, 0, st);
     case 1: DISPATCH(gemv_out, h, B, h, l, 0, st);
@@ -383,7 +403,6 @@ extern "C" int ixtts_gpt_create(ixtts_gpt** out, const ixtts_gpt_cfg* c) {
   IX_ARG(c->layers > 0 && c->n_mel_codes > 0 && c->n_mel_pos > 2 && c->max_seq > 8, "gpt_create: bad sizes");
   IX_ARG(c->max_batch >= 1 && c->max_batch <= MAXB, "gpt_create: max_batch %d (1..%d)", c->max_batch, MAXB);
   IX_ARG(c->weight_dtype == IXTTS_DTYPE_F32 || c->weight_dtype == IXTTS_DTYPE_BF16, "gpt_create: weight_dtype");
-  IX_ARG(c->max_batch <= MAXB_REG || c->weight_dtype == IXTTS_DTYPE_BF16, "gpt_create: max_batch %d > %d runs on the bf16 matrix cores: needs bf16 weights", c->max_batch, MAXB_REG);
   IX_ARG(c->start_mel_token >= 0 && c->start_mel_token < c->n_mel_codes && c->stop_mel_token >= 0 && c->stop_mel_token < c->n_mel_codes, "gpt_create: start/stop token out of range");
   auto* h = new (std::nothrow) ixtts_gpt();
   if (!h) return IXTTS_ERR_NOMEM;
@@ -809,7 +828,7 @@ extern "C" int ixtts_gpt_decode(ixtts_gpt* h, int n_active, int n_steps, const i
 
 // ------------------------------------------------------------------------------------ beam-sample
 // Group g = the beams of ONE prompt, in slots g*NB .. g*NB+NB-1.  Engines of up to 4 slots hold one group (register GEMVs);
-// wide engines (5..16 slots, bf16) hold floor(max_batch / NB) groups that step together: the text segments of a request, or
+// wide engines (5..16 slots) hold floor(max_batch / NB) groups that step together: the text segments of a request, or
 // of several requests, each with its own scorer state (the reference decodes them one after another, infer_v2.py:616).
 static int beam_begin_impl(ixtts_gpt* h, int g, int num_beams, unsigned long long stream_id, hipStream_t st) {
   IX_ARG(num_beams >= 2 && num_beams <= BEAM_MAX, "gpt_beam_begin: num_beams %d (2..%d)", num_beams, BEAM_MAX);
@@ -904,7 +923,7 @@ static int beam_decode_impl(ixtts_gpt* h, int n_groups, int n_steps, const ixtts
   IX_ARG(h->V <= 1024 * SAMP_PT, "gpt_beam_decode: vocabulary %d exceeds the sampler tile", h->V);
   const int nb = h->num_beams;
   IX_ARG(n_groups >= 1 && n_groups <= MAXG && n_groups * nb <= h->cfg.max_batch, "gpt_beam_decode: %d groups of %d beams exceed max_batch %d", n_groups, nb, h->cfg.max_batch);
-  IX_ARG(n_groups == 1 || h->wide, "gpt_beam_decode: several groups step together on the wide engines only (max_batch > %d, bf16)", MAXB_REG);
+  IX_ARG(n_groups == 1 || h->wide, "gpt_beam_decode: several groups step together on the wide engines only (max_batch > %d)", MAXB_REG);
   int ctx0 = 0, live = 0;
   for (int g = 0; g < n_groups; ++g) {
     if (!h->group_live[g]) continue;  // parked (or never begun: created parked)

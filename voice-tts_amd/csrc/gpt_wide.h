@@ -1,4 +1,5 @@
-// gpt_wide.h -- the decode-step GEMVs for WIDE batches (5..16 sequences stepped together) on the bf16 matrix cores.
+// gpt_wide.h -- the decode-step GEMVs for WIDE batches (5..16 sequences stepped together) on the matrix cores: gemv_wide_kernel for
+// bf16 weights (described first), gemv_wide_f32_kernel for fp32 weights (the parity mode; at the end of the file).
 //
 // The register GEMVs of gpt_kernels.h keep one copy of the activations per sequence in every lane, which stops at 4 sequences.
 // Beyond that the product is a skinny GEMM  D[row][slot] = W[row][:] . X[slot][:]  with the batch on the N side of
@@ -222,6 +223,189 @@ __global__ __launch_bounds__(64 * NW) void gemv_wide_kernel(const bf16* __restri
         reinterpret_cast<float*>(out)[(size_t)eslot * out_stride + n] = pre_res[t] + v;
       } else if constexpr (EPI == EPI_GELU) {
         reinterpret_cast<bf16*>(out)[(size_t)eslot * out_stride + n] = __float2bfloat16(gelu_new_f(v));
+      } else if constexpr (EPI == EPI_LOGITS) {
+        reinterpret_cast<float*>(out)[(size_t)eslot * out_stride + n] = v;
+      } else {  // EPI_QKV: q -> buffer, k / v -> cache at position cur_len[slot]  (K == model_dim here)
+        if (n < K) {
+          reinterpret_cast<float*>(out)[(size_t)eslot * out_stride + n] = v;
+        } else {
+          const int which = n / K, cc = n - which * K;
+          KVT* cache = reinterpret_cast<KVT*>(which == 1 ? kcache : vcache);
+          store_kv(cache + (((size_t)eslot * heads + cc / HD) * smax + pre_pos) * HD + cc % HD, v);
+        }
+      }
+    }
+  }
+}
+
+// ------------------------------------------------------------------------------------------------------------------------
+// The same product for fp32 weights (the parity mode), on v_mfma_f32_16x16x4_f32: exact fp32 products, fp32 sums, no hi + lo
+// split, the ff activations stay fp32.  A k-step is 16 elements: lane (c, g) of wave w supplies, for k-step s = w + NW i,
+//   A: W[row0 + 16 t + c][16 s + 4 g .. +4]   (16 bytes straight from the arena's [N][K] fp32 layout, read once)
+//   B: X[slot c][16 s + 4 g .. +4]            (4 activations of sequence c)
+// and MFMA j of the step takes component j on both sides (MFMA k index g <-> element 4 g + j: any pairing is a valid
+// contraction order as long as A and B agree, and this one is fixed by construction).  The C/D map is the bf16 kernel's.  The
+// staging threads keep their layout with 4-float chunks -- thread (c, q = tid >> 4) loads the float4 chunks q, q + 16, ... of
+// sequence c, (q >> 2) its wave, (q & 3) its g -- so the LayerNorm statistics (seq_sum4 / seq_block_sum) are unchanged and
+// every lane again ends up holding its own B fragments.  Few-row tiles pack 16 / RP k-steps per load as above (one dword per
+// lane per row shift is now one k-element).
+//
+// Registers are the constraint: a sequence's row is K / 16 floats per lane at 4 waves, and so is a full 16-row weight tile.  At
+// K = 4 D (MLP-out, NW = 8) the activations are therefore walked in NPH phases, the next phase's loads in flight under the
+// current phase's MFMAs (they come from L2: the FC launch has just written them); the weights are still all issued up front.
+__device__ __forceinline__ uint4 row_shl4_n(const uint4& v, int n) {  // (n is compile-time after unrolling: folds to one shift)
+  switch (n) {
+    case 0: return v;
+    case 1: return row_shl4<1>(v);
+    case 2: return row_shl4<2>(v);
+    case 3: return row_shl4<3>(v);
+    case 4: return row_shl4<4>(v);
+    case 5: return row_shl4<5>(v);
+    case 6: return row_shl4<6>(v);
+    case 7: return row_shl4<7>(v);
+    case 8: return row_shl4<8>(v);
+    case 9: return row_shl4<9>(v);
+    case 10: return row_shl4<10>(v);
+    case 11: return row_shl4<11>(v);
+    case 12: return row_shl4<12>(v);
+    case 13: return row_shl4<13>(v);
+    case 14: return row_shl4<14>(v);
+    default: return row_shl4<15>(v);
+  }
+}
+
+template <int K, int NT, int INP, int EPI, typename KVT, int NW, int RP0, int RP1>
+__global__ __launch_bounds__(64 * NW) void gemv_wide_f32_kernel(const float* __restrict__ wt, const void* __restrict__ xin, const float* __restrict__ bias, void* out,
+                                                            int N, int B, int slot0, int out_stride, int smax, void* kcache, void* vcache,
+                                                            const int* __restrict__ cur_len, int heads, const float* __restrict__ ln_w,
+                                                            const float* __restrict__ ln_b) {
+  static_assert(K % (16 * NW) == 0, "K is dealt to the waves in 16-element k-steps");
+  static_assert(NW == 4 || INP == WIN_FF, "the in-register staging of the LayerNorm inputs is laid out for 4 waves");
+  constexpr int NI = K / (16 * NW);  // k-steps per wave = 4-float chunks per staging thread
+  constexpr int NPH = (INP == WIN_FF && NI >= 16 && NI % 4 == 0) ? 4 : 1;  // activation phases
+  constexpr int NIP = NI / NPH;
+  constexpr int NPASS = INP == WIN_LN ? 1 : (INP == WIN_LN2 ? 2 : 0);
+  static_assert(RP0 >= 1 && RP0 <= 16 && RP1 >= 0 && RP1 <= 16 && (NT == 2) == (RP1 > 0), "rows per tile");
+  constexpr int KP0 = 16 / RP0, KP1 = RP1 > 0 ? 16 / RP1 : 1;              // k-steps per weight load
+  constexpr int NL0 = (NI + KP0 - 1) / KP0, NL1 = (NI + KP1 - 1) / KP1;      // weight loads per lane
+  constexpr int NLM = NL0 > NL1 ? NL0 : NL1;
+  __shared__ float red[4 * NPASS + 1][4 * WIDE_COLS];
+  __shared__ __attribute__((aligned(16))) float part[NW][NT][64][4];
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int c = lane & 15, g = lane >> 4;
+  const int row0 = blockIdx.x * (RP0 + RP1);
+  const int slot_c = slot0 + min(c, B - 1);  // columns beyond the batch repeat the last sequence (finite, never stored)
+
+  // ---- 1. activations of this lane: chunk (4 wave + g) + 4 NW i of sequence c  ==  k-step wave + NW i, elements 4 g .. 4 g + 3
+  const float* xb = reinterpret_cast<const float*>(xin) + (size_t)slot_c * K + g * 4;
+  float4 x[NPH > 1 ? 2 * NIP : NI];  // (phased: two buffers of NIP chunks)
+  float4 lw[NPASS == 2 ? NI : 1], lb[NPASS == 2 ? NI : 1];
+#pragma unroll
+  for (int i = 0; i < NIP; ++i) {
+    const int k0 = (wave + NW * i) * 16;
+    x[i] = *reinterpret_cast<const float4*>(xb + k0);
+    if constexpr (NPASS == 2) {  // explicit affine of the first norm (ln_f); the second norm's affine is folded into W
+      lw[i] = *reinterpret_cast<const float4*>(ln_w + k0 + g * 4);
+      lb[i] = *reinterpret_cast<const float4*>(ln_b + k0 + g * 4);
+    }
+  }
+  __builtin_amdgcn_sched_barrier(0);
+  // ---- 2. epilogue operands: thread (m = tid >> 4, n = tid & 15) finishes row 16 t + m of sequence n
+  const int em = (tid >> 4) & 15, en = tid & 15;  // (threads 256.. of an 8-wave workgroup mirror 0..255 and store nothing)
+  const int eslot = slot0 + min(en, B - 1);
+  float pre_bias[NT], pre_res[NT];
+  int pre_pos = 0;
+#pragma unroll
+  for (int t = 0; t < NT; ++t) {
+    const int n = min(row0 + (t == 0 ? 0 : RP0) + min(em, (t == 0 ? RP0 : RP1) - 1), N - 1);
+    pre_bias[t] = bias[n];
+    pre_res[t] = 0.f;
+    if constexpr (EPI == EPI_RESID) pre_res[t] = reinterpret_cast<const float*>(out)[(size_t)eslot * out_stride + n];
+  }
+  if constexpr (EPI == EPI_QKV) pre_pos = cur_len[eslot];
+  __builtin_amdgcn_sched_barrier(0);
+  // ---- 3. weight stream: load j of tile t = k-steps j KP .. j KP + KP - 1 of the rows of that tile (rows / packs beyond the
+  // range repeat a valid address; their products land in accumulator rows nobody reads)
+  uint4 a[NT][NLM];
+#pragma unroll
+  for (int t = 0; t < NT; ++t) {
+    const int RP = t == 0 ? RP0 : RP1, KP = t == 0 ? KP0 : KP1, NL = t == 0 ? NL0 : NL1;
+    const int pk = min(c / RP, KP - 1);
+    const float* wrow = wt + (size_t)min(row0 + (t == 0 ? 0 : RP0) + c % RP, N - 1) * K + g * 4;
+#pragma unroll
+    for (int j = 0; j < NL; ++j) a[t][j] = load_w16<false>(wrow + (wave + NW * min(j * KP + pk, NI - 1)) * 16);
+  }
+  __builtin_amdgcn_sched_barrier(0);
+  // ---- 4. LayerNorm of sequence c over its 16 threads (4 lanes in each of the 4 waves), in registers
+#pragma unroll
+  for (int pass = 0; pass < NPASS; ++pass) {
+    float s = 0.f;
+#pragma unroll
+    for (int i = 0; i < NI; ++i) s += (x[i].x + x[i].y) + (x[i].z + x[i].w);
+    const float mean = seq_block_sum(s, red[2 * pass], wave, lane) * (1.0f / K);
+    float q = 0.f;
+#pragma unroll
+    for (int i = 0; i < NI; ++i) {
+      x[i].x -= mean; x[i].y -= mean; x[i].z -= mean; x[i].w -= mean;
+      q = fmaf(x[i].x, x[i].x, q); q = fmaf(x[i].y, x[i].y, q); q = fmaf(x[i].z, x[i].z, q); q = fmaf(x[i].w, x[i].w, q);
+    }
+    const float rstd = 1.0f / sqrtf(seq_block_sum(q, red[2 * pass + 1], wave, lane) * (1.0f / K) + 1e-5f);
+#pragma unroll
+    for (int i = 0; i < NI; ++i) {
+      x[i].x *= rstd; x[i].y *= rstd; x[i].z *= rstd; x[i].w *= rstd;
+      if constexpr (NPASS == 2) {
+        if (pass == 0) {
+          x[i].x = fmaf(x[i].x, lw[i].x, lb[i].x); x[i].y = fmaf(x[i].y, lw[i].y, lb[i].y);
+          x[i].z = fmaf(x[i].z, lw[i].z, lb[i].z); x[i].w = fmaf(x[i].w, lw[i].w, lb[i].w);
+        }
+      }
+    }
+  }
+  // ---- 5. matrix cores: acc[t] (rows 4 g .. 4 g + 3 of tile t, sequence c) += W fragment . activations, 4 MFMAs per k-step
+  wf32x4 acc[NT];
+#pragma unroll
+  for (int t = 0; t < NT; ++t) acc[t] = wf32x4{0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+  for (int ph = 0; ph < NPH; ++ph) {
+    if constexpr (NPH > 1) {  // the next phase's activations, in flight under this phase's MFMAs
+      if (ph + 1 < NPH) {
+#pragma unroll
+        for (int i = 0; i < NIP; ++i) x[((ph + 1) & 1) * NIP + i] = *reinterpret_cast<const float4*>(xb + (wave + NW * ((ph + 1) * NIP + i)) * 16);
+      }
+      __builtin_amdgcn_sched_barrier(0);
+    }
+#pragma unroll
+    for (int ii = 0; ii < NIP; ++ii) {
+      const int i = ph * NIP + ii;
+      const float4 b = x[NPH > 1 ? (ph & 1) * NIP + ii : i];
+#pragma unroll
+      for (int t = 0; t < NT; ++t) {
+        const int KP = t == 0 ? KP0 : KP1;
+        const uint4 raw = row_shl4_n(a[t][i / KP], (i % KP) * (t == 0 ? RP0 : RP1));
+        acc[t] = __builtin_amdgcn_mfma_f32_16x16x4f32(__uint_as_float(raw.x), b.x, acc[t], 0, 0, 0);
+        acc[t] = __builtin_amdgcn_mfma_f32_16x16x4f32(__uint_as_float(raw.y), b.y, acc[t], 0, 0, 0);
+        acc[t] = __builtin_amdgcn_mfma_f32_16x16x4f32(__uint_as_float(raw.z), b.z, acc[t], 0, 0, 0);
+        acc[t] = __builtin_amdgcn_mfma_f32_16x16x4f32(__uint_as_float(raw.w), b.w, acc[t], 0, 0, 0);
+      }
+    }
+    if constexpr (NPH > 1) __builtin_amdgcn_sched_barrier(0);
+  }
+  // ---- 6. the NW K-partials through LDS (fixed order), then the epilogue of (row 16 t + em, sequence en)
+#pragma unroll
+  for (int t = 0; t < NT; ++t) *reinterpret_cast<float4*>(&part[wave][t][lane][0]) = make_float4(acc[t][0], acc[t][1], acc[t][2], acc[t][3]);
+  __syncthreads();
+  const int src_lane = (em >> 2) * 16 + en, src_j = em & 3;  // C/D map: col = lane & 15, row = (lane >> 4) * 4 + j
+#pragma unroll
+  for (int t = 0; t < NT; ++t) {
+    const int n = row0 + (t == 0 ? 0 : RP0) + em;  // accumulator row em of tile t
+    if (tid < 256 && em < (t == 0 ? RP0 : RP1) && n < N && en < B) {
+      float v = (part[0][t][src_lane][src_j] + part[1][t][src_lane][src_j]) + (part[2][t][src_lane][src_j] + part[3][t][src_lane][src_j]);
+      if constexpr (NW == 8) v += (part[4][t][src_lane][src_j] + part[5][t][src_lane][src_j]) + (part[6][t][src_lane][src_j] + part[7][t][src_lane][src_j]);
+      v += pre_bias[t];
+      if constexpr (EPI == EPI_RESID) {
+        reinterpret_cast<float*>(out)[(size_t)eslot * out_stride + n] = pre_res[t] + v;
+      } else if constexpr (EPI == EPI_GELU) {
+        reinterpret_cast<float*>(out)[(size_t)eslot * out_stride + n] = gelu_new_f(v);
       } else if constexpr (EPI == EPI_LOGITS) {
         reinterpret_cast<float*>(out)[(size_t)eslot * out_stride + n] = v;
       } else {  // EPI_QKV: q -> buffer, k / v -> cache at position cur_len[slot]  (K == model_dim here)

@@ -495,10 +495,10 @@ class IndexTTS2:
     # ------------------------------------------------------------------ row N3 at the API level: requests decoded together
     def _many_engine(self, slots):
         """A second decode engine whose slots are shared by the segments of several requests (wide MFMA GEMVs above 4 slots,
-        bf16 only; an fp32 model keeps 4)."""
+        on the bf16 or the fp32 matrix cores by the model's precision)."""
         from . import _lib
 
-        slots = max(1, min(int(slots), _lib.max_batch() if self.use_fp16 else 4))
+        slots = max(1, min(int(slots), _lib.max_batch()))
         if slots not in self._engines:
             # a second engine SHAPE over the same device weights (ixtts_gpt_share_arena): it costs its KV cache only
             eng = GptEngine(self.gpt_cfg, dtype="bf16" if self.use_fp16 else "f32", max_seq=self.gpt.max_seq, max_batch=slots, device=self.device)
@@ -506,14 +506,19 @@ class IndexTTS2:
         return self._engines[slots]
 
     def _beam_group_engine(self, num_beams, n_segments):
-        """The engine several beam groups step together on: wide (5..16 slots on the bf16 matrix cores) when the model runs in
-        bf16 and there is more than one segment to decode, else None (one group at a time on the register engine, as the
-        reference decodes: segment after segment).  `IXTTS_BEAM_GROUPS` caps the groups (0 / 1: off)."""
+        """The engine several beam groups step together on: wide (5..16 slots on the matrix cores, bf16 or fp32 by the model's
+        precision) when there is more than one segment to decode, else None (one group at a time on the register engine, as the
+        reference decodes: segment after segment).  `IXTTS_BEAM_GROUPS` caps the groups (0 / 1: off); a bf16 model defaults to 5,
+        an fp32 model joins the groups only when the variable is set."""
         from . import _lib
 
         cap = int(os.environ.get("IXTTS_BEAM_GROUPS", "5"))
         groups = min(cap, _lib.max_batch() // num_beams, n_segments)
-        if not self.use_fp16 or groups < 2 or groups * num_beams <= 4:
+        # An fp32 model takes this path only when IXTTS_BEAM_GROUPS is set explicitly: the fp32 wide step has no recorded timing
+        # against the register engine yet (DESIGN.md 4.1b), and the second engine's fp32 K/V cache is 8 GB at max_seq 2048.
+        if not self.use_fp16 and "IXTTS_BEAM_GROUPS" not in os.environ:
+            return None
+        if groups < 2 or groups * num_beams <= 4:
             return None
         want = min(cap, _lib.max_batch() // num_beams) * num_beams  # one engine shape per worker, whatever the request's segment count
         eng = self._many_engine(want)
@@ -535,7 +540,7 @@ class IndexTTS2:
         -- and the post-decode stages run per segment as in `infer`.  Each request is a dict with `spk_audio_prompt`, `text` and
         optionally `emo_audio_prompt`, `emo_alpha`, `emo_vector`, `use_random`.  Generation kwargs and defaults are `infer`'s:
         with `num_beams > 1` (the served default, 3) every segment is a beam GROUP and floor(decode_slots / num_beams) groups step
-        together (bf16 engines; an fp32 model decodes group after group); `num_beams=1` samples without beams, one slot per
+        together; `num_beams=1` samples without beams, one slot per
         segment (argmax when `top_k == 1`).  Returns one entry per request: `(22050, int16 [N, 1])`, None (empty text), or the
         EXCEPTION that request raised (bad prompt audio, a code outside the codebook ...) -- one request's failure leaves the
         others of the batch alone."""
@@ -557,7 +562,7 @@ class IndexTTS2:
             if not (2 <= num_beams <= 4 and 1 <= top_k <= 128):
                 raise NotImplementedError("beam-sample on the device: 2 <= num_beams <= 4, 1 <= top_k <= 128")
             groups = max(1, min(int(decode_slots), _lib.max_batch()) // num_beams)
-            eng = self._many_engine(groups * num_beams) if self.use_fp16 and groups * num_beams > 4 else self.gpt
+            eng = self._many_engine(groups * num_beams) if groups * num_beams > 4 else self.gpt
         else:
             eng = self._many_engine(decode_slots)
         start = time.perf_counter()
@@ -782,7 +787,8 @@ class IndexTTS2:
 
         # Without beams the segments are independent sequences: decode them together, the weights are read once per step for
         # all of them (the reference decodes segment after segment, infer_v2.py:616; tokens per segment are the same for
-        # greedy; with sampling each slot draws from its own counter-based stream).  Beam search keeps one segment at a time.
+        # greedy; with sampling each slot draws from its own counter-based stream).  With beams every segment is a beam GROUP and the
+        # groups step together on the wide engine when `_beam_group_engine` gives one; else one segment at a time.
         pre = None
         beam_eng = None
         if num_beams > 1 and len(segments) > 1 and not stream_return and not generation_kwargs.get("logits_processor") and 1 <= top_k <= 128:

@@ -108,12 +108,19 @@ struct GemmX6Params {
 // the back edge.
 // NST LDS stages: the operand copies run NST - 1 steps ahead of the MFMAs.  DBG (developer timing, results meaningless): 1 = no operand
 // copies in the main loop, 2 = no fragment reads / MFMAs, 3 = phase stamps.
-template <int MT, int NT, int NST, int DBG = 0>
+// The epilogue is chosen at compile time: EPI (EPI_*), ACC (EPI_PLAIN: C += ...), SEQ (EPI_GATE: gate row by the sequence table
+// p.gate_seq_off instead of row / rows_per_batch); `run_gemm_x6` dispatches on p.epi / p.accumulate / p.gate_seq_off.
+// PIN: 1 = a step's MFMAs are fenced ahead of its closing wait and barrier (developer A/B, tiles 42 / 43); 0 = the scheduler places
+// them, which measured 1-2 % faster on both production kernels (profiles/r07_notes.md).
+template <int MT, int NT, int NST, int EPI = EPI_PLAIN, int ACC = 0, int SEQ = 0, int DBG = 0, int PIN = 0>
 __global__ __launch_bounds__(256, (NST * (MT + NT) * 6 * 64 * 16 <= 80 * 1024) ? 2 : 1) void gemm_x6_kernel(GemmX6Params p) {
   constexpr int BM = 64 * MT, BN = 64 * NT;
   constexpr int A_UNITS = 6 * BM, W_UNITS = 6 * BN, STAGE = A_UNITS + W_UNITS;
   constexpr int NDMA = (6 * (MT + NT)) / 4;       // LDS-DMA instructions per wave and step
-  static_assert((6 * (MT + NT)) % 4 == 0, "the copies are dealt evenly to the 4 waves");
+  constexpr int NA = (6 * MT) / 4, NW = NDMA - NA;  // of which the first NA copy A pieces and the rest W pieces, in every wave
+  static_assert((6 * MT) % 4 == 0 && (6 * NT) % 4 == 0, "the A pieces and the W pieces are each dealt evenly to the 4 waves");
+  static_assert(EPI == EPI_PLAIN || (ACC == 0 && NT == 2), "pair epilogues: the wave's two 32-column blocks are the two halves");
+  static_assert(EPI == EPI_GATE || SEQ == 0, "the sequence table belongs to the gate epilogue");
   constexpr int D = NST - 1;                      // steps the copies run ahead
   extern __shared__ uint4 smem[];                 // NST stages x [A image [3][2][BM] | W image [3][2][BN]]
 
@@ -126,7 +133,8 @@ __global__ __launch_bounds__(256, (NST * (MT + NT) * 6 * 64 * 16 <= 80 * 1024) ?
   const int m_tile = lin / p.n_tiles, n_tile = lin - m_tile * p.n_tiles;
   const int m0 = m_tile * BM, n0 = n_tile * BN;
 
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int tid = threadIdx.x, lane = tid & 63;
+  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);  // uniform to the compiler too: what depends on it stays in SGPRs
   const int wm = wave >> 1, wn = wave & 1;
   const int l31 = lane & 31, lh = lane >> 5;
 
@@ -139,22 +147,46 @@ __global__ __launch_bounds__(256, (NST * (MT + NT) * 6 * 64 * 16 <= 80 * 1024) ?
       for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
 
   // one step's copies: 6 runs (plane, k-half) of BM + BN units, in pieces of 64 units (one LDS-DMA wave-instruction each)
+  // Piece e = q * 4 + wave of the step's 6 (MT + NT): the A pieces come first and 6 MT is a multiple of 4, so a wave's copies q < NA
+  // are A pieces and the others W pieces.  Step s reads A at k-group s % tap_steps of the planes, rows shifted down by s / tap_steps,
+  // and W at k-group s: both affine in s, so each piece's source (at step 0) and LDS offset are fixed here and a step's copy is that
+  // source plus one running offset, uniform over the wave.
   const uint4* asrc = p.Ap + p.arow0 + m0 + lane;
   const uint4* wsrc = p.Wp + n0 + lane;
-  auto issue = [&](int s, uint4* st) {
-    const int tap = s / p.tap_steps, sa = s - tap * p.tap_steps;  // A: k-group sa of the planes, rows shifted down by `tap`
+  long a_off[NA], w_off[NW];  // units
+  int a_lds[NA], w_lds[NW];
 #pragma unroll
-    for (int q = 0; q < NDMA; ++q) {
-      const int e = q * 4 + wave;  // piece id among the step's 6 (MT + NT)
-      if (e < 6 * MT) {
-        const int run = e / MT, piece = e % MT;
-        __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(asrc + ((long)sa * 6 + run) * p.Mpad + tap + piece * 64),
-                                         (__attribute__((address_space(3))) void*)(st + run * BM + piece * 64), 16, 0, 0);
-      } else {
-        const int e2 = e - 6 * MT, run = e2 / NT, piece = e2 % NT;
-        __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(wsrc + ((long)s * 6 + run) * p.Npad + piece * 64),
-                                         (__attribute__((address_space(3))) void*)(st + A_UNITS + run * BN + piece * 64), 16, 0, 0);
-      }
+  for (int q = 0; q < NA; ++q) {
+    const int e = q * 4 + wave, run = e / MT, piece = e % MT;
+    a_off[q] = run * p.Mpad + piece * 64;
+    a_lds[q] = run * BM + piece * 64;
+  }
+#pragma unroll
+  for (int q = 0; q < NW; ++q) {
+    const int e = q * 4 + wave, run = e / NT, piece = e % NT;
+    w_off[q] = (long)run * p.Npad + piece * 64;
+    w_lds[q] = A_UNITS + run * BN + piece * 64;
+  }
+  const long a_step = 6 * p.Mpad, w_step = 6L * p.Npad;
+  const long a_wrap = 1 - p.tap_steps * a_step;  // after the last k-group of a tap: back to k-group 0, one row down
+  long a_run = 0, w_run = 0;                      // the next step's offsets
+  int a_group = 0;                                // and its k-group within the tap
+  // STATEFUL: the k-th call issues the copies of step k.  The prologue calls it for steps 0 .. D - 1 and main-loop step s for step
+  // s + D, in that order and with none left out (DBG == 1 stops after the prologue).
+  auto issue_next = [&](uint4* st) {
+#pragma unroll
+    for (int q = 0; q < NA; ++q)
+      __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(asrc + (a_off[q] + a_run)),
+                                       (__attribute__((address_space(3))) void*)(st + a_lds[q]), 16, 0, 0);
+#pragma unroll
+    for (int q = 0; q < NW; ++q)
+      __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(wsrc + (w_off[q] + w_run)),
+                                       (__attribute__((address_space(3))) void*)(st + w_lds[q]), 16, 0, 0);
+    a_run += a_step;
+    w_run += w_step;
+    if (++a_group == p.tap_steps) {
+      a_group = 0;
+      a_run += a_wrap;
     }
   };
 
@@ -172,7 +204,7 @@ __global__ __launch_bounds__(256, (NST * (MT + NT) * 6 * 64 * 16 <= 80 * 1024) ?
   };
   static_assert(D >= 1 && D <= 3, "1..3 steps of copies in flight behind the one waited for");
   wg_stamp(0);
-  for (int t = 0; t < D && t < steps; ++t) issue(t, smem + t * STAGE);
+  for (int t = 0; t < D && t < steps; ++t) issue_next(smem + t * STAGE);  // steps 0 .. D - 1
   wait_younger(min(D, steps) - 1);  // step 0's copies (the oldest) have landed
   __builtin_amdgcn_s_barrier();
   asm volatile("" ::: "memory");
@@ -194,7 +226,7 @@ __global__ __launch_bounds__(256, (NST * (MT + NT) * 6 * 64 * 16 <= 80 * 1024) ?
       }
     };
     stamp(0);
-    if (DBG != 1 && s + D < steps) issue(s + D, smem + st_nxt * STAGE);
+    if (DBG != 1 && s + D < steps) issue_next(smem + st_nxt * STAGE);  // step s + D
     stamp(1);
     const unsigned cur_addr = base_addr + (unsigned)(st_cur * STAGE * 16);
     if constexpr (DBG != 2) {
@@ -247,6 +279,9 @@ __global__ __launch_bounds__(256, (NST * (MT + NT) * 6 * 64 * 16 <= 80 * 1024) ?
           acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah, bh, acc[i][j], 0, 0, 0);
         }
       if constexpr (DBG == 3) asm volatile("" ::"v"(acc[0][0][0]), "v"(acc[MT - 1][NT - 1][15]));  // (the stamp below sits behind the last MFMAs' results)
+      // The MFMAs touch registers only, so nothing orders them against the wait below and the scheduler may put the wait and the
+      // barrier in front of some of them.  Fencing them here was timed and lost (the CU's other workgroup keeps the matrix pipe fed).
+      if constexpr (PIN != 0) __builtin_amdgcn_sched_barrier(0);
     }
     stamp(3);
     wait_younger(DBG == 1 ? 0 : max(0, min(D - 1, steps - s - 2)));
@@ -260,11 +295,13 @@ __global__ __launch_bounds__(256, (NST * (MT + NT) * 6 * 64 * 16 <= 80 * 1024) ?
 
   wg_stamp(2);
   // ---- epilogue: register r of a lane = row (r & 3) + 8 (r >> 2) + 4 lh of the 32 x 32 tile, column l31
-  if (p.epi != EPI_PLAIN) {
-    static_assert(NT == 2, "pair epilogues: the wave's two 32-column blocks are the two halves");
+  if constexpr (EPI != EPI_PLAIN) {
     const int oc = (n0 + wn * 64) / 2 + l31;  // output column
     const int nh = p.N >> 1;
     if (oc < nh) {
+      // rows and batch sizes are below 2^31 (a larger rows_per_batch gives batch 0 either way): one 32-bit division per element
+      // where the 64-bit one was some 230 instructions, 32 times per lane
+      const unsigned rpb = (unsigned)min(p.rows_per_batch, (long)0x7fffffff);
       const float ba = p.bias != nullptr ? p.bias[n0 + wn * 64 + l31] : 0.f, bb = p.bias != nullptr ? p.bias[n0 + wn * 64 + 32 + l31] : 0.f;
 #pragma unroll
       for (int i = 0; i < MT; ++i) {
@@ -274,10 +311,12 @@ __global__ __launch_bounds__(256, (NST * (MT + NT) * 6 * 64 * 16 <= 80 * 1024) ?
           const int row = rbase + (r & 3) + 8 * (r >> 2);
           if (row < p.M) {
             float a = acc[i][0][r] + ba, b = acc[i][1][r] + bb, v;
-            if (p.epi == EPI_SWIGLU) {
+            if constexpr (EPI == EPI_SWIGLU) {
               v = a / (1.0f + expf(-a)) * b;  // swiglu_kernel's arithmetic
             } else {
-              const long gb = p.gate_seq_off ? (long)seq_of_row(p.gate_seq_off, p.nbatch, row) : min((long)row / p.rows_per_batch, (long)p.nbatch - 1);
+              long gb;
+              if constexpr (SEQ != 0) gb = (long)seq_of_row(p.gate_seq_off, p.nbatch, row);
+              else gb = min((long)((unsigned)row / rpb), (long)p.nbatch - 1);
               const float* g = p.gate + gb * p.gate_ld;
               a += g[oc];
               b += g[nh + oc];
@@ -303,7 +342,7 @@ __global__ __launch_bounds__(256, (NST * (MT + NT) * 6 * 64 * 16 <= 80 * 1024) ?
         if (col_ok && row < p.M) {
           float* c = p.C + (long)row * p.ldc + col;
           float v = acc[i][j][r] + bv;
-          if (p.accumulate) v += *c;
+          if constexpr (ACC != 0) v += *c;
           *c = v;
         }
       }
@@ -315,7 +354,7 @@ __global__ __launch_bounds__(256, (NST * (MT + NT) * 6 * 64 * 16 <= 80 * 1024) ?
   }
 }
 
-template <int MT, int NT, int NST, int DBG = 0>
+template <int MT, int NT, int NST, int EPI = EPI_PLAIN, int ACC = 0, int SEQ = 0, int DBG = 0, int PIN = 0>
 static int launch_gemm_x6(GemmX6Params p, hipStream_t st) {
   constexpr int BM = 64 * MT, BN = 64 * NT;
   constexpr size_t smem = (size_t)NST * (6 * BM + 6 * BN) * 16;
@@ -326,7 +365,7 @@ static int launch_gemm_x6(GemmX6Params p, hipStream_t st) {
   const int taps = (p.K >> 4) / p.tap_steps;  // the last tap reads taps - 1 rows below the tile
   IX_ARG(p.arow0 + (long)p.m_tiles * BM + taps - 1 <= p.Mpad, "gemm_x6: activation planes hold %ld rows, the %d-row tiles reach row %ld", p.Mpad, BM,
          p.arow0 + (long)p.m_tiles * BM + taps - 1);
-  auto kern = gemm_x6_kernel<MT, NT, NST, DBG>;
+  auto kern = gemm_x6_kernel<MT, NT, NST, EPI, ACC, SEQ, DBG, PIN>;
   static bool done = false;
   if (!done) {
     IX_HIP(hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem));
@@ -335,6 +374,19 @@ static int launch_gemm_x6(GemmX6Params p, hipStream_t st) {
   hipLaunchKernelGGL(kern, dim3(p.m_tiles * p.n_tiles), dim3(256), smem, st, p);
   IX_HIP(hipGetLastError());
   return IXTTS_OK;
+}
+
+// the kernel instantiation for what the tile writes (p.epi, p.accumulate, p.gate_seq_off); PAIR: this tile shape takes the pair epilogues
+template <int MT, int NT, int NST, bool PAIR>
+static int launch_gemm_x6_epilogue(const GemmX6Params& p, hipStream_t st) {
+  if (p.epi == EPI_PLAIN) return p.accumulate ? launch_gemm_x6<MT, NT, NST, EPI_PLAIN, 1>(p, st) : launch_gemm_x6<MT, NT, NST, EPI_PLAIN, 0>(p, st);
+  if constexpr (PAIR) {
+    if (p.epi == EPI_SWIGLU) return launch_gemm_x6<MT, NT, NST, EPI_SWIGLU>(p, st);
+    if (p.epi == EPI_GATE)
+      return p.gate_seq_off ? launch_gemm_x6<MT, NT, NST, EPI_GATE, 0, 1>(p, st) : launch_gemm_x6<MT, NT, NST, EPI_GATE, 0, 0>(p, st);
+  }
+  set_error("gemm_x6: epilogue %d on a tile shape built without it", p.epi);
+  return IXTTS_ERR_ARG;
 }
 
 }  // namespace ixtts
@@ -376,16 +428,25 @@ static int run_gemm_x6(GemmX6Params p, int tile, hipStream_t st) {
   }
   switch (tile) {
     // two workgroups per CU (2 x 73.7 KB of LDS): one's copies, fragment reads and epilogue run under the other's MFMAs
-    case 2: return launch_gemm_x6<4, 2, 2>(p, st);
-    case 3: return launch_gemm_x6<2, 2, 3>(p, st);
-    // one workgroup per CU, copies three steps ahead (A/B timing)
-    case 4: return launch_gemm_x6<4, 2, 4>(p, st);
-    case 5: return launch_gemm_x6<2, 2, 4>(p, st);
+    case 2: return launch_gemm_x6_epilogue<4, 2, 2, true>(p, st);
+    case 3: return launch_gemm_x6_epilogue<2, 2, 3, true>(p, st);
+    // one workgroup per CU, copies three steps ahead (A/B timing; plain epilogue only)
+    case 4: return launch_gemm_x6_epilogue<4, 2, 4, false>(p, st);
+    case 5: return launch_gemm_x6_epilogue<2, 2, 4, false>(p, st);
+  }
+  if (tile >= 12 && (p.epi != EPI_PLAIN || p.accumulate)) {
+    set_error("gemm_x6: the developer variants (tile %d) are built with the plain, overwriting epilogue only", tile);
+    return IXTTS_ERR_ARG;
+  }
+  switch (tile) {
     // developer timing variants (results meaningless)
-    case 12: return launch_gemm_x6<4, 2, 2, 1>(p, st);
-    case 22: return launch_gemm_x6<4, 2, 2, 2>(p, st);
-    case 32: return launch_gemm_x6<4, 2, 2, 3>(p, st);
-    case 33: return launch_gemm_x6<2, 2, 3, 3>(p, st);
+    case 12: return launch_gemm_x6<4, 2, 2, EPI_PLAIN, 0, 0, 1>(p, st);
+    case 22: return launch_gemm_x6<4, 2, 2, EPI_PLAIN, 0, 0, 2>(p, st);
+    case 32: return launch_gemm_x6<4, 2, 2, EPI_PLAIN, 0, 0, 3>(p, st);
+    case 33: return launch_gemm_x6<2, 2, 3, EPI_PLAIN, 0, 0, 3>(p, st);
+    // the loop with a fence between a step's MFMAs and its closing wait (results as tiles 2 / 3; A/B timing of the fence)
+    case 42: return launch_gemm_x6<4, 2, 2, EPI_PLAIN, 0, 0, 0, 1>(p, st);
+    case 43: return launch_gemm_x6<2, 2, 3, EPI_PLAIN, 0, 0, 0, 1>(p, st);
   }
   set_error("gemm_x6: tile %d (0 auto; 2 / 3: 256x128 / 128x128, two workgroups per CU; 4 / 5: the same, one per CU with a 4-stage ring)", tile);
   return IXTTS_ERR_ARG;

@@ -213,6 +213,17 @@ int ixtts_bigvgan_destroy(ixtts_bigvgan* h);
  */
 #define IXTTS_DTYPE_F32 0
 #define IXTTS_DTYPE_BF16 1
+#define IXTTS_DTYPE_F16 2
+/* weight_dtype of the GPT: the type of the five matrices per layer + mel_head in the arena AND of the K/V cache (vectors,
+ * embeddings, the residual stream and every accumulation stay fp32).
+ *   F32   parity mode: bit-exact against the fp32 oracle.
+ *   BF16  throughput mode (what `use_fp16=True` selects by default).
+ *   F16   IEEE half, the precision the reference serves with `use_fp16=True`: same bytes per step as BF16, three more
+ *         mantissa bits.  Weights are rounded to nearest even at finalize; a folded weight beyond +-65504 is never stored
+ *         as inf -- ixtts_gpt_finalize returns IXTTS_ERR_ARG ("fp16 overflow") instead.  Every fp32 -> fp16 conversion of an
+ *         activation or a K/V row saturates at +-65504 (no inf, no NaN).  IXTTS_WIDE=1 applies as it does to BF16;
+ *         IXTTS_MLP=fused is a BF16 kernel and is ignored.
+ * ixtts_gpt_share_arena refuses two engines of different weight_dtype. */
 
 typedef struct ixtts_gpt_cfg {
   int model_dim;       /* 1280 */
@@ -226,7 +237,7 @@ typedef struct ixtts_gpt_cfg {
   int stop_mel_token;  /* 8193 */
   int max_seq;         /* KV-cache capacity per sequence (prompt + generated) */
   int max_batch;       /* concurrent sequences (1 greedy; beams / segment batching later) */
-  int weight_dtype;    /* IXTTS_DTYPE_F32 (parity mode) | IXTTS_DTYPE_BF16 (throughput mode) */
+  int weight_dtype;    /* IXTTS_DTYPE_F32 (parity mode) | IXTTS_DTYPE_BF16 (throughput mode) | IXTTS_DTYPE_F16 (see above) */
 } ixtts_gpt_cfg;
 
 typedef struct ixtts_sampler_cfg {
@@ -346,7 +357,6 @@ int ixtts_gpt_destroy(ixtts_gpt* h);
  * counter-based stream (seed, 0, generated count).
  * Usage: create -> set_tensor (HF names) for every tensor -> finalize -> prefill(prompt ids) -> generate, or step + read.
  */
-#define IXTTS_DTYPE_F16 2
 #define IXTTS_QWEN_TOPK_MAX 64
 #define IXTTS_QWEN_MAX_EOS 8
 

@@ -62,6 +62,29 @@ __device__ __forceinline__ int seq_of_row(const int* __restrict__ off, int n, lo
 __device__ __forceinline__ float lo_bf16(unsigned int w) { return __uint_as_float(w << 16); }
 __device__ __forceinline__ float hi_bf16(unsigned int w) { return __uint_as_float(w & 0xffff0000u); }
 
+// ---- IEEE half (the GPT's third weight / K-V type).  Widening is exact (v_cvt_f32_f16; the high half of a dword is taken
+// with an SDWA word select, so a 16-byte load unpacks in 8 instructions, as the 4 shifts + 4 ands of bf16 do).
+typedef _Float16 f16;
+constexpr float F16_MAX = 65504.0f;
+__device__ __forceinline__ float lo_f16(unsigned int w) { return (float)__builtin_bit_cast(f16, (unsigned short)(w & 0xffffu)); }
+__device__ __forceinline__ float hi_f16(unsigned int w) { return (float)__builtin_bit_cast(f16, (unsigned short)(w >> 16)); }
+// fp32 -> fp16 of an ACTIVATION, round to nearest even, saturating: a finite value never becomes inf (|v| > 65504 stores
+// +-65504), and NaN cannot arise from a finite input
+__device__ __forceinline__ f16 f16_sat(float v) { return (f16)__builtin_fminf(__builtin_fmaxf(v, -F16_MAX), F16_MAX); }
+// 16 bytes -> 8 floats, element 2w in the low half of word w
+template <typename T>
+__device__ __forceinline__ void unpack8(const uint4& r, float (&o)[8]);
+template <>
+__device__ __forceinline__ void unpack8<bf16>(const uint4& r, float (&o)[8]) {
+  o[0] = lo_bf16(r.x); o[1] = hi_bf16(r.x); o[2] = lo_bf16(r.y); o[3] = hi_bf16(r.y);
+  o[4] = lo_bf16(r.z); o[5] = hi_bf16(r.z); o[6] = lo_bf16(r.w); o[7] = hi_bf16(r.w);
+}
+template <>
+__device__ __forceinline__ void unpack8<f16>(const uint4& r, float (&o)[8]) {
+  o[0] = lo_f16(r.x); o[1] = hi_f16(r.x); o[2] = lo_f16(r.y); o[3] = hi_f16(r.y);
+  o[4] = lo_f16(r.z); o[5] = hi_f16(r.z); o[6] = lo_f16(r.w); o[7] = hi_f16(r.w);
+}
+
 // ---- wavefront reductions on DPP (no LDS crossbar): fixed order -> bit-reproducible.
 template <int CTRL, int ROW_MASK, int BANK_MASK>
 __device__ __forceinline__ float dpp_take(float v) {

@@ -74,6 +74,7 @@ struct ixtts_gpt {
   // state
   float *h = nullptr, *q = nullptr, *ff = nullptr, *att = nullptr, *part = nullptr, *logits = nullptr, *rowbuf = nullptr;
   float* stage = nullptr;  // fp32 [N][K] staging of every matrix until finalize folds/converts it
+  unsigned* fold_overflow = nullptr;  // fp16 engines: folded weight elements beyond +-65504, counted by fold_convert_kernel
   size_t stage_floats = 0;
   void *kc = nullptr, *vc = nullptr;
   int *cur_len = nullptr, *gen_count = nullptr, *prompt_len = nullptr, *valid_from = nullptr, *finished = nullptr,

@@ -11,9 +11,9 @@
 // HBM layout (one arena, broadcastable with one RCCL call):
 //   per layer: ln_1 w,b | Wqkv^T [3D][D] | b | Wo^T [D][D] | b | ln_2 w,b | Wfc^T [4D][D] | b | Wpr^T [D][4D] | b
 //   ln_f, final_norm, Whead [V][D], b, mel_embedding [V][D] fp32, mel_pos_embedding [n_pos][D] fp32.
-//   Matrices are stored TRANSPOSED (output row contiguous over K) in fp32 or bf16 so one
+//   Matrices are stored TRANSPOSED (output row contiguous over K) in fp32, bf16 or fp16 so one
 //   wavefront streams whole rows with 16-byte-per-lane loads; vectors stay fp32.
-//   KV cache: [layer][slot][head][max_seq][64] (fp32 in parity mode, bf16 in throughput mode).
+//   KV cache: [layer][slot][head][max_seq][64] in the weights' type (fp32 in parity mode, bf16 in throughput mode, fp16).
 #define IXTTS_ENGINE_TU 1
 #include <type_traits>
 
@@ -290,6 +290,9 @@ static void launch_sampler(ixtts_gpt* h, int n_active, hipStream_t st) {
     if ((h)->cfg.weight_dtype == IXTTS_DTYPE_F32) {                                          \
       if ((h)->D == 1280) { DISPATCH_B(FN, float, float, 1280, B, __VA_ARGS__) }             \
       else { DISPATCH_B(FN, float, float, 128, B, __VA_ARGS__) }                             \
+    } else if ((h)->cfg.weight_dtype == IXTTS_DTYPE_F16) {                                   \
+      if ((h)->D == 1280) { DISPATCH_B(FN, f16, f16, 1280, B, __VA_ARGS__) }                 \
+      else { DISPATCH_B(FN, f16, f16, 128, B, __VA_ARGS__) }                                 \
     } else {                                                                                 \
       if ((h)->D == 1280) { DISPATCH_B(FN, bf16, bf16, 1280, B, __VA_ARGS__) }               \
       else { DISPATCH_B(FN, bf16, bf16, 128, B, __VA_ARGS__) }                               \
@@ -299,7 +302,8 @@ static void launch_sampler(ixtts_gpt* h, int n_active, hipStream_t st) {
 
 // ------------------------------------------------------------------------------------ wide engines (gpt_wide.h)
 // max_batch > 4, either weight type.  Rows per workgroup (RP0 + RP1) make one workgroup per CU at model_dim 1280:
-//   bf16 (v_mfma_f32_16x16x32_bf16): 15 / 5 / 16 + 4 / 5 / 16 + 16 for QKV / out-proj / FC / MLP-out / head, 4 waves each;
+//   bf16 (v_mfma_f32_16x16x32_bf16) and fp16 (v_mfma_f32_16x16x32_f16, the same kernel on the other element type):
+//   15 / 5 / 16 + 4 / 5 / 16 + 16 for QKV / out-proj / FC / MLP-out / head, 4 waves each;
 //   fp32 (v_mfma_f32_16x16x4_f32):   15 / 5 / 16 + 4 / 5 (8 waves, K walked in 4 phases) / 16 + 16 -- the same split: a row is
 //   twice the bytes, so a workgroup streams twice as much, but 256 workgroups of equal size still balance over 256 CUs and a
 //   finer split would only add rounds.
@@ -311,8 +315,8 @@ static int launch_wide(const void* wt, const void* xin, const float* bias, void*
     hipLaunchKernelGGL((gemv_wide_f32_kernel<K, NT, INP, EPI, KVT, NW, RP0, RP1>), dim3(ceil_div(N, RP0 + RP1)), dim3(64 * NW), 0, st,
                        reinterpret_cast<const float*>(wt), xin, bias, out, N, B, slot0, out_stride, h->smax, kc, vc, (const int*)h->cur_len, h->H, ln_w, ln_b);
   } else {
-    hipLaunchKernelGGL((gemv_wide_kernel<K, NT, INP, EPI, KVT, NW, RP0, RP1>), dim3(ceil_div(N, RP0 + RP1)), dim3(64 * NW), 0, st,
-                       reinterpret_cast<const bf16*>(wt), xin, bias, out, N, B, slot0, out_stride, h->smax, kc, vc, (const int*)h->cur_len, h->H, ln_w, ln_b);
+    hipLaunchKernelGGL((gemv_wide_kernel<WT, K, NT, INP, EPI, KVT, NW, RP0, RP1>), dim3(ceil_div(N, RP0 + RP1)), dim3(64 * NW), 0, st,
+                       reinterpret_cast<const WT*>(wt), xin, bias, out, N, B, slot0, out_stride, h->smax, kc, vc, (const int*)h->cur_len, h->H, ln_w, ln_b);
   }
   return IXTTS_OK;
 }
@@ -365,6 +369,8 @@ static int forward_layers_wide(ixtts_gpt* h, int B, int slot0, hipStream_t st) {
   do {                                                                                                 \
     if ((h)->cfg.weight_dtype == IXTTS_DTYPE_F32)                                                      \
       return (h)->D == 1280 ? FN<float, 1280>(__VA_ARGS__) : FN<float, 128>(__VA_ARGS__);              \
+    if ((h)->cfg.weight_dtype == IXTTS_DTYPE_F16)                                                      \
+      return (h)->D == 1280 ? FN<f16, 1280>(__VA_ARGS__) : FN<f16, 128>(__VA_ARGS__);                  \
     return (h)->D == 1280 ? FN<bf16, 1280>(__VA_ARGS__) : FN<bf16, 128>(__VA_ARGS__);                  \
   } while (0)
 
@@ -402,7 +408,8 @@ extern "C" int ixtts_gpt_create(ixtts_gpt** out, const ixtts_gpt_cfg* c) {
   IX_ARG(c->heads * HD == c->model_dim, "gpt_create: head dim must be 64 (heads %d, dim %d)", c->heads, c->model_dim);
   IX_ARG(c->layers > 0 && c->n_mel_codes > 0 && c->n_mel_pos > 2 && c->max_seq > 8, "gpt_create: bad sizes");
   IX_ARG(c->max_batch >= 1 && c->max_batch <= MAXB, "gpt_create: max_batch %d (1..%d)", c->max_batch, MAXB);
-  IX_ARG(c->weight_dtype == IXTTS_DTYPE_F32 || c->weight_dtype == IXTTS_DTYPE_BF16, "gpt_create: weight_dtype");
+  IX_ARG(c->weight_dtype == IXTTS_DTYPE_F32 || c->weight_dtype == IXTTS_DTYPE_BF16 || c->weight_dtype == IXTTS_DTYPE_F16,
+         "gpt_create: weight_dtype %d (IXTTS_DTYPE_F32 | IXTTS_DTYPE_BF16 | IXTTS_DTYPE_F16)", c->weight_dtype);
   IX_ARG(c->start_mel_token >= 0 && c->start_mel_token < c->n_mel_codes && c->stop_mel_token >= 0 && c->stop_mel_token < c->n_mel_codes, "gpt_create: start/stop token out of range");
   auto* h = new (std::nothrow) ixtts_gpt();
   if (!h) return IXTTS_ERR_NOMEM;
@@ -533,7 +540,7 @@ extern "C" int ixtts_gpt_create(ixtts_gpt** out, const ixtts_gpt_cfg* c) {
   if (hipStreamCreateWithFlags(&h->cap_stream, hipStreamNonBlocking) != hipSuccess) return fail("stream");
   if (const char* e = getenv("IXTTS_ATTN")) h->attn_split = strcmp(e, "legacy") != 0;
   h->wide = c->max_batch > MAXB_REG;
-  if (const char* e = getenv("IXTTS_WIDE")) h->wide = h->wide || (strcmp(e, "1") == 0 && c->weight_dtype == IXTTS_DTYPE_BF16);  // A/B: small batches on the MFMA GEMVs
+  if (const char* e = getenv("IXTTS_WIDE")) h->wide = h->wide || (strcmp(e, "1") == 0 && c->weight_dtype != IXTTS_DTYPE_F32);  // A/B: small batches on the MFMA GEMVs (bf16 and fp16)
   if (const char* e = getenv("IXTTS_BEAM_REORDER")) h->beam_every_row = strcmp(e, "full") == 0;
   if (const char* e = getenv("IXTTS_PF_KIB")) h->pf_per = atoi(e);  // IXTTS_PF builds: KiB fetched ahead per consumer wave (0: none)
   if (h->wide) h->attn_split = false;  // one workgroup per (head, slot): see forward_layers_wide
@@ -588,7 +595,7 @@ static int fold_one(ixtts_gpt* h, const char* wname, const float* g, const float
   // staging is [N][K]: Conv1D tensors were registered as [K][N], nn.Linear as [N][K]
   const int N = (int)(t.kind == T_MAT_T ? t.d1 : t.d0), K = (int)(t.kind == T_MAT_T ? t.d0 : t.d1);
   hipLaunchKernelGGL(fold_convert_kernel<WT>, dim3(ceil_div(N, 4)), dim3(256), 0, 0, h->stage + t.stage_off, g, beta, bias,
-                     reinterpret_cast<WT*>(h->arena + dst_off), N, K);
+                     reinterpret_cast<WT*>(h->arena + dst_off), N, K, h->fold_overflow);
   IX_HIP(hipGetLastError());
   return IXTTS_OK;
 }
@@ -612,12 +619,12 @@ static int fold_all(ixtts_gpt* h) {
 
 // The launch fused on the XCD-local hand-off, opt-in: IXTTS_MLP=fused (mlp_fused_kernel: LN2 + c_fc + gelu + c_proj, 315 MB
 // for the per-XCD copy of c_proj; measured -1.7 % per step at B=2 and nothing at B=1, profiles/r01_spikes.md).  It needs
-// bf16 weights at model_dim 1280 and workgroups dealt round-robin over the 8 XCDs -- probed here with HW_REG_XCC_ID;
+// bf16 weights (fp16 engines ignore the switch: the kernel is written on the bf16 unpack) at model_dim 1280 and workgroups dealt round-robin over the 8 XCDs -- probed here with HW_REG_XCC_ID;
 // anything else keeps the split kernels.  Called once the arena holds the final weights.
 static int derive_fused_mlp(ixtts_gpt* h) {
   h->mlp_fused = false;
   static const bool dbg = getenv("IXTTS_DEBUG") != nullptr;
-  if (h->esize != 2 || h->D != MLP_D || h->FF != MLP_FF || h->L < 2 || h->wide) return IXTTS_OK;
+  if (h->cfg.weight_dtype != IXTTS_DTYPE_BF16 || h->D != MLP_D || h->FF != MLP_FF || h->L < 2 || h->wide) return IXTTS_OK;
   const char* m_mlp = getenv("IXTTS_MLP");
   if (!m_mlp || strcmp(m_mlp, "fused")) return IXTTS_OK;
   IX_HIP(hipDeviceSynchronize());  // (a broadcast into the arena may still be in flight on another stream)
@@ -669,8 +676,23 @@ extern "C" int ixtts_gpt_finalize(ixtts_gpt* h) {
       set_error("gpt_finalize: tensor '%s' was not supplied", kv.first.c_str());
       return IXTTS_ERR_STATE;
     }
-  if (h->esize == 4) IX_TRY(fold_all<float>(h));
-  else IX_TRY(fold_all<bf16>(h));
+  if (h->cfg.weight_dtype == IXTTS_DTYPE_F32) {
+    IX_TRY(fold_all<float>(h));
+  } else if (h->cfg.weight_dtype == IXTTS_DTYPE_F16) {
+    // fp16 keeps 5 exponent bits: a folded weight beyond +-65504 has no representation.  The kernel stores the bound (never inf)
+    // and counts; a model that needs the range is refused here rather than served clipped.
+    if (!h->fold_overflow && hipMalloc(&h->fold_overflow, sizeof(unsigned)) != hipSuccess) {
+      set_error("gpt_finalize: allocation failed (overflow counter): %s", hipGetErrorString(hipGetLastError()));
+      return IXTTS_ERR_NOMEM;
+    }
+    IX_HIP(hipMemset(h->fold_overflow, 0, sizeof(unsigned)));
+    IX_TRY(fold_all<f16>(h));
+    unsigned n_over = 0;
+    IX_HIP(hipMemcpy(&n_over, h->fold_overflow, sizeof(unsigned), hipMemcpyDeviceToHost));
+    IX_ARG(n_over == 0, "gpt_finalize: fp16 overflow: %u folded weight element(s) exceed +-65504 (or are not finite); load this model as bf16 or f32", n_over);
+  } else {
+    IX_TRY(fold_all<bf16>(h));
+  }
   hipFree(h->stage);
   h->stage = nullptr;
   h->finalized = true;
@@ -700,7 +722,7 @@ extern "C" int ixtts_gpt_adopt_arena(ixtts_gpt* h) {
 extern "C" int ixtts_gpt_share_arena(ixtts_gpt* h, ixtts_gpt* owner) {
   IX_ARG(h && owner && h != owner, "gpt_share_arena: bad handles");
   IX_ARG(owner->finalized && !owner->arena_borrowed, "gpt_share_arena: the owner must hold finalized weights of its own");
-  IX_ARG(h->D == owner->D && h->L == owner->L && h->H == owner->H && h->V == owner->V && h->esize == owner->esize &&
+  IX_ARG(h->D == owner->D && h->L == owner->L && h->H == owner->H && h->V == owner->V && h->cfg.weight_dtype == owner->cfg.weight_dtype &&
              h->cfg.n_mel_pos == owner->cfg.n_mel_pos && h->arena_bytes == owner->arena_bytes,
          "gpt_share_arena: the two engines differ in shape or weight type");
   IX_HIP(hipDeviceSynchronize());
@@ -1190,7 +1212,7 @@ extern "C" int ixtts_gpt_destroy(ixtts_gpt* h) {
   void* ptrs[] = {h->arena, h->stage, h->kc, h->vc, h->h, h->q, h->ff, h->att, h->part, h->logits, h->rowbuf, h->cur_len, h->gen_count,
                   h->prompt_len, h->valid_from, h->finished, h->forced, h->tokens, h->seen, h->d_samp, h->probs, h->scratch, h->beam_scores, h->hyp_score, h->hyp_worst, h->beam_src, h->hyp_len,
                   h->n_hyp, h->beam_done, h->beam_forced_flag, h->beam_forced, h->hyp_tok, h->beam_cand_v, h->beam_cand_i, h->beam_cand_n, h->beam_lcp, h->beam_stream,
-                  h->rx, h->rxn, h->rq, h->ratt, h->rff, h->h2, h->wprx, h->mlp_part, h->mlp_ctr};
+                  h->rx, h->rxn, h->rq, h->ratt, h->rff, h->h2, h->wprx, h->mlp_part, h->mlp_ctr, h->fold_overflow};
   for (void* p : ptrs)
     if (p) hipFree(p);
   delete h;

@@ -75,7 +75,7 @@ constexpr int NSPLIT_MAX = 8;
 enum { EPI_QKV = 0, EPI_RESID = 1, EPI_GELU = 2, EPI_LOGITS = 3 };
 
 struct GemvArgs {
-  const void* wt;       // [N][K] weights (float or bf16), K contiguous; LN gain pre-folded
+  const void* wt;       // [N][K] weights (float, bf16 or f16), K contiguous; LN gain pre-folded
   const float* bias;    // [N] (LN bias pre-folded)
   int N;
   int slot0;            // first sequence slot
@@ -168,9 +168,15 @@ struct WVec<bf16> {
     w[4] = lo_bf16(v.z); w[5] = hi_bf16(v.z); w[6] = lo_bf16(v.w); w[7] = hi_bf16(v.w);
   }
 };
+template <>
+struct WVec<f16> {
+  static constexpr int VEC = 8;
+  __device__ static __forceinline__ void unpack(const uint4& v, float (&w)[8]) { unpack8<f16>(v, w); }
+};
 
 __device__ __forceinline__ void store_kv(float* p, float v) { *p = v; }
 __device__ __forceinline__ void store_kv(bf16* p, float v) { *p = __float2bfloat16(v); }
+__device__ __forceinline__ void store_kv(f16* p, float v) { *p = f16_sat(v); }  // round to nearest even, +-65504 beyond the range
 
 __device__ __forceinline__ float gelu_new_f(float x) {
   // 0.5*x*(1+tanh(sqrt(2/pi)*(x+0.044715*x^3)))   (transformers_gpt2.py:571-585, ACT2FN["gelu_new"])
@@ -229,6 +235,11 @@ __device__ __forceinline__ void gemv_epilogue(const GemvArgs& a, int lane, int u
 //     LayerNorm statistics once with two block reductions, and hands the normalised rows to the waves through LDS;
 //     IN_ATTN2/4 merge the split-S attention partials in the same staging step;
 //   * the dot products run on packed fp32 math (v_pk_fma_f32: two FMAs per lane per instruction).
+// fp16 weights take the same path: a 16-byte load is widened with 8 v_cvt_f32_f16 (the odd elements through an SDWA word
+// select) where bf16 spends 4 shifts + 4 ands, then the SAME packed FMAs in the same order against the unrounded fp32
+// activations.  (v_dot2_f32_f16 would round the activations to half; v_fma_mix_f32 folds the widening into the FMA but is one
+// FMA per instruction, 8 per load and slot against 8 + 4 B packed ones for B slots: fewer only at B = 1, and the compiler
+// already emits it where the code is a scalar fmaf chain -- gemv_lds_kernel.)
 typedef float f32x2 __attribute__((ext_vector_type(2)));
 
 template <typename WT>
@@ -244,6 +255,14 @@ __device__ __forceinline__ void unpack2<bf16>(const uint4& r, f32x2 (&w)[4]) {
   w[1] = f32x2{lo_bf16(r.y), hi_bf16(r.y)};
   w[2] = f32x2{lo_bf16(r.z), hi_bf16(r.z)};
   w[3] = f32x2{lo_bf16(r.w), hi_bf16(r.w)};
+}
+// fp16 weights: widened exactly (v_cvt_f32_f16), then the same packed fp32 FMAs against the UNROUNDED fp32 activations
+template <>
+__device__ __forceinline__ void unpack2<f16>(const uint4& r, f32x2 (&w)[4]) {
+  w[0] = f32x2{lo_f16(r.x), hi_f16(r.x)};
+  w[1] = f32x2{lo_f16(r.y), hi_f16(r.y)};
+  w[2] = f32x2{lo_f16(r.z), hi_f16(r.z)};
+  w[3] = f32x2{lo_f16(r.w), hi_f16(r.w)};
 }
 
 // sums of s[0..B) over the workgroup's WPB waves, in a fixed order (bit-reproducible); `red` is a private [WPB][B] LDS region
@@ -943,12 +962,13 @@ struct KVLayout {
   static constexpr int LPP = HD / DPL;          // lanes per key position
   static constexpr int PPW = 64 / LPP;          // key positions per wave-instruction
 };
-__device__ __forceinline__ void kv_unpack(const uint4& r, float (&o)[4]) {
-  o[0] = __uint_as_float(r.x); o[1] = __uint_as_float(r.y); o[2] = __uint_as_float(r.z); o[3] = __uint_as_float(r.w);
-}
-__device__ __forceinline__ void kv_unpack(const uint4& r, float (&o)[8]) {
-  o[0] = lo_bf16(r.x); o[1] = hi_bf16(r.x); o[2] = lo_bf16(r.y); o[3] = hi_bf16(r.y);
-  o[4] = lo_bf16(r.z); o[5] = hi_bf16(r.z); o[6] = lo_bf16(r.w); o[7] = hi_bf16(r.w);
+template <typename KVT>
+__device__ __forceinline__ void kv_unpack(const uint4& r, float (&o)[KVLayout<KVT>::DPL]) {
+  if constexpr (sizeof(KVT) == 4) {
+    o[0] = __uint_as_float(r.x); o[1] = __uint_as_float(r.y); o[2] = __uint_as_float(r.z); o[3] = __uint_as_float(r.w);
+  } else {
+    unpack8<KVT>(r, o);
+  }
 }
 
 // Online-softmax state of one lane group over the key positions it owns.
@@ -1003,7 +1023,7 @@ __device__ __forceinline__ void attn_sweep(SoftAcc<KVLayout<KVT>::DPL>& st, cons
       const int p = base + (it * NW + wave) * PPW + pg;
       ok[it] = (p >= p_lo) && (p < p_hi);
       float kv[DPL];
-      kv_unpack(kr[it], kv);
+      kv_unpack<KVT>(kr[it], kv);
       float d = 0.f;
 #pragma unroll
       for (int i = 0; i < DPL; ++i) d = fmaf(qv[i], kv[i], d);
@@ -1023,7 +1043,7 @@ __device__ __forceinline__ void attn_sweep(SoftAcc<KVLayout<KVT>::DPL>& st, cons
       for (int it = 0; it < IT; ++it) {
         const float pw = ok[it] ? expf(s[it] - mn) : 0.f;
         float vv[DPL];
-        kv_unpack(vr[it], vv);
+        kv_unpack<KVT>(vr[it], vv);
         st.l += pw;
         // rows outside the range were read speculatively and may hold anything (NaN/Inf bit patterns): 0 * NaN != 0
 #pragma unroll
@@ -1190,7 +1210,7 @@ __global__ __launch_bounds__(256) void attn_split_kernel(const float* q, const v
   for (int it = 0; it < IT0; ++it) {
     const int p = ((it * NSP + sp) * 4 + wave) * PPW + pg;
     float kv[DPL];
-    kv_unpack(kr[it], kv);
+    kv_unpack<KVT>(kr[it], kv);
     float d = 0.f;
 #pragma unroll
     for (int i = 0; i < DPL; ++i) d = fmaf(qv[i], kv[i], d);
@@ -1212,7 +1232,7 @@ __global__ __launch_bounds__(256) void attn_split_kernel(const float* q, const v
     const bool ok = s[it] > -INFINITY;
     const float pw = ok ? expf(s[it] - M) : 0.f;
     float vv[DPL];
-    kv_unpack(vr[it], vv);
+    kv_unpack<KVT>(vr[it], vv);
     l += pw;
     // rows outside the range were read speculatively and may hold anything (NaN/Inf bit patterns): 0 * NaN != 0
 #pragma unroll
@@ -2011,11 +2031,12 @@ __global__ void pack_transpose_kernel(const float* __restrict__ src, float* __re
 #endif  // IXTTS_ENGINE_TU
 
 // finalize: dst[n][k] = WT(src[n][k] * g[k]) ; bias[n] += sum_k src[n][k] * beta[k]   (g/beta may be null)
-// one wave per output row.
+// one wave per output row.  fp16: round to nearest even; a folded weight beyond +-65504 (or not finite) is stored as
+// +-65504, never as inf, and counted in *overflow -- finalize refuses the model when the count is not zero.
 template <typename WT>
 __global__ __launch_bounds__(256) void fold_convert_kernel(const float* __restrict__ src, const float* __restrict__ g,
                                                             const float* __restrict__ beta, float* __restrict__ bias,
-                                                            WT* __restrict__ dst, int N, int K) {
+                                                            WT* __restrict__ dst, int N, int K, unsigned* __restrict__ overflow) {
   const int n = blockIdx.x * 4 + (threadIdx.x >> 6);
   const int lane = threadIdx.x & 63;
   if (n >= N) return;
@@ -2026,7 +2047,10 @@ __global__ __launch_bounds__(256) void fold_convert_kernel(const float* __restri
     const float wf = g ? w * g[k] : w;
     if (beta) acc = fmaf(w, beta[k], acc);
     if constexpr (sizeof(WT) == 4) dst[(size_t)n * K + k] = wf;
-    else dst[(size_t)n * K + k] = __float2bfloat16(wf);
+    else if constexpr (std::is_same<WT, f16>::value) {
+      if (!(fabsf(wf) <= F16_MAX)) atomicAdd(overflow, 1u);
+      dst[(size_t)n * K + k] = f16_sat(wf);
+    } else dst[(size_t)n * K + k] = __float2bfloat16(wf);
   }
   if (beta) {
     acc = wave_sum(acc);

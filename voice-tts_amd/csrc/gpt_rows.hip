@@ -4,9 +4,10 @@
 // T rows go through the 24 layers together: LayerNorm rows -> MFMA GEMM against the same
 // transposed/folded weight arena the decode GEMVs stream (QKV with KV-cache scatter, out-proj
 // + residual, FC + gelu_new, MLP-out + residual) and a causal row-attention that reads the
-// cache.  fp32 mode uses v_mfma_f32_32x32x2_f32 (exact fp32 fmaf chains, parity mode), bf16
-// mode converts the activation tile to bf16 in the LDS staging pass and uses
-// v_mfma_f32_32x32x16_bf16 with fp32 accumulation.
+// cache.  fp32 mode uses v_mfma_f32_32x32x2_f32 (exact fp32 fmaf chains, parity mode); in the bf16
+// and fp16 modes the producers (LayerNorm, attention, gelu) write rows of the weights' type and the
+// GEMMs run on v_mfma_f32_32x32x16_bf16 / v_mfma_f32_32x32x16_f16 with fp32 accumulation (fp16 rows
+// saturate at +-65504 where they are written).
 //
 // Reference arithmetic: indextts/gpt/transformers_gpt2.py:480-667.
 #include "gpt_engine.h"
@@ -16,6 +17,21 @@ namespace ixtts {
 
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
+typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
+
+// the 32x32x16 MFMA of a 16-bit element type (bf16 | fp16), fp32 accumulation
+template <typename ET>
+struct RowsEl;
+template <>
+struct RowsEl<bf16> {
+  typedef bf16x8 vec8;
+  __device__ static __forceinline__ f32x16 mfma(const vec8& a, const vec8& b, const f32x16& c) { return __builtin_amdgcn_mfma_f32_32x32x16_bf16(a, b, c, 0, 0, 0); }
+};
+template <>
+struct RowsEl<f16> {
+  typedef f16x8 vec8;
+  __device__ static __forceinline__ f32x16 mfma(const vec8& a, const vec8& b, const f32x16& c) { return __builtin_amdgcn_mfma_f32_32x32x16_f16(a, b, c, 0, 0, 0); }
+};
 
 // two fp32 -> packed bf16 pair (round-to-nearest-even, the plain cast lowers to v_cvt_pk_bf16_f32)
 __device__ __forceinline__ unsigned int pack_bf16x2(float a, float b) {
@@ -255,7 +271,7 @@ __global__ __launch_bounds__(256) void gemm_rows_kernel(GemmArgs g) {
     }
 }
 
-// ---- bf16 GEMM of the rows path: C[T][N] = A16[T][K] . Wt[N][K]^T (+ epilogue), tile 128 x 128 x 64, 4 waves (2 x 2),
+// ---- 16-bit GEMM of the rows path (ET = bf16 | f16; written for bf16, fp16 swaps the MFMA and the stores): C[T][N] = A16[T][K] . Wt[N][K]^T (+ epilogue), tile 128 x 128 x 64, 4 waves (2 x 2),
 // wave tile 64 x 64 on v_mfma_f32_32x32x16_bf16.  Both operands are bf16 in global memory (the LayerNorm / attention /
 // gelu producers write bf16 rows), so a k-tile is 32 one-KiB pieces copied global -> LDS by LDS-DMA
 // (global_load_lds_dwordx4: no VGPRs, no ds_write pass) into two LDS buffers: the copy of k-tile i+1 is in flight under the
@@ -284,7 +300,9 @@ constexpr int G16_TILE = 128 * 64 * 2;            // 16 KiB per operand tile
 constexpr int G16_SMEM = G16_NBUF * 2 * G16_TILE; // 64 KiB: two workgroups per CU
 
 template <int EPI, typename KVT>
-__global__ __launch_bounds__(256) void gemm_rows_bf16_kernel(GemmArgs16 g) {
+__global__ __launch_bounds__(256) void gemm_rows_bf16_kernel(GemmArgs16 g) {  // KVT is also the operands' element type
+  using EL = RowsEl<KVT>;
+  typedef typename EL::vec8 vec8;
   constexpr int BM = 128, BN = 128, BK = 64, TILE = G16_TILE, NBUF = G16_NBUF;
   extern __shared__ __attribute__((aligned(1024))) unsigned char smem_raw[];
   unsigned char (*smem)[2][TILE] = reinterpret_cast<unsigned char (*)[2][TILE]>(smem_raw);
@@ -331,21 +349,21 @@ __global__ __launch_bounds__(256) void gemm_rows_bf16_kernel(GemmArgs16 g) {
     const unsigned char* Wt = smem[kt % NBUF][1];
 #pragma unroll
     for (int kk = 0; kk < BK / 16; ++kk) {
-      bf16x8 a[2], b[2];
+      vec8 a[2], b[2];
 #pragma unroll
       for (int mi = 0; mi < 2; ++mi) {
         const int row = wm * 64 + mi * 32 + l31;
-        a[mi] = *reinterpret_cast<const bf16x8*>(At + row * 128 + (((kk * 2 + lh) ^ ((row >> 1) & 7)) << 4));
+        a[mi] = *reinterpret_cast<const vec8*>(At + row * 128 + (((kk * 2 + lh) ^ ((row >> 1) & 7)) << 4));
       }
 #pragma unroll
       for (int j = 0; j < 2; ++j) {
         const int row = wn * 64 + j * 32 + l31;
-        b[j] = *reinterpret_cast<const bf16x8*>(Wt + row * 128 + (((kk * 2 + lh) ^ ((row >> 1) & 7)) << 4));
+        b[j] = *reinterpret_cast<const vec8*>(Wt + row * 128 + (((kk * 2 + lh) ^ ((row >> 1) & 7)) << 4));
       }
 #pragma unroll
       for (int mi = 0; mi < 2; ++mi)
 #pragma unroll
-        for (int j = 0; j < 2; ++j) acc[mi][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[mi], b[j], acc[mi][j], 0, 0, 0);
+        for (int j = 0; j < 2; ++j) acc[mi][j] = EL::mfma(a[mi], b[j], acc[mi][j]);
     }
     __builtin_amdgcn_s_barrier();  // every wave is done with this buffer before the next iteration's copy lands in it
   }
@@ -394,7 +412,7 @@ __global__ __launch_bounds__(256) void gemm_rows_bf16_kernel(GemmArgs16 g) {
           if constexpr (EPI == RE_GELU) {
             // gelu_new(v) = v * sigmoid(2u), u = sqrt(2/pi) (v + 0.044715 v^3): one exp instead of tanhf (the result is rounded to bf16)
             const float u2 = 1.5957691216057308f * (v + 0.044715f * v * v * v);
-            store_kv(reinterpret_cast<bf16*>(g.out) + (size_t)m * g.N + n, v / (1.0f + __expf(-u2)));
+            store_kv(reinterpret_cast<KVT*>(g.out) + (size_t)m * g.N + n, v / (1.0f + __expf(-u2)));
           } else {
             if (n < g.D) {
               reinterpret_cast<float*>(g.out)[(size_t)m * g.D + n] = v;
@@ -460,6 +478,15 @@ __device__ __forceinline__ void load_row16<float>(const float* p, float (&v)[16]
   for (int i = 0; i < 4; ++i) {
     const float4 t = reinterpret_cast<const float4*>(p)[i];
     v[4 * i] = t.x; v[4 * i + 1] = t.y; v[4 * i + 2] = t.z; v[4 * i + 3] = t.w;
+  }
+}
+template <>
+__device__ __forceinline__ void load_row16<f16>(const f16* p, float (&v)[16]) {
+#pragma unroll
+  for (int i = 0; i < 2; ++i) {
+    const uint4 r = reinterpret_cast<const uint4*>(p)[i];
+    v[8 * i] = lo_f16(r.x); v[8 * i + 1] = hi_f16(r.x); v[8 * i + 2] = lo_f16(r.y); v[8 * i + 3] = hi_f16(r.y);
+    v[8 * i + 4] = lo_f16(r.z); v[8 * i + 5] = hi_f16(r.z); v[8 * i + 6] = lo_f16(r.w); v[8 * i + 7] = hi_f16(r.w);
   }
 }
 template <>
@@ -664,18 +691,18 @@ static int forward_rows_t(ixtts_gpt* h, int slot, int T, int pos0, int valid_fro
   return IXTTS_OK;
 }
 
-// bf16 weights: the producers write bf16 rows (into the same workspaces) and the GEMMs are the LDS-DMA kernel
-template <int D>
-static int forward_rows_bf16(ixtts_gpt* h, int slot, int T, int pos0, int valid_from, hipStream_t st) {
-  using KVT = bf16;
+// bf16 / fp16 weights: the producers write rows of the weights' type (into the same workspaces; fp16 rows saturate at
+// +-65504, store_kv) and the GEMMs are the LDS-DMA kernel
+template <typename KVT, int D>
+static int forward_rows_16(ixtts_gpt* h, int slot, int T, int pos0, int valid_from, hipStream_t st) {
   const size_t lstride = (size_t)h->slots * D * h->smax * sizeof(KVT);
   const size_t sstride = (size_t)D * h->smax * sizeof(KVT);
-  bf16* xn16 = reinterpret_cast<bf16*>(h->rxn);
-  bf16* att16 = reinterpret_cast<bf16*>(h->ratt);
-  bf16* ff16 = reinterpret_cast<bf16*>(h->rff);
+  KVT* xn16 = reinterpret_cast<KVT*>(h->rxn);
+  KVT* att16 = reinterpret_cast<KVT*>(h->ratt);
+  KVT* ff16 = reinterpret_cast<KVT*>(h->rff);
   const dim3 blk(256);
   auto grid = [&](int N) { return dim3(ceil_div(N, 128), ceil_div(T, 128)); };
-  static bool attr_done = false;
+  static bool attr_done = false;  // (one flag per element type: the function is a template)
   if (!attr_done) {
     IX_HIP(hipFuncSetAttribute((const void*)gemm_rows_bf16_kernel<RE_QKV, KVT>, hipFuncAttributeMaxDynamicSharedMemorySize, G16_SMEM));
     IX_HIP(hipFuncSetAttribute((const void*)gemm_rows_bf16_kernel<RE_RESID, KVT>, hipFuncAttributeMaxDynamicSharedMemorySize, G16_SMEM));
@@ -686,18 +713,18 @@ static int forward_rows_bf16(ixtts_gpt* h, int slot, int T, int pos0, int valid_
     const LayerOff& o = h->lo[l];
     uint8_t* kc = (uint8_t*)h->kc + l * lstride + slot * sstride;
     uint8_t* vc = (uint8_t*)h->vc + l * lstride + slot * sstride;
-    hipLaunchKernelGGL((ln_rows_kernel<D, bf16>), dim3(ceil_div(T, 4)), blk, 0, st, h->rx, xn16, T);
+    hipLaunchKernelGGL((ln_rows_kernel<D, KVT>), dim3(ceil_div(T, 4)), blk, 0, st, h->rx, xn16, T);
     GemmArgs16 g;
     g.A = reinterpret_cast<const unsigned short*>(xn16); g.wt = reinterpret_cast<const unsigned short*>(A_PTR(o.wqkv)); g.bias = A_F32(o.bqkv);
     g.out = h->rq; g.kcache = kc; g.vcache = vc; g.T = T; g.N = 3 * D; g.K = D; g.pos0 = pos0; g.smax = h->smax; g.D = D;
     hipLaunchKernelGGL((gemm_rows_bf16_kernel<RE_QKV, KVT>), grid(g.N), blk, G16_SMEM, st, g);
     AttnRowsArgs a;
     a.q = h->rq; a.kcache = kc; a.vcache = vc; a.out = att16; a.T = T; a.D = D; a.smax = h->smax; a.pos0 = pos0; a.valid_from = valid_from;
-    launch_attn_rows<KVT, bf16>(h, a, st);
+    launch_attn_rows<KVT, KVT>(h, a, st);
     g.A = reinterpret_cast<const unsigned short*>(att16); g.wt = reinterpret_cast<const unsigned short*>(A_PTR(o.wo)); g.bias = A_F32(o.bo);
     g.out = h->rx; g.N = D; g.K = D;
     hipLaunchKernelGGL((gemm_rows_bf16_kernel<RE_RESID, KVT>), grid(g.N), blk, G16_SMEM, st, g);
-    hipLaunchKernelGGL((ln_rows_kernel<D, bf16>), dim3(ceil_div(T, 4)), blk, 0, st, h->rx, xn16, T);
+    hipLaunchKernelGGL((ln_rows_kernel<D, KVT>), dim3(ceil_div(T, 4)), blk, 0, st, h->rx, xn16, T);
     g.A = reinterpret_cast<const unsigned short*>(xn16); g.wt = reinterpret_cast<const unsigned short*>(A_PTR(o.wfc)); g.bias = A_F32(o.bfc);
     g.out = ff16; g.N = 4 * D; g.K = D;
     hipLaunchKernelGGL((gemm_rows_bf16_kernel<RE_GELU, KVT>), grid(g.N), blk, G16_SMEM, st, g);
@@ -715,7 +742,9 @@ int forward_rows(ixtts_gpt* h, int slot, int T, int pos0, int valid_from, hipStr
     return h->D == 1280 ? forward_rows_t<float, float, 1280>(h, slot, T, pos0, valid_from, st)
                         : forward_rows_t<float, float, 128>(h, slot, T, pos0, valid_from, st);
   }
-  return h->D == 1280 ? forward_rows_bf16<1280>(h, slot, T, pos0, valid_from, st) : forward_rows_bf16<128>(h, slot, T, pos0, valid_from, st);
+  if (h->cfg.weight_dtype == IXTTS_DTYPE_F16)
+    return h->D == 1280 ? forward_rows_16<f16, 1280>(h, slot, T, pos0, valid_from, st) : forward_rows_16<f16, 128>(h, slot, T, pos0, valid_from, st);
+  return h->D == 1280 ? forward_rows_16<bf16, 1280>(h, slot, T, pos0, valid_from, st) : forward_rows_16<bf16, 128>(h, slot, T, pos0, valid_from, st);
 }
 
 int final_norm_rows(ixtts_gpt* h, const float* x, float* y, int T, hipStream_t st) {

@@ -1,5 +1,6 @@
 // gpt_wide.h -- the decode-step GEMVs for WIDE batches (5..16 sequences stepped together) on the matrix cores: gemv_wide_kernel for
-// bf16 weights (described first), gemv_wide_f32_kernel for fp32 weights (the parity mode; at the end of the file).
+// bf16 weights (described first) and, as a second instantiation of the same template, fp16 weights (WideEl<f16>:
+// v_mfma_f32_16x16x32_f16, same lane maps, same row splits); gemv_wide_f32_kernel for fp32 weights (the parity mode; at the end of the file).
 //
 // The register GEMVs of gpt_kernels.h keep one copy of the activations per sequence in every lane, which stops at 4 sequences.
 // Beyond that the product is a skinny GEMM  D[row][slot] = W[row][:] . X[slot][:]  with the batch on the N side of
@@ -30,7 +31,40 @@
 namespace ixtts {
 
 typedef __bf16 wbf16x8 __attribute__((ext_vector_type(8)));
+typedef _Float16 wf16x8 __attribute__((ext_vector_type(8)));
 typedef float wf32x4 __attribute__((ext_vector_type(4)));
+
+// The 16-bit element type of a wide launch: its 8-vector, its 16x16x32 MFMA, and the hi + lo split of an fp32 activation.
+//   bf16: x = bf16(x) + bf16(x - bf16(x)), both parts into ONE accumulator.
+//   fp16: xc = clamp(x, +-65504), hi = f16(xc), lo = f16(2^11 (xc - hi)), the lo products into a SECOND accumulator that is folded in as 2^-11 acc_lo at the
+//   end.  fp16 has 5 exponent bits: an unscaled remainder of an |x| < 2^-3 would be a subnormal half and lose bits (or be
+//   flushed); scaled by 2^11 it is a normal number whenever x itself is, so hi + lo carries ~22 significant bits of x at every
+//   magnitude the LayerNorm output takes.  The activation is clamped to +-65504 before it is split: no inf, no NaN, at any input.
+template <typename ET>
+struct WideEl;
+template <>
+struct WideEl<bf16> {
+  typedef wbf16x8 vec8;
+  static constexpr bool LO_SCALED = false;
+  __device__ static __forceinline__ void split(float x, vec8& hi, vec8& lo, int j) {
+    hi[j] = (__bf16)x;
+    lo[j] = (__bf16)(x - (float)hi[j]);
+  }
+  __device__ static __forceinline__ wf32x4 mfma(const vec8& a, const vec8& b, const wf32x4& c) { return __builtin_amdgcn_mfma_f32_16x16x32_bf16(a, b, c, 0, 0, 0); }
+};
+template <>
+struct WideEl<f16> {
+  typedef wf16x8 vec8;
+  static constexpr bool LO_SCALED = true;
+  static constexpr float LO_SCALE = 2048.0f, LO_INV = 1.0f / 2048.0f;
+  __device__ static __forceinline__ void split(float x, vec8& hi, vec8& lo, int j) {
+    // one clamp serves both parts: the remainder of the CLAMPED value is at most half an ulp of hi (<= 16), 32768 after scaling
+    const float xc = __builtin_fminf(__builtin_fmaxf(x, -F16_MAX), F16_MAX);
+    hi[j] = (f16)xc;
+    lo[j] = (f16)((xc - (float)hi[j]) * LO_SCALE);
+  }
+  __device__ static __forceinline__ wf32x4 mfma(const vec8& a, const vec8& b, const wf32x4& c) { return __builtin_amdgcn_mfma_f32_16x16x32_f16(a, b, c, 0, 0, 0); }
+};
 
 enum { WIN_LN = 0, WIN_LN2 = 1, WIN_PLAIN = 2, WIN_FF = 3 };
 constexpr int WIDE_COLS = 16;  // sequence slots a wide launch can carry (the N of the MFMA)
@@ -67,8 +101,8 @@ __device__ __forceinline__ uint4 row_shl4(const uint4& v) {
 // with few rows would waste most of every 16-row weight load (5 rows x 64 B per wave-instruction instead of 1 KiB), so its
 // loads are PACKED: 16 / RP k-steps per instruction, lane (m, g) fetching row m % RP of k-step pack m / RP, and the fragment of
 // pack p is moved into place with a DPP row shift (4 v_mov_dpp) when its MFMA is issued.
-template <int K, int NT, int INP, int EPI, typename KVT, int NW, int RP0, int RP1>
-__global__ __launch_bounds__(64 * NW) void gemv_wide_kernel(const bf16* __restrict__ wt, const void* __restrict__ xin, const float* __restrict__ bias, void* out,
+template <typename ET, int K, int NT, int INP, int EPI, typename KVT, int NW, int RP0, int RP1>
+__global__ __launch_bounds__(64 * NW) void gemv_wide_kernel(const ET* __restrict__ wt, const void* __restrict__ xin, const float* __restrict__ bias, void* out,
                                                         int N, int B, int slot0, int out_stride, int smax, void* kcache, void* vcache,
                                                         const int* __restrict__ cur_len, int heads, const float* __restrict__ ln_w,
                                                         const float* __restrict__ ln_b) {
@@ -92,7 +126,7 @@ __global__ __launch_bounds__(64 * NW) void gemv_wide_kernel(const bf16* __restri
   float lw[NPASS == 2 ? NI : 1][8], lb[NPASS == 2 ? NI : 1][8];
   uint4 braw[INP == WIN_FF ? NI : 1];
   if constexpr (INP == WIN_FF) {
-    const bf16* xb = reinterpret_cast<const bf16*>(xin) + (size_t)slot_c * K + g * 8;
+    const ET* xb = reinterpret_cast<const ET*>(xin) + (size_t)slot_c * K + g * 8;
 #pragma unroll
     for (int i = 0; i < NI; ++i) braw[i] = *reinterpret_cast<const uint4*>(xb + (wave + NW * i) * 32);
   } else {
@@ -132,7 +166,7 @@ __global__ __launch_bounds__(64 * NW) void gemv_wide_kernel(const bf16* __restri
   for (int t = 0; t < NT; ++t) {
     const int RP = t == 0 ? RP0 : RP1, KP = t == 0 ? KP0 : KP1, NL = t == 0 ? NL0 : NL1;
     const int pk = min(c / RP, KP - 1);
-    const bf16* wrow = wt + (size_t)min(row0 + (t == 0 ? 0 : RP0) + c % RP, N - 1) * K + g * 8;
+    const ET* wrow = wt + (size_t)min(row0 + (t == 0 ? 0 : RP0) + c % RP, N - 1) * K + g * 8;
 #pragma unroll
     for (int j = 0; j < NL; ++j) a[t][j] = load_w16<false>(wrow + (wave + NW * min(j * KP + pk, NI - 1)) * 32);
   }
@@ -162,20 +196,24 @@ __global__ __launch_bounds__(64 * NW) void gemv_wide_kernel(const bf16* __restri
       }
   }
   // ---- 5. matrix cores: acc[t] (rows 4 g .. 4 g + 3 of tile t, sequence c) += W fragment . (hi + lo) activations
-  wf32x4 acc[NT];
+  using EL = WideEl<ET>;
+  typedef typename EL::vec8 vec8;
+  constexpr bool LO2 = EL::LO_SCALED && INP != WIN_FF;  // the lo products have an accumulator of their own
+  wf32x4 acc[NT], accl[LO2 ? NT : 1];
 #pragma unroll
   for (int t = 0; t < NT; ++t) acc[t] = wf32x4{0.f, 0.f, 0.f, 0.f};
+  if constexpr (LO2) {
+#pragma unroll
+    for (int t = 0; t < NT; ++t) accl[t] = wf32x4{0.f, 0.f, 0.f, 0.f};
+  }
 #pragma unroll
   for (int i = 0; i < NI; ++i) {
-    wbf16x8 bh, bl;
+    vec8 bh, bl;
     if constexpr (INP == WIN_FF) {
-      bh = __builtin_bit_cast(wbf16x8, braw[i]);
+      bh = __builtin_bit_cast(vec8, braw[i]);
     } else {
 #pragma unroll
-      for (int j = 0; j < 8; ++j) {
-        bh[j] = (__bf16)x[i][j];
-        bl[j] = (__bf16)(x[i][j] - (float)bh[j]);
-      }
+      for (int j = 0; j < 8; ++j) EL::split(x[i][j], bh, bl, j);
     }
 #pragma unroll
     for (int t = 0; t < NT; ++t) {
@@ -202,10 +240,17 @@ __global__ __launch_bounds__(64 * NW) void gemv_wide_kernel(const bf16* __restri
         case 14: raw = row_shl4<14>(a[t][i / KP]); break;
         default: raw = row_shl4<15>(a[t][i / KP]); break;
       }
-      const wbf16x8 af = __builtin_bit_cast(wbf16x8, raw);
-      acc[t] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(af, bh, acc[t], 0, 0, 0);
-      if constexpr (INP != WIN_FF) acc[t] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(af, bl, acc[t], 0, 0, 0);
+      const vec8 af = __builtin_bit_cast(vec8, raw);
+      acc[t] = EL::mfma(af, bh, acc[t]);
+      if constexpr (LO2) accl[t] = EL::mfma(af, bl, accl[t]);
+      else if constexpr (INP != WIN_FF) acc[t] = EL::mfma(af, bl, acc[t]);
     }
+  }
+  if constexpr (LO2) {
+#pragma unroll
+    for (int t = 0; t < NT; ++t)
+#pragma unroll
+      for (int j = 0; j < 4; ++j) acc[t][j] = fmaf(accl[t][j], WideEl<f16>::LO_INV, acc[t][j]);
   }
   // ---- 6. the 4 K-partials through LDS (fixed order), then the epilogue of (row 16 t + em, sequence en)
 #pragma unroll
@@ -222,7 +267,7 @@ __global__ __launch_bounds__(64 * NW) void gemv_wide_kernel(const bf16* __restri
       if constexpr (EPI == EPI_RESID) {
         reinterpret_cast<float*>(out)[(size_t)eslot * out_stride + n] = pre_res[t] + v;
       } else if constexpr (EPI == EPI_GELU) {
-        reinterpret_cast<bf16*>(out)[(size_t)eslot * out_stride + n] = __float2bfloat16(gelu_new_f(v));
+        store_kv(reinterpret_cast<ET*>(out) + (size_t)eslot * out_stride + n, gelu_new_f(v));  // ff travels in the weights' type (fp16: saturating)
       } else if constexpr (EPI == EPI_LOGITS) {
         reinterpret_cast<float*>(out)[(size_t)eslot * out_stride + n] = v;
       } else {  // EPI_QKV: q -> buffer, k / v -> cache at position cur_len[slot]  (K == model_dim here)

@@ -15,11 +15,38 @@ import torch
 from . import _lib
 from .weights import GPT_CFG
 
+# weight (and K/V cache) types of the engine -> ixtts_gpt_cfg.weight_dtype (include/ixtts_hip.h)
+GPT_DTYPES = {"f32": 0, "bf16": 1, "f16": 2}
+
+
+def _dtype_code(dtype):
+    if dtype not in GPT_DTYPES:
+        raise ValueError(f"GPT weight dtype {dtype!r}: expected one of " + ", ".join(GPT_DTYPES))
+    return GPT_DTYPES[dtype]
+
+
+def resolve_gpt_dtype(use_fp16, gpt_dtype=None, env=None):
+    """The GPT's weight type for a model built with `use_fp16`: an explicit `gpt_dtype` wins, then `IXTTS_GPT_DTYPE` (read from
+    `env`, default the process environment), then the default -- bf16 under `use_fp16`, f32 otherwise.  `f16` is the
+    reference's own precision under `use_fp16=True` (IEEE half).  Anything but f32 / bf16 / f16 raises ValueError."""
+    import os
+
+    if gpt_dtype is None:
+        gpt_dtype = (os.environ if env is None else env).get("IXTTS_GPT_DTYPE") or None
+        if gpt_dtype is not None:
+            gpt_dtype = gpt_dtype.strip().lower()
+    if gpt_dtype is None:
+        return "bf16" if use_fp16 else "f32"
+    _dtype_code(gpt_dtype)
+    return gpt_dtype
+
+
 GPT_TENSOR_PREFIXES = ("gpt.h.", "gpt.ln_f.", "final_norm.", "mel_head.", "mel_embedding.", "mel_pos_embedding.")
 
 
 class GptEngine:
     def __init__(self, cfg=None, dtype="f32", max_seq=2048, max_batch=1, device=None):
+        code = _dtype_code(dtype)
         cfg = dict(GPT_CFG if cfg is None else cfg)
         self.cfg = cfg
         self.device = torch.device(device if device is not None else "cuda:0")
@@ -36,7 +63,7 @@ class GptEngine:
         c.stop_mel_token = cfg["stop_mel_token"]
         c.max_seq = max_seq
         c.max_batch = max_batch
-        c.weight_dtype = {"f32": 0, "bf16": 1}[dtype]
+        c.weight_dtype = code
         self._c = c
         self.max_seq = max_seq
         self.max_batch = max_batch

@@ -25,7 +25,7 @@ import numpy as np
 import torch
 
 from .bigvgan import BigVGAN
-from .gpt_engine import GptEngine
+from .gpt_engine import GptEngine, resolve_gpt_dtype
 from .pipeline import prepare_gpt_inputs
 from .weights import BIGVGAN_CFG, GPT_CFG, load_bigvgan_checkpoint, load_gpt_checkpoint
 
@@ -136,7 +136,7 @@ class IndexTTS2:
                  s2mel_state_dict=None, gpt_cfg=None, bigvgan_cfg=None, cond_cfg=None, s2mel_cfg=None, tokenizer=None,
                  max_seq=2048, max_frames=4096, w2v_bert=None, w2v_stats=None, semantic_codec_state_dict=None, codec_cfg=None,
                  campplus_state_dict=None, emo_matrix=None, spk_matrix=None, emo_num=None, weight_broadcast=None, qwen_emo=None,
-                 qwen_emo_dtype="f16"):
+                 qwen_emo_dtype="f16", gpt_dtype=None):
         if device is None:
             if not torch.cuda.is_available():
                 raise RuntimeError("the HIP hot path needs a GPU (no CPU fallback); pass device='cuda:N'")
@@ -160,8 +160,10 @@ class IndexTTS2:
         self.cfg = cfg
         self.model_version = cfg.get("version")
         self.stop_mel_token = gcfg["stop_mel_token"]
-        # reference precision: fp16 GPT under use_fp16 (infer_v2.py:79,88-89); here bf16 is the throughput mode
-        self.gpt = GptEngine(gcfg, dtype="bf16" if use_fp16 else "f32", max_seq=max_seq, max_batch=3, device=self.device)
+        # reference precision: fp16 GPT under use_fp16 (infer_v2.py:79,88-89); here bf16 is the throughput mode and the default,
+        # gpt_dtype="f16" / IXTTS_GPT_DTYPE=f16 gives the reference's IEEE half (resolve_gpt_dtype)
+        self.gpt_dtype = resolve_gpt_dtype(self.use_fp16, gpt_dtype)
+        self.gpt = GptEngine(gcfg, dtype=self.gpt_dtype, max_seq=max_seq, max_batch=3, device=self.device)
         # ---- weights: rank 0 (or a lone worker) reads model_dir; with `weight_broadcast=(rank, world)` (torch.distributed initialised,
         # backend nccl = RCCL over xGMI) the other workers of the node read nothing but config.yaml / bpe.model / the w2v-bert
         # directory: the glue tensors arrive as one packed message, the GPT and BigVGAN weights as their packed device arenas
@@ -495,20 +497,20 @@ class IndexTTS2:
     # ------------------------------------------------------------------ row N3 at the API level: requests decoded together
     def _many_engine(self, slots):
         """A second decode engine whose slots are shared by the segments of several requests (wide MFMA GEMVs above 4 slots,
-        on the bf16 or the fp32 matrix cores by the model's precision)."""
+        on the bf16, fp16 or fp32 matrix cores by the model's GPT weight type)."""
         from . import _lib
 
         slots = max(1, min(int(slots), _lib.max_batch()))
         if slots not in self._engines:
             # a second engine SHAPE over the same device weights (ixtts_gpt_share_arena): it costs its KV cache only
-            eng = GptEngine(self.gpt_cfg, dtype="bf16" if self.use_fp16 else "f32", max_seq=self.gpt.max_seq, max_batch=slots, device=self.device)
+            eng = GptEngine(self.gpt_cfg, dtype=self.gpt_dtype, max_seq=self.gpt.max_seq, max_batch=slots, device=self.device)
             self._engines[slots] = eng.share_arena(self.gpt)
         return self._engines[slots]
 
     def _beam_group_engine(self, num_beams, n_segments):
         """The engine several beam groups step together on: wide (5..16 slots on the matrix cores, bf16 or fp32 by the model's
         precision) when there is more than one segment to decode, else None (one group at a time on the register engine, as the
-        reference decodes: segment after segment).  `IXTTS_BEAM_GROUPS` caps the groups (0 / 1: off); a bf16 model defaults to 5,
+        reference decodes: segment after segment).  `IXTTS_BEAM_GROUPS` caps the groups (0 / 1: off); a bf16 or fp16 model defaults to 5,
         an fp32 model joins the groups only when the variable is set."""
         from . import _lib
 
@@ -516,7 +518,7 @@ class IndexTTS2:
         groups = min(cap, _lib.max_batch() // num_beams, n_segments)
         # An fp32 model takes this path only when IXTTS_BEAM_GROUPS is set explicitly: the fp32 wide step has no recorded timing
         # against the register engine yet, and the second engine's fp32 K/V cache is 8 GB at max_seq 2048.
-        if not self.use_fp16 and "IXTTS_BEAM_GROUPS" not in os.environ:
+        if self.gpt_dtype == "f32" and "IXTTS_BEAM_GROUPS" not in os.environ:
             return None
         if groups < 2 or groups * num_beams <= 4:
             return None

@@ -283,10 +283,12 @@ def create_app(model_factory=default_model_factory):
             except Exception as e:
                 gpu["error"] = str(e)
         m = state["model"]
+        model_info = {"loaded": m is not None, "device": str(m.device) if m else "not loaded", "use_fp16": m.use_fp16 if m else None,
+                      "use_deepspeed": False}
+        if getattr(m, "gpt_dtype", None) is not None:  # the GPT weight type the worker resolved (IXTTS_GPT_DTYPE / gpt_dtype)
+            model_info["gpt_dtype"] = m.gpt_dtype
         return {"worker_id": os.environ.get("WORKER_ID", "unknown"), "pid": os.getpid(),
-                "cuda_visible_devices": os.environ.get("CUDA_VISIBLE_DEVICES", "not set"), "gpu_info": gpu,
-                "model_info": {"loaded": m is not None, "device": str(m.device) if m else "not loaded", "use_fp16": m.use_fp16 if m else None,
-                               "use_deepspeed": False}}
+                "cuda_visible_devices": os.environ.get("CUDA_VISIBLE_DEVICES", "not set"), "gpu_info": gpu, "model_info": model_info}
 
     @app.post("/tts", response_model=TTSResponse)
     def text_to_speech(request: TTSRequest):

@@ -265,8 +265,45 @@ __device__ __forceinline__ void unpack2<f16>(const uint4& r, f32x2 (&w)[4]) {
   w[3] = f32x2{lo_f16(r.w), hi_f16(r.w)};
 }
 
-// sums of s[0..B) over the workgroup's WPB waves, in a fixed order (bit-reproducible); `red` is a private [WPB][B] LDS region
-template <int B, int WPB>
+// Which elements of a unit (ROWS consecutive weight rows of length K) a lane takes with wave-load j, and which activations it
+// therefore keeps.  A lane holds a FIXED k slice over all rows of the unit: per row K / PER full wave-loads at k = i*PER + lane*VEC,
+// and, where half a wave-load is left (K % PER == PER/2: bf16 / f16 at K = 1280), the tails of rows 2t and 2t+1 share one
+// wave-load -- lanes 0..31 row 2t, lanes 32..63 row 2t+1, both at k = (K/PER)*PER + (lane & 31)*VEC (two 512-byte runs).  The lane
+// then needs K/PER (+1) activation chunks per slot instead of one per load: 24 floats, 6 ds_read_b128, instead of 40 / 10 (bf16, f16;
+// fp32 stays at 20 / 5: the flat map's k offsets repeat there with period K/PER and the compiler already merged the reads).
+// Measured (r09, tools/step_ab.py): B=2 577.4-581.4 -> 561.1-566.5 us per step, B=3 663.9-667.2 -> 650.0-652.7, B=4 804.3-808.2 -> 761.4-763.3.
+// Any other residue, K < PER (the tiny width) and IXTTS_XMAP=0 builds keep the flat map: load j covers elements j*PER + lane*VEC
+// of the unit, k = that modulo K.
+#ifndef IXTTS_XMAP
+#define IXTTS_XMAP 1  // 0 builds the flat map everywhere, for the A/B (tools/step_ab.py)
+#endif
+template <int K, int ROWS, int VEC>
+struct RegMap {
+  static constexpr int PER = 64 * VEC;       // elements per wave-load
+  static constexpr int NL = ROWS * K / PER;  // loads per lane per unit
+  static constexpr int NF = K / PER;         // full wave-loads per row
+  static constexpr bool TAIL = K % PER != 0;
+  static constexpr bool XMAP = IXTTS_XMAP != 0 && K >= PER && (!TAIL || (K % PER == PER / 2 && ROWS % 2 == 0));
+  static constexpr int NFR = ROWS * NF;                         // XMAP: loads [0, NFR) are full (row j / NF, chunk j % NF), [NFR, NL) shared tails
+  static constexpr int NX = XMAP ? NF + (TAIL ? 1 : 0) : NL;    // activation chunks per lane and slot
+  static_assert(!XMAP || NFR + (TAIL ? ROWS / 2 : 0) == NL, "every element of the unit is loaded once");
+  __device__ static constexpr int chunk(int j) { return XMAP ? (j < NFR ? j % NF : NF) : j; }  // activation chunk that load j multiplies
+  __device__ static constexpr int xk(int c, int lane) {                                        // first k of activation chunk c
+    return XMAP ? (c < NF ? c * PER + lane * VEC : NF * PER + (lane & 31) * VEC) : (c * PER + lane * VEC) % K;
+  }
+  __device__ static constexpr int row(int j, int lane) {  // row of the unit that load j holds in this lane
+    return XMAP ? (j < NFR ? j / NF : 2 * (j - NFR) + (lane >> 5)) : (j * PER + lane * VEC) / K;
+  }
+  __device__ static constexpr int elem(int j, int lane) {  // element of the unit ([ROWS][K]) at which the lane's 16 bytes start
+    return XMAP ? row(j, lane) * K + xk(chunk(j), lane) : j * PER + lane * VEC;
+  }
+};
+
+// sums of s[0..B) over the workgroup's WPB waves, in a fixed order (bit-reproducible); `red` is a private [WPB][B] LDS region.
+// WSHIFT: slot b's elements sit b*WSHIFT waves further on than slot 0's (same lanes, same grouping per thread: the staging of
+// gemv_reg_kernel when a slot's K/4 float4s are a whole number of waves but not of workgroups -- 320 over 256 threads), so its
+// sum starts b*WSHIFT waves further on too: a slot's statistics are bit for bit those it has alone in slot 0.
+template <int B, int WPB, int WSHIFT = 0>
 __device__ __forceinline__ void block_sum(float (&s)[B], float* red, int wave, int lane) {
 #pragma unroll
   for (int b = 0; b < B; ++b) {
@@ -278,7 +315,7 @@ __device__ __forceinline__ void block_sum(float (&s)[B], float* red, int wave, i
   for (int b = 0; b < B; ++b) {
     float t = 0.f;
 #pragma unroll
-    for (int w = 0; w < WPB; ++w) t += red[w * B + b];
+    for (int w = 0; w < WPB; ++w) t += red[((w + b * WSHIFT) % WPB) * B + b];
     s[b] = t;
   }
 }
@@ -298,8 +335,10 @@ __global__ __launch_bounds__(64 * WPB) void gemv_reg_kernel(const void* wt, cons
   if (aux != nullptr && blockIdx.x == 0 && threadIdx.x < MLP_XCDS) aux[threadIdx.x * 32] = 0u;
   TraceScope trace(EPI, IXTTS_TRACE_SEQ);
   constexpr int VEC = WVec<WT>::VEC;
-  constexpr int PER = 64 * VEC;       // elements per wave-load
-  constexpr int NL = ROWS * K / PER;  // loads per lane per unit
+  using Map = RegMap<K, ROWS, VEC>;  // lane <-> (row, k) of every wave-load
+  constexpr int PER = Map::PER;
+  constexpr int NL = Map::NL;
+  constexpr int NX = Map::NX;
   static_assert(ROWS * K % PER == 0, "unit must be a whole number of wave loads");
   static_assert(K % VEC == 0 && K % 4 == 0, "row length must be a multiple of the vector width");
   static_assert(XLDS || INP == IN_PLAIN, "LayerNorm / split-S merge inputs are staged by the workgroup (XLDS)");
@@ -314,7 +353,8 @@ __global__ __launch_bounds__(64 * WPB) void gemv_reg_kernel(const void* wt, cons
 
   // ---- 1. activations: issue the loads
   constexpr int K4 = K / 4, X4 = B * K4, NT = 64 * WPB, XV = (X4 + NT - 1) / NT;  // XLDS: float4 per thread
-  f32x2 xr[B][NL][VEC / 2];
+  constexpr int WSHIFT = K4 % 64 == 0 ? (K4 / 64) % WPB : 0;  // waves between consecutive slots' elements in the staging (block_sum)
+  f32x2 xr[B][NX][VEC / 2];
   float4 xs4[XLDS ? XV : 1];             // staged element i of this thread: float4 number threadIdx.x + i*NT of [B][K]
   float4 lw4[NPASS == 2 ? XV : 1], lb4[NPASS == 2 ? XV : 1];
   float4 pbias4[INP == IN_LN_PART ? XV : 1], ppart4[INP == IN_LN_PART ? XV : 1][MLP_XCDS];
@@ -356,8 +396,8 @@ __global__ __launch_bounds__(64 * WPB) void gemv_reg_kernel(const void* wt, cons
     for (int b = 0; b < B; ++b) {
       const float* xs = a.xin + (size_t)(a.slot0 + b) * K;
 #pragma unroll
-      for (int j = 0; j < NL; ++j) {
-        const int k0 = (j * PER + lane * VEC) % K;
+      for (int j = 0; j < NX; ++j) {
+        const int k0 = Map::xk(j, lane);
 #pragma unroll
         for (int v4 = 0; v4 < VEC / 4; ++v4) {
           const float4 t = *reinterpret_cast<const float4*>(xs + k0 + v4 * 4);
@@ -389,7 +429,7 @@ __global__ __launch_bounds__(64 * WPB) void gemv_reg_kernel(const void* wt, cons
     const WT* base = reinterpret_cast<const WT*>(a.wt) + (size_t)unit_c * ROWS * K;
 #pragma unroll
     for (int j = 0; j < NL; ++j) {
-      const int e = j * PER + lane * VEC;
+      const int e = Map::elem(j, lane);
       wraw[u][j] = load_w16(base + (e < min(ROWS, a.N - unit_c * ROWS) * K ? e : 0));
     }
   }
@@ -449,7 +489,7 @@ __global__ __launch_bounds__(64 * WPB) void gemv_reg_kernel(const void* wt, cons
 #pragma unroll
         for (int b = 0; b < B; ++b) s[b] += (sl == b) ? v : 0.f;
       }
-      block_sum<B, WPB>(s, red + (2 * pass) * WPB * B, wave, lane);
+      block_sum<B, WPB, WSHIFT>(s, red + (2 * pass) * WPB * B, wave, lane);
 #pragma unroll
       for (int b = 0; b < B; ++b) {
         s[b] *= (1.0f / K);  // mean
@@ -467,7 +507,7 @@ __global__ __launch_bounds__(64 * WPB) void gemv_reg_kernel(const void* wt, cons
 #pragma unroll
         for (int b = 0; b < B; ++b) q[b] += (sl == b) ? v : 0.f;
       }
-      block_sum<B, WPB>(q, red + (2 * pass + 1) * WPB * B, wave, lane);
+      block_sum<B, WPB, WSHIFT>(q, red + (2 * pass + 1) * WPB * B, wave, lane);
 #pragma unroll
       for (int b = 0; b < B; ++b) q[b] = 1.0f / sqrtf(q[b] * (1.0f / K) + 1e-5f);  // rstd
 #pragma unroll
@@ -493,8 +533,8 @@ __global__ __launch_bounds__(64 * WPB) void gemv_reg_kernel(const void* wt, cons
 #pragma unroll
     for (int b = 0; b < B; ++b)
 #pragma unroll
-      for (int j = 0; j < NL; ++j) {
-        const int k0 = (j * PER + lane * VEC) % K;
+      for (int j = 0; j < NX; ++j) {
+        const int k0 = Map::xk(j, lane);
 #pragma unroll
         for (int v4 = 0; v4 < VEC / 4; ++v4) {
           const float4 t = *reinterpret_cast<const float4*>(xsh + b * K + k0 + v4 * 4);
@@ -517,18 +557,30 @@ __global__ __launch_bounds__(64 * WPB) void gemv_reg_kernel(const void* wt, cons
       for (int b = 0; b < B; ++b) acc[r][b] = 0.f;
 #pragma unroll
     for (int j = 0; j < NL; ++j) {
-      const int e = j * PER + lane * VEC;
-      const int row = (e < rows_here * K) ? e / K : ROWS;  // ROWS: element beyond the matrix (its load was clamped)
+      const int xc = Map::chunk(j);
       f32x2 w2[VEC / 2];
       unpack2<WT>(wraw[u][j], w2);
 #pragma unroll
       for (int b = 0; b < B; ++b) {
-        f32x2 d2 = w2[0] * xr[b][j][0];
+        f32x2 d2 = w2[0] * xr[b][xc][0];
 #pragma unroll
-        for (int v = 1; v < VEC / 2; ++v) d2 = __builtin_elementwise_fma(w2[v], xr[b][j][v], d2);
+        for (int v = 1; v < VEC / 2; ++v) d2 = __builtin_elementwise_fma(w2[v], xr[b][xc][v], d2);
         const float d = d2.x + d2.y;
+        if constexpr (Map::XMAP) {
+          // a row beyond the matrix (its loads were clamped) is never written, so its sum may be anything: no products to drop
+          if (j < Map::NFR) {  // a full load holds one row, known at compile time
+            acc[j / Map::NF][b] += d;
+          } else {             // the shared tail load: lanes 0..31 row 2t, lanes 32..63 row 2t+1
+            const int t = j - Map::NFR;
+            acc[2 * t][b] += (lane < 32) ? d : 0.f;
+            acc[2 * t + 1][b] += (lane < 32) ? 0.f : d;
+          }
+        } else {
+          const int e = Map::elem(j, lane);
+          const int row = (e < rows_here * K) ? e / K : ROWS;  // ROWS: element beyond the matrix (its load was clamped)
 #pragma unroll
-        for (int r = 0; r < ROWS; ++r) acc[r][b] += (row == r) ? d : 0.f;
+          for (int r = 0; r < ROWS; ++r) acc[r][b] += (row == r) ? d : 0.f;
+        }
       }
     }
     float tot[ROWS][B];

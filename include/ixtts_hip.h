@@ -347,7 +347,7 @@ int ixtts_gpt_max_batch(void);
 int ixtts_gpt_destroy(ixtts_gpt* h);
 
 /* ------------------------------------------------------------------------------------
- * Text emotion model -- Qwen3 causal-LM decode, one sequence
+ * Text emotion model -- Qwen3 causal-LM decode, 1..IXTTS_QWEN_MAX_SLOTS sequences ("slots") per engine
  * replaces: `QwenEmotion.model.generate(...)` (indextts/infer_v2.py:795-906), the arithmetic of
  *   transformers/models/qwen3/modeling_qwen3.py (embed -> L x {RMSNorm, q|k|v, q_norm/k_norm, RoPE, GQA attention,
  *   o_proj + residual, RMSNorm, SiLU(gate) * up, down + residual} -> norm -> lm_head).
@@ -356,9 +356,17 @@ int ixtts_gpt_destroy(ixtts_gpt* h);
  * sampling = temperature -> top-k -> top-p (HF warper order), 1 <= top_k <= IXTTS_QWEN_TOPK_MAX, draws from the
  * counter-based stream (seed, 0, generated count).
  * Usage: create -> set_tensor (HF names) for every tensor -> finalize -> prefill(prompt ids) -> generate, or step + read.
+ * Slots: create_slots(n_slots) -> ... -> prefill_slots(prompts) -> generate_slots, or step_slots, + read_slot per slot.
+ *   Slot 0 is the sequence of the one-sequence calls.  One decode step forwards every slot with one pass over the
+ *   weights; slot c's logits, kept set and ids are bit for bit those of a one-sequence engine given its prompt alone.
+ *   The K/V caches of slots 1.. are allocated by the first prefill_slots of more than one sequence.
+ *   f16 engines prefill the prompts of a batch as rows of GEMMs on the f16 matrix cores (activations as two f16 planes,
+ *   fp32 accumulation; at most IXTTS_QWEN_ROWS_MAX rows per pass, environment, default 1024 -- lowered by tests);
+ *   f32 engines prefill slot after slot exactly as ixtts_qwen_prefill does.
  */
 #define IXTTS_QWEN_TOPK_MAX 64
 #define IXTTS_QWEN_MAX_EOS 8
+#define IXTTS_QWEN_MAX_SLOTS 4
 
 typedef struct ixtts_qwen_cfg {
   int hidden_size;         /* 1024 (multiple of 512) */
@@ -387,7 +395,8 @@ typedef struct ixtts_qwen_sampling {
 
 typedef struct ixtts_qwen ixtts_qwen;
 
-int ixtts_qwen_create(ixtts_qwen** out, const ixtts_qwen_cfg* cfg);
+int ixtts_qwen_create(ixtts_qwen** out, const ixtts_qwen_cfg* cfg); /* = create_slots(out, cfg, 1) */
+int ixtts_qwen_create_slots(ixtts_qwen** out, const ixtts_qwen_cfg* cfg, int n_slots);
 /* `name` as in the HF state dict (model.embed_tokens.weight, model.layers.N.self_attn.q_proj.weight, ..., lm_head.weight);
  * data_host fp32, converted to the engine's weight dtype.  Synchronous. */
 int ixtts_qwen_set_tensor(ixtts_qwen* h, const char* name, const float* data_host, const int64_t* shape, int ndim);
@@ -411,6 +420,18 @@ int ixtts_qwen_read_kept(ixtts_qwen* h, int32_t* ids_host, float* probs_host, in
 int ixtts_qwen_draw(ixtts_qwen* h, uint64_t seed, int n, int32_t* ids_host, void* stream);
 /* HBM bytes of one decode step at context S (weights + K/V rows). */
 double ixtts_qwen_step_bytes(const ixtts_qwen* h, int S);
+/* Resets slots 0..n-1 to their prompts (ids_host: the prompts one after the other, lens_host[n] their lengths, each
+ * 1 <= len < max_seq) and runs each one's first len-1 positions through the layers.  Slots n.. are left as they are. */
+int ixtts_qwen_prefill_slots(ixtts_qwen* h, int n, const int32_t* ids_host, const int* lens_host, void* stream);
+/* n_steps decode steps of slots 0..n-1 (all prefilled).  A finished slot stays put: it appends no K/V and emits no token. */
+int ixtts_qwen_step_slots(ixtts_qwen* h, int n, int n_steps, const ixtts_qwen_sampling* sc, void* stream);
+/* Steps slots 0..n-1 until every one is finished or has max_new tokens (the host looks every 16 steps).  Synchronous;
+ * read the ids with ixtts_qwen_read_slot. */
+int ixtts_qwen_generate_slots(ixtts_qwen* h, int n, int max_new, const ixtts_qwen_sampling* sc, void* stream);
+/* ixtts_qwen_read / read_logits / read_kept of one slot. */
+int ixtts_qwen_read_slot(ixtts_qwen* h, int slot, int32_t* ids_host, int cap, int* n_ids, int* finished, void* stream);
+int ixtts_qwen_read_logits_slot(ixtts_qwen* h, int slot, float* logits_host, void* stream);
+int ixtts_qwen_read_kept_slot(ixtts_qwen* h, int slot, int32_t* ids_host, float* probs_host, int cap, int* n_kept, void* stream);
 int ixtts_qwen_destroy(ixtts_qwen* h);
 
 #ifdef __cplusplus

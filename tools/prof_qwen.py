@@ -1,10 +1,15 @@
 """Emotion-model decode at the Qwen3-0.6B shape with seeded random f16 weights (csrc/qwen_engine.hip).
 
     python tools/prof_qwen.py [--out profiles/qwen_emo.json]
+    python tools/prof_qwen.py --slots 4 [--out profiles/qwen_emo_slots.json]
 
 Prints the decode-step time at contexts 128 / 512 / 1024, the `QwenEmotion.inference()` wall time for a 128-token prompt
 plus 64 new tokens (tokenization and parsing included; greedy, and sampled as the production generation config does), the
 prefill time of that prompt, and the step's HBM bytes over its time as a fraction of 8 TB/s.
+
+`--slots N` times the batch path instead: N different 128-token prompts plus 64 new tokens through `inference_many` (greedy
+and sampled) against the same N through N `inference()` calls, the rows prefill of the N prompts alone against N chunk
+prefills, and the decode step at context 512 with 1 / 2 / N active slots.
 """
 import argparse
 import json
@@ -59,11 +64,79 @@ def step_time(e, ctx, steps=64, reps=3):
     return best
 
 
+def median_ms(fn, reps=6):
+    times = []
+    for _ in range(reps):
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        fn()
+        torch.cuda.synchronize()
+        times.append((time.perf_counter() - t0) * 1e3)
+    return round(float(np.median(times[1:])), 2)
+
+
+def slots_step_time(e, n, ctx, steps=64, reps=3):
+    prompts = [torch.randint(0, 151000, (ctx,), generator=torch.Generator().manual_seed(ctx + s)).tolist() for s in range(n)]
+    best = None
+    for _ in range(reps):
+        e.prefill_many(prompts)
+        e.step_many(8)
+        torch.cuda.synchronize()
+        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        a.record()
+        e.step_many(steps)
+        b.record()
+        torch.cuda.synchronize()
+        t = a.elapsed_time(b) / steps * 1e3
+        best = t if best is None else min(best, t)
+    return best
+
+
+def slots_leg(n, out):
+    import qwen_twin as T
+    from transformers import AutoTokenizer
+
+    e = QwenEngine(CFG, dtype="f16", max_seq=2048, device="cuda:0", eos_token_id=[151935], slots=n).load_state_dict(random_state_dict())
+    res = dict(shape=f"Qwen3-0.6B (28 x 1024, 16/8 heads x 128, ffn 3072, vocab 151936, tied), f16 weights, {n} slots")
+    d = tempfile.mkdtemp()
+    T.write_tokenizer(d)
+    q = QwenEmotion(None, tokenizer=AutoTokenizer.from_pretrained(d, local_files_only=True), engine=e)
+    texts = []
+    for ch in "wxyzuv"[:n]:
+        text = ch * 200
+        while len(q.prompt_ids(text)) > 128:
+            text = text[:-1]
+        assert len(q.prompt_ids(text)) == 128
+        texts.append(text)
+    for tag, gen in (("", dict(do_sample=False, temperature=1.0, top_k=50, top_p=1.0)),
+                     ("_sampled", dict(do_sample=True, temperature=0.6, top_k=20, top_p=0.95))):
+        q.generation = dict(gen, eos_token_id=[151935])
+        many = [None]
+        res[f"inference_many_ms_{n}x128_plus_64{tag}"] = median_ms(lambda: many.__setitem__(0, q.inference_many(texts, max_new_tokens=64)))
+        res[f"new_tokens{tag}"] = [len(e.read_slot(s)[0]) for s in range(n)]
+        serial = [None]
+        res[f"serial_inference_ms_{n}x128_plus_64{tag}"] = median_ms(lambda: serial.__setitem__(0, [q.inference(t, max_new_tokens=64) for t in texts]))
+        res[f"same_answers{tag}"] = many[0] == serial[0]
+    prompts = [q.prompt_ids(t) for t in texts]
+    res[f"rows_prefill_ms_{n}x127"] = median_ms(lambda: e.prefill_many(prompts))
+    res[f"chunk_prefill_ms_{n}x127_serial"] = median_ms(lambda: [e.prefill(p) for p in prompts])
+    res["step_us_ctx512_one_sequence"] = round(step_time(e, 512), 1)
+    for k in sorted({1, 2, n}):
+        res[f"step_us_ctx512_{k}_slots"] = round(slots_step_time(e, k, 512), 1)
+    print(json.dumps(res))
+    if out:
+        os.makedirs(os.path.dirname(os.path.abspath(out)), exist_ok=True)
+        json.dump(res, open(out, "w"), indent=1)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--out", default=None)
+    ap.add_argument("--slots", type=int, default=0, help="time the batch path with this many slots (2..4) instead")
     args = ap.parse_args()
     torch.cuda.init()
+    if args.slots:
+        return slots_leg(args.slots, args.out)
     e = QwenEngine(CFG, dtype="f16", max_seq=2048, device="cuda:0", eos_token_id=[151935]).load_state_dict(random_state_dict())
     res = dict(shape="Qwen3-0.6B (28 x 1024, 16/8 heads x 128, ffn 3072, vocab 151936, tied), f16 weights, B=1")
     res["step_bytes_ctx512"] = e.step_bytes(512)

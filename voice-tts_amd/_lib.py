@@ -41,6 +41,7 @@ class SamplerCfg(C.Structure):
 
 QWEN_TOPK_MAX = 64  # IXTTS_QWEN_TOPK_MAX
 QWEN_MAX_EOS = 8
+QWEN_MAX_SLOTS = 4  # IXTTS_QWEN_MAX_SLOTS
 
 
 class QwenCfg(C.Structure):
@@ -134,6 +135,13 @@ SYMBOLS = {
     "ixtts_qwen_read_kept": (C.c_int, [_P, _P, _P, C.c_int, C.POINTER(C.c_int), _P]),
     "ixtts_qwen_draw": (C.c_int, [_P, C.c_uint64, C.c_int, _P, _P]),
     "ixtts_qwen_step_bytes": (C.c_double, [_P, C.c_int]),
+    "ixtts_qwen_create_slots": (C.c_int, [C.POINTER(_P), C.POINTER(QwenCfg), C.c_int]),
+    "ixtts_qwen_prefill_slots": (C.c_int, [_P, C.c_int, _P, _P, _P]),
+    "ixtts_qwen_step_slots": (C.c_int, [_P, C.c_int, C.c_int, C.POINTER(QwenSampling), _P]),
+    "ixtts_qwen_generate_slots": (C.c_int, [_P, C.c_int, C.c_int, C.POINTER(QwenSampling), _P]),
+    "ixtts_qwen_read_slot": (C.c_int, [_P, C.c_int, _P, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int), _P]),
+    "ixtts_qwen_read_logits_slot": (C.c_int, [_P, C.c_int, _P, _P]),
+    "ixtts_qwen_read_kept_slot": (C.c_int, [_P, C.c_int, _P, _P, C.c_int, C.POINTER(C.c_int), _P]),
     "ixtts_qwen_destroy": (C.c_int, [_P]),
 }
 

@@ -1,5 +1,5 @@
-// qwen_engine.hip -- the Qwen3 causal LM of the text-emotion model (QwenEmotion, indextts/infer_v2.py:795-906): one
-// sequence (B = 1), decoded on gfx950.
+// qwen_engine.hip -- the Qwen3 causal LM of the text-emotion model (QwenEmotion, indextts/infer_v2.py:795-906), decoded
+// on gfx950: 1..IXTTS_QWEN_MAX_SLOTS sequences ("slots") per engine.  Slot 0 is the sequence of the one-sequence calls.
 //
 // One decode step = 5 launches per layer + 3:
 //   L x { RMSNorm (in the staging of x) + q|k|v GEMV   [layer 0: the embedding row gather is that staging]
@@ -15,11 +15,17 @@
 // they fit in registers (the layer GEMVs in f16), else one chunk ahead of the arithmetic.  The token, the position
 // and the sampling parameters live on the device: a captured chain replays for any step.
 //
+// Slots: a decode step of n slots is the same chain with column c of the GEMVs being slot c (its own token, position,
+// K/V cache, logits row and token selection), so slot c's arithmetic is the one-sequence step's, bit for bit.  On f16
+// engines the prompts of a batch are prefilled as rows: every prompt position of every slot is one row of fp32 activations,
+// and the layer matrices are GEMMs on v_mfma_f32_32x32x16_f16 (qrows_*; one pass over the weights for the whole batch).
+//
 // Arithmetic: transformers/models/qwen3/modeling_qwen3.py (Qwen3RMSNorm, Qwen3Attention, Qwen3MLP, rotate_half RoPE with
 // inv_freq = 1 / theta^(2i/d), scaling = head_dim^-0.5); token selection: TemperatureLogitsWarper -> TopKLogitsWarper ->
 // TopPLogitsWarper -> multinomial (transformers generation/logits_process.py).
 #include <algorithm>
 #include <cmath>
+#include <cstdlib>
 #include <map>
 #include <string>
 #include <vector>
@@ -83,6 +89,8 @@ struct GemvP {
   float* h_out;
   const float* part;  // PRO_MERGE: [heads][NSP][PSTR]
   int* advance;       // non-null: block 0 increments it at the end (a prefill step moves the position)
+  int slots, tstride; // slots != 0: column c is slot c, PRO_EMBED gathers tokens[c * tstride + cur_len[c]]
+  int nact;           // columns [nact, NC) are idle (a step of 3 slots on the 4-column kernel): computed, never stored
 };
 
 // ---- GEMV: stage x (optionally normalised / gathered / merged) in LDS, then each wave streams ROWS weight rows.
@@ -154,13 +162,13 @@ __global__ __launch_bounds__(64 * WAVES) void qgemv_kernel(GemvP p) {
     for (int c = 0; c < NC; ++c) {
       ss[c] = 0.f;
       if constexpr (PRO == PRO_EMBED) {
-        const int tok = p.tokens[*p.cur_len + c];
+        const int tok = p.slots ? p.tokens[(size_t)c * p.tstride + p.cur_len[c]] : p.tokens[*p.cur_len + c];
         const WT* e = reinterpret_cast<const WT*>(p.emb) + (size_t)tok * K;
         for (int k = tid; k < K; k += 64 * WAVES) {
           const float v = (float)e[k];
           xs[c * K + k] = v;
           ss[c] = fmaf(v, v, ss[c]);
-          if (blockIdx.x == 0) p.h_out[c * K + k] = v;
+          if (blockIdx.x == 0 && c < p.nact) p.h_out[c * K + k] = v;
         }
       } else {
         for (int k = tid; k < K; k += 64 * WAVES) {
@@ -233,6 +241,7 @@ __global__ __launch_bounds__(64 * WAVES) void qgemv_kernel(GemvP p) {
   if (lane == 0) {
 #pragma unroll
     for (int c = 0; c < NC; ++c) {
+      if (c >= p.nact) continue;
       float* out = p.out + (size_t)c * N;
       if constexpr (EPI == EPI_SWIGLU) {
 #pragma unroll
@@ -256,16 +265,20 @@ __global__ __launch_bounds__(64 * WAVES) void qgemv_kernel(GemvP p) {
   if (p.advance && blockIdx.x == 0 && tid == 0) *p.advance += NC;
 }
 
-// ---- attention.  grid (kv_heads, NSP): split sp owns keys [sp*ch, min((sp+1)*ch, pos+1)), ch = ceil((pos+1)/NSP).
+// ---- attention.  grid (kv_heads, NSP, slots): split sp owns keys [sp*ch, min((sp+1)*ch, pos+1)), ch = ceil((pos+1)/NSP).
 // Prologue: q_norm + RoPE of the NREP query heads of this KV head (every workgroup), k_norm + RoPE of the new key and the
 // new value (the workgroup whose range holds `pos`: it appends them to the cache and reads them from LDS).
+// Slot z takes qkv / part of column z, cur_len[z] and its own cache; a finished slot's new key and value stay in LDS.
+constexpr int MAXS = IXTTS_QWEN_MAX_SLOTS;
+static_assert(MAXS == PCH, "a decode step of all slots is the PCH-column GEMV");
 struct AttnP {
-  const float* qkv;  // raw projections [heads*HDIM | kv_heads*HDIM | kv_heads*HDIM]
+  const float* qkv;  // raw projections [heads*HDIM | kv_heads*HDIM | kv_heads*HDIM] per column
   const float *qn, *kn;  // q_norm / k_norm weights [HDIM]
   const float *cosb, *sinb;  // [max_seq][HDIM/2]
-  float *kc, *vc;    // this layer's cache [kv_heads][smax][HDIM]
-  const int* cur_len;
-  float* part;       // [heads][NSP][PSTR]
+  float *kc[MAXS], *vc[MAXS];  // this layer's cache of each slot [kv_heads][smax][HDIM] (the chunk path: [0])
+  const int* cur_len;  // [slots]
+  const int* finished;  // slots path: [slots]; null: always append
+  float* part;       // [heads][NSP][PSTR] per column
   int heads, kv_heads, smax;
   float eps, scale;
   float* qb;        // prefill chunks: q_norm + RoPE of [PCH][heads][HDIM]
@@ -288,36 +301,51 @@ __device__ __forceinline__ void norm_rope_head(const float* x, const float* w, c
   }
 }
 
+// p[slot] without a run-time index into the kernel argument (which would move the whole argument to scratch)
+template <typename PT>
+__device__ __forceinline__ PT pick_slot(PT const (&p)[MAXS], int slot) {
+  return slot == 0 ? p[0] : slot == 1 ? p[1] : slot == 2 ? p[2] : p[3];
+}
+
 template <int NREP>
 __global__ __launch_bounds__(256) void qattn_kernel(AttnP p) {
   __shared__ __attribute__((aligned(16))) float qs[NREP][HDIM];
   __shared__ __attribute__((aligned(16))) float knew[HDIM], vnew[HDIM];
   __shared__ float gm[16][NREP], gl[16][NREP];
   __shared__ __attribute__((aligned(16))) float gacc[16][NREP][HDIM];
-  const int kvh = blockIdx.x, sp = blockIdx.y;
+  const int kvh = blockIdx.x, sp = blockIdx.y, slot = blockIdx.z;
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const int pos = *p.cur_len;
+  const int pos = p.cur_len[slot];
   const int n = pos + 1, ch = (n + NSP - 1) / NSP;
   const int lo = sp * ch, hi = min(n, lo + ch);
   const bool owner = lo <= pos && pos < hi;
+  const bool append = p.finished == nullptr || p.finished[slot] == 0;
+  const float* const qkv = p.qkv + (size_t)slot * (p.heads + 2 * p.kv_heads) * HDIM;
+  float* const part = p.part + (size_t)slot * p.heads * NSP * PSTR;
+  float* const kcache = pick_slot(p.kc, slot);
+  float* const vcache = pick_slot(p.vc, slot);
   const float* cs = p.cosb + (size_t)pos * (HDIM / 2);
   const float* sn = p.sinb + (size_t)pos * (HDIM / 2);
   const int qdim = p.heads * HDIM, kvdim = p.kv_heads * HDIM;
   for (int j = wave; j < NREP + 2; j += 4) {
     if (j < NREP) {
-      norm_rope_head(p.qkv + (size_t)(kvh * NREP + j) * HDIM, p.qn, cs, sn, p.eps, true, lane, qs[j]);
+      norm_rope_head(qkv + (size_t)(kvh * NREP + j) * HDIM, p.qn, cs, sn, p.eps, true, lane, qs[j]);
     } else if (owner && j == NREP) {
-      norm_rope_head(p.qkv + qdim + (size_t)kvh * HDIM, p.kn, cs, sn, p.eps, true, lane, knew);
-      float* kd = p.kc + ((size_t)kvh * p.smax + pos) * HDIM;
-      kd[lane] = knew[lane];
-      kd[lane + 64] = knew[lane + 64];
+      norm_rope_head(qkv + qdim + (size_t)kvh * HDIM, p.kn, cs, sn, p.eps, true, lane, knew);
+      if (append) {
+        float* kd = kcache + ((size_t)kvh * p.smax + pos) * HDIM;
+        kd[lane] = knew[lane];
+        kd[lane + 64] = knew[lane + 64];
+      }
     } else if (owner) {
-      const float* v = p.qkv + qdim + kvdim + (size_t)kvh * HDIM;
+      const float* v = qkv + qdim + kvdim + (size_t)kvh * HDIM;
       vnew[lane] = v[lane];
       vnew[lane + 64] = v[lane + 64];
-      float* vd = p.vc + ((size_t)kvh * p.smax + pos) * HDIM;
-      vd[lane] = v[lane];
-      vd[lane + 64] = v[lane + 64];
+      if (append) {
+        float* vd = vcache + ((size_t)kvh * p.smax + pos) * HDIM;
+        vd[lane] = v[lane];
+        vd[lane + 64] = v[lane + 64];
+      }
     }
   }
   __syncthreads();
@@ -335,8 +363,8 @@ __global__ __launch_bounds__(256) void qattn_kernel(AttnP p) {
 #pragma unroll
     for (int i = 0; i < 8; ++i) acc[j][i] = 0.f;
   }
-  const float* kb = p.kc + (size_t)kvh * p.smax * HDIM + dl * 8;
-  const float* vb = p.vc + (size_t)kvh * p.smax * HDIM + dl * 8;
+  const float* kb = kcache + (size_t)kvh * p.smax * HDIM + dl * 8;
+  const float* vb = vcache + (size_t)kvh * p.smax * HDIM + dl * 8;
   for (int key = lo + g; key < hi; key += 16) {
     float kv[8], vv[8];
     if (key == pos) {
@@ -387,7 +415,7 @@ __global__ __launch_bounds__(256) void qattn_kernel(AttnP p) {
         L = fmaf(e, gl[gg][j], L);
       }
     }
-    float* pp = p.part + ((size_t)(kvh * NREP + j) * NSP + sp) * PSTR;
+    float* pp = part + ((size_t)(kvh * NREP + j) * NSP + sp) * PSTR;
     pp[2 + d] = o;
     if (d == 0) pp[0] = M, pp[1] = L;  // an empty split: M = -inf, L = 0, the merge gives it weight 0
   }
@@ -406,9 +434,9 @@ __global__ __launch_bounds__(64) void qprep_kernel(AttnP p) {
     norm_rope_head(x + (size_t)hh * HDIM, p.qn, cs, sn, p.eps, true, lane, p.qb + ((size_t)c * p.heads + hh) * HDIM);
   } else {
     const int kvh = hh - p.heads;
-    norm_rope_head(x + qdim + (size_t)kvh * HDIM, p.kn, cs, sn, p.eps, true, lane, p.kc + ((size_t)kvh * p.smax + pos) * HDIM);
+    norm_rope_head(x + qdim + (size_t)kvh * HDIM, p.kn, cs, sn, p.eps, true, lane, p.kc[0] + ((size_t)kvh * p.smax + pos) * HDIM);
     const float* v = x + qdim + kvdim + (size_t)kvh * HDIM;
-    float* vd = p.vc + ((size_t)kvh * p.smax + pos) * HDIM;
+    float* vd = p.vc[0] + ((size_t)kvh * p.smax + pos) * HDIM;
     vd[lane] = v[lane];
     vd[lane + 64] = v[lane + 64];
   }
@@ -435,8 +463,8 @@ __global__ __launch_bounds__(256) void qattn_chunk_kernel(AttnP p) {
       for (int i = 0; i < 8; ++i) q[c * NREP + j][i] = qp[i], acc[c * NREP + j][i] = 0.f;
       m[c * NREP + j] = -INFINITY, l[c * NREP + j] = 0.f;
     }
-  const float* kb = p.kc + (size_t)kvh * p.smax * HDIM + dl * 8;
-  const float* vb = p.vc + (size_t)kvh * p.smax * HDIM + dl * 8;
+  const float* kb = p.kc[0] + (size_t)kvh * p.smax * HDIM + dl * 8;
+  const float* vb = p.vc[0] + (size_t)kvh * p.smax * HDIM + dl * 8;
   for (int key = lo + g; key < hi; key += 16) {
     const float4 k0 = *reinterpret_cast<const float4*>(kb + (size_t)key * HDIM);
     const float4 k1 = *reinterpret_cast<const float4*>(kb + (size_t)key * HDIM + 4);
@@ -496,6 +524,275 @@ __global__ __launch_bounds__(256) void qattn_chunk_kernel(AttnP p) {
   }
 }
 
+// ---- rows prefill (f16 engines): every prompt position of every slot of a batch is one row.  row_slot / row_pos name the
+// row's sequence and position; rows are packed in (slot, position) order, so a pass of at most rows_max rows finds the
+// keys of earlier passes in the cache.
+struct RowsP {
+  const int *row_slot, *row_pos;  // [M]
+  int M;
+};
+
+// x[row] = embedding row of the row's token (grid M)
+__global__ __launch_bounds__(256) void qrows_embed_kernel(RowsP r, const _Float16* emb, const int32_t* tokens, int tstride, int K, float* x) {
+  const int row = blockIdx.x;
+  const int tok = tokens[(size_t)r.row_slot[row] * tstride + r.row_pos[row]];
+  const _Float16* e = emb + (size_t)tok * K;
+  for (int k = threadIdx.x; k < K; k += 256) x[(size_t)row * K + k] = (float)e[k];
+}
+
+// Qwen3RMSNorm of each row (grid M): y = weight * (x * rsqrt(mean(x^2) + eps))
+__global__ __launch_bounds__(256) void qrows_norm_kernel(const float* x, const float* g, float eps, int K, float* y) {
+  __shared__ float red[4];
+  const int row = blockIdx.x, tid = threadIdx.x;
+  const float* xr = x + (size_t)row * K;
+  float ss = 0.f;
+  for (int k = tid; k < K; k += 256) ss = fmaf(xr[k], xr[k], ss);
+  ss = wave_sum(ss);
+  if ((tid & 63) == 0) red[tid >> 6] = ss;
+  __syncthreads();
+  const float rs = rsqrtf((red[0] + red[1] + red[2] + red[3]) / (float)K + eps);
+  for (int k = tid; k < K; k += 256) y[(size_t)row * K + k] = g[k] * (xr[k] * rs);
+}
+
+// GEMM of the rows: C[M][N] (+)= A[M][K] . W[N][K]^T, A fp32 rows, W the f16 arena in the layout the GEMVs stream.
+// Tile 64 x 128 x 64, 4 waves as 2 x 2, wave tile 32 x 64 on v_mfma_f32_32x32x16_f16.  The staging pass writes an A tile as two
+// f16 planes, hi = f16(a) and lo = f16(a - hi): f16 x f16 products are exact in the fp32 accumulator, so hi.W + lo.W
+// carries ~22 bits of the activation and the result differs from the GEMV path by the order of the sums (the
+// split-product idea of DESIGN.md 4.4 with the weight side already exact).  |a| saturates at the f16 maximum.  LDS rows
+// are padded to 144 bytes: the 16-byte fragment reads of 8 consecutive rows fall in 8 different bank groups.  The
+// global loads of k-tile i+1 are issued before the MFMAs of k-tile i and written to LDS after them.
+// RE_SWIGLU: N = intermediate size; W holds gate rows [0, N) then up rows [N, 2N); a workgroup computes 64 outputs, wave
+// column block j = 0 the gate and j = 1 the up of the same outputs, out = SiLU(gate) * up.
+enum { RE_STORE = 0, RE_ADD = 1, RE_SWIGLU = 2 };
+constexpr int RBM = 64, RBN = 128, RBK = 64, RPITCH = RBK + 8;  // pitch in halfs
+typedef float f32x16_t __attribute__((ext_vector_type(16)));
+typedef _Float16 h4_t __attribute__((ext_vector_type(4)));
+typedef float f32x4_t __attribute__((ext_vector_type(4)));
+
+struct RGemmP {
+  const float* A;     // [M][K]
+  const _Float16* W;  // [N][K] (RE_SWIGLU: [2N][K])
+  float* out;         // [M][N]
+  int M, N, K;
+};
+
+template <int EPI>
+__global__ __launch_bounds__(256) void qrows_gemm_kernel(RGemmP g) {
+  __shared__ __attribute__((aligned(16))) _Float16 Ah[RBM * RPITCH];
+  __shared__ __attribute__((aligned(16))) _Float16 Al[RBM * RPITCH];
+  __shared__ __attribute__((aligned(16))) _Float16 Ws[RBN * RPITCH];
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int wm = wave >> 1, wn = wave & 1;
+  const int l31 = lane & 31, lh = lane >> 5;
+  const int m0 = blockIdx.y * RBM;
+  const int n0 = blockIdx.x * (EPI == RE_SWIGLU ? RBN / 2 : RBN);
+
+  f32x16_t acc[2];
+#pragma unroll
+  for (int j = 0; j < 2; ++j)
+#pragma unroll
+    for (int r = 0; r < 16; ++r) acc[j][r] = 0.f;
+
+  constexpr int NA = RBM * RBK / 4 / 256;  // float4 of A per thread per k-tile
+  constexpr int NW = RBN * RBK / 8 / 256;  // 16-byte pieces of W per thread
+  constexpr int AC = RBK / 4, WC = RBK / 8;
+  const float* asrc[NA];
+  const _Float16* wsrc[NW];
+#pragma unroll
+  for (int i = 0; i < NA; ++i) {
+    const int idx = tid + i * 256;
+    asrc[i] = g.A + (size_t)min(m0 + idx / AC, g.M - 1) * g.K + (idx % AC) * 4;  // rows beyond M repeat the last one; never stored
+  }
+#pragma unroll
+  for (int i = 0; i < NW; ++i) {
+    const int idx = tid + i * 256;
+    const int t = idx / WC;
+    int row;
+    if constexpr (EPI == RE_SWIGLU) row = ((t >> 5) & 1) * g.N + min(n0 + (t >> 6) * 32 + (t & 31), g.N - 1);
+    else row = min(n0 + t, g.N - 1);
+    wsrc[i] = g.W + (size_t)row * g.K + (idx % WC) * 8;
+  }
+  f32x4_t aR[NA];
+  u32x4_t wR[NW];
+  auto stage_load = [&](int k0) {
+#pragma unroll
+    for (int i = 0; i < NA; ++i) aR[i] = *reinterpret_cast<const f32x4_t*>(asrc[i] + k0);
+#pragma unroll
+    for (int i = 0; i < NW; ++i) wR[i] = *reinterpret_cast<const u32x4_t*>(wsrc[i] + k0);
+  };
+  auto stage_write = [&]() {
+#pragma unroll
+    for (int i = 0; i < NA; ++i) {
+      const int idx = tid + i * 256;
+      const int o = (idx / AC) * RPITCH + (idx % AC) * 4;
+      h4_t hi, lo;
+#pragma unroll
+      for (int e = 0; e < 4; ++e) {
+        float c = fminf(fmaxf(aR[i][e], -65504.f), 65504.f);
+        if (aR[i][e] != aR[i][e]) c = aR[i][e];  // fminf / fmaxf drop a NaN: keep it, so the step's non-finite stop sees it
+        hi[e] = (_Float16)c;
+        lo[e] = (_Float16)(c - (float)hi[e]);
+      }
+      *reinterpret_cast<uint2*>(Ah + o) = __builtin_bit_cast(uint2, hi);
+      *reinterpret_cast<uint2*>(Al + o) = __builtin_bit_cast(uint2, lo);
+    }
+#pragma unroll
+    for (int i = 0; i < NW; ++i) {
+      const int idx = tid + i * 256;
+      *reinterpret_cast<u32x4_t*>(Ws + (idx / WC) * RPITCH + (idx % WC) * 8) = wR[i];
+    }
+  };
+
+  const int nkt = g.K / RBK;
+  stage_load(0);
+  for (int kt = 0; kt < nkt; ++kt) {
+    __syncthreads();  // every wave is done with the previous k-tile
+    stage_write();
+    __syncthreads();
+    stage_load(min(kt + 1, nkt - 1) * RBK);
+#pragma unroll
+    for (int kk = 0; kk < RBK; kk += 16) {
+      const h8_t ahi = *reinterpret_cast<const h8_t*>(Ah + (wm * 32 + l31) * RPITCH + kk + lh * 8);
+      const h8_t alo = *reinterpret_cast<const h8_t*>(Al + (wm * 32 + l31) * RPITCH + kk + lh * 8);
+#pragma unroll
+      for (int j = 0; j < 2; ++j) {
+        const h8_t b = *reinterpret_cast<const h8_t*>(Ws + (wn * 64 + j * 32 + l31) * RPITCH + kk + lh * 8);
+        acc[j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(ahi, b, acc[j], 0, 0, 0);
+        acc[j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(alo, b, acc[j], 0, 0, 0);
+      }
+    }
+  }
+  // ---- epilogue (C layout: col = lane & 31 -> n, row = (r & 3) + 8 (r >> 2) + 4 (lane >> 5) -> m)
+  if constexpr (EPI == RE_SWIGLU) {
+    const int o = n0 + wn * 32 + l31;
+#pragma unroll
+    for (int r = 0; r < 16; ++r) {
+      const int m = m0 + wm * 32 + (r & 3) + 8 * (r >> 2) + 4 * lh;
+      const float gt = acc[0][r], up = acc[1][r];
+      if (m < g.M && o < g.N) g.out[(size_t)m * g.N + o] = gt / (1.f + expf(-gt)) * up;
+    }
+  } else {
+    // loads first, all of them, indices clamped; only the stores are predicated
+    float old[2][16];
+    if constexpr (EPI == RE_ADD) {
+#pragma unroll
+      for (int j = 0; j < 2; ++j)
+#pragma unroll
+        for (int r = 0; r < 16; ++r) {
+          const int m = min(m0 + wm * 32 + (r & 3) + 8 * (r >> 2) + 4 * lh, g.M - 1);
+          old[j][r] = g.out[(size_t)m * g.N + min(n0 + wn * 64 + j * 32 + l31, g.N - 1)];
+        }
+    }
+#pragma unroll
+    for (int j = 0; j < 2; ++j) {
+      const int n = n0 + wn * 64 + j * 32 + l31;
+#pragma unroll
+      for (int r = 0; r < 16; ++r) {
+        const int m = m0 + wm * 32 + (r & 3) + 8 * (r >> 2) + 4 * lh;
+        if (m >= g.M || n >= g.N) continue;
+        if constexpr (EPI == RE_ADD) g.out[(size_t)m * g.N + n] = old[j][r] + acc[j][r];
+        else g.out[(size_t)m * g.N + n] = acc[j][r];
+      }
+    }
+  }
+}
+
+// q_norm / k_norm + RoPE at the row's position, K/V appended to the row's slot cache: grid (M, heads + kv_heads), one wave each
+struct RowsAttnP {
+  RowsP r;
+  const float* qkv;  // [M][heads*HDIM | kv_heads*HDIM | kv_heads*HDIM]
+  const float *qn, *kn, *cosb, *sinb;
+  float *kc[MAXS], *vc[MAXS];  // this layer's cache of each slot
+  float* qb;   // [M][heads][HDIM]
+  float* att;  // [M][heads][HDIM]
+  int heads, kv_heads, smax;
+  float eps, scale;
+};
+
+__global__ __launch_bounds__(64) void qrows_prep_kernel(RowsAttnP p) {
+  const int row = blockIdx.x, hh = blockIdx.y, lane = threadIdx.x;
+  const int slot = p.r.row_slot[row], pos = p.r.row_pos[row];
+  const float* cs = p.cosb + (size_t)pos * (HDIM / 2);
+  const float* sn = p.sinb + (size_t)pos * (HDIM / 2);
+  const int qdim = p.heads * HDIM, kvdim = p.kv_heads * HDIM;
+  const float* x = p.qkv + (size_t)row * (qdim + 2 * kvdim);
+  if (hh < p.heads) {
+    norm_rope_head(x + (size_t)hh * HDIM, p.qn, cs, sn, p.eps, true, lane, p.qb + ((size_t)row * p.heads + hh) * HDIM);
+  } else {
+    const int kvh = hh - p.heads;
+    norm_rope_head(x + qdim + (size_t)kvh * HDIM, p.kn, cs, sn, p.eps, true, lane, pick_slot(p.kc, slot) + ((size_t)kvh * p.smax + pos) * HDIM);
+    const float* v = x + qdim + kvdim + (size_t)kvh * HDIM;
+    float* vd = pick_slot(p.vc, slot) + ((size_t)kvh * p.smax + pos) * HDIM;
+    vd[lane] = v[lane];
+    vd[lane + 64] = v[lane + 64];
+  }
+}
+
+// causal attention of the rows, grid (kv_heads, M): row (s, pos) and its NREP query heads over keys 0..pos of slot s (fp32,
+// the lane layout and the online softmax of qattn_kernel; the 16 lane groups are merged and normalised here)
+template <int NREP>
+__global__ __launch_bounds__(256) void qrows_attn_kernel(RowsAttnP p) {
+  __shared__ float gm[16][NREP], gl[16][NREP];
+  __shared__ __attribute__((aligned(16))) float gacc[16][NREP][HDIM];
+  const int kvh = blockIdx.x, row = blockIdx.y, tid = threadIdx.x;
+  const int slot = p.r.row_slot[row], pos = p.r.row_pos[row];
+  const int g = tid >> 4, dl = tid & 15;
+  float q[NREP][8], m[NREP], l[NREP], acc[NREP][8];
+#pragma unroll
+  for (int j = 0; j < NREP; ++j) {
+    const float* qp = p.qb + ((size_t)row * p.heads + kvh * NREP + j) * HDIM + dl * 8;
+    m[j] = -INFINITY, l[j] = 0.f;
+#pragma unroll
+    for (int i = 0; i < 8; ++i) q[j][i] = qp[i], acc[j][i] = 0.f;
+  }
+  const float* kb = pick_slot(p.kc, slot) + (size_t)kvh * p.smax * HDIM + dl * 8;
+  const float* vb = pick_slot(p.vc, slot) + (size_t)kvh * p.smax * HDIM + dl * 8;
+  for (int key = g; key <= pos; key += 16) {
+    const float4 k0 = *reinterpret_cast<const float4*>(kb + (size_t)key * HDIM);
+    const float4 k1 = *reinterpret_cast<const float4*>(kb + (size_t)key * HDIM + 4);
+    const float4 v0 = *reinterpret_cast<const float4*>(vb + (size_t)key * HDIM);
+    const float4 v1 = *reinterpret_cast<const float4*>(vb + (size_t)key * HDIM + 4);
+    const float kv[8] = {k0.x, k0.y, k0.z, k0.w, k1.x, k1.y, k1.z, k1.w};
+    const float vv[8] = {v0.x, v0.y, v0.z, v0.w, v1.x, v1.y, v1.z, v1.w};
+#pragma unroll
+    for (int j = 0; j < NREP; ++j) {
+      float d = 0.f;
+#pragma unroll
+      for (int i = 0; i < 8; ++i) d = fmaf(q[j][i], kv[i], d);
+#pragma unroll
+      for (int o = 1; o < 16; o <<= 1) d += __shfl_xor(d, o, 64);
+      const float sc = d * p.scale;
+      const float mn = fmaxf(m[j], sc);
+      const float a = expf(m[j] - mn), e = expf(sc - mn);
+      l[j] = fmaf(l[j], a, e);
+#pragma unroll
+      for (int i = 0; i < 8; ++i) acc[j][i] = fmaf(acc[j][i], a, e * vv[i]);
+      m[j] = mn;
+    }
+  }
+#pragma unroll
+  for (int j = 0; j < NREP; ++j) {
+    if (dl == 0) gm[g][j] = m[j], gl[g][j] = l[j];
+#pragma unroll
+    for (int i = 0; i < 8; ++i) gacc[g][j][dl * 8 + i] = acc[j][i];
+  }
+  __syncthreads();
+  for (int t = tid; t < NREP * HDIM; t += 256) {
+    const int j = t / HDIM, d = t % HDIM;
+    float M = -INFINITY;
+#pragma unroll
+    for (int gg = 0; gg < 16; ++gg) M = fmaxf(M, gm[gg][j]);
+    float o = 0.f, L = 0.f;
+#pragma unroll
+    for (int gg = 0; gg < 16; ++gg) {
+      const float e = gm[gg][j] == -INFINITY ? 0.f : expf(gm[gg][j] - M);  // key 0 always exists: M is finite
+      o = fmaf(e, gacc[gg][j][d], o);
+      L = fmaf(e, gl[gg][j], L);
+    }
+    p.att[((size_t)row * p.heads + kvh * NREP + j) * HDIM + d] = o / L;
+  }
+}
+
 // ---- token selection
 // order: larger value first, then the lower id (the argmax tie rule of this project)
 __device__ __forceinline__ bool before(float a, int ia, float b, int ib) { return a > b || (a == b && ia < ib); }
@@ -519,11 +816,12 @@ __device__ void bitonic_sort(float* v, int* id, int n) {
     }
 }
 
-// pass 1: workgroup b takes logits [b*chunk, (b+1)*chunk) and writes its best kc (value, id) pairs in order
+// pass 1, grid (SAMP_WG, slots): workgroup b takes logits [b*chunk, (b+1)*chunk) of its slot and writes its best kc (value, id) pairs in order
 __global__ __launch_bounds__(256) void qsamp_a_kernel(const float* logits, int V, int chunk, const SampDev* sd, float* cv, int* ci) {
   __shared__ float v[SAMP_CHUNK];
   __shared__ int id[SAMP_CHUNK];
   const int kc = sd->kc;
+  logits += (size_t)blockIdx.y * V, cv += (size_t)blockIdx.y * SAMP_WG * KC_MAX, ci += (size_t)blockIdx.y * SAMP_WG * KC_MAX;  // this slot's
   const int b = blockIdx.x, tid = threadIdx.x;
   const int beg = b * chunk, end = min(V, beg + chunk);
   if (kc == 1) {
@@ -555,7 +853,7 @@ __global__ __launch_bounds__(256) void qsamp_a_kernel(const float* logits, int V
   for (int i = tid; i < kc; i += 256) cv[b * KC_MAX + i] = v[i], ci[b * KC_MAX + i] = id[i];
 }
 
-struct SeqDev {
+struct SeqDev {  // slot 0's; slot z is z * tstride tokens, z ints and z * KC_MAX kept entries further on
   int32_t* tokens;  // [max_seq + 1]: prompt, then generated
   int* cur_len;     // position the next step forwards
   int* gen_count;
@@ -565,6 +863,7 @@ struct SeqDev {
   int32_t* kept_id;  // [KC_MAX]
   float* kept_p;
   int* n_kept;
+  int tstride;
 };
 
 __device__ __forceinline__ int pick(const int32_t* ids, const float* pr, int n, float u) {
@@ -576,12 +875,15 @@ __device__ __forceinline__ int pick(const int32_t* ids, const float* pr, int n, 
   return ids[n - 1];
 }
 
-// pass 2 (one workgroup): the best top_k of the candidates, temperature, top-p, the draw; moves the sequence
+// pass 2 (one workgroup per slot): the best top_k of the candidates, temperature, top-p, the draw; moves the sequence
 __global__ __launch_bounds__(1024) void qsamp_b_kernel(const float* cv, const int* ci, const SampDev* sd, SeqDev s) {
   __shared__ float v[SAMP_WG * KC_MAX];
   __shared__ int id[SAMP_WG * KC_MAX];
   __shared__ float e[KC_MAX];
-  const int kc = sd->kc, tid = threadIdx.x;
+  const int kc = sd->kc, tid = threadIdx.x, z = blockIdx.x;
+  cv += (size_t)z * SAMP_WG * KC_MAX, ci += (size_t)z * SAMP_WG * KC_MAX;
+  s.tokens += (size_t)z * s.tstride, s.cur_len += z, s.gen_count += z, s.finished += z, s.n_kept += z;
+  s.kept_id += z * KC_MAX, s.kept_p += z * KC_MAX;
   if (*s.finished) return;  // block-uniform
   const int n = SAMP_WG * kc;  // a power of two
   for (int i = tid; i < n; i += 1024) {
@@ -686,14 +988,24 @@ struct ixtts_qwen {
   SampDev* d_samp = nullptr;
   SampDev samp_host;
   hipStream_t cap_stream = nullptr;
-  hipGraphExec_t full_exec[2] = {}, pre_exec[2] = {}, chunk_exec[2] = {};  // [0] one step, [1] STEPS_PER_GRAPH steps
+  // [0] one step, [1] STEPS_PER_GRAPH steps; pre / chunk per slot (f32 engines prefill slot after slot), slots_exec[n - 2]
+  hipGraphExec_t full_exec[2] = {}, pre_exec[MAXS][2] = {}, chunk_exec[MAXS][2] = {}, slots_exec[MAXS - 1][2] = {};
   float* qb = nullptr;  // [PCH][heads][HDIM]
-  int prompt_len = 0;
+  // slots: tokens, cur_len, gen_count, finished, n_kept, kept_*, logits, cv / ci hold MAXS entries from create on (slot 0
+  // first); the K/V caches of slots 1.. and the buffers of the rows prefill come with the first batched call
+  int n_slots = 1, rows_max = 1024;
+  int plen[MAXS] = {};  // prompt length per slot
+  float *kcs[MAXS] = {}, *vcs[MAXS] = {};
+  float *rx = nullptr, *rxn = nullptr, *rqkv = nullptr, *rqb = nullptr, *ratt = nullptr, *rff = nullptr;
+  int *row_slot = nullptr, *row_pos = nullptr;
+  int tstride() const { return smax + 1; }
 };
 
 #define Q_ARENA(off) reinterpret_cast<void*>(h->arena + (off))
 
-static int q_launch_gemv(ixtts_qwen* h, int pro, int epi, GemvP p, hipStream_t st, int nc = 1) {
+static int q_launch_gemv(ixtts_qwen* h, int pro, int epi, GemvP p, hipStream_t st, int nc = 1, int nact = 0) {
+  p.tstride = h->tstride();
+  p.nact = nact ? nact : nc;
   const int rows = p.N > 16384 && nc == 1 ? 4 : 2;
   const int outs = epi == EPI_SWIGLU ? rows / 2 : rows;
   const int units = (p.N + outs - 1) / outs;
@@ -702,6 +1014,7 @@ static int q_launch_gemv(ixtts_qwen* h, int pro, int epi, GemvP p, hipStream_t s
 #define Q_GEMV(WT, PRO, EPI)                                                                            \
   do {                                                                                                  \
     if (nc == PCH) hipLaunchKernelGGL((qgemv_kernel<WT, PRO, EPI, 2, PCH>), grid, block, lds, st, p);  \
+    else if (nc == 2) hipLaunchKernelGGL((qgemv_kernel<WT, PRO, EPI, 2, 2>), grid, block, lds, st, p); \
     else if (rows == 4) hipLaunchKernelGGL((qgemv_kernel<WT, PRO, EPI, 4, 1>), grid, block, lds, st, p); \
     else hipLaunchKernelGGL((qgemv_kernel<WT, PRO, EPI, 2, 1>), grid, block, lds, st, p);              \
   } while (0)
@@ -724,28 +1037,40 @@ static int q_launch_gemv(ixtts_qwen* h, int pro, int epi, GemvP p, hipStream_t s
   return IXTTS_OK;
 }
 
-enum { STEP_PRE = 0, STEP_FULL = 1, STEP_CHUNK = 2 };
+enum { STEP_PRE = 0, STEP_FULL = 1, STEP_CHUNK = 2, STEP_SLOTS = 3 };
 
 // STEP_PRE: one prompt position through the layers, the position moves on; STEP_FULL: the same, then norm + lm_head + token
-// selection; STEP_CHUNK: PCH prompt positions through the layers with one pass over the weights, the position moves PCH on
-static int q_issue_step(ixtts_qwen* h, int mode, hipStream_t st) {
+// selection; STEP_CHUNK: PCH prompt positions through the layers with one pass over the weights, the position moves PCH on.
+// These three act on slot `arg`.  STEP_SLOTS: one decode step (as STEP_FULL) of slots 0..arg-1, column c = slot c; the
+// GEMVs are built 2 and PCH columns wide, so a step of 3 slots carries an idle 4th column: it reads slot 3's (valid) token
+// and stores nothing (GemvP::nact), and it has no attention and no token selection: slot 3 is left as it is, logits included.
+static int q_issue_step(ixtts_qwen* h, int mode, hipStream_t st, int arg = 0) {
   const int D = h->D, qd = h->H * HDIM, kvd = h->KVH * HDIM;
   const float eps = h->cfg.rms_norm_eps;
-  const bool full = mode == STEP_FULL;
-  const int nc = mode == STEP_CHUNK ? PCH : 1;
+  const bool slots = mode == STEP_SLOTS;
+  const bool full = mode == STEP_FULL || slots;
+  const int nc = mode == STEP_CHUNK ? PCH : slots ? (arg <= 2 ? 2 : PCH) : 1;
+  const int ns = slots ? arg : 1, s0 = slots ? 0 : arg;
+  const int nact = slots ? ns : nc;
+  int32_t* const tokens = h->tokens + (size_t)s0 * h->tstride();
+  int* const cur_len = h->cur_len + s0;
   for (int l = 0; l < h->L; ++l) {
     const LW& w = h->lw[l];
     GemvP a = {};
     a.w = Q_ARENA(w.wqkv), a.N = qd + 2 * kvd, a.K = D, a.x = h->h, a.g = (const float*)Q_ARENA(w.ln1), a.eps = eps, a.out = h->qkv;
-    a.emb = Q_ARENA(h->emb), a.tokens = h->tokens, a.cur_len = h->cur_len, a.h_out = h->h;
-    IX_TRY(q_launch_gemv(h, l == 0 ? PRO_EMBED : PRO_NORM, EPI_STORE, a, st, nc));
+    a.emb = Q_ARENA(h->emb), a.tokens = tokens, a.cur_len = cur_len, a.h_out = h->h, a.slots = slots;
+    IX_TRY(q_launch_gemv(h, l == 0 ? PRO_EMBED : PRO_NORM, EPI_STORE, a, st, nc, nact));
     AttnP at;
     at.qkv = h->qkv, at.qn = (const float*)Q_ARENA(w.qn), at.kn = (const float*)Q_ARENA(w.kn), at.cosb = h->cosb, at.sinb = h->sinb;
-    at.kc = h->kc + (size_t)l * h->KVH * h->smax * HDIM, at.vc = h->vc + (size_t)l * h->KVH * h->smax * HDIM;
-    at.cur_len = h->cur_len, at.part = h->part, at.heads = h->H, at.kv_heads = h->KVH, at.smax = h->smax, at.eps = eps;
+    for (int z = 0; z < MAXS; ++z) {
+      const int sl = std::min(s0 + z, h->n_slots - 1);
+      at.kc[z] = h->kcs[sl] ? h->kcs[sl] + (size_t)l * h->KVH * h->smax * HDIM : nullptr;
+      at.vc[z] = h->vcs[sl] ? h->vcs[sl] + (size_t)l * h->KVH * h->smax * HDIM : nullptr;
+    }
+    at.cur_len = cur_len, at.finished = slots ? h->finished : nullptr, at.part = h->part, at.heads = h->H, at.kv_heads = h->KVH, at.smax = h->smax, at.eps = eps;
     at.scale = 1.f / sqrtf((float)HDIM), at.qb = h->qb;
-    const dim3 ag(h->KVH, NSP);
-    if (nc == PCH) {
+    const dim3 ag(h->KVH, NSP, ns);
+    if (mode == STEP_CHUNK) {
       hipLaunchKernelGGL(qprep_kernel, dim3(PCH, h->H + h->KVH), dim3(64), 0, st, at);
       if (h->nrep == 1) hipLaunchKernelGGL(qattn_chunk_kernel<1>, ag, dim3(256), 0, st, at);
       else if (h->nrep == 2) hipLaunchKernelGGL(qattn_chunk_kernel<2>, ag, dim3(256), 0, st, at);
@@ -755,34 +1080,35 @@ static int q_issue_step(ixtts_qwen* h, int mode, hipStream_t st) {
     else hipLaunchKernelGGL(qattn_kernel<4>, ag, dim3(256), 0, st, at);
     GemvP o = {};
     o.w = Q_ARENA(w.wo), o.N = D, o.K = qd, o.out = h->h, o.part = h->part;
-    IX_TRY(q_launch_gemv(h, PRO_MERGE, EPI_ADD, o, st, nc));
+    IX_TRY(q_launch_gemv(h, PRO_MERGE, EPI_ADD, o, st, nc, nact));
     GemvP gu = {};
     gu.w = Q_ARENA(w.wgu), gu.N = h->I, gu.K = D, gu.x = h->h, gu.g = (const float*)Q_ARENA(w.ln2), gu.eps = eps, gu.out = h->ff;
-    IX_TRY(q_launch_gemv(h, PRO_NORM, EPI_SWIGLU, gu, st, nc));
+    IX_TRY(q_launch_gemv(h, PRO_NORM, EPI_SWIGLU, gu, st, nc, nact));
     GemvP dn = {};
     dn.w = Q_ARENA(w.wd), dn.N = D, dn.K = h->I, dn.x = h->ff, dn.out = h->h;
-    dn.advance = (!full && l == h->L - 1) ? h->cur_len : nullptr;
-    IX_TRY(q_launch_gemv(h, PRO_PLAIN, EPI_ADD, dn, st, nc));
+    dn.advance = (!full && l == h->L - 1) ? cur_len : nullptr;
+    IX_TRY(q_launch_gemv(h, PRO_PLAIN, EPI_ADD, dn, st, nc, nact));
   }
   if (full) {
     GemvP hd = {};
     hd.w = Q_ARENA(h->lmh), hd.N = h->V, hd.K = D, hd.x = h->h, hd.g = (const float*)Q_ARENA(h->fnorm), hd.eps = eps, hd.out = h->logits;
-    IX_TRY(q_launch_gemv(h, PRO_NORM, EPI_STORE, hd, st));
+    IX_TRY(q_launch_gemv(h, PRO_NORM, EPI_STORE, hd, st, nc, nact));
     const int chunk = (h->V + SAMP_WG - 1) / SAMP_WG;
-    hipLaunchKernelGGL(qsamp_a_kernel, dim3(SAMP_WG), dim3(256), 0, st, h->logits, h->V, chunk, h->d_samp, h->cv, h->ci);
-    SeqDev s{h->tokens, h->cur_len, h->gen_count, h->finished, h->eos, h->cfg.n_eos, h->smax, h->V, h->kept_id, h->kept_p, h->n_kept};
-    hipLaunchKernelGGL(qsamp_b_kernel, dim3(1), dim3(1024), 0, st, h->cv, h->ci, h->d_samp, s);
+    hipLaunchKernelGGL(qsamp_a_kernel, dim3(SAMP_WG, ns), dim3(256), 0, st, h->logits, h->V, chunk, h->d_samp, h->cv, h->ci);
+    SeqDev s{h->tokens, h->cur_len, h->gen_count, h->finished, h->eos, h->cfg.n_eos, h->smax, h->V, h->kept_id, h->kept_p, h->n_kept,
+             h->tstride()};
+    hipLaunchKernelGGL(qsamp_b_kernel, dim3(ns), dim3(1024), 0, st, h->cv, h->ci, h->d_samp, s);
   }
   IX_HIP(hipGetLastError());
   return IXTTS_OK;
 }
 
-static int q_graph(ixtts_qwen* h, int mode, int reps, hipGraphExec_t* out) {
+static int q_graph(ixtts_qwen* h, int mode, int reps, hipGraphExec_t* out, int arg) {
   hipGraph_t g;
   hipStream_t cs = h->cap_stream;
   IX_HIP(hipStreamBeginCapture(cs, hipStreamCaptureModeThreadLocal));
   int rc = IXTTS_OK;
-  for (int r = 0; r < reps && rc == IXTTS_OK; ++r) rc = q_issue_step(h, mode, cs);
+  for (int r = 0; r < reps && rc == IXTTS_OK; ++r) rc = q_issue_step(h, mode, cs, arg);
   hipError_t e = hipStreamEndCapture(cs, &g);
   if (rc != IXTTS_OK) return rc;
   IX_HIP(e);
@@ -791,11 +1117,14 @@ static int q_graph(ixtts_qwen* h, int mode, int reps, hipGraphExec_t* out) {
   return IXTTS_OK;
 }
 
-static int q_run(ixtts_qwen* h, int mode, int n, hipStream_t st) {
+static int q_run(ixtts_qwen* h, int mode, int n, hipStream_t st, int arg = 0) {
   for (int done = 0; done < n;) {
     const int big = n - done >= STEPS_PER_GRAPH ? 1 : 0;
-    hipGraphExec_t* slot = mode == STEP_FULL ? &h->full_exec[big] : mode == STEP_CHUNK ? &h->chunk_exec[big] : &h->pre_exec[big];
-    if (!*slot) IX_TRY(q_graph(h, mode, big ? STEPS_PER_GRAPH : 1, slot));
+    hipGraphExec_t* slot = mode == STEP_FULL    ? &h->full_exec[big]
+                           : mode == STEP_CHUNK ? &h->chunk_exec[arg][big]
+                           : mode == STEP_PRE   ? &h->pre_exec[arg][big]
+                                                : &h->slots_exec[arg - 2][big];
+    if (!*slot) IX_TRY(q_graph(h, mode, big ? STEPS_PER_GRAPH : 1, slot, arg));
     IX_HIP(hipGraphLaunch(*slot, st));
     done += big ? STEPS_PER_GRAPH : 1;
   }
@@ -814,19 +1143,30 @@ static int q_run(ixtts_qwen* h, int mode, int n, hipStream_t st) {
 static void q_free(ixtts_qwen* h) {
   for (int i = 0; i < 2; ++i) {
     if (h->full_exec[i]) hipGraphExecDestroy(h->full_exec[i]);
-    if (h->pre_exec[i]) hipGraphExecDestroy(h->pre_exec[i]);
-    if (h->chunk_exec[i]) hipGraphExecDestroy(h->chunk_exec[i]);
+    for (int z = 0; z < MAXS; ++z) {
+      if (h->pre_exec[z][i]) hipGraphExecDestroy(h->pre_exec[z][i]);
+      if (h->chunk_exec[z][i]) hipGraphExecDestroy(h->chunk_exec[z][i]);
+      if (z < MAXS - 1 && h->slots_exec[z][i]) hipGraphExecDestroy(h->slots_exec[z][i]);
+    }
   }
   void* ptrs[] = {h->arena, h->h, h->qkv, h->part, h->ff, h->logits, h->kc, h->vc, h->cosb, h->sinb, h->cv, h->kept_p, h->tmp, h->qb, h->ci,
-                  h->cur_len, h->gen_count, h->finished, h->n_kept, h->eos, h->tokens, h->kept_id, h->draws, h->d_samp};
+                  h->cur_len, h->gen_count, h->finished, h->n_kept, h->eos, h->tokens, h->kept_id, h->draws, h->d_samp,
+                  h->rx, h->rxn, h->rqkv, h->rqb, h->ratt, h->rff, h->row_slot, h->row_pos};
   for (void* p : ptrs)
     if (p) hipFree(p);
+  for (int z = 1; z < MAXS; ++z) {  // [0] are kc / vc
+    if (h->kcs[z]) hipFree(h->kcs[z]);
+    if (h->vcs[z]) hipFree(h->vcs[z]);
+  }
   if (h->cap_stream) hipStreamDestroy(h->cap_stream);
 }
 
-extern "C" int ixtts_qwen_create(ixtts_qwen** out, const ixtts_qwen_cfg* c) {
+extern "C" int ixtts_qwen_create(ixtts_qwen** out, const ixtts_qwen_cfg* c) { return ixtts_qwen_create_slots(out, c, 1); }
+
+extern "C" int ixtts_qwen_create_slots(ixtts_qwen** out, const ixtts_qwen_cfg* c, int n_slots) {
   IX_ARG(out && c, "qwen_create: null argument");
   *out = nullptr;
+  IX_ARG(n_slots >= 1 && n_slots <= MAXS, "qwen_create: %d slots (1..%d)", n_slots, MAXS);
   IX_ARG(c->head_dim == HDIM, "qwen_create: head_dim %d (only %d is built)", c->head_dim, HDIM);
   IX_ARG(c->layers >= 1 && c->heads >= 1 && c->kv_heads >= 1 && c->heads % c->kv_heads == 0, "qwen_create: heads %d / kv_heads %d", c->heads,
          c->kv_heads);
@@ -848,6 +1188,16 @@ extern "C" int ixtts_qwen_create(ixtts_qwen** out, const ixtts_qwen_cfg* c) {
   h->D = c->hidden_size, h->L = c->layers, h->H = c->heads, h->KVH = c->kv_heads, h->I = c->intermediate_size, h->V = c->vocab_size;
   h->smax = c->max_seq, h->nrep = nrep, h->f16 = c->weight_dtype == IXTTS_DTYPE_F16;
   h->esz = h->f16 ? 2 : 4;
+  h->n_slots = n_slots;
+  if (const char* e = getenv("IXTTS_QWEN_ROWS_MAX")) {  // tests: several passes of the rows prefill without long prompts
+    const int v = atoi(e);
+    if (v < 1 || v > 65536) {
+      set_error("qwen_create: IXTTS_QWEN_ROWS_MAX=%s (1..65536)", e);
+      delete h;
+      return IXTTS_ERR_ARG;
+    }
+    h->rows_max = v;
+  }
   // ---- arena layout: matrices in the weight dtype, vectors fp32; every tensor 256-byte aligned
   size_t off = 0;
   const int D = h->D, qd = h->H * HDIM, kvd = h->KVH * HDIM;
@@ -907,25 +1257,27 @@ extern "C" int ixtts_qwen_create(ixtts_qwen** out, const ixtts_qwen_cfg* c) {
   al((void**)&h->part, (size_t)PCH * h->H * NSP * PSTR * 4);
   al((void**)&h->ff, (size_t)PCH * h->I * 4);
   al((void**)&h->qb, (size_t)PCH * qd * 4);
-  al((void**)&h->logits, (size_t)h->V * 4);
+  al((void**)&h->logits, (size_t)MAXS * h->V * 4);
   al((void**)&h->kc, kv * 4);
   al((void**)&h->vc, kv * 4);
   al((void**)&h->cosb, (size_t)h->smax * (HDIM / 2) * 4);
   al((void**)&h->sinb, (size_t)h->smax * (HDIM / 2) * 4);
-  al((void**)&h->cv, (size_t)SAMP_WG * KC_MAX * 4);
-  al((void**)&h->ci, (size_t)SAMP_WG * KC_MAX * 4);
-  al((void**)&h->kept_id, (size_t)KC_MAX * 4);
-  al((void**)&h->kept_p, (size_t)KC_MAX * 4);
-  al((void**)&h->tokens, (size_t)(h->smax + 1) * 4);
-  al((void**)&h->cur_len, 4);
-  al((void**)&h->gen_count, 4);
-  al((void**)&h->finished, 4);
-  al((void**)&h->n_kept, 4);
+  al((void**)&h->cv, (size_t)MAXS * SAMP_WG * KC_MAX * 4);
+  al((void**)&h->ci, (size_t)MAXS * SAMP_WG * KC_MAX * 4);
+  al((void**)&h->kept_id, (size_t)MAXS * KC_MAX * 4);
+  al((void**)&h->kept_p, (size_t)MAXS * KC_MAX * 4);
+  al((void**)&h->tokens, (size_t)MAXS * (h->smax + 1) * 4);
+  al((void**)&h->cur_len, MAXS * 4);
+  al((void**)&h->gen_count, MAXS * 4);
+  al((void**)&h->finished, MAXS * 4);
+  al((void**)&h->n_kept, MAXS * 4);
+  h->kcs[0] = h->kc, h->vcs[0] = h->vc;
   al((void**)&h->eos, (size_t)IXTTS_QWEN_MAX_EOS * 4);
   al((void**)&h->d_samp, sizeof(SampDev));
   if (rc == IXTTS_OK && (hipMemset(h->kc, 0, kv * 4) != hipSuccess || hipMemset(h->vc, 0, kv * 4) != hipSuccess ||
-                         hipMemset(h->tokens, 0, (size_t)(h->smax + 1) * 4) != hipSuccess || hipMemset(h->cur_len, 0, 4) != hipSuccess ||
-                         hipMemset(h->gen_count, 0, 4) != hipSuccess || hipMemset(h->n_kept, 0, 4) != hipSuccess ||
+                         hipMemset(h->tokens, 0, (size_t)MAXS * (h->smax + 1) * 4) != hipSuccess ||
+                         hipMemset(h->cur_len, 0, MAXS * 4) != hipSuccess || hipMemset(h->gen_count, 0, MAXS * 4) != hipSuccess ||
+                         hipMemset(h->n_kept, 0, MAXS * 4) != hipSuccess || hipMemset(h->logits, 0, (size_t)MAXS * h->V * 4) != hipSuccess ||
                          hipMemcpy(h->eos, c->eos_ids, (size_t)c->n_eos * 4, hipMemcpyHostToDevice) != hipSuccess ||
                          hipStreamCreateWithFlags(&h->cap_stream, hipStreamNonBlocking) != hipSuccess)) {
     set_error("qwen_create: device initialisation failed");
@@ -933,8 +1285,8 @@ extern "C" int ixtts_qwen_create(ixtts_qwen** out, const ixtts_qwen_cfg* c) {
   }
   if (rc == IXTTS_OK) {
     // finished = 1 until a prefill: a step before it changes nothing
-    const int one = 1;
-    if (hipMemcpy(h->finished, &one, 4, hipMemcpyHostToDevice) != hipSuccess) rc = IXTTS_ERR_HIP;
+    const int one[MAXS] = {1, 1, 1, 1};
+    if (hipMemcpy(h->finished, one, sizeof(one), hipMemcpyHostToDevice) != hipSuccess) rc = IXTTS_ERR_HIP;
   }
   if (rc == IXTTS_OK) {
     // RoPE tables as HF builds them: inv_freq = 1 / theta^(2i/d) in fp32, angle = fp32(pos * inv_freq), cos/sin of it
@@ -1037,7 +1389,7 @@ extern "C" int ixtts_qwen_prefill(ixtts_qwen* h, const int32_t* ids, int n, void
   IX_HIP(hipMemsetAsync(h->finished, 0, 4, st));
   IX_HIP(hipMemsetAsync(h->n_kept, 0, 4, st));
   IX_HIP(hipStreamSynchronize(st));
-  h->prompt_len = n;
+  h->plen[0] = n;
   // the first n-1 positions: PCH per weight pass, the rest one by one
   IX_TRY(q_run(h, STEP_CHUNK, (n - 1) / PCH, st));
   IX_TRY(q_run(h, STEP_PRE, (n - 1) % PCH, st));
@@ -1047,40 +1399,47 @@ extern "C" int ixtts_qwen_prefill(ixtts_qwen* h, const int32_t* ids, int n, void
 extern "C" int ixtts_qwen_step(ixtts_qwen* h, int n_steps, const ixtts_qwen_sampling* sc, void* stream) {
   Q_READY(h, "qwen_step");
   IX_ARG(n_steps >= 0, "qwen_step: n_steps %d", n_steps);
-  IX_ARG(h->prompt_len > 0, "qwen_step: no prompt (call ixtts_qwen_prefill)");
+  IX_ARG(h->plen[0] > 0, "qwen_step: no prompt (call ixtts_qwen_prefill)");
   hipStream_t st = (hipStream_t)stream;
   IX_TRY(q_set_sampling(h, sc, st));
   IX_TRY(q_run(h, STEP_FULL, n_steps, st));
   return IXTTS_OK;
 }
 
-extern "C" int ixtts_qwen_read(ixtts_qwen* h, int32_t* ids, int cap, int* n_ids, int* finished, void* stream) {
+#define Q_SLOT(h, slot, who) IX_ARG((slot) >= 0 && (slot) < (h)->n_slots, who ": slot %d of an engine of %d", slot, (h)->n_slots)
+
+extern "C" int ixtts_qwen_read_slot(ixtts_qwen* h, int slot, int32_t* ids, int cap, int* n_ids, int* finished, void* stream) {
   Q_READY(h, "qwen_read");
+  Q_SLOT(h, slot, "qwen_read");
   IX_ARG(n_ids && finished && (ids || cap == 0) && cap >= 0, "qwen_read: bad arguments");
   hipStream_t st = (hipStream_t)stream;
   IX_HIP(hipStreamSynchronize(st));
   int g = 0, f = 0;
-  IX_HIP(hipMemcpy(&g, h->gen_count, 4, hipMemcpyDeviceToHost));
-  IX_HIP(hipMemcpy(&f, h->finished, 4, hipMemcpyDeviceToHost));
+  IX_HIP(hipMemcpy(&g, h->gen_count + slot, 4, hipMemcpyDeviceToHost));
+  IX_HIP(hipMemcpy(&f, h->finished + slot, 4, hipMemcpyDeviceToHost));
   if (f == 3) {
     set_error("qwen_read: the logits of step %d were not finite, no token could be selected", g);
     return IXTTS_ERR_STATE;
   }
   const int m = std::min(g, cap);
-  if (m > 0) IX_HIP(hipMemcpy(ids, h->tokens + h->prompt_len, (size_t)m * 4, hipMemcpyDeviceToHost));
+  if (m > 0) IX_HIP(hipMemcpy(ids, h->tokens + (size_t)slot * h->tstride() + h->plen[slot], (size_t)m * 4, hipMemcpyDeviceToHost));
   *n_ids = g, *finished = f;
   return IXTTS_OK;
+}
+
+extern "C" int ixtts_qwen_read(ixtts_qwen* h, int32_t* ids, int cap, int* n_ids, int* finished, void* stream) {
+  return ixtts_qwen_read_slot(h, 0, ids, cap, n_ids, finished, stream);
 }
 
 extern "C" int ixtts_qwen_generate(ixtts_qwen* h, int max_new, const ixtts_qwen_sampling* sc, int32_t* ids, int cap, int* n_ids, int* finished,
                                    void* stream) {
   Q_READY(h, "qwen_generate");
   IX_ARG(max_new >= 0, "qwen_generate: max_new %d", max_new);
-  IX_ARG(h->prompt_len > 0, "qwen_generate: no prompt (call ixtts_qwen_prefill)");
+  IX_ARG(h->plen[0] > 0, "qwen_generate: no prompt (call ixtts_qwen_prefill)");
   hipStream_t st = (hipStream_t)stream;
   IX_TRY(q_set_sampling(h, sc, st));
   // steps past EOS change nothing, so the host only looks every 16 tokens
-  max_new = std::min(max_new, h->smax - h->prompt_len);
+  max_new = std::min(max_new, h->smax - h->plen[0]);
   int done = 0, g = 0, f = 0;
   while (done < max_new) {
     const int n = std::min(16, max_new - done);
@@ -1095,26 +1454,198 @@ extern "C" int ixtts_qwen_generate(ixtts_qwen* h, int max_new, const ixtts_qwen_
   return IXTTS_OK;
 }
 
-extern "C" int ixtts_qwen_read_logits(ixtts_qwen* h, float* out, void* stream) {
+extern "C" int ixtts_qwen_read_logits_slot(ixtts_qwen* h, int slot, float* out, void* stream) {
   Q_READY(h, "qwen_read_logits");
+  Q_SLOT(h, slot, "qwen_read_logits");
   IX_ARG(out, "qwen_read_logits: null output");
   IX_HIP(hipStreamSynchronize((hipStream_t)stream));
-  IX_HIP(hipMemcpy(out, h->logits, (size_t)h->V * 4, hipMemcpyDeviceToHost));
+  IX_HIP(hipMemcpy(out, h->logits + (size_t)slot * h->V, (size_t)h->V * 4, hipMemcpyDeviceToHost));
+  return IXTTS_OK;
+}
+
+extern "C" int ixtts_qwen_read_logits(ixtts_qwen* h, float* out, void* stream) { return ixtts_qwen_read_logits_slot(h, 0, out, stream); }
+
+extern "C" int ixtts_qwen_read_kept_slot(ixtts_qwen* h, int slot, int32_t* ids, float* probs, int cap, int* n_kept, void* stream) {
+  Q_READY(h, "qwen_read_kept");
+  Q_SLOT(h, slot, "qwen_read_kept");
+  IX_ARG(ids && probs && n_kept && cap >= 0, "qwen_read_kept: bad arguments");
+  IX_HIP(hipStreamSynchronize((hipStream_t)stream));
+  int n = 0;
+  IX_HIP(hipMemcpy(&n, h->n_kept + slot, 4, hipMemcpyDeviceToHost));
+  const int m = std::min(n, cap);
+  if (m > 0) {
+    IX_HIP(hipMemcpy(ids, h->kept_id + slot * KC_MAX, (size_t)m * 4, hipMemcpyDeviceToHost));
+    IX_HIP(hipMemcpy(probs, h->kept_p + slot * KC_MAX, (size_t)m * 4, hipMemcpyDeviceToHost));
+  }
+  *n_kept = n;
   return IXTTS_OK;
 }
 
 extern "C" int ixtts_qwen_read_kept(ixtts_qwen* h, int32_t* ids, float* probs, int cap, int* n_kept, void* stream) {
-  Q_READY(h, "qwen_read_kept");
-  IX_ARG(ids && probs && n_kept && cap >= 0, "qwen_read_kept: bad arguments");
-  IX_HIP(hipStreamSynchronize((hipStream_t)stream));
-  int n = 0;
-  IX_HIP(hipMemcpy(&n, h->n_kept, 4, hipMemcpyDeviceToHost));
-  const int m = std::min(n, cap);
-  if (m > 0) {
-    IX_HIP(hipMemcpy(ids, h->kept_id, (size_t)m * 4, hipMemcpyDeviceToHost));
-    IX_HIP(hipMemcpy(probs, h->kept_p, (size_t)m * 4, hipMemcpyDeviceToHost));
+  return ixtts_qwen_read_kept_slot(h, 0, ids, probs, cap, n_kept, stream);
+}
+
+// ---- slots
+// the K/V caches of slots 1.. (a batched call of more than one slot needs them)
+static int q_slots_ready(ixtts_qwen* h) {
+  const size_t kv = (size_t)h->L * h->KVH * h->smax * HDIM * 4;
+  for (int z = 1; z < h->n_slots; ++z) {
+    if (h->kcs[z] && h->vcs[z]) continue;
+    if ((!h->kcs[z] && hipMalloc(&h->kcs[z], kv) != hipSuccess) || (!h->vcs[z] && hipMalloc(&h->vcs[z], kv) != hipSuccess)) {
+      (void)hipGetLastError();
+      set_error("qwen: hipMalloc of the K/V cache of slot %d (2 x %zu bytes) failed", z, kv);
+      return IXTTS_ERR_NOMEM;
+    }
+    IX_HIP(hipMemset(h->kcs[z], 0, kv));
+    IX_HIP(hipMemset(h->vcs[z], 0, kv));
   }
-  *n_kept = n;
+  return IXTTS_OK;
+}
+
+static int q_rows_ready(ixtts_qwen* h) {
+  const size_t R = h->rows_max, qd = (size_t)h->H * HDIM, kvd = (size_t)h->KVH * HDIM;
+  // each buffer only if it is not there yet: a call after a failed one allocates the rest
+  auto al = [](auto** p, size_t bytes) {
+    if (*p || hipMalloc(p, bytes) == hipSuccess) return true;
+    (void)hipGetLastError();
+    *p = nullptr;
+    set_error("qwen: hipMalloc of %zu bytes for the rows prefill failed", bytes);
+    return false;
+  };
+  const bool ok = al(&h->row_slot, (size_t)MAXS * h->smax * 4) && al(&h->row_pos, (size_t)MAXS * h->smax * 4) && al(&h->rx, R * h->D * 4) &&
+                  al(&h->rxn, R * h->D * 4) && al(&h->rqkv, R * (qd + 2 * kvd) * 4) && al(&h->rqb, R * qd * 4) && al(&h->ratt, R * qd * 4) &&
+                  al(&h->rff, R * h->I * 4);
+  return ok ? IXTTS_OK : IXTTS_ERR_NOMEM;
+}
+
+static void q_rows_gemm(int epi, const float* A, const void* W, float* out, int M, int N, int K, hipStream_t st) {
+  RGemmP g{A, reinterpret_cast<const _Float16*>(W), out, M, N, K};
+  const dim3 grid((N + (epi == RE_SWIGLU ? RBN / 2 : RBN) - 1) / (epi == RE_SWIGLU ? RBN / 2 : RBN), (M + RBM - 1) / RBM), blk(256);
+  if (epi == RE_STORE) hipLaunchKernelGGL(qrows_gemm_kernel<RE_STORE>, grid, blk, 0, st, g);
+  else if (epi == RE_ADD) hipLaunchKernelGGL(qrows_gemm_kernel<RE_ADD>, grid, blk, 0, st, g);
+  else hipLaunchKernelGGL(qrows_gemm_kernel<RE_SWIGLU>, grid, blk, 0, st, g);
+}
+
+// the first len - 1 positions of slots 0..n-1 through the layers as rows (f16 engines); cur_len is set by the caller
+static int q_prefill_rows(ixtts_qwen* h, int n, const int* lens, hipStream_t st) {
+  std::vector<int> rs, rp;
+  for (int s = 0; s < n; ++s)
+    for (int p = 0; p + 1 < lens[s]; ++p) rs.push_back(s), rp.push_back(p);
+  const int total = (int)rs.size();
+  if (!total) return IXTTS_OK;
+  IX_TRY(q_rows_ready(h));
+  IX_HIP(hipMemcpy(h->row_slot, rs.data(), (size_t)total * 4, hipMemcpyHostToDevice));
+  IX_HIP(hipMemcpy(h->row_pos, rp.data(), (size_t)total * 4, hipMemcpyHostToDevice));
+  const int D = h->D, qd = h->H * HDIM, kvd = h->KVH * HDIM;
+  const float eps = h->cfg.rms_norm_eps;
+  for (int r0 = 0; r0 < total; r0 += h->rows_max) {
+    const int M = std::min(h->rows_max, total - r0);
+    const RowsP r{h->row_slot + r0, h->row_pos + r0, M};
+    hipLaunchKernelGGL(qrows_embed_kernel, dim3(M), dim3(256), 0, st, r, (const _Float16*)Q_ARENA(h->emb), h->tokens, h->tstride(), D, h->rx);
+    for (int l = 0; l < h->L; ++l) {
+      const LW& w = h->lw[l];
+      hipLaunchKernelGGL(qrows_norm_kernel, dim3(M), dim3(256), 0, st, h->rx, (const float*)Q_ARENA(w.ln1), eps, D, h->rxn);
+      q_rows_gemm(RE_STORE, h->rxn, Q_ARENA(w.wqkv), h->rqkv, M, qd + 2 * kvd, D, st);
+      RowsAttnP a;
+      a.r = r, a.qkv = h->rqkv, a.qn = (const float*)Q_ARENA(w.qn), a.kn = (const float*)Q_ARENA(w.kn), a.cosb = h->cosb, a.sinb = h->sinb;
+      for (int z = 0; z < MAXS; ++z) {
+        const int sl = std::min(z, n - 1);
+        a.kc[z] = h->kcs[sl] + (size_t)l * h->KVH * h->smax * HDIM, a.vc[z] = h->vcs[sl] + (size_t)l * h->KVH * h->smax * HDIM;
+      }
+      a.qb = h->rqb, a.att = h->ratt, a.heads = h->H, a.kv_heads = h->KVH, a.smax = h->smax, a.eps = eps, a.scale = 1.f / sqrtf((float)HDIM);
+      hipLaunchKernelGGL(qrows_prep_kernel, dim3(M, h->H + h->KVH), dim3(64), 0, st, a);
+      if (l == h->L - 1) break;  // the last layer's keys and values are all a later step reads of it
+      const dim3 ag(h->KVH, M);
+      if (h->nrep == 1) hipLaunchKernelGGL(qrows_attn_kernel<1>, ag, dim3(256), 0, st, a);
+      else if (h->nrep == 2) hipLaunchKernelGGL(qrows_attn_kernel<2>, ag, dim3(256), 0, st, a);
+      else hipLaunchKernelGGL(qrows_attn_kernel<4>, ag, dim3(256), 0, st, a);
+      q_rows_gemm(RE_ADD, h->ratt, Q_ARENA(w.wo), h->rx, M, D, qd, st);
+      hipLaunchKernelGGL(qrows_norm_kernel, dim3(M), dim3(256), 0, st, h->rx, (const float*)Q_ARENA(w.ln2), eps, D, h->rxn);
+      q_rows_gemm(RE_SWIGLU, h->rxn, Q_ARENA(w.wgu), h->rff, M, h->I, D, st);
+      q_rows_gemm(RE_ADD, h->rff, Q_ARENA(w.wd), h->rx, M, D, h->I, st);
+    }
+  }
+  IX_HIP(hipGetLastError());
+  return IXTTS_OK;
+}
+
+extern "C" int ixtts_qwen_prefill_slots(ixtts_qwen* h, int n, const int32_t* ids, const int* lens, void* stream) {
+  Q_READY(h, "qwen_prefill_slots");
+  IX_ARG(ids && lens, "qwen_prefill_slots: null argument");
+  IX_ARG(n >= 1 && n <= h->n_slots, "qwen_prefill_slots: %d sequences on an engine of %d slots", n, h->n_slots);
+  size_t off = 0;
+  for (int s = 0; s < n; ++s) {
+    IX_ARG(lens[s] >= 1 && lens[s] < h->smax, "qwen_prefill_slots: %d prompt ids in slot %d (1..%d)", lens[s], s, h->smax - 1);
+    for (int i = 0; i < lens[s]; ++i)
+      IX_ARG(ids[off + i] >= 0 && ids[off + i] < h->V, "qwen_prefill_slots: id %d at %d of slot %d outside the vocabulary", ids[off + i], i, s);
+    off += lens[s];
+  }
+  hipStream_t st = (hipStream_t)stream;
+  IX_HIP(hipStreamSynchronize(st));  // the previous sequences are done with the token buffers
+  if (n > 1) IX_TRY(q_slots_ready(h));
+  int cur[MAXS] = {}, zero[MAXS] = {};
+  off = 0;
+  for (int s = 0; s < n; ++s) {
+    IX_HIP(hipMemcpy(h->tokens + (size_t)s * h->tstride(), ids + off, (size_t)lens[s] * 4, hipMemcpyHostToDevice));
+    off += lens[s];
+    cur[s] = h->f16 ? lens[s] - 1 : 0;  // the rows path reads positions from its table; the chunk path moves cur_len itself
+    h->plen[s] = lens[s];
+  }
+  IX_HIP(hipMemcpy(h->cur_len, cur, (size_t)n * 4, hipMemcpyHostToDevice));
+  IX_HIP(hipMemcpy(h->gen_count, zero, (size_t)n * 4, hipMemcpyHostToDevice));
+  IX_HIP(hipMemcpy(h->finished, zero, (size_t)n * 4, hipMemcpyHostToDevice));
+  IX_HIP(hipMemcpy(h->n_kept, zero, (size_t)n * 4, hipMemcpyHostToDevice));
+  if (h->f16) return q_prefill_rows(h, n, lens, st);
+  // f32 (parity mode): slot after slot on the chunk path, into that slot's cache
+  for (int s = 0; s < n; ++s) {
+    IX_TRY(q_run(h, STEP_CHUNK, (lens[s] - 1) / PCH, st, s));
+    IX_TRY(q_run(h, STEP_PRE, (lens[s] - 1) % PCH, st, s));
+  }
+  return IXTTS_OK;
+}
+
+static int q_check_slots(ixtts_qwen* h, int n, const char* who) {
+  IX_ARG(n >= 1 && n <= h->n_slots, "%s: %d sequences on an engine of %d slots", who, n, h->n_slots);
+  for (int s = 0; s < n; ++s) IX_ARG(h->plen[s] > 0 && h->kcs[s], "%s: slot %d has no prompt (call ixtts_qwen_prefill_slots)", who, s);
+  return IXTTS_OK;
+}
+
+static int q_run_slots(ixtts_qwen* h, int n, int n_steps, hipStream_t st) {
+  return n == 1 ? q_run(h, STEP_FULL, n_steps, st) : q_run(h, STEP_SLOTS, n_steps, st, n);
+}
+
+extern "C" int ixtts_qwen_step_slots(ixtts_qwen* h, int n, int n_steps, const ixtts_qwen_sampling* sc, void* stream) {
+  Q_READY(h, "qwen_step_slots");
+  IX_ARG(n_steps >= 0, "qwen_step_slots: n_steps %d", n_steps);
+  IX_TRY(q_check_slots(h, n, "qwen_step_slots"));
+  hipStream_t st = (hipStream_t)stream;
+  IX_TRY(q_set_sampling(h, sc, st));
+  return q_run_slots(h, n, n_steps, st);
+}
+
+extern "C" int ixtts_qwen_generate_slots(ixtts_qwen* h, int n, int max_new, const ixtts_qwen_sampling* sc, void* stream) {
+  Q_READY(h, "qwen_generate_slots");
+  IX_ARG(max_new >= 0, "qwen_generate_slots: max_new %d", max_new);
+  IX_TRY(q_check_slots(h, n, "qwen_generate_slots"));
+  hipStream_t st = (hipStream_t)stream;
+  IX_TRY(q_set_sampling(h, sc, st));
+  // a slot whose cache fills up stops by itself; the steps end with the slot that has the most room
+  int room = 0;
+  for (int s = 0; s < n; ++s) room = std::max(room, h->smax - h->plen[s]);
+  max_new = std::min(max_new, room);
+  int done = 0;
+  while (done < max_new) {
+    const int k = std::min(16, max_new - done);
+    IX_TRY(q_run_slots(h, n, k, st));
+    done += k;
+    IX_HIP(hipStreamSynchronize(st));
+    int f[MAXS] = {};
+    IX_HIP(hipMemcpy(f, h->finished, (size_t)n * 4, hipMemcpyDeviceToHost));
+    bool all = true;
+    for (int s = 0; s < n; ++s) all = all && f[s] != 0;
+    if (all) break;
+  }
+  IX_HIP(hipStreamSynchronize(st));
   return IXTTS_OK;
 }
 

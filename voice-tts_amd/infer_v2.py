@@ -535,12 +535,42 @@ class IndexTTS2:
             if top >= rows:
                 raise ValueError(f"mel code {top} outside the semantic codec's codebook ({rows} entries)")
 
+    def _emo_text_vectors(self, requests, failed):
+        """{request index: emo_vector} for the requests with `use_emo_text`: the emotion texts of the batch (`emo_text`, else the
+        request's `text`) go through the Qwen emotion model together.  A failure lands in `failed` under the request's index."""
+        want = {}
+        for ri, rq in enumerate(requests):
+            if not rq.get("use_emo_text"):
+                continue
+            if self.qwen_emo is None:
+                failed[ri] = NotImplementedError(
+                    f"use_emo_text needs the Qwen emotion model: no directory at model_dir/qwen_emo_path "
+                    f"({self.qwen_emo_dir or 'config.yaml names no qwen_emo_path'}); pass qwen_emo=... or provide it")
+                continue
+            try:
+                want[ri] = rq["emo_text"] if rq.get("emo_text") is not None else rq["text"]
+            except Exception as e:  # a request without `text`
+                failed[ri] = e
+        if not want:
+            return {}
+        texts = list(want.values())
+        many = getattr(self.qwen_emo, "inference_many", None)
+        try:
+            dicts = many(texts) if many is not None else [self.qwen_emo.inference(t) for t in texts]
+        except Exception as e:
+            for ri in want:
+                failed[ri] = e
+            return {}
+        logger.info(f"detected emotion vectors from text: {dicts}")
+        return {ri: list(d.values()) for ri, d in zip(want, dicts)}
+
     @torch.no_grad()
     def infer_many(self, requests, interval_silence=200, max_text_tokens_per_segment=120, decode_slots=8, **generation_kwargs):
         """Several `/tts` requests served TOGETHER (the worker's global lock, server.py:25,384, replaced by the
         decode scheduler): every request's segments share the decode slots -- the weights are read once per step for all of them
         -- and the post-decode stages run per segment as in `infer`.  Each request is a dict with `spk_audio_prompt`, `text` and
-        optionally `emo_audio_prompt`, `emo_alpha`, `emo_vector`, `use_random`.  Generation kwargs and defaults are `infer`'s:
+        optionally `emo_audio_prompt`, `emo_alpha`, `emo_vector`, `use_random`, `use_emo_text`, `emo_text` (the emotion from
+        text, as in `infer`; the emotion texts of the whole batch are decoded together).  Generation kwargs and defaults are `infer`'s:
         with `num_beams > 1` (the served default, 3) every segment is a beam GROUP and floor(decode_slots / num_beams) groups step
         together; `num_beams=1` samples without beams, one slot per
         segment (argmax when `top_k == 1`).  Returns one entry per request: `(22050, int16 [N, 1])`, None (empty text), or the
@@ -570,10 +600,15 @@ class IndexTTS2:
         start = time.perf_counter()
         plans, todo = [None] * len(requests), []
         failed = {}
+        text_emo = self._emo_text_vectors(requests, failed)
         for ri, rq in enumerate(requests):
+            if ri in failed:
+                continue
             try:
                 spk_prompt, emo_prompt = rq["spk_audio_prompt"], rq.get("emo_audio_prompt")
                 emo_alpha, emo_vector = rq.get("emo_alpha", 1.0), rq.get("emo_vector")
+                if ri in text_emo:  # infer_v2.py:475-488: the emotion from text takes the place of a given vector
+                    emo_vector = text_emo[ri]
                 if emo_vector is not None:  # infer_v2.py:476-505
                     emo_prompt = None
                     scale = max(0.0, min(1.0, emo_alpha))

@@ -92,9 +92,10 @@ def load_model_dir(model_dir):
 
 # ---------------------------------------------------------------------------------------------------- engine
 class QwenEngine:
-    """ctypes wrapper of ixtts_qwen_* (one sequence, KV cache of max_seq positions)."""
+    """ctypes wrapper of ixtts_qwen_*: `slots` sequences (1..4), each with a KV cache of max_seq positions.  Slot 0 is the
+    sequence of prefill / step / read / generate; the *_many calls decode up to `slots` prompts per step."""
 
-    def __init__(self, cfg, dtype="f16", max_seq=2048, device=None, eos_token_id=None):
+    def __init__(self, cfg, dtype="f16", max_seq=2048, device=None, eos_token_id=None, slots=1):
         self.device = torch.device(device if device is not None else "cuda:0")
         eos = eos_token_id if eos_token_id is not None else cfg.get("eos_token_id")
         eos = [] if eos is None else [int(eos)] if isinstance(eos, int) else [int(e) for e in eos]
@@ -110,10 +111,14 @@ class QwenEngine:
         for i, e in enumerate(eos):
             c.eos_ids[i] = int(e)
         self.cfg, self.dtype, self.max_seq, self.V, self.eos = dict(cfg), dtype, int(max_seq), int(cfg["vocab_size"]), eos
+        self.slots = int(slots)
+        if not 1 <= self.slots <= _lib.QWEN_MAX_SLOTS:
+            raise ValueError(f"slots={slots}: an engine holds 1..{_lib.QWEN_MAX_SLOTS} sequences")
         self._h = C.c_void_p()
         with torch.cuda.device(self.device):
-            _lib.check(_lib.lib().ixtts_qwen_create(C.byref(self._h), C.byref(c)), "ixtts_qwen_create")
+            _lib.check(_lib.lib().ixtts_qwen_create_slots(C.byref(self._h), C.byref(c), self.slots), "ixtts_qwen_create_slots")
         self.prompt_len = 0
+        self.prompt_lens = []
 
     def load_state_dict(self, sd):
         L = _lib.lib()
@@ -197,6 +202,71 @@ class QwenEngine:
             _lib.check(_lib.lib().ixtts_qwen_draw(self._h, int(seed) & (2**64 - 1), int(n), out.ctypes.data, self._stream()), "ixtts_qwen_draw")
         return out
 
+    # ---- slots
+    def prefill_many(self, prompts):
+        """Slots 0..len(prompts)-1 take the prompts: each one's first len-1 positions run through the layers."""
+        arrs = [np.asarray(p, dtype=np.int32).reshape(-1) for p in prompts]
+        if not 1 <= len(arrs) <= self.slots:
+            raise ValueError(f"{len(arrs)} prompts for an engine of {self.slots} slots")
+        for a in arrs:
+            if not 1 <= a.size < self.max_seq:
+                raise ValueError(f"prompt of {a.size} ids does not fit a KV cache of {self.max_seq} positions")
+        ids = np.ascontiguousarray(np.concatenate(arrs))
+        lens = np.ascontiguousarray(np.array([a.size for a in arrs], dtype=np.int32))
+        with torch.cuda.device(self.device):
+            _lib.check(_lib.lib().ixtts_qwen_prefill_slots(self._h, len(arrs), ids.ctypes.data, lens.ctypes.data, self._stream()),
+                       "ixtts_qwen_prefill_slots")
+        self.prompt_lens = lens.tolist()
+        self.prompt_len = self.prompt_lens[0]
+
+    def step_many(self, n_steps=1, n=None, **sampling):
+        sc = self.sampling(**sampling)
+        n = len(self.prompt_lens) if n is None else int(n)
+        with torch.cuda.device(self.device):
+            _lib.check(_lib.lib().ixtts_qwen_step_slots(self._h, n, int(n_steps), C.byref(sc), self._stream()), "ixtts_qwen_step_slots")
+
+    def read_slot(self, slot):
+        ids = np.zeros(self.max_seq + 1, np.int32)
+        n, fin = C.c_int(), C.c_int()
+        with torch.cuda.device(self.device):
+            _lib.check(_lib.lib().ixtts_qwen_read_slot(self._h, int(slot), ids.ctypes.data, ids.size, C.byref(n), C.byref(fin), self._stream()),
+                       "ixtts_qwen_read_slot")
+        return ids[: n.value].tolist(), int(fin.value)
+
+    def read_logits_slot(self, slot):
+        out = np.zeros(self.V, np.float32)
+        with torch.cuda.device(self.device):
+            _lib.check(_lib.lib().ixtts_qwen_read_logits_slot(self._h, int(slot), out.ctypes.data, self._stream()), "ixtts_qwen_read_logits_slot")
+        return out
+
+    def read_kept_slot(self, slot):
+        ids = np.zeros(_lib.QWEN_TOPK_MAX, np.int32)
+        pr = np.zeros(_lib.QWEN_TOPK_MAX, np.float32)
+        n = C.c_int()
+        with torch.cuda.device(self.device):
+            _lib.check(_lib.lib().ixtts_qwen_read_kept_slot(self._h, int(slot), ids.ctypes.data, pr.ctypes.data, ids.size, C.byref(n),
+                                                            self._stream()), "ixtts_qwen_read_kept_slot")
+        return ids[: n.value].copy(), pr[: n.value].copy()
+
+    def generate_many(self, prompts, max_new_tokens, **sampling):
+        """`generate` for up to `slots` prompts at once -> one id list per prompt, each what `generate` gives for it alone
+        (f32 engines: bit for bit; f16 engines prefill the batch on the matrix cores)."""
+        self.prefill_many(prompts)
+        sc = self.sampling(**sampling)
+        n = len(self.prompt_lens)
+        with torch.cuda.device(self.device):
+            _lib.check(_lib.lib().ixtts_qwen_generate_slots(self._h, n, int(max_new_tokens), C.byref(sc), self._stream()),
+                       "ixtts_qwen_generate_slots")
+        outs = []
+        for s, plen in enumerate(self.prompt_lens):
+            ids, fin = self.read_slot(s)
+            cap = self.max_seq - plen
+            if int(max_new_tokens) > cap and fin != 1 and len(ids) >= cap:
+                warnings.warn(f"emotion model: max_new_tokens={max_new_tokens} capped to the {cap} positions the KV cache has left "
+                              f"(max_seq={self.max_seq}); the answer was cut there")
+            outs.append(ids[: min(int(max_new_tokens), cap)])
+        return outs
+
     def step_bytes(self, S):
         return _lib.lib().ixtts_qwen_step_bytes(self._h, int(S))
 
@@ -215,7 +285,7 @@ class QwenEmotion:
     (torch_dtype="float16"); "f32" is the parity mode of the tests.  `seed` feeds the device sampler when the model's
     generation config samples."""
 
-    def __init__(self, model_dir, dtype="f16", device=None, max_seq=2048, seed=0, tokenizer=None, engine=None):
+    def __init__(self, model_dir, dtype="f16", device=None, max_seq=2048, seed=0, tokenizer=None, engine=None, slots=None):
         self.model_dir = model_dir
         if tokenizer is None:
             from transformers import AutoTokenizer
@@ -226,7 +296,10 @@ class QwenEmotion:
         self.generation = dict(GEN_DEFAULTS)
         if engine is None and model_dir is not None:
             cfg, self.generation, sd = load_model_dir(model_dir)
-            self.engine = QwenEngine(cfg, dtype=dtype, max_seq=max_seq, device=device, eos_token_id=self.generation["eos_token_id"]).load_state_dict(sd)
+            if slots is None:
+                slots = int(os.environ.get("IXTTS_QWEN_SLOTS", "4"))  # sequences decoded per step by inference_many; 1 = off
+            self.engine = QwenEngine(cfg, dtype=dtype, max_seq=max_seq, device=device, eos_token_id=self.generation["eos_token_id"],
+                                     slots=slots).load_state_dict(sd)
         self.seed = int(seed)
         self.prompt = "文本情感分类"
         self.cn_key_to_en = {
@@ -306,5 +379,29 @@ class QwenEmotion:
         out = self.engine.generate(ids, max_new_tokens, do_sample=g["do_sample"], temperature=g["temperature"], top_k=g["top_k"],
                                    top_p=g["top_p"], seed=self.seed)
         res = self.parse(out, text_input)
+        self.last_time = time.perf_counter() - start
+        return res
+
+    def inference_many(self, texts, max_new_tokens=32768):
+        """`inference` for several texts -> one dict per text, in order.  Equal texts are decoded once; the unique prompts go
+        through the engine in groups of at most its `slots`, longest first (prompts of similar length share a group)."""
+        if self.engine is None:
+            raise RuntimeError("QwenEmotion built without a model (parse-only)")
+        texts = list(texts)
+        slots = int(getattr(self.engine, "slots", 1))
+        if slots <= 1 or not hasattr(self.engine, "generate_many"):
+            return [self.inference(t, max_new_tokens) for t in texts]
+        start = time.perf_counter()
+        unique = list(dict.fromkeys(texts))
+        prompts = {t: self.prompt_ids(t) for t in unique}
+        order = sorted(unique, key=lambda t: -len(prompts[t]))  # stable: equal lengths keep the order of the texts
+        g = self.generation
+        outs = {}
+        for i in range(0, len(order), slots):
+            group = order[i: i + slots]
+            ids = self.engine.generate_many([prompts[t] for t in group], max_new_tokens, do_sample=g["do_sample"], temperature=g["temperature"],
+                                            top_k=g["top_k"], top_p=g["top_p"], seed=self.seed)
+            outs.update(zip(group, ids))
+        res = [self.parse(outs[t], t) for t in texts]
         self.last_time = time.perf_counter() - start
         return res

@@ -20,13 +20,14 @@ import os
 import time
 import warnings
 import wave
+from types import SimpleNamespace
 
 import numpy as np
 import torch
 
 from .bigvgan import BigVGAN
 from .gpt_engine import GptEngine, resolve_gpt_dtype
-from .pipeline import prepare_gpt_inputs
+from .pipeline import conds_latent, decode_segment, latent_prefix, prepare_gpt_inputs, vocode
 from .weights import BIGVGAN_CFG, GPT_CFG, load_bigvgan_checkpoint, load_gpt_checkpoint
 
 logger = logging.getLogger("indextts.infer_v2")
@@ -459,7 +460,7 @@ class IndexTTS2:
             f.setnchannels(1)
             f.setsampwidth(2)
             f.setframerate(22050)
-            f.writeframes((np.clip(x, -1, 1) * 32767).astype("<i2").tobytes())
+            f.writeframes((np.clip(x, -1, 1) * np.iinfo(np.int16).max).astype("<i2").tobytes())
         try:
             with warnings.catch_warnings():
                 warnings.simplefilter("ignore")
@@ -480,21 +481,7 @@ class IndexTTS2:
             return None
         return emo_vector_mix(emo_vector, style, self.emo_matrix, self.spk_matrix, self.emo_num, use_random)
 
-    # ------------------------------------------------------------------ API
-    def infer(self, spk_audio_prompt, text, output_path, emo_audio_prompt=None, emo_alpha=1.0, emo_vector=None,
-              use_emo_text=False, emo_text=None, use_random=False, interval_silence=200, verbose=False,
-              max_text_tokens_per_segment=120, stream_return=False, more_segment_before=0, **generation_kwargs):
-        gen = self.infer_generator(spk_audio_prompt, text, output_path, emo_audio_prompt, emo_alpha, emo_vector, use_emo_text,
-                                   emo_text, use_random, interval_silence, verbose, max_text_tokens_per_segment, stream_return,
-                                   more_segment_before, **generation_kwargs)
-        if stream_return:
-            return gen
-        try:
-            return list(gen)[0]
-        except IndexError:
-            return None
-
-    # ------------------------------------------------------------------ row N3 at the API level: requests decoded together
+    # ------------------------------------------------------------------ decode engines beside `self.gpt` (infer_many, beam groups)
     def _many_engine(self, slots):
         """A second decode engine whose slots are shared by the segments of several requests (wide MFMA GEMVs above 4 slots,
         on the bf16, fp16 or fp32 matrix cores by the model's GPT weight type)."""
@@ -543,9 +530,7 @@ class IndexTTS2:
             if not rq.get("use_emo_text"):
                 continue
             if self.qwen_emo is None:
-                failed[ri] = NotImplementedError(
-                    f"use_emo_text needs the Qwen emotion model: no directory at model_dir/qwen_emo_path "
-                    f"({self.qwen_emo_dir or 'config.yaml names no qwen_emo_path'}); pass qwen_emo=... or provide it")
+                failed[ri] = self._no_qwen_emo()
                 continue
             try:
                 want[ri] = rq["emo_text"] if rq.get("emo_text") is not None else rq["text"]
@@ -564,37 +549,173 @@ class IndexTTS2:
         logger.info(f"detected emotion vectors from text: {dicts}")
         return {ri: list(d.values()) for ri, d in zip(want, dicts)}
 
+    # ------------------------------------------------------------------ the request path: every step once, for infer and infer_many
+    def _generation_args(self, generation_kwargs):
+        """Generation kwargs and their defaults (infer_v2.py:598-606) -> (namespace of the parsed values, the kwargs left over);
+        do_sample is popped and then forced True (:648).  `typical_mass` and `seed` are read for the schedulers and stay among the
+        leftovers, which `infer` forwards to `gpt.generate`."""
+        rest = dict(generation_kwargs)
+        rest.pop("do_sample", True)
+        g = SimpleNamespace(top_p=rest.pop("top_p", 0.8), top_k=rest.pop("top_k", 30), temperature=rest.pop("temperature", 0.8),
+                            num_beams=rest.pop("num_beams", 3), length_penalty=rest.pop("length_penalty", 0.0),
+                            repetition_penalty=rest.pop("repetition_penalty", 10.0), max_mel_tokens=rest.pop("max_mel_tokens", 1500),
+                            typical_mass=float(rest.get("typical_mass", 0.9)) if rest.get("typical_sampling") else 0.0,
+                            seed=int(rest.get("seed", 0)))
+        return g, rest
+
+    def _no_qwen_emo(self):
+        return NotImplementedError(
+            f"use_emo_text needs the Qwen emotion model: no directory at model_dir/qwen_emo_path "
+            f"({self.qwen_emo_dir or 'config.yaml names no qwen_emo_path'}); pass qwen_emo=... or provide it")
+
+    @staticmethod
+    def _resolve_emotion(emo_audio_prompt, emo_alpha, emo_vector):
+        """infer_v2.py:476-505 -> (emo_prompt, emo_alpha, emo_vector, emo_is_spk): a vector takes the emotion prompt's place and is
+        scaled by the clamped alpha (truncated to four decimals); without an emotion prompt the speaker prompt stands in at alpha
+        1.0 (`emo_is_spk`)."""
+        if emo_vector is not None:
+            emo_audio_prompt = None
+            scale = max(0.0, min(1.0, emo_alpha))
+            if scale != 1.0:
+                emo_vector = [int(x * scale * 10000) / 10000 for x in emo_vector]
+        emo_is_spk = emo_audio_prompt is None
+        return emo_audio_prompt, 1.0 if emo_is_spk else emo_alpha, emo_vector, emo_is_spk
+
+    def _prompt_stages(self):
+        return (self._stage("speaker", self.prompt.speaker if self.prompt else None),
+                self._stage("emotion", self.prompt.emotion if self.prompt else None))
+
+    def _encode_prompts(self, spk_prompt, emo_prompt):
+        """-> (speaker dict, emotion features) through the prompt caches (infer_v2.py:508-580); no emotion prompt: the speaker's.
+        A failing encode leaves no stale pair behind: the next request with the earlier prompt encodes it again."""
+        speaker_fn, emotion_fn = self._prompt_stages()
+        if emo_prompt is None:
+            emo_prompt = spk_prompt
+        if self.cache_spk is None or not _same_prompt(self.cache_spk_audio_prompt, spk_prompt):
+            self.cache_spk, self.cache_spk_audio_prompt = None, None
+            self.cache_spk, self.cache_spk_audio_prompt = speaker_fn(spk_prompt), spk_prompt
+        if self.cache_emo_cond is None or not _same_prompt(self.cache_emo_audio_prompt, emo_prompt):
+            self.cache_emo_cond, self.cache_emo_audio_prompt = None, None
+            self.cache_emo_cond, self.cache_emo_audio_prompt = emotion_fn(emo_prompt), emo_prompt
+        return self.cache_spk, self.cache_emo_cond
+
+    def _conds_latent(self, spk, emo_cond, emo_is_spk, emo_alpha, emo_vector, use_random):
+        """-> conds_latent [34, D], a function of the request's prompts only: computed once per request (the reference recomputes it
+        per segment, infer_v2.py:629-635, model_v2.py:684-696 -- same values).  `emo_is_spk`: the built-in encoder takes the speaker's
+        features for the emotion's too, one emotion-encoder pass instead of two."""
+        if self.cond is not None:
+            cond32, emovec = self.cond.encode_prompt(spk["spk_cond_emb"], None if emo_is_spk else emo_cond, emo_alpha)
+        else:
+            emovec = self._stage("merge_emovec", None)(spk["spk_cond_emb"], emo_cond, emo_alpha)
+            cond32 = self._stage("get_conditioning", None)(spk["spk_cond_emb"])
+        if emo_vector is not None:  # infer_v2.py:552-563,637-638
+            mix = self._stage("emo_vector_mix", (lambda v, st, r: self._builtin_emo_mix(v, st, r)) if self.emo_matrix is not None else None)
+            emovec_mat, weight_sum = mix(emo_vector, spk["style"], use_random)
+            emovec = emovec_mat + (1 - weight_sum) * emovec
+        return conds_latent(cond32, emovec, self.speed_emb)
+
+    def _segments_of(self, text, max_text_tokens_per_segment, quick_streaming_tokens=0):
+        """-> the text's segments as lists of token ids (infer_v2.py:582-589,617)."""
+        if self.tokenizer is None:
+            return self._stage("tokenize", None)(text, max_text_tokens_per_segment, quick_streaming_tokens)
+        text_tokens_list = self.tokenizer.tokenize(text)
+        text_token_ids = self.tokenizer.convert_tokens_to_ids(text_tokens_list)
+        unk = self.tokenizer.unk_token_id
+        if unk in text_token_ids:
+            logger.warning(f"Input text contains {text_token_ids.count(unk)} unknown tokens (id={unk})")
+            logger.warning(f"Tokens which can't be encoded: {[t for t, i in zip(text_tokens_list, text_token_ids) if i == unk]}")
+        return [self.tokenizer.convert_tokens_to_ids(sent) for sent in
+                self.tokenizer.split_segments(text_tokens_list, max_text_tokens_per_segment, quick_streaming_tokens=quick_streaming_tokens)]
+
+    def _segment(self, conds_latent, ids, engine, max_mel_tokens, request=0, index=0, payload=None, stream=None):
+        """One segment's text ids -> what the schedulers decode; `max_new` is taken against the engine that will decode it."""
+        embeds, n_pad, P = prepare_gpt_inputs(self.gpt_cfg, self.text_embedding, self.text_pos_embedding, conds_latent, ids)
+        max_new = max(0, min(max_mel_tokens, engine.max_seq - P - 2, self.gpt_cfg["max_mel_tokens"] - 1))
+        return decode_segment(index, embeds, n_pad, max_new, request, payload, stream)
+
+    def _decode(self, engine, todo, g):
+        """The segments through the engine's slots, weights read once per step for all of them -> {(request, index): ids}: beam
+        groups when `g.num_beams > 1`, else one slot per segment (argmax when `top_k == 1`; with sampling each slot draws from its
+        own counter-based stream)."""
+        from .scheduler import BeamGroupScheduler, DecodeScheduler
+
+        out = {}
+        sampler = dict(repetition_penalty=g.repetition_penalty, temperature=g.temperature, top_k=g.top_k, top_p=g.top_p, seed=g.seed,
+                       typical_mass=g.typical_mass)
+        if todo and g.num_beams > 1:
+            BeamGroupScheduler(engine, g.num_beams).run(todo, lambda seg, ids, score: out.__setitem__((seg.request, seg.index), ids),
+                                                        length_penalty=g.length_penalty, **sampler)
+        elif todo:
+            DecodeScheduler(engine, engine.max_batch, self.stop_mel_token).run(
+                todo, lambda seg, ids: out.__setitem__((seg.request, seg.index), ids), do_sample=g.top_k != 1, **sampler)
+        torch.cuda.synchronize(self.device)
+        return out
+
+    def _trim_codes(self, ids):
+        """-> codes [1, n] (int64, on the device): cut at the first stop token (infer_v2.py:676-687)."""
+        row = (ids if torch.is_tensor(ids) else torch.from_numpy(np.asarray(ids).astype(np.int64))).to(self.device).reshape(-1)
+        stops = (row == self.stop_mel_token).nonzero(as_tuple=False)
+        n = int(stops[0]) if stops.numel() else row.numel()
+        return row[:n].reshape(1, -1)
+
+    def _s2mel_item(self, conds_latent, text_ids, codes, spk):
+        """-> (latent [1, n, D], codes, prompt_condition, ref_mel, style): the latent pass (UnifiedVoice.forward, model_v2.py:554-596)
+        over [conds; text] and the codes, refused on the host when a code lies outside the codebook."""
+        self._check_codes(codes)
+        prefix = latent_prefix(self.gpt_cfg, self.text_embedding, self.text_pos_embedding, conds_latent, text_ids)
+        latent = self.gpt.latent(prefix, codes[0]).unsqueeze(0)
+        return latent, codes, spk["prompt_condition"], spk["ref_mel"], spk["style"]
+
+    def _mels(self, items, spk, packed=False):
+        """s2mel items -> one mel [1, 80, F] each (infer_v2.py:713-731): segment after segment through the built-in or the injected
+        stage (which gets the speaker dict `spk`), or -- `packed`, IXTTS_S2MEL_BATCH=1 -- as ONE packed solve (S2Mel.solve_many)."""
+        if packed:
+            return self.s2mel.solve_many(items, n_timesteps=25, inference_cfg_rate=0.7)
+        mels = []
+        for latent, codes, pc, rm, st in items:
+            lens = torch.tensor([codes.shape[1]], dtype=torch.long, device=self.device)
+            if self.s2mel is not None:
+                mels.append(self.s2mel(latent, codes, lens, pc, rm, st, n_timesteps=25, inference_cfg_rate=0.7))
+            else:
+                mels.append(self._stage("s2mel", None)(latent, codes, lens, spk))
+        return mels
+
+    # ------------------------------------------------------------------ API
+    def infer(self, spk_audio_prompt, text, output_path, emo_audio_prompt=None, emo_alpha=1.0, emo_vector=None,
+              use_emo_text=False, emo_text=None, use_random=False, interval_silence=200, verbose=False,
+              max_text_tokens_per_segment=120, stream_return=False, more_segment_before=0, **generation_kwargs):
+        gen = self.infer_generator(spk_audio_prompt, text, output_path, emo_audio_prompt, emo_alpha, emo_vector, use_emo_text,
+                                   emo_text, use_random, interval_silence, verbose, max_text_tokens_per_segment, stream_return,
+                                   more_segment_before, **generation_kwargs)
+        if stream_return:
+            return gen
+        try:
+            return list(gen)[0]
+        except IndexError:
+            return None
+
     @torch.no_grad()
     def infer_many(self, requests, interval_silence=200, max_text_tokens_per_segment=120, decode_slots=8, **generation_kwargs):
         """Several `/tts` requests served TOGETHER (the worker's global lock, server.py:25,384, replaced by the
         decode scheduler): every request's segments share the decode slots -- the weights are read once per step for all of them
-        -- and the post-decode stages run per segment as in `infer`.  Each request is a dict with `spk_audio_prompt`, `text` and
-        optionally `emo_audio_prompt`, `emo_alpha`, `emo_vector`, `use_random`, `use_emo_text`, `emo_text` (the emotion from
-        text, as in `infer`; the emotion texts of the whole batch are decoded together).  Generation kwargs and defaults are `infer`'s:
-        with `num_beams > 1` (the served default, 3) every segment is a beam GROUP and floor(decode_slots / num_beams) groups step
-        together; `num_beams=1` samples without beams, one slot per
-        segment (argmax when `top_k == 1`).  Returns one entry per request: `(22050, int16 [N, 1])`, None (empty text), or the
-        EXCEPTION that request raised (bad prompt audio, a code outside the codebook ...) -- one request's failure leaves the
-        others of the batch alone."""
+        -- and the post-decode stages run per segment as in `infer`, through the same helpers.  Each request is a dict with
+        `spk_audio_prompt`, `text` and optionally `emo_audio_prompt`, `emo_alpha`, `emo_vector`, `use_random`, `use_emo_text`,
+        `emo_text` (the emotion from text, as in `infer`; the emotion texts of the whole batch are decoded together).  Generation
+        kwargs and defaults are `infer`'s: with `num_beams > 1` (the served default, 3) every segment is a beam GROUP and
+        floor(decode_slots / num_beams) groups step together; `num_beams=1` samples without beams, one slot per segment (argmax
+        when `top_k == 1`).  Returns one entry per request: `(22050, int16 [N, 1])`, None (empty text), or the EXCEPTION that
+        request raised (bad prompt audio, a code outside the codebook ...) -- one request's failure leaves the others of the
+        batch alone."""
         from . import _lib
-        from .scheduler import BeamGroupScheduler, DecodeScheduler, Segment
 
-        generation_kwargs.pop("do_sample", True)
-        top_p = generation_kwargs.pop("top_p", 0.8)
-        top_k = generation_kwargs.pop("top_k", 30)
-        temperature = generation_kwargs.pop("temperature", 0.8)
-        num_beams = int(generation_kwargs.pop("num_beams", 3))
-        length_penalty = generation_kwargs.pop("length_penalty", 0.0)
-        repetition_penalty = generation_kwargs.pop("repetition_penalty", 10.0)
-        max_mel_tokens = generation_kwargs.pop("max_mel_tokens", 1500)
-        typical_mass = float(generation_kwargs.get("typical_mass", 0.9)) if generation_kwargs.get("typical_sampling") else 0.0
-        speaker_fn = self._stage("speaker", self.prompt.speaker if self.prompt else None)
-        emotion_fn = self._stage("emotion", self.prompt.emotion if self.prompt else None)
-        if num_beams > 1:
-            if not (2 <= num_beams <= 4 and 1 <= top_k <= 128):
+        g, _ = self._generation_args(generation_kwargs)
+        g.num_beams = int(g.num_beams)
+        self._prompt_stages()  # a model without prompt stages refuses the whole call
+        if g.num_beams > 1:
+            if not (2 <= g.num_beams <= 4 and 1 <= g.top_k <= 128):
                 raise NotImplementedError("beam-sample on the device: 2 <= num_beams <= 4, 1 <= top_k <= 128")
-            groups = max(1, min(int(decode_slots), _lib.max_batch()) // num_beams)
-            eng = self._many_engine(groups * num_beams) if groups * num_beams > 4 else self.gpt
+            groups = max(1, min(int(decode_slots), _lib.max_batch()) // g.num_beams)
+            eng = self._many_engine(groups * g.num_beams) if groups * g.num_beams > 4 else self.gpt
         else:
             eng = self._many_engine(decode_slots)
         start = time.perf_counter()
@@ -605,90 +726,36 @@ class IndexTTS2:
             if ri in failed:
                 continue
             try:
-                spk_prompt, emo_prompt = rq["spk_audio_prompt"], rq.get("emo_audio_prompt")
-                emo_alpha, emo_vector = rq.get("emo_alpha", 1.0), rq.get("emo_vector")
-                if ri in text_emo:  # infer_v2.py:475-488: the emotion from text takes the place of a given vector
-                    emo_vector = text_emo[ri]
-                if emo_vector is not None:  # infer_v2.py:476-505
-                    emo_prompt = None
-                    scale = max(0.0, min(1.0, emo_alpha))
-                    if scale != 1.0:
-                        emo_vector = [int(x * scale * 10000) / 10000 for x in emo_vector]
-                emo_is_spk = emo_prompt is None  # (then both emotion-encoder passes see the same features: computed once)
-                if emo_prompt is None:
-                    emo_prompt, emo_alpha = spk_prompt, 1.0
-                if self.cache_spk is None or not _same_prompt(self.cache_spk_audio_prompt, spk_prompt):
-                    self.cache_spk, self.cache_spk_audio_prompt = None, None  # (a failing encode must not leave a stale pair behind)
-                    self.cache_spk, self.cache_spk_audio_prompt = speaker_fn(spk_prompt), spk_prompt
-                spk = self.cache_spk
-                if self.cache_emo_cond is None or not _same_prompt(self.cache_emo_audio_prompt, emo_prompt):
-                    self.cache_emo_cond, self.cache_emo_audio_prompt = None, None
-                    self.cache_emo_cond, self.cache_emo_audio_prompt = emotion_fn(emo_prompt), emo_prompt
-                emo_cond = self.cache_emo_cond
-                if self.cond is not None:
-                    cond32, emovec = self.cond.encode_prompt(spk["spk_cond_emb"], None if emo_is_spk else emo_cond, emo_alpha)
-                else:
-                    emovec = self._stage("merge_emovec", None)(spk["spk_cond_emb"], emo_cond, emo_alpha)
-                    cond32 = self._stage("get_conditioning", None)(spk["spk_cond_emb"])
-                if emo_vector is not None:
-                    mix = self._stage("emo_vector_mix", (lambda v, st, r: self._builtin_emo_mix(v, st, r)) if self.emo_matrix is not None else None)
-                    emovec_mat, weight_sum = mix(emo_vector, spk["style"], rq.get("use_random", False))
-                    emovec = emovec_mat + (1 - weight_sum) * emovec
-                cl = torch.cat((cond32 + emovec.reshape(1, -1), self.speed_emb[1:2], self.speed_emb[0:1]), 0)
-                if self.tokenizer is not None:
-                    toks = self.tokenizer.tokenize(rq["text"])
-                    segments = [self.tokenizer.convert_tokens_to_ids(sent) for sent in self.tokenizer.split_segments(toks, max_text_tokens_per_segment)]
-                else:
-                    segments = self._stage("tokenize", None)(rq["text"], max_text_tokens_per_segment, 0)
-                mine = []
-                for si, ids in enumerate(segments):
-                    tt = torch.as_tensor(ids, dtype=torch.int32, device=self.device).reshape(-1)
-                    fake, embeds, mask = self._prepare_gpt_inputs(cl, tt)
-                    n_pad = int((mask == 0).sum().item())
-                    max_new = max(0, min(max_mel_tokens, eng.max_seq - fake.shape[1] - 2, self.gpt_cfg["max_mel_tokens"] - 1))
-                    mine.append(Segment(ri, si, embeds[0], n_pad, max_new))
-                plans[ri] = dict(spk=spk, cl=cl, segments=segments, codes=[None] * len(segments))
+                spk_prompt = rq["spk_audio_prompt"]
+                # infer_v2.py:475-488: the emotion from text takes the place of a given vector
+                emo_prompt, emo_alpha, emo_vector, emo_is_spk = self._resolve_emotion(
+                    rq.get("emo_audio_prompt"), rq.get("emo_alpha", 1.0), text_emo[ri] if ri in text_emo else rq.get("emo_vector"))
+                spk, emo_cond = self._encode_prompts(spk_prompt, emo_prompt)
+                cl = self._conds_latent(spk, emo_cond, emo_is_spk, emo_alpha, emo_vector, rq.get("use_random", False))
+                segments = self._segments_of(rq["text"], max_text_tokens_per_segment)
+                mine = [self._segment(cl, ids, eng, g.max_mel_tokens, request=ri, index=si) for si, ids in enumerate(segments)]
+                plans[ri] = dict(spk=spk, cl=cl, segments=segments)
                 todo += mine  # only once the whole request is known to be well-formed
             except Exception as e:  # this request only
                 failed[ri] = e
-        sampler = dict(repetition_penalty=repetition_penalty, temperature=temperature, top_k=top_k, top_p=top_p, seed=int(generation_kwargs.get("seed", 0)),
-                       typical_mass=typical_mass)
-        if todo and num_beams > 1:
-            BeamGroupScheduler(eng, num_beams).run(todo, lambda seg, ids, score: plans[seg.request]["codes"].__setitem__(seg.index, ids),
-                                                   length_penalty=length_penalty, **sampler)
-        elif todo:
-            DecodeScheduler(eng, eng.max_batch, self.stop_mel_token).run(
-                todo, lambda seg, ids: plans[seg.request]["codes"].__setitem__(seg.index, ids), do_sample=top_k != 1, **sampler)
-        torch.cuda.synchronize(self.device)
+        decoded = self._decode(eng, todo, g)
         t_decode = time.perf_counter() - start
-        # per request: codes -> latents (a code outside the codebook fails its request only, before anything is packed)
+        # per request: codes -> latents (a code outside the codebook fails its request only, before anything is packed); a segment
+        # without codes is left out
         for ri, plan in enumerate(plans):
             if ri in failed:
                 continue
             try:
-                plan["items"] = []
-                for ids, seg in zip(plan["codes"], plan["segments"]):
-                    row = torch.from_numpy(np.asarray(ids).astype(np.int64)).to(self.device)
-                    stops = (row == self.stop_mel_token).nonzero(as_tuple=False)
-                    n = int(stops[0]) if stops.numel() else row.numel()
-                    if n == 0:
-                        continue
-                    codes = row[:n].reshape(1, -1)
-                    self._check_codes(codes)
-                    tt = torch.as_tensor(seg, dtype=torch.int32, device=self.device).reshape(-1)
-                    t = torch.cat((tt.new_tensor([self.gpt_cfg["start_text_token"]]), tt, tt.new_tensor([self.gpt_cfg["stop_text_token"]]))).long()
-                    prefix = torch.cat((plan["cl"], self.text_embedding[t] + self.text_pos_embedding[: t.numel()]), 0)
-                    latent = self.gpt.latent(prefix, codes[0]).unsqueeze(0)
-                    spk = plan["spk"]
-                    plan["items"].append((latent, codes, spk["prompt_condition"], spk["ref_mel"], spk["style"]))
+                codes = [self._trim_codes(decoded[ri, si]) for si in range(len(plan["segments"]))]
+                plan["items"] = [self._s2mel_item(plan["cl"], seg, c, plan["spk"]) for seg, c in zip(plan["segments"], codes) if c.shape[1]]
             except Exception as e:  # this request only
                 failed[ri] = e
-        # s2mel, IXTTS_S2MEL_BATCH=1: every surviving segment of every request in one packed solve (S2Mel.solve_many) -- an exception
-        # raised inside it is returned for every request of the batch; default, or an injected s2mel stage: segment after segment
+        # s2mel, IXTTS_S2MEL_BATCH=1: every surviving segment of every request in one packed solve -- an exception raised inside it
+        # is returned for every request of the batch; default, or an injected s2mel stage: segment after segment
         live = [ri for ri in range(len(plans)) if ri not in failed]
         if self.s2mel is not None and s2mel_batching():
             try:
-                mels = iter(self.s2mel.solve_many([it for ri in live for it in plans[ri]["items"]], n_timesteps=25, inference_cfg_rate=0.7))
+                mels = iter(self._mels([it for ri in live for it in plans[ri]["items"]], None, packed=True))
                 for ri in live:
                     plans[ri]["mels"] = [next(mels) for _ in plans[ri]["items"]]
             except Exception as e:
@@ -697,14 +764,7 @@ class IndexTTS2:
         else:
             for ri in live:
                 try:
-                    plans[ri]["mels"] = []
-                    for latent, codes, pc, rm, st in plans[ri]["items"]:
-                        lens = torch.tensor([codes.shape[1]], dtype=torch.long, device=self.device)
-                        if self.s2mel is not None:
-                            mel = self.s2mel(latent, codes, lens, pc, rm, st, n_timesteps=25, inference_cfg_rate=0.7)
-                        else:
-                            mel = self._stage("s2mel", None)(latent, codes, lens, plans[ri]["spk"])
-                        plans[ri]["mels"].append(mel)
+                    plans[ri]["mels"] = self._mels(plans[ri]["items"], plans[ri]["spk"])
                 except Exception as e:  # this request only
                     failed[ri] = e
         out = []
@@ -713,10 +773,7 @@ class IndexTTS2:
                 out.append(failed[ri])
                 continue
             try:
-                wavs = []
-                for mel in plan["mels"]:
-                    wav = torch.clamp(32767 * self.bigvgan(mel.float()).squeeze().unsqueeze(0), -32767.0, 32767.0)
-                    wavs.append(wav.cpu())
+                wavs = [vocode(self.bigvgan, mel).cpu() for mel in plan["mels"]]
                 if not wavs:
                     out.append(None)
                     continue
@@ -736,204 +793,88 @@ class IndexTTS2:
                         max_text_tokens_per_segment=120, stream_return=False, quick_streaming_tokens=0, **generation_kwargs):
         logger.info("Starting inference...")
         start_time = time.perf_counter()
-        glue = self.glue
-        speaker_fn = self._stage("speaker", self.prompt.speaker if self.prompt else None)
-        emotion_fn = self._stage("emotion", self.prompt.emotion if self.prompt else None)
-        qwen_time = 0.0
+        self._prompt_stages()
+        gpt_gen_time = gpt_forward_time = s2mel_time = bigvgan_time = 0.0
         if use_emo_text:
             # infer_v2.py:475-488: the emotion reference clip gives way, the text (or `text`) becomes the emotion vector
             if self.qwen_emo is None:
-                raise NotImplementedError(
-                    f"use_emo_text needs the Qwen emotion model: no directory at model_dir/qwen_emo_path "
-                    f"({self.qwen_emo_dir or 'config.yaml names no qwen_emo_path'}); pass qwen_emo=... or provide it")
-            emo_audio_prompt = None
-            if emo_text is None:
-                emo_text = text
+                raise self._no_qwen_emo()
             q0 = time.perf_counter()
-            emo_dict = self.qwen_emo.inference(emo_text)
-            qwen_time = time.perf_counter() - q0
+            emo_dict = self.qwen_emo.inference(text if emo_text is None else emo_text)
+            gpt_gen_time += time.perf_counter() - q0  # the emotion decode counts as generation time (the reference books it under the total only)
             logger.info(f"detected emotion vectors from text: {emo_dict}")
             emo_vector = list(emo_dict.values())
-        if emo_vector is not None:
-            emo_audio_prompt = None
-            scale = max(0.0, min(1.0, emo_alpha))
-            if scale != 1.0:
-                emo_vector = [int(x * scale * 10000) / 10000 for x in emo_vector]
-        if emo_audio_prompt is None:
-            emo_audio_prompt = spk_audio_prompt
-            emo_alpha = 1.0
-        if self.cache_spk is None or not _same_prompt(self.cache_spk_audio_prompt, spk_audio_prompt):
-            self.cache_spk = speaker_fn(spk_audio_prompt)
-            self.cache_spk_audio_prompt = spk_audio_prompt
-        spk = self.cache_spk
-        emovec_mat = weight_sum = None
-        if emo_vector is not None:
-            mix = self._stage("emo_vector_mix", (lambda v, st, r: self._builtin_emo_mix(v, st, r)) if self.emo_matrix is not None else None)
-            emovec_mat, weight_sum = mix(emo_vector, spk["style"], use_random)
-        if self.cache_emo_cond is None or not _same_prompt(self.cache_emo_audio_prompt, emo_audio_prompt):
-            self.cache_emo_cond = emotion_fn(emo_audio_prompt)
-            self.cache_emo_audio_prompt = emo_audio_prompt
-        emo_cond_emb = self.cache_emo_cond
-
-        if self.tokenizer is not None:  # infer_v2.py:582-589,617
-            text_tokens_list = self.tokenizer.tokenize(text)
-            text_token_ids = self.tokenizer.convert_tokens_to_ids(text_tokens_list)
-            unk = self.tokenizer.unk_token_id
-            if unk in text_token_ids:
-                logger.warning(f"Input text contains {text_token_ids.count(unk)} unknown tokens (id={unk})")
-                logger.warning(f"Tokens which can't be encoded: {[t for t, i in zip(text_tokens_list, text_token_ids) if i == unk]}")
-            segments = [self.tokenizer.convert_tokens_to_ids(sent) for sent in
-                        self.tokenizer.split_segments(text_tokens_list, max_text_tokens_per_segment, quick_streaming_tokens=quick_streaming_tokens)]
-        else:
-            segments = self._stage("tokenize", None)(text, max_text_tokens_per_segment, quick_streaming_tokens)
-        # generation kwargs and their defaults (infer_v2.py:598-606); do_sample is popped and then forced True (:648)
-        generation_kwargs.pop("do_sample", True)
-        top_p = generation_kwargs.pop("top_p", 0.8)
-        top_k = generation_kwargs.pop("top_k", 30)
-        temperature = generation_kwargs.pop("temperature", 0.8)
-        length_penalty = generation_kwargs.pop("length_penalty", 0.0)
-        num_beams = generation_kwargs.pop("num_beams", 3)
-        repetition_penalty = generation_kwargs.pop("repetition_penalty", 10.0)
-        max_mel_tokens = generation_kwargs.pop("max_mel_tokens", 1500)
+        emo_prompt, emo_alpha, emo_vector, _ = self._resolve_emotion(emo_audio_prompt, emo_alpha, emo_vector)
+        spk, emo_cond = self._encode_prompts(spk_audio_prompt, emo_prompt)
+        segments = self._segments_of(text, max_text_tokens_per_segment, quick_streaming_tokens)
+        g, rest = self._generation_args(generation_kwargs)
         sampling_rate = 22050
-
-        wavs = []
-        gpt_gen_time = gpt_forward_time = s2mel_time = bigvgan_time = 0.0
-        gpt_gen_time += qwen_time  # the emotion decode counts as generation time (the reference books it under the total only)
-        has_warned = False
-        silence = None
-        req_emovec = req_cond32 = None
-        if self.cond is not None:
-            # merge_emovec + get_conditioning are functions of the request's prompts only; the reference recomputes them per
-            # segment (infer_v2.py:629-635, model_v2.py:684-689) -- computed once here, same values.  The length arguments
-            # are the reference's: spk_cond_emb.shape[-1] (= 1024, the feature size: no frame is ever masked).
-            m0 = time.perf_counter()
-            sc = spk["spk_cond_emb"].to(self.device, torch.float32)
-            ec = emo_cond_emb.to(self.device, torch.float32)
-            ls, le = torch.tensor([sc.shape[-1]], device=self.device), torch.tensor([ec.shape[-1]], device=self.device)
-            req_emovec = self.cond.merge_emovec(sc, ec, ls, le, alpha=emo_alpha)
-            req_cond32 = self.cond.get_conditioning(sc.transpose(1, 2), ls)[0]
-            gpt_gen_time += time.perf_counter() - m0
-        def conds_for_segment():
-            emovec = req_emovec if req_emovec is not None else self._stage("merge_emovec", None)(spk["spk_cond_emb"], emo_cond_emb, emo_alpha)
-            if emo_vector is not None:
-                emovec = emovec_mat + (1 - weight_sum) * emovec
-            cond32 = req_cond32 if req_cond32 is not None else self._stage("get_conditioning", None)(spk["spk_cond_emb"])
-            # inference_speech (model_v2.py:693-734)
-            return torch.cat((cond32 + emovec.reshape(1, -1), self.speed_emb[1:2], self.speed_emb[0:1]), 0)
-
+        m0 = time.perf_counter()
+        # Without an emotion prompt `infer` still hands the encoder the emotion stage's own features of the speaker prompt (loaded at
+        # 16 kHz, as the reference loads them: infer_v2.py:565-580) at alpha 1.0, where `infer_many` reuses the speaker's features
+        # in one pass: the two differ in the last bits with the built-in prompt encoder, so `emo_is_spk` stays False here.
+        cl = self._conds_latent(spk, emo_cond, False, emo_alpha, emo_vector, use_random)
         # Without beams the segments are independent sequences: decode them together, the weights are read once per step for
         # all of them (the reference decodes segment after segment, infer_v2.py:616; tokens per segment are the same for
-        # greedy; with sampling each slot draws from its own counter-based stream).  With beams every segment is a beam GROUP and the
-        # groups step together on the wide engine when `_beam_group_engine` gives one; else one segment at a time.
+        # greedy).  With beams every segment is a beam GROUP (its own scorer state, its own random stream: the segment index) and
+        # the groups step together on the wide engine when `_beam_group_engine` gives one; else -- and for one segment, streaming
+        # or a logits processor -- `gpt.generate`, one segment at a time.
+        eng = None
+        if len(segments) > 1 and not stream_return and not rest.get("logits_processor"):
+            if g.num_beams == 1:
+                eng = self.gpt
+            elif g.num_beams > 1 and 1 <= g.top_k <= 128:
+                eng = self._beam_group_engine(g.num_beams, len(segments))
         pre = None
-        beam_eng = None
-        if num_beams > 1 and len(segments) > 1 and not stream_return and not generation_kwargs.get("logits_processor") and 1 <= top_k <= 128:
-            beam_eng = self._beam_group_engine(num_beams, len(segments))
-        if beam_eng is not None:
-            # The served default (num_beams=3): every segment is a beam group of num_beams slots and the groups step TOGETHER on the
-            # wide engine -- the weights are read once per step for all of them (the reference runs `inference_speech` segment after
-            # segment, infer_v2.py:616-658).  Each segment has its own scorer state and its own random stream (segment index).
-            from .scheduler import BeamGroupScheduler, Segment
-
-            m0 = time.perf_counter()
-            todo = []
-            for i, sent_ids in enumerate(segments):
-                tt = torch.as_tensor(sent_ids, dtype=torch.int32, device=self.device).reshape(-1)
-                cl = conds_for_segment()
-                fake, embeds, mask = self._prepare_gpt_inputs(cl, tt)
-                n_pad = int((mask == 0).sum().item())
-                max_new = max(0, min(max_mel_tokens, beam_eng.max_seq - fake.shape[1] - 2, self.gpt_cfg["max_mel_tokens"] - 1))
-                todo.append(Segment(0, i, embeds[0], n_pad, max_new, payload=cl, stream=i))
-            pre = [None] * len(segments)
-            BeamGroupScheduler(beam_eng, num_beams).run(
-                todo, lambda seg, ids, score: pre.__setitem__(seg.index, (ids, seg.payload)), repetition_penalty=repetition_penalty,
-                temperature=temperature, top_k=top_k, top_p=top_p, seed=int(generation_kwargs.get("seed", 0)), length_penalty=length_penalty,
-                typical_mass=float(generation_kwargs.get("typical_mass", 0.9)) if generation_kwargs.get("typical_sampling") else 0.0)
-            torch.cuda.synchronize(self.device)
-            gpt_gen_time += time.perf_counter() - m0
-        elif num_beams == 1 and len(segments) > 1 and not stream_return and not generation_kwargs.get("logits_processor"):
-            from .scheduler import DecodeScheduler, Segment
-
-            m0 = time.perf_counter()
-            greedy = top_k == 1
-            todo = []
-            for i, sent_ids in enumerate(segments):
-                tt = torch.as_tensor(sent_ids, dtype=torch.int32, device=self.device).reshape(-1)
-                cl = conds_for_segment()
-                fake, embeds, mask = self._prepare_gpt_inputs(cl, tt)
-                n_pad = int((mask == 0).sum().item())
-                max_new = max(0, min(max_mel_tokens, self.gpt.max_seq - fake.shape[1] - 2, self.gpt_cfg["max_mel_tokens"] - 1))
-                todo.append(Segment(0, i, embeds[0], n_pad, max_new, payload=cl))
-            pre = [None] * len(segments)
-            DecodeScheduler(self.gpt, self.gpt.max_batch, self.stop_mel_token).run(
-                todo, lambda seg, ids: pre.__setitem__(seg.index, (ids, seg.payload)), repetition_penalty=repetition_penalty,
-                temperature=temperature, top_k=top_k, top_p=top_p, do_sample=not greedy, seed=int(generation_kwargs.get("seed", 0)),
-                typical_mass=float(generation_kwargs.get("typical_mass", 0.9)) if generation_kwargs.get("typical_sampling") else 0.0)
-            torch.cuda.synchronize(self.device)
-            gpt_gen_time += time.perf_counter() - m0
-        # several segments, whole audio at the end, IXTTS_S2MEL_BATCH=1: their CFM solves run as ONE packed solve (S2Mel.solve_many;
-        # default: segment after segment, as the reference); streaming keeps the per-segment order for its first-chunk latency
+        if eng is not None:
+            beams = g.num_beams > 1
+            pre = self._decode(eng, [self._segment(cl, ids, eng, g.max_mel_tokens, index=i, stream=i if beams else None)
+                                     for i, ids in enumerate(segments)], g)
+        gpt_gen_time += time.perf_counter() - m0
+        # several segments, whole audio at the end, IXTTS_S2MEL_BATCH=1: their CFM solves run as ONE packed solve (default: segment
+        # after segment, as the reference); streaming keeps the per-segment order for its first-chunk latency
         packed = [] if (not stream_return and len(segments) > 1 and self.s2mel is not None and s2mel_batching()) else None
+        wavs = []
+        has_warned = False
+        silence = None
         for seg_index, sent_ids in enumerate(segments):
-            text_tokens = torch.as_tensor(sent_ids, dtype=torch.int32, device=self.device).reshape(-1)
             m0 = time.perf_counter()
             if pre is not None:
-                ids, conds_latent = pre[seg_index]
-                codes = torch.from_numpy(np.asarray(ids).astype(np.int64)).reshape(1, -1).to(self.device)
+                codes = torch.from_numpy(np.asarray(pre[0, seg_index]).astype(np.int64)).reshape(1, -1).to(self.device)
             else:
-                conds_latent = conds_for_segment()
-                fake, embeds, mask = self._prepare_gpt_inputs(conds_latent, text_tokens)
+                fake, embeds, mask = self._prepare_gpt_inputs(cl, sent_ids)
                 self.gpt.store_mel_emb(embeds)
                 trunc = fake.shape[1]
                 out = self.gpt.generate(fake, bos_token_id=self.gpt_cfg["start_mel_token"], pad_token_id=self.stop_mel_token,
-                                        eos_token_id=self.stop_mel_token, attention_mask=mask, max_length=trunc + max_mel_tokens,
-                                        num_return_sequences=1, do_sample=True, top_p=top_p, top_k=top_k, temperature=temperature,
-                                        num_beams=num_beams, repetition_penalty=repetition_penalty, length_penalty=length_penalty,
-                                        **generation_kwargs)
+                                        eos_token_id=self.stop_mel_token, attention_mask=mask, max_length=trunc + g.max_mel_tokens,
+                                        num_return_sequences=1, do_sample=True, top_p=g.top_p, top_k=g.top_k, temperature=g.temperature,
+                                        num_beams=g.num_beams, repetition_penalty=g.repetition_penalty, length_penalty=g.length_penalty,
+                                        **rest)
                 codes = out[:, trunc:]
                 torch.cuda.synchronize(self.device)
                 gpt_gen_time += time.perf_counter() - m0
             if codes.shape[1] == 0:  # no room left to generate (max_mel_tokens == 0 or a prompt as long as max_seq)
-                raise RuntimeError(f"no mel codes could be generated for segment {seg_index} (max_mel_tokens={max_mel_tokens}, max_seq={self.gpt.max_seq})")
+                raise RuntimeError(f"no mel codes could be generated for segment {seg_index} (max_mel_tokens={g.max_mel_tokens}, max_seq={self.gpt.max_seq})")
             if not has_warned and bool((codes[:, -1] != self.stop_mel_token).any()):
-                warnings.warn(f"WARN: generation stopped due to exceeding `max_mel_tokens` ({max_mel_tokens}). "
-                              f"Input text tokens: {text_tokens.shape[0]}. Consider reducing `max_text_tokens_per_segment`"
+                warnings.warn(f"WARN: generation stopped due to exceeding `max_mel_tokens` ({g.max_mel_tokens}). "
+                              f"Input text tokens: {len(sent_ids)}. Consider reducing `max_text_tokens_per_segment`"
                               f"({max_text_tokens_per_segment}) or increasing `max_mel_tokens`.", category=RuntimeWarning)
                 has_warned = True
-            # trim at the first stop token (infer_v2.py:676-687)
-            row = codes[0]
-            stops = (row == self.stop_mel_token).nonzero(as_tuple=False)
-            code_len = int(stops[0]) if stops.numel() else row.numel()
-            codes = codes[:, :code_len]
-            code_lens = torch.tensor([code_len], dtype=torch.long, device=self.device)
-
             m0 = time.perf_counter()
-            t = torch.cat((text_tokens.new_tensor([self.gpt_cfg["start_text_token"]]), text_tokens,
-                           text_tokens.new_tensor([self.gpt_cfg["stop_text_token"]]))).long()
-            prefix = torch.cat((conds_latent, self.text_embedding[t] + self.text_pos_embedding[: t.numel()]), 0)
-            latent = self.gpt.latent(prefix, codes[0]).unsqueeze(0)  # UnifiedVoice.forward (model_v2.py:554-596)
+            item = self._s2mel_item(cl, sent_ids, self._trim_codes(codes), spk)
             torch.cuda.synchronize(self.device)
             gpt_forward_time += time.perf_counter() - m0
-
-            m0 = time.perf_counter()
-            self._check_codes(codes)
             if packed is not None:  # every segment's CFM in one solve after the loop
-                packed.append((latent, codes, spk["prompt_condition"], spk["ref_mel"], spk["style"]))
+                packed.append(item)
                 continue
-            if self.s2mel is not None:  # infer_v2.py:713-731
-                mel = self.s2mel(latent, codes, code_lens, spk["prompt_condition"], spk["ref_mel"], spk["style"],
-                                 n_timesteps=25, inference_cfg_rate=0.7)
-            else:
-                mel = self._stage("s2mel", None)(latent, codes, code_lens, spk)
+            m0 = time.perf_counter()
+            mel = self._mels([item], spk)[0]
             torch.cuda.synchronize(self.device)
             s2mel_time += time.perf_counter() - m0
-
             m0 = time.perf_counter()
-            wav = self.bigvgan(mel.float()).squeeze().unsqueeze(0)
+            wav = vocode(self.bigvgan, mel)
             torch.cuda.synchronize(self.device)
             bigvgan_time += time.perf_counter() - m0
-            wav = torch.clamp(32767 * wav, -32767.0, 32767.0)
             wavs.append(wav.cpu())
             if stream_return:
                 yield wav.cpu()
@@ -942,15 +883,12 @@ class IndexTTS2:
                 yield silence
         if packed:
             m0 = time.perf_counter()
-            mels = self.s2mel.solve_many(packed, n_timesteps=25, inference_cfg_rate=0.7)
+            mels = self._mels(packed, spk, packed=True)
             torch.cuda.synchronize(self.device)
             s2mel_time += time.perf_counter() - m0
-            for mel in mels:
-                m0 = time.perf_counter()
-                wav = self.bigvgan(mel.float()).squeeze().unsqueeze(0)
-                torch.cuda.synchronize(self.device)
-                bigvgan_time += time.perf_counter() - m0
-                wavs.append(torch.clamp(32767 * wav, -32767.0, 32767.0).cpu())
+            m0 = time.perf_counter()
+            wavs = [vocode(self.bigvgan, mel).cpu() for mel in mels]  # (.cpu() waits for the vocoder)
+            bigvgan_time += time.perf_counter() - m0
         end_time = time.perf_counter()
         if not wavs:
             return

@@ -28,23 +28,56 @@ def arena_tensor(ptr, nbytes, device):
     return torch.as_tensor(_RawDeviceBuffer(ptr, nbytes), device=device)
 
 
+def _text_rows(cfg, text_embedding, text_pos_embedding, text_ids, drop_inner=False):
+    """[start] text [stop] embedded with its positions -> [L + 2, D] (model_v2.py:579-583,620-640); `drop_inner` first drops the
+    start / stop text ids found inside the text, as `prepare_gpt_inputs` does."""
+    t = torch.as_tensor(text_ids, dtype=torch.long, device=text_embedding.device).reshape(-1)
+    start, stop = t.new_tensor([cfg["start_text_token"]]), t.new_tensor([cfg["stop_text_token"]])
+    if drop_inner:
+        t = t[(t != stop) & (t != start)]
+    t = torch.cat((start, t, stop))
+    return text_embedding[t] + text_pos_embedding[: t.numel()]
+
+
 def prepare_gpt_inputs(cfg, text_embedding, text_pos_embedding, conds_latent, text_ids):
     """UnifiedVoice.prepare_gpt_inputs (model_v2.py:598-661), one sequence: start/stop text ids found INSIDE the text are
     dropped and made up for by zero rows on the left (mask 0 there), then [start] text [stop] is embedded.
 
     conds_latent [34, D] device; text_ids int [L].  Returns (embeds [P-1, D], n_left_pad, P)."""
     device = text_embedding.device
-    t = torch.as_tensor(text_ids, dtype=torch.long, device=device).reshape(-1)
-    L = t.numel()
-    t = t[(t != cfg["stop_text_token"]) & (t != cfg["start_text_token"])]
-    t = torch.cat((t.new_tensor([cfg["start_text_token"]]), t, t.new_tensor([cfg["stop_text_token"]])))
-    temb = text_embedding[t] + text_pos_embedding[: t.numel()]
-    pad = L + 2 - t.numel()
+    temb = _text_rows(cfg, text_embedding, text_pos_embedding, text_ids, drop_inner=True)
+    pad = torch.as_tensor(text_ids).numel() + 2 - temb.shape[0]
     parts = [conds_latent.to(device, torch.float32), temb]
     if pad > 0:
         parts.insert(0, torch.zeros(pad, temb.shape[1], device=device))
     embeds = torch.cat(parts, 0)
     return embeds, pad, embeds.shape[0] + 1
+
+
+def conds_latent(cond32, emovec, speed_emb):
+    """inference_speech (model_v2.py:693-696): the 32 conditioning rows plus the emotion vector, then the two speed rows -> [34, D].
+    One implementation for `HotPath` and `IndexTTS2`."""
+    dev = speed_emb.device
+    c = cond32.to(dev, torch.float32) + emovec.to(dev, torch.float32).reshape(1, -1)
+    return torch.cat((c, speed_emb[1:2], speed_emb[0:1]), 0)
+
+
+def latent_prefix(cfg, text_embedding, text_pos_embedding, conds_latent, text_ids):
+    """[conds ; text_emb] rows of UnifiedVoice.forward (model_v2.py:579-589); one implementation, as above."""
+    return torch.cat((conds_latent.to(text_embedding.device, torch.float32), _text_rows(cfg, text_embedding, text_pos_embedding, text_ids)), 0)
+
+
+def vocode(bigvgan, mel):
+    """bigvgan(mel.float()) then the PCM clamp of infer_v2.py:735-744: fp32 [B, T] scaled to +-32767; one implementation, as above."""
+    wav = bigvgan(mel.to(bigvgan.device_, torch.float32)).squeeze(1)
+    return torch.clamp(32767 * wav, -32767.0, 32767.0)
+
+
+def decode_segment(index, embeds, n_left_pad, max_new, request=0, payload=None, stream=None):
+    """One prepared sequence as the decode schedulers take it (`scheduler.Segment`); `HotPath` and `IndexTTS2` build theirs here."""
+    from .scheduler import Segment
+
+    return Segment(request, index, embeds, n_left_pad, max_new, payload, stream)
 
 
 class HotPath:
@@ -88,17 +121,12 @@ class HotPath:
         return prepare_gpt_inputs(self.gpt_cfg, self.text_embedding, self.text_pos_embedding, conds_latent, text_ids)
 
     def conds_latent(self, cond32, emo_vec):
-        """inference_speech (model_v2.py:693-696)."""
-        c = cond32.to(self.device, torch.float32) + emo_vec.to(self.device, torch.float32).reshape(1, -1)
-        return torch.cat((c, self.speed_emb[1:2], self.speed_emb[0:1]), 0)
+        """inference_speech (model_v2.py:693-696); see the module-level `conds_latent`."""
+        return conds_latent(cond32, emo_vec, self.speed_emb)
 
     def latent_prefix(self, conds_latent, text_ids):
-        """[conds ; text_emb] rows of UnifiedVoice.forward (model_v2.py:579-589)."""
-        c = self.gpt_cfg
-        t = torch.as_tensor(text_ids, dtype=torch.long, device=self.device).reshape(-1)
-        t = torch.cat((t.new_tensor([c["start_text_token"]]), t, t.new_tensor([c["stop_text_token"]])))
-        temb = self.text_embedding[t] + self.text_pos_embedding[: t.numel()]
-        return torch.cat((conds_latent.to(self.device, torch.float32), temb), 0)
+        """-> [34 + L + 2, D]; see the module-level `latent_prefix`."""
+        return latent_prefix(self.gpt_cfg, self.text_embedding, self.text_pos_embedding, conds_latent, text_ids)
 
     # ------------------------------------------------------------------ G1-G8
     def generate(self, prompts, max_new, repetition_penalty=10.0, fixed_length=False, sync_every=64, **sampler):
@@ -130,11 +158,11 @@ class HotPath:
     def generate_many(self, segments, fixed_length=False, repetition_penalty=10.0, sync_every=64):
         """Row N3: decode any number of segments (of any number of requests) with continuous batching over the engine's
         slots.  segments: list of (embeds [P-1,D], n_left_pad, max_new).  Returns the id arrays in submission order."""
-        from .scheduler import DecodeScheduler, Segment
+        from .scheduler import DecodeScheduler
 
         out = [None] * len(segments)
         sched = DecodeScheduler(self.gpt, self.gpt.max_batch, self.gpt_cfg["stop_mel_token"], sync_every=sync_every)
-        segs = [Segment(0, i, e, p, n) for i, (e, p, n) in enumerate(segments)]
+        segs = [decode_segment(i, *s) for i, s in enumerate(segments)]
         self.last_sched_stats = sched.run(segs, lambda seg, ids: out.__setitem__(seg.index, ids), fixed_length=fixed_length,
                                           repetition_penalty=repetition_penalty)
         return out
@@ -145,11 +173,11 @@ class HotPath:
         beam group of `num_beams` slots, the engine's groups step together (a wide engine holds floor(max_batch / num_beams);
         up to 4 slots: one group, the segments in turn as the reference runs them).  segments: list of (embeds [P-1,D],
         n_left_pad, max_new).  Returns the best hypothesis per segment, in submission order."""
-        from .scheduler import BeamGroupScheduler, Segment
+        from .scheduler import BeamGroupScheduler
 
         out = [None] * len(segments)
         sched = BeamGroupScheduler(self.gpt, num_beams, sync_every=sync_every)
-        segs = [Segment(0, i, e, p, n) for i, (e, p, n) in enumerate(segments)]
+        segs = [decode_segment(i, *s) for i, s in enumerate(segments)]
         self.last_sched_stats = sched.run(segs, lambda seg, ids, score: out.__setitem__(seg.index, ids), fixed_length=fixed_length,
                                           repetition_penalty=repetition_penalty, temperature=temperature, top_k=top_k, top_p=top_p, seed=seed,
                                           length_penalty=length_penalty, typical_mass=typical_mass)
@@ -202,9 +230,8 @@ class HotPath:
 
     # ------------------------------------------------------------------ V0-V5
     def vocode(self, mel):
-        """bigvgan(mel.float()) then the PCM clamp of infer_v2.py:735-744: returns fp32 [1, T] scaled to +-32767."""
-        wav = self.bigvgan(mel.to(self.device, torch.float32)).squeeze(1)
-        return torch.clamp(32767 * wav, -32767.0, 32767.0)
+        """-> fp32 [1, T] scaled to +-32767; see the module-level `vocode`."""
+        return vocode(self.bigvgan, mel)
 
 
 def audio_seconds(n_codes_per_segment, interval_silence_ms=200):

@@ -45,7 +45,30 @@ __global__ __launch_bounds__(256) void row_norm_mod_kernel(const float* __restri
       q += (a * a + b * b) + (cc * cc + d * d);
     }
   }
-  const float rstd = 1.0f / sqrtf(wave_sum(q) / (float)H + eps);
+  float var = wave_sum(q) / (float)H;
+  // A row whose common offset dwarfs its spread (|mean| > 4 sigma): the fp32 sum over H leaves the mean off by a few ulp of the
+  // OFFSET, which is no longer small against sigma (offset 300, sigma 1: 1e-4 of the normalised row).  The residuals x - mean are
+  // exact there and small, so their own mean `corr` is accurate: centre by it as well.  Every other row keeps corr = 0 and, bit for
+  // bit, the arithmetic it had; the branch is uniform over the wave.
+  float corr = 0.f;
+  if constexpr (CENTER) {
+    if (mean * mean > 16.0f * var) {
+      float r = 0.f;
+#pragma unroll
+      for (int i = 0; i < ROW_NV; ++i)
+        if (lane + 64 * i < H4) r += ((v[i].x - mean) + (v[i].y - mean)) + ((v[i].z - mean) + (v[i].w - mean));
+      corr = wave_sum(r) / (float)H;
+      float q2 = 0.f;
+#pragma unroll
+      for (int i = 0; i < ROW_NV; ++i)
+        if (lane + 64 * i < H4) {
+          const float a = (v[i].x - mean) - corr, b = (v[i].y - mean) - corr, cc = (v[i].z - mean) - corr, d = (v[i].w - mean) - corr;
+          q2 += (a * a + b * b) + (cc * cc + d * d);
+        }
+      var = wave_sum(q2) / (float)H;
+    }
+  }
+  const float rstd = 1.0f / sqrtf(var + eps);
   const long bidx = seq_off ? seq_of_row(seq_off, nseq, row) : row / T;  // modulation vectors are per batch entry (or packed sequence)
   const float4* w4 = reinterpret_cast<const float4*>(mw + bidx * mstride);
   const float4* b4 = reinterpret_cast<const float4*>(mb + bidx * mstride);
@@ -56,7 +79,9 @@ __global__ __launch_bounds__(256) void row_norm_mod_kernel(const float* __restri
     const int c = lane + 64 * i;
     if (c < H4) {
       const float4 w = w4[c], b = b4[c];
-      float4 n = make_float4((v[i].x - mean) * rstd, (v[i].y - mean) * rstd, (v[i].z - mean) * rstd, (v[i].w - mean) * rstd);
+      float4 n;
+      if constexpr (CENTER) n = make_float4(((v[i].x - mean) - corr) * rstd, ((v[i].y - mean) - corr) * rstd, ((v[i].z - mean) - corr) * rstd, ((v[i].w - mean) - corr) * rstd);
+      else n = make_float4(v[i].x * rstd, v[i].y * rstd, v[i].z * rstd, v[i].w * rstd);
       if (g) {
         const float4 gg = g4[c];
         n.x *= gg.x; n.y *= gg.y; n.z *= gg.z; n.w *= gg.w;

@@ -464,18 +464,25 @@ def extend_tuned_gemms(T, Th, path=TUNED_GEMMS):
 
 
 class S2Mel:
-    def __init__(self, W, cfg=S2MEL_CFG, device="cpu"):
+    def __init__(self, W, cfg=S2MEL_CFG, device="cpu", dtype=torch.float32):
+        """dtype: torch.float64 on the CPU gives the high-precision twin of the stage (tests/test_s2mel_twin.py): every weight,
+        activation and accumulator in fp64.  What the fp32 path computes before it touches activations -- the folded weights, `t_span`
+        and the running t, `t_freqs`, the sinusoid arguments 1000 t f with their cos / sin, the RoPE table -- is the model's definition:
+        the twin computes those in fp32 exactly as the default does and widens them, so it differs from fp32 by rounding alone."""
         self.cfg = dict(cfg)
         self.device = torch.device(device)
+        self.dtype = dtype
+        if dtype not in (torch.float32, torch.float64) or (self.device.type == "cuda" and dtype != torch.float32):
+            raise ValueError(f"S2Mel: dtype {dtype} on {self.device} (fp32 anywhere; fp64 on the CPU leg only: the HIP kernels are fp32)")
         self.tuned_gemms = False
         if self.device.type == "cuda" and os.environ.get("IXTTS_NO_TUNED_GEMMS") != "1":
             self.tuned_gemms = use_tuned_gemms()
         W = fold_weight_norm(dict(W))
-        self.W = {k: v.to(self.device, torch.float32) for k, v in W.items()}
+        self.W = {k: v.to(self.device, torch.float32).to(dtype) for k, v in W.items()}
         H = cfg["hidden_dim"]
         self.head_dim = H // cfg["num_heads"]
         half = 128
-        self.t_freqs = torch.exp(-math.log(10000.0) * torch.arange(half, dtype=torch.float32) / half).to(self.device)
+        self.t_freqs = torch.exp(-math.log(10000.0) * torch.arange(half, dtype=torch.float32) / half).to(self.device).to(dtype)
         self._rope = None
         # derived weights (exact re-arrangements: concatenations / column splits of the reference's matrices)
         W, C_, L = self.W, cfg["in_channels"], cfg["depth"]
@@ -496,8 +503,8 @@ class S2Mel:
         # conv(x + c) = conv(x) + (sum of taps) c) and the skip ones are added once at the end
         nl, Hw = cfg["wavenet_layers"], cfg["wavenet_hidden"]
         self.wn_r1, self.wn_r2, self.wn_bin = [], [], []
-        carry = torch.zeros(Hw, device=self.device)
-        self.wn_out_bias = torch.zeros(Hw, device=self.device)
+        carry = torch.zeros(Hw, device=self.device, dtype=dtype)
+        self.wn_out_bias = torch.zeros(Hw, device=self.device, dtype=dtype)
         for i in range(nl):
             rw, rb = W[wn + f"res_skip_layers.{i}.conv.conv.weight"][:, :, 0], W[wn + f"res_skip_layers.{i}.conv.conv.bias"]
             self.wn_bin.append(W[wn + f"in_layers.{i}.conv.conv.bias"] + sum(self.wn_taps[i]) @ carry)
@@ -543,7 +550,12 @@ class S2Mel:
         W = self.W
         x = _lin(x, W, "length_regulator.content_in_proj")
         T = int(ylens.max())
-        x = F.interpolate(x.transpose(1, 2).contiguous(), size=T, mode="nearest")
+        x = x.transpose(1, 2).contiguous()
+        if x.dtype == torch.float32:
+            x = F.interpolate(x, size=T, mode="nearest")
+        else:  # the fp32 op's choice of source frames (its index arithmetic runs in the tensor's precision): the model's definition
+            src = F.interpolate(torch.arange(x.shape[-1], dtype=torch.float32)[None, None], size=T, mode="nearest")[0, 0].long()
+            x = x[..., src.to(x.device)]
         for i in range(self.cfg["lr_n_blocks"]):
             x = conv1d(x, W[f"length_regulator.model.{3 * i}.weight"], W[f"length_regulator.model.{3 * i}.bias"], padding=1)
             x = F.group_norm(x, 1, W[f"length_regulator.model.{3 * i + 1}.weight"], W[f"length_regulator.model.{3 * i + 1}.bias"], 1e-5)
@@ -554,8 +566,8 @@ class S2Mel:
         return x.transpose(1, 2) * mask
 
     def _t_embed(self, t, prefix):
-        args = 1000.0 * t[:, None].float() * self.t_freqs[None]
-        emb = torch.cat([torch.cos(args), torch.sin(args)], dim=-1)
+        args = 1000.0 * t[:, None].float() * self.t_freqs[None].float()  # fp32 arguments, cos and sin whatever self.dtype is
+        emb = torch.cat([torch.cos(args), torch.sin(args)], dim=-1).to(self.dtype)
         h = F.silu(_lin(emb, self.W, prefix + ".mlp.0"))
         return _lin(h, self.W, prefix + ".mlp.2")
 
@@ -565,6 +577,8 @@ class S2Mel:
             freqs = 1.0 / (10000.0 ** (torch.arange(0, n, 2)[: n // 2].float() / n))
             ang = torch.outer(torch.arange(max(T, 64)).float(), freqs)
             self._rope = torch.polar(torch.ones_like(ang), ang).to(self.device)  # complex64 [T, d/2]
+            if self.dtype == torch.float64:
+                self._rope = self._rope.to(torch.complex128)  # the fp32 table, widened
         return self._rope[:T]
 
     @staticmethod
@@ -788,7 +802,7 @@ class S2Mel:
         """BASECFM.inference + solve_euler (flow_matching.py:30-115).  mu [B,T,content]; prompt [B,80,Tp]; noise [B,80,T]."""
         B, T = mu.shape[0], mu.shape[1]
         assert B == 1, "CFM inference is batch-1 (as the reference)"
-        z = (torch.randn(B, self.cfg["in_channels"], T, device=mu.device) if noise is None else noise.to(mu.device, torch.float32)) * temperature
+        z = (torch.randn(B, self.cfg["in_channels"], T, device=mu.device) if noise is None else noise.to(mu.device, torch.float32)).to(self.dtype) * temperature
         t_span = torch.linspace(0, 1, n_timesteps + 1, device=mu.device)
         x = z.clone()
         Tp = prompt.shape[-1]
@@ -946,12 +960,12 @@ class S2Mel:
         # x rows [R, C]: the noise with the prompt frames zeroed; the velocities of frames >= Tp are the only ones used
         x = torch.cat([s["z"][0].t() for s in segs], 0).contiguous()
         keep = torch.cat([torch.arange(xo[i] + Tps[i], xo[i + 1]) for i in range(n)]).to(dev)
-        pmask = torch.ones(R, 1, device=dev)
+        pmask = torch.ones(R, 1, device=dev, dtype=self.dtype)
         for i in range(n):
             pmask[xo[i]:xo[i] + Tps[i]] = 0
         x.mul_(pmask)
         # dit_prepare: the (x, t)-independent part of the merge linear, per row
-        prompt_rows = torch.zeros(R, C_, device=dev)
+        prompt_rows = torch.zeros(R, C_, device=dev, dtype=self.dtype)
         for i, s in enumerate(segs):
             prompt_rows[xo[i]:xo[i] + Tps[i]] = s["prompt"][0, :, :Tps[i]].t()
         mu = torch.cat([s["mu"][0] for s in segs], 0)
@@ -1016,6 +1030,7 @@ class S2Mel:
             T = mu.shape[1]
             z = torch.randn(1, self.cfg["in_channels"], T, device=mu.device) if noises is None or noises[i] is None else \
                 noises[i].to(mu.device, torch.float32)
+            z = z.to(self.dtype)
             segs.append(dict(mu=mu, prompt=ref_mel, style=style, z=z, Tp=ref_mel.shape[-1]))
         xs = [None] * len(segs)
         budget = max(1, int(os.environ.get("IXTTS_S2MEL_BATCH_FRAMES", str(S2MEL_BATCH_FRAMES))))

@@ -284,6 +284,15 @@ int ixtts_gpt_prefill(ixtts_gpt* h, int b, const float* embeds_dev, int n_rows, 
  * embed -> 24 layers.  No host synchronisation inside; a slot that emits stop_mel_token
  * keeps emitting it (generation_utils.py:3255-3256).  Tokens accumulate on the device. */
 int ixtts_gpt_decode(ixtts_gpt* h, int n_active, int n_steps, const ixtts_sampler_cfg* sc, void* stream);
+/* The same with the sampler settings and the random stream belonging to the SEQUENCE: slot b runs its processors and warpers
+ * from per_slot[b] (every field, greedy and sampling slots in one launch included) and draws from
+ * uniform(per_slot[b].seed, rng_stream[b], step) -- rng_stream == NULL: the slot index.  ixtts_gpt_decode is the uniform case
+ * (every entry *sc, stream = slot index).  A sequence's tokens are a function of its prompt, its entry and its stream: not of
+ * the slot it sits in, nor of what the other slots run (on one engine shape; wide and register engines differ in logit bits).
+ * Each entry is checked as ixtts_gpt_decode checks *sc; a failure returns IXTTS_ERR_ARG and names the slot.  The arrays are
+ * copied before the call returns. */
+int ixtts_gpt_decode_slots(ixtts_gpt* h, int n_active, int n_steps, const ixtts_sampler_cfg* per_slot, const uint32_t* rng_stream,
+                           void* stream);
 /* Synchronises `stream`; returns generated ids of slot b (up to and including the first
  * stop token) and whether the slot has finished. */
 int ixtts_gpt_read(ixtts_gpt* h, int b, int32_t* ids_host, int cap, int* n_ids, int* finished, void* stream);
@@ -324,6 +333,10 @@ int ixtts_gpt_beam_force(ixtts_gpt* h, const int32_t* picks_host, int n, void* s
 int ixtts_gpt_beam_begin_group(ixtts_gpt* h, int group, int num_beams, uint64_t rng_stream, void* stream);
 int ixtts_gpt_beam_park_group(ixtts_gpt* h, int group, void* stream);
 int ixtts_gpt_beam_decode_groups(ixtts_gpt* h, int n_groups, int n_steps, const ixtts_sampler_cfg* sc, void* stream);
+/* The same with one cfg per GROUP (per_group[g], every field: do_sample and length_penalty included; ixtts_gpt_beam_read_group
+ * finalizes group g with its own length penalty).  num_beams stays the engine run's.  ixtts_gpt_beam_decode_groups is the
+ * uniform case.  Each entry is checked as *sc is; a failure returns IXTTS_ERR_ARG and names the group. */
+int ixtts_gpt_beam_decode_groups_cfg(ixtts_gpt* h, int n_groups, int n_steps, const ixtts_sampler_cfg* per_group, void* stream);
 int ixtts_gpt_beam_read_group(ixtts_gpt* h, int group, int max_new, int32_t* ids_host, int cap, int* n_ids, int* done, float* score,
                               float* beam_scores_host, int32_t* last_tokens_host, int32_t* beam_idx_host, void* stream);
 int ixtts_gpt_beam_force_group(ixtts_gpt* h, int group, const int32_t* picks_host, int n, void* stream);

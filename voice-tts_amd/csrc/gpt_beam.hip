@@ -14,7 +14,9 @@
 // element from all source beams before writing any destination.  Several groups -- the text segments of one request, or of
 // several requests (infer_v2.py:616 decodes them one after another) -- step together: every kernel below takes the group
 // from its block index and works on that group's slots and that group's scorer state only, so a group's tokens do not
-// depend on its company (tests/test_gpu_beam_groups.py).
+// depend on its company (tests/test_gpu_beam_groups.py).  The sampler configuration is the group's too: SamplerState.cfg holds one
+// entry per engine slot and the host writes group g's entry to every slot of the group, so the per-beam kernel reads it at its
+// own slot and the per-group kernel at the group's first slot (tests/test_gpu_sampler_per_slot.py).  num_beams is the engine run's.
 #include "gpt_engine.h"
 #include "gpt_kernels.h"
 
@@ -57,6 +59,7 @@ __device__ __forceinline__ BeamArgs beam_group_view(const BeamArgs& in, int g) {
   s.cur_len += sb;
   s.prompt_len += sb;
   s.finished += sb;
+  s.cfg += sb;  // the group's sampler cfg: the entry at its first slot
   s.h += sb * s.D;
   a.beam_scores += sb;
   a.src += sb;
@@ -100,7 +103,7 @@ __global__ __launch_bounds__(1024) void beam_cand_kernel(BeamArgs a) {
     vals[i] = lg[v];
     sn[i] = seen[v];
   }
-  const ixtts_sampler_cfg cfg = *s.cfg;
+  const ixtts_sampler_cfg cfg = s.cfg[b];  // the host writes a group's cfg to each of its slots
   const int done = a.done[b / a.NB];  // (b is the engine slot: beam b % NB of group b / NB)
   __builtin_amdgcn_sched_barrier(0);
   if (done) return;  // hypotheses complete: HF leaves the loop here; later graph replays are no-ops
@@ -183,7 +186,7 @@ __global__ __launch_bounds__(1024) void beam_step_kernel(BeamArgs a_all) {
   const int NB = a.NB;
   const int V = s.V;
   const int t = threadIdx.x;
-  const ixtts_sampler_cfg cfg = *s.cfg;
+  const ixtts_sampler_cfg cfg = s.cfg[0];  // (the view starts at the group's first slot)
   const int st_done = *a.done, st_gen = s.gen_count[0], st_nhyp = *a.n_hyp;
   const bool forced = *a.forced_flag != 0;
   const float st_worst = *a.worst;

@@ -81,9 +81,13 @@ struct ixtts_gpt {
       *forced = nullptr;
   int32_t* tokens = nullptr;
   uint8_t* seen = nullptr;
-  ixtts_sampler_cfg* d_samp = nullptr;
+  // sampler settings and random stream of every slot, at fixed device addresses (the captured step graphs read them in place;
+  // each decode call refreshes them with an async copy on its stream).  Beam mode: group g's cfg sits at each of its slots.
+  ixtts_sampler_cfg* d_samp = nullptr;  // [MAXB]
+  unsigned int* d_rng = nullptr;        // [MAXB]
   float* probs = nullptr;  // [slots][V] processed probabilities of the last sampling step (parity tests)
-  ixtts_sampler_cfg samp_host;
+  ixtts_sampler_cfg samp_host[ixtts::MAXB] = {};  // what the last decode call put at each slot
+  unsigned int rng_host[ixtts::MAXB] = {};
   float* scratch = nullptr;
   size_t scratch_floats = 0;
   hipStream_t cap_stream = nullptr;

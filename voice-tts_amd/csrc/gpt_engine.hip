@@ -261,6 +261,7 @@ static SamplerState make_sampler_state(ixtts_gpt* h) {
   s.mel_emb = A_F32(h->mel_emb);
   s.mel_pos = A_F32(h->mel_pos);
   s.cfg = h->d_samp;
+  s.rng_stream = h->d_rng;
   s.V = h->V;
   s.D = h->D;
   s.max_new = h->smax;
@@ -499,7 +500,8 @@ extern "C" int ixtts_gpt_create(ixtts_gpt** out, const ixtts_gpt_cfg* c) {
   ok &= hipMalloc(&h->forced, S * 4) == hipSuccess;
   ok &= hipMalloc(&h->tokens, (size_t)S * h->smax * 4) == hipSuccess;
   ok &= hipMalloc(&h->seen, (size_t)S * V) == hipSuccess;
-  ok &= hipMalloc(&h->d_samp, sizeof(ixtts_sampler_cfg)) == hipSuccess;
+  ok &= hipMalloc(&h->d_samp, MAXB * sizeof(ixtts_sampler_cfg)) == hipSuccess;
+  ok &= hipMalloc(&h->d_rng, MAXB * sizeof(unsigned int)) == hipSuccess;
   ok &= hipMalloc(&h->beam_scores, MAXB * 4) == hipSuccess;
   ok &= hipMalloc(&h->hyp_score, MAXB * 4) == hipSuccess;
   ok &= hipMalloc(&h->hyp_worst, MAXG * 4) == hipSuccess;
@@ -818,22 +820,36 @@ static int pick_bucket(const ixtts_gpt* h, int ctx) {
   return NBKT;
 }
 
-extern "C" int ixtts_gpt_decode(ixtts_gpt* h, int n_active, int n_steps, const ixtts_sampler_cfg* sc, void* stream) {
-  NEED_READY(h, "gpt_decode");
-  IX_ARG(sc, "gpt_decode: null sampler cfg");
-  IX_ARG(n_active >= 1 && n_active <= h->cfg.max_batch, "gpt_decode: n_active %d", n_active);
-  IX_ARG(n_steps >= 0, "gpt_decode: n_steps %d", n_steps);
-  if (sc->do_sample) {
-    IX_ARG(sc->temperature > 0.f && sc->top_p > 0.f, "gpt_decode: temperature and top_p must be positive");
+// Sampler settings and random streams to their fixed device addresses, ahead of the graph launches on the same stream (the
+// captured graphs read them in place: no configuration is baked into a graph).  `per` == nullptr: the uniform case -- `*uni` at
+// EVERY slot of the engine, stream = slot index.
+static int upload_sampler(ixtts_gpt* h, int n, const ixtts_sampler_cfg* uni, const ixtts_sampler_cfg* per, const uint32_t* streams, hipStream_t st) {
+  const int fill = per ? n : h->cfg.max_batch;
+  for (int b = 0; b < fill; ++b) {
+    h->samp_host[b] = per ? per[b] : *uni;
+    h->rng_host[b] = (per && streams) ? streams[b] : (unsigned int)b;
   }
-  IX_ARG(h->V <= 1024 * SAMP_PT, "gpt_decode: vocabulary %d exceeds the sampler tile", h->V);
+  IX_HIP(hipMemcpyAsync(h->d_samp, h->samp_host, (size_t)fill * sizeof(ixtts_sampler_cfg), hipMemcpyHostToDevice, st));
+  IX_HIP(hipMemcpyAsync(h->d_rng, h->rng_host, (size_t)fill * sizeof(unsigned int), hipMemcpyHostToDevice, st));
+  return IXTTS_OK;
+}
+
+static int decode_impl(ixtts_gpt* h, int n_active, int n_steps, const ixtts_sampler_cfg* uni, const ixtts_sampler_cfg* per, const uint32_t* streams,
+                       hipStream_t st, const char* who) {
+  IX_ARG(n_active >= 1 && n_active <= h->cfg.max_batch, "%s: n_active %d", who, n_active);
+  IX_ARG(n_steps >= 0, "%s: n_steps %d", who, n_steps);
+  if (per) {
+    for (int b = 0; b < n_active; ++b)
+      if (per[b].do_sample) IX_ARG(per[b].temperature > 0.f && per[b].top_p > 0.f, "%s: slot %d: temperature and top_p must be positive", who, b);
+  } else if (uni->do_sample) {
+    IX_ARG(uni->temperature > 0.f && uni->top_p > 0.f, "%s: temperature and top_p must be positive", who);
+  }
+  IX_ARG(h->V <= 1024 * SAMP_PT, "%s: vocabulary %d exceeds the sampler tile", who, h->V);
   for (int b = 0; b < n_active; ++b) {
-    IX_ARG(h->host_prompt_len[b] > 0, "gpt_decode: slot %d has no prefilled prompt", b);
-    IX_ARG(h->host_prompt_len[b] + h->host_gen_est[b] + n_steps < h->smax, "gpt_decode: slot %d would overflow max_seq %d", b, h->smax);
+    IX_ARG(h->host_prompt_len[b] > 0, "%s: slot %d has no prefilled prompt", who, b);
+    IX_ARG(h->host_prompt_len[b] + h->host_gen_est[b] + n_steps < h->smax, "%s: slot %d would overflow max_seq %d", who, b, h->smax);
   }
-  hipStream_t st = (hipStream_t)stream;
-  h->samp_host = *sc;
-  IX_HIP(hipMemcpyAsync(h->d_samp, &h->samp_host, sizeof(ixtts_sampler_cfg), hipMemcpyHostToDevice, st));
+  IX_TRY(upload_sampler(h, n_active, uni, per, streams, st));
   int ctx0 = 0;  // keys the longest sequence holds before this call (the host counts the steps it issues)
   for (int b = 0; b < n_active; ++b) ctx0 = std::max(ctx0, h->host_prompt_len[b] + h->host_gen_est[b]);
   for (int done = 0; done < n_steps;) {
@@ -846,6 +862,18 @@ extern "C" int ixtts_gpt_decode(ixtts_gpt* h, int n_active, int n_steps, const i
   }
   for (int b = 0; b < n_active; ++b) h->host_gen_est[b] += n_steps;
   return IXTTS_OK;
+}
+
+extern "C" int ixtts_gpt_decode(ixtts_gpt* h, int n_active, int n_steps, const ixtts_sampler_cfg* sc, void* stream) {
+  NEED_READY(h, "gpt_decode");
+  IX_ARG(sc, "gpt_decode: null sampler cfg");
+  return decode_impl(h, n_active, n_steps, sc, nullptr, nullptr, (hipStream_t)stream, "gpt_decode");
+}
+
+extern "C" int ixtts_gpt_decode_slots(ixtts_gpt* h, int n_active, int n_steps, const ixtts_sampler_cfg* per_slot, const uint32_t* rng_stream, void* stream) {
+  NEED_READY(h, "gpt_decode_slots");
+  IX_ARG(per_slot, "gpt_decode_slots: null sampler cfgs");
+  return decode_impl(h, n_active, n_steps, nullptr, per_slot, rng_stream, (hipStream_t)stream, "gpt_decode_slots");
 }
 
 // ------------------------------------------------------------------------------------ beam-sample
@@ -936,16 +964,23 @@ extern "C" int ixtts_gpt_beam_force_group(ixtts_gpt* h, int group, const int32_t
   return beam_force_impl(h, group, picks, n, (hipStream_t)stream);
 }
 
-static int beam_decode_impl(ixtts_gpt* h, int n_groups, int n_steps, const ixtts_sampler_cfg* sc, hipStream_t st) {
-  IX_ARG(sc && n_steps >= 0, "gpt_beam_decode: bad argument");
+// `per` == nullptr: the uniform case, `*uni` for every group; else per[g] is group g's cfg.
+static int beam_decode_impl(ixtts_gpt* h, int n_groups, int n_steps, const ixtts_sampler_cfg* uni, const ixtts_sampler_cfg* per, hipStream_t st) {
+  IX_ARG((uni || per) && n_steps >= 0, "gpt_beam_decode: bad argument");
   IX_ARG(h->num_beams >= 2, "gpt_beam_decode: call gpt_beam_begin first");
-  // do_sample == 0 is beam search proper: the warpers do not run (generation_utils.py:1020), their settings are not looked at
-  IX_ARG(!sc->do_sample || (sc->top_k >= 1 && sc->top_k <= SAMP_MAXK && sc->temperature > 0.f && sc->top_p > 0.f),
-         "gpt_beam_decode: 1 <= top_k <= %d, positive temperature/top_p", SAMP_MAXK);
   IX_ARG(h->V <= 1024 * SAMP_PT, "gpt_beam_decode: vocabulary %d exceeds the sampler tile", h->V);
   const int nb = h->num_beams;
   IX_ARG(n_groups >= 1 && n_groups <= MAXG && n_groups * nb <= h->cfg.max_batch, "gpt_beam_decode: %d groups of %d beams exceed max_batch %d", n_groups, nb, h->cfg.max_batch);
   IX_ARG(n_groups == 1 || h->wide, "gpt_beam_decode: several groups step together on the wide engines only (max_batch > %d)", MAXB_REG);
+  // do_sample == 0 is beam search proper: the warpers do not run (generation_utils.py:1020), their settings are not looked at
+  if (per) {
+    for (int g = 0; g < n_groups; ++g)
+      IX_ARG(!per[g].do_sample || (per[g].top_k >= 1 && per[g].top_k <= SAMP_MAXK && per[g].temperature > 0.f && per[g].top_p > 0.f),
+             "gpt_beam_decode: group %d: 1 <= top_k <= %d, positive temperature/top_p", g, SAMP_MAXK);
+  } else {
+    IX_ARG(!uni->do_sample || (uni->top_k >= 1 && uni->top_k <= SAMP_MAXK && uni->temperature > 0.f && uni->top_p > 0.f),
+           "gpt_beam_decode: 1 <= top_k <= %d, positive temperature/top_p", SAMP_MAXK);
+  }
   int ctx0 = 0, live = 0;
   for (int g = 0; g < n_groups; ++g) {
     if (!h->group_live[g]) continue;  // parked (or never begun: created parked)
@@ -964,8 +999,13 @@ static int beam_decode_impl(ixtts_gpt* h, int n_groups, int n_steps, const ixtts
       }
     h->beam_exec_nb = nb;
   }
-  h->samp_host = *sc;
-  IX_HIP(hipMemcpyAsync(h->d_samp, &h->samp_host, sizeof(ixtts_sampler_cfg), hipMemcpyHostToDevice, st));
+  if (per) {  // group g's entry at each of its slots (gpt_beam.hip reads it there; beam_read takes its length penalty from the first)
+    ixtts_sampler_cfg slots[MAXB];
+    for (int b = 0; b < n_groups * nb; ++b) slots[b] = per[b / nb];
+    IX_TRY(upload_sampler(h, n_groups * nb, nullptr, slots, nullptr, st));  // (copied into h->samp_host before the async copy reads it)
+  } else {
+    IX_TRY(upload_sampler(h, 0, uni, nullptr, nullptr, st));
+  }
   h->beam_groups = n_groups;
   for (int done = 0; done < n_steps;) {
     const int reps = n_steps - done >= STEPS_PER_GRAPH ? STEPS_PER_GRAPH : 1;
@@ -983,12 +1023,18 @@ static int beam_decode_impl(ixtts_gpt* h, int n_groups, int n_steps, const ixtts
 
 extern "C" int ixtts_gpt_beam_decode(ixtts_gpt* h, int n_steps, const ixtts_sampler_cfg* sc, void* stream) {
   NEED_READY(h, "gpt_beam_decode");
-  return beam_decode_impl(h, 1, n_steps, sc, (hipStream_t)stream);
+  return beam_decode_impl(h, 1, n_steps, sc, nullptr, (hipStream_t)stream);
 }
 
 extern "C" int ixtts_gpt_beam_decode_groups(ixtts_gpt* h, int n_groups, int n_steps, const ixtts_sampler_cfg* sc, void* stream) {
   NEED_READY(h, "gpt_beam_decode_groups");
-  return beam_decode_impl(h, n_groups, n_steps, sc, (hipStream_t)stream);
+  return beam_decode_impl(h, n_groups, n_steps, sc, nullptr, (hipStream_t)stream);
+}
+
+extern "C" int ixtts_gpt_beam_decode_groups_cfg(ixtts_gpt* h, int n_groups, int n_steps, const ixtts_sampler_cfg* per_group, void* stream) {
+  NEED_READY(h, "gpt_beam_decode_groups_cfg");
+  IX_ARG(per_group, "gpt_beam_decode_groups_cfg: null sampler cfgs");
+  return beam_decode_impl(h, n_groups, n_steps, nullptr, per_group, (hipStream_t)stream);
 }
 
 // BeamSearchScorer.finalize (transformers_beam_search.py:320-417), num_return_sequences = 1, on the host.
@@ -1029,7 +1075,7 @@ static int beam_read_impl(ixtts_gpt* h, int g, int max_new, int32_t* ids, int ca
   for (int i = 0; i < nh; ++i) beams.emplace_back(hs[i], hyp[i]);
   float worst = 1e9f;
   for (auto& bsc : beams) worst = std::min(worst, bsc.first);
-  const float lp = h->samp_host.length_penalty;  // of the last beam_decode call
+  const float lp = h->samp_host[sb].length_penalty;  // the group's own, of the last beam_decode call that stepped it
   if (!dn) {
     for (int b = 0; b < nb; ++b) {
       // finalize: beam_hyp.add(final_tokens, final_score, generated_len = tokens generated)  (transformers_beam_search.py:360-371)
@@ -1210,7 +1256,7 @@ extern "C" int ixtts_gpt_destroy(ixtts_gpt* h) {
   if (h->cap_stream) hipStreamDestroy(h->cap_stream);
   if (h->arena_borrowed) h->arena = nullptr;  // the owner frees it
   void* ptrs[] = {h->arena, h->stage, h->kc, h->vc, h->h, h->q, h->ff, h->att, h->part, h->logits, h->rowbuf, h->cur_len, h->gen_count,
-                  h->prompt_len, h->valid_from, h->finished, h->forced, h->tokens, h->seen, h->d_samp, h->probs, h->scratch, h->beam_scores, h->hyp_score, h->hyp_worst, h->beam_src, h->hyp_len,
+                  h->prompt_len, h->valid_from, h->finished, h->forced, h->tokens, h->seen, h->d_samp, h->d_rng, h->probs, h->scratch, h->beam_scores, h->hyp_score, h->hyp_worst, h->beam_src, h->hyp_len,
                   h->n_hyp, h->beam_done, h->beam_forced_flag, h->beam_forced, h->hyp_tok, h->beam_cand_v, h->beam_cand_i, h->beam_cand_n, h->beam_lcp, h->beam_stream,
                   h->rx, h->rxn, h->rq, h->ratt, h->rff, h->h2, h->wprx, h->mlp_part, h->mlp_ctr, h->fold_overflow};
   for (void* p : ptrs)

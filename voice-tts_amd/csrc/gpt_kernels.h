@@ -1331,7 +1331,9 @@ struct SamplerState {
   float* h;             // [slots][D] out: embedding of the chosen token
   const float* mel_emb; // [V][D]
   const float* mel_pos; // [n_pos][D]
-  const ixtts_sampler_cfg* cfg;  // device copy
+  const ixtts_sampler_cfg* cfg;  // [slots] device copies: every slot has its own processors, warpers and seed (beam mode: a
+                                 // group's entry sits at each of its slots, gpt_beam.hip reads it at the group's first)
+  const unsigned int* rng_stream;  // [slots] the random stream a sampling slot draws from (a property of the sequence, not of the slot it sits in)
   float* probs_out;     // optional [slots][V]: the processed probability vector (tests), or null
   int V, D, max_new, n_pos, stop, slot0;
 };
@@ -1801,7 +1803,8 @@ __global__ __launch_bounds__(1024) void sampler_kernel(SamplerState s) {
     raw[i] = lg[v];
     sn[i] = seen[v];
   }
-  const ixtts_sampler_cfg cfg = *s.cfg;
+  const ixtts_sampler_cfg cfg = s.cfg[slot];
+  const unsigned int st_stream = s.rng_stream[slot];
   const int st_finished = s.finished[slot], st_forced = s.forced[slot], st_gen = s.gen_count[slot], st_prompt = s.prompt_len[slot];
   __builtin_amdgcn_sched_barrier(0);
   // the positional row of the token about to be chosen is known already (k = gen_count + 1 -> row k + 1)
@@ -1971,7 +1974,7 @@ __global__ __launch_bounds__(1024) void sampler_kernel(SamplerState s) {
       total += gs.red[w];
     }
     const float excl = before + inc - mine;
-    const float target = uniform01(cfg.seed, (unsigned int)slot, (unsigned int)st_gen) * total;
+    const float target = uniform01(cfg.seed, st_stream, (unsigned int)st_gen) * total;
     if (mine > 0.f && target >= excl && target < excl + mine) {  // at most one thread owns the target
       float c = excl;
       int pk = -1;
@@ -2009,7 +2012,7 @@ __global__ __launch_bounds__(1024) void sampler_kernel(SamplerState s) {
       float Z;
       const int keep = topp_wave0(sort_v, n, cfg.top_p, 1, ev, qv, &Z);
       const float Zk = seq_sum_lds(ev, keep);
-      const float u = uniform01(cfg.seed, (unsigned int)slot, (unsigned int)st_gen) * Zk;
+      const float u = uniform01(cfg.seed, st_stream, (unsigned int)st_gen) * Zk;
       float c = 0.f;
       int pick = -1;
       for (int r0 = 0; r0 < keep; r0 += 8) {

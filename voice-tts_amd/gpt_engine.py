@@ -128,6 +128,38 @@ class GptEngine:
             rc = _lib.lib().ixtts_gpt_decode(self._h, n_active, n_steps, C.byref(sc), self._stream())
         _lib.check(rc, "ixtts_gpt_decode")
 
+    _DECODE_KEYS = dict(repetition_penalty=10.0, temperature=1.0, top_k=0, top_p=1.0, do_sample=False, suppress_stop=False, seed=0,
+                        typical_mass=0.0)
+    _BEAM_KEYS = dict(repetition_penalty=10.0, temperature=0.8, top_k=30, top_p=0.8, suppress_stop=False, seed=0, typical_mass=0.0,
+                      length_penalty=0.0, do_sample=True)
+
+    @staticmethod
+    def _sampler_array(cfgs, defaults, what):
+        """A list of dicts (the keyword names and defaults of `decode()` / `beam_decode()`) -> a ctypes array of SamplerCfg."""
+        arr = (_lib.SamplerCfg * len(cfgs))()
+        for i, cfg in enumerate(cfgs):
+            unknown = set(cfg) - set(defaults)
+            if unknown:
+                raise TypeError(f"{what}: entry {i} has unexpected keys {sorted(unknown)}")
+            v = {**defaults, **cfg}
+            arr[i] = _lib.SamplerCfg(v["repetition_penalty"], v["temperature"], int(v["top_k"]), v["top_p"], int(bool(v["do_sample"])),
+                                     int(bool(v["suppress_stop"])), int(v["seed"]), float(v["typical_mass"]), float(v.get("length_penalty", 0.0)))
+        return arr
+
+    def decode_slots(self, n_steps, cfgs, streams=None):
+        """`decode()` with the settings and the random stream belonging to each sequence: slots 0..len(cfgs)-1 step together,
+        slot b under `cfgs[b]` (a dict with `decode()`'s keyword names; what it leaves out takes `decode()`'s default) and drawing
+        from stream `streams[b]` (None: the slot index, as `decode()` does)."""
+        n = len(cfgs)
+        arr = self._sampler_array(cfgs, self._DECODE_KEYS, "decode_slots")
+        st = None
+        if streams is not None:
+            assert len(streams) == n, (len(streams), n)
+            st = (C.c_uint32 * n)(*[int(s) for s in streams])
+        with torch.cuda.device(self.device):
+            rc = _lib.lib().ixtts_gpt_decode_slots(self._h, n, n_steps, arr, st, self._stream())
+        _lib.check(rc, "ixtts_gpt_decode_slots")
+
     def read(self, slot):
         ids = np.zeros(self.max_seq, dtype=np.int32)
         n, fin = C.c_int(), C.c_int()
@@ -167,9 +199,18 @@ class GptEngine:
                     length_penalty=0.0, groups=1, do_sample=True):
         """`do_sample=False`: beam search proper -- the joint top 2 * num_beams instead of the multinomial draw, no warpers."""
         sc = _lib.SamplerCfg(repetition_penalty, temperature, top_k, top_p, int(bool(do_sample)), int(suppress_stop), seed, float(typical_mass), float(length_penalty))
-        self._lp = float(length_penalty)
+        self._lp = [float(length_penalty)] * int(groups)  # per group
         with torch.cuda.device(self.device):
             _lib.check(_lib.lib().ixtts_gpt_beam_decode_groups(self._h, int(groups), n_steps, C.byref(sc), self._stream()), "ixtts_gpt_beam_decode_groups")
+
+    def beam_decode_groups(self, n_steps, cfgs):
+        """`beam_decode(groups=len(cfgs))` with one cfg per group: group g steps under `cfgs[g]` (a dict with `beam_decode()`'s
+        keyword names but `groups`; what it leaves out takes `beam_decode()`'s default), `beam_read(group=g)` finalizes with its own
+        length penalty.  The groups' random streams are the ones `beam_begin` gave them."""
+        arr = self._sampler_array(cfgs, self._BEAM_KEYS, "beam_decode_groups")
+        self._lp = [float(a.length_penalty) for a in arr]  # per group
+        with torch.cuda.device(self.device):
+            _lib.check(_lib.lib().ixtts_gpt_beam_decode_groups_cfg(self._h, len(cfgs), n_steps, arr, self._stream()), "ixtts_gpt_beam_decode_groups_cfg")
 
     def beam_force(self, picks, group=0):
         a = np.ascontiguousarray(np.asarray(picks, dtype=np.int32))

@@ -627,11 +627,61 @@ class IndexTTS2:
         return [self.tokenizer.convert_tokens_to_ids(sent) for sent in
                 self.tokenizer.split_segments(text_tokens_list, max_text_tokens_per_segment, quick_streaming_tokens=quick_streaming_tokens)]
 
-    def _segment(self, conds_latent, ids, engine, max_mel_tokens, request=0, index=0, payload=None, stream=None):
+    def _segment(self, conds_latent, ids, engine, max_mel_tokens, request=0, index=0, payload=None, stream=None, sampler=None):
         """One segment's text ids -> what the schedulers decode; `max_new` is taken against the engine that will decode it."""
         embeds, n_pad, P = prepare_gpt_inputs(self.gpt_cfg, self.text_embedding, self.text_pos_embedding, conds_latent, ids)
         max_new = max(0, min(max_mel_tokens, engine.max_seq - P - 2, self.gpt_cfg["max_mel_tokens"] - 1))
-        return decode_segment(index, embeds, n_pad, max_new, request, payload, stream)
+        return decode_segment(index, embeds, n_pad, max_new, request, payload, stream, sampler)
+
+    # what a request's `generation` dict may hold (infer_many): `infer`'s generation kwargs, parsed by `_generation_args`
+    GENERATION_KEYS = ("top_p", "top_k", "temperature", "repetition_penalty", "length_penalty", "max_mel_tokens", "typical_sampling",
+                       "typical_mass", "seed", "num_beams")
+
+    def _request_generation(self, rq, generation_kwargs, g):
+        """-> (generation namespace of this request, pinned): a request with a `generation` dict overrides the call's kwargs with
+        it and is PINNED -- its settings, seed and random streams are its own; one without it takes the call's (`g`)."""
+        if "generation" not in rq:
+            return g, False
+        gen = dict(rq["generation"] or {})
+        for k in gen:
+            if k not in self.GENERATION_KEYS:
+                raise ValueError(f"generation: unknown key {k!r} (known: {', '.join(self.GENERATION_KEYS)})")
+        gr, _ = self._generation_args({**generation_kwargs, **gen})
+        gr.num_beams = int(gr.num_beams)
+        if gr.num_beams < 1:
+            raise ValueError(f"generation: num_beams {gr.num_beams}")
+        if gr.num_beams > 1 and not (2 <= gr.num_beams <= 4 and 1 <= gr.top_k <= 128):
+            raise NotImplementedError("beam-sample on the device: 2 <= num_beams <= 4, 1 <= top_k <= 128")
+        return gr, True
+
+    @staticmethod
+    def _segment_sampler(g):
+        """The namespace's settings under the keyword names the engine's decode() / beam_decode() take (`scheduler.Segment.sampler`)."""
+        s = dict(repetition_penalty=g.repetition_penalty, temperature=g.temperature, top_k=g.top_k, top_p=g.top_p, seed=g.seed,
+                 typical_mass=g.typical_mass)
+        if g.num_beams > 1:
+            s["length_penalty"] = g.length_penalty
+        else:
+            s["do_sample"] = g.top_k != 1
+        return s
+
+    def _many_engine_for(self, num_beams, decode_slots):
+        """The engine `infer_many` decodes a `num_beams` class on: floor(decode_slots / num_beams) groups (the register engine up
+        to 4 slots), or `decode_slots` single slots."""
+        from . import _lib
+
+        if num_beams > 1:
+            groups = max(1, min(int(decode_slots), _lib.max_batch()) // num_beams)
+            return self._many_engine(groups * num_beams) if groups * num_beams > 4 else self.gpt
+        return self._many_engine(decode_slots)
+
+    def _pinned_noise(self, item, seed, index):
+        """The CFM noise [1, in_channels, T] of segment `index` of a pinned request: drawn from (seed, index) alone, not from the
+        process-wide generator whose state depends on what was served before."""
+        codes, pc = item[1], item[2]
+        T = pc.shape[1] + int((torch.tensor([codes.shape[-1]]) * 1.72).long())
+        gen = torch.Generator(device=self.device).manual_seed((int(seed) * 1000003 + int(index)) & 0x7FFFFFFFFFFFFFFF)
+        return torch.randn(1, self.s2mel.cfg["in_channels"], T, device=self.device, generator=gen)
 
     def _decode(self, engine, todo, g):
         """The segments through the engine's slots, weights read once per step for all of them -> {(request, index): ids}: beam
@@ -666,16 +716,18 @@ class IndexTTS2:
         latent = self.gpt.latent(prefix, codes[0]).unsqueeze(0)
         return latent, codes, spk["prompt_condition"], spk["ref_mel"], spk["style"]
 
-    def _mels(self, items, spk, packed=False):
+    def _mels(self, items, spk, packed=False, noises=None):
         """s2mel items -> one mel [1, 80, F] each (infer_v2.py:713-731): segment after segment through the built-in or the injected
-        stage (which gets the speaker dict `spk`), or -- `packed`, IXTTS_S2MEL_BATCH=1 -- as ONE packed solve (S2Mel.solve_many)."""
+        stage (which gets the speaker dict `spk`), or -- `packed`, IXTTS_S2MEL_BATCH=1 -- as ONE packed solve (S2Mel.solve_many).
+        `noises`: per item the CFM noise of the built-in stage, or None for a draw from the default generator."""
         if packed:
-            return self.s2mel.solve_many(items, n_timesteps=25, inference_cfg_rate=0.7)
+            return self.s2mel.solve_many(items, n_timesteps=25, inference_cfg_rate=0.7, noises=noises)
         mels = []
-        for latent, codes, pc, rm, st in items:
+        for i, (latent, codes, pc, rm, st) in enumerate(items):
             lens = torch.tensor([codes.shape[1]], dtype=torch.long, device=self.device)
             if self.s2mel is not None:
-                mels.append(self.s2mel(latent, codes, lens, pc, rm, st, n_timesteps=25, inference_cfg_rate=0.7))
+                mels.append(self.s2mel(latent, codes, lens, pc, rm, st, n_timesteps=25, inference_cfg_rate=0.7,
+                                       noise=None if noises is None else noises[i]))
             else:
                 mels.append(self._stage("s2mel", None)(latent, codes, lens, spk))
         return mels
@@ -703,23 +755,31 @@ class IndexTTS2:
         `emo_text` (the emotion from text, as in `infer`; the emotion texts of the whole batch are decoded together).  Generation
         kwargs and defaults are `infer`'s: with `num_beams > 1` (the served default, 3) every segment is a beam GROUP and
         floor(decode_slots / num_beams) groups step together; `num_beams=1` samples without beams, one slot per segment (argmax
-        when `top_k == 1`).  Returns one entry per request: `(22050, int16 [N, 1])`, None (empty text), or the EXCEPTION that
+        when `top_k == 1`).
+
+        A request may carry `generation`, a dict with any of `GENERATION_KEYS` (top_p, top_k, temperature, repetition_penalty,
+        length_penalty, max_mel_tokens, typical_sampling, typical_mass, seed, num_beams): it overrides the call's kwargs for that
+        request, and the request is PINNED (even with `{}`): segment i decodes under the request's settings and seed from random
+        stream i, and the built-in s2mel's noise comes from (seed, i).  Its codes and PCM are then a function of the request
+        alone -- bit-identical alone or in any batch, in any order -- at a given `decode_slots` (the engine's shape: wide and
+        register engines differ in logit bits) and outside IXTTS_S2MEL_BATCH=1 (the packed solve reassociates with its pack).
+        `num_beams` may differ between requests: each value decodes as its own class, one after another.  An unknown key, or a
+        `num_beams` the engine chosen for `decode_slots` cannot hold, fails that request only.  Requests without the key behave
+        as ever: the call's settings, streams by slot / submission order, noise from the default generator.
+
+        Returns one entry per request: `(22050, int16 [N, 1])`, None (empty text), or the EXCEPTION that
         request raised (bad prompt audio, a code outside the codebook ...) -- one request's failure leaves the others of the
         batch alone."""
-        from . import _lib
-
         g, _ = self._generation_args(generation_kwargs)
         g.num_beams = int(g.num_beams)
         self._prompt_stages()  # a model without prompt stages refuses the whole call
-        if g.num_beams > 1:
-            if not (2 <= g.num_beams <= 4 and 1 <= g.top_k <= 128):
-                raise NotImplementedError("beam-sample on the device: 2 <= num_beams <= 4, 1 <= top_k <= 128")
-            groups = max(1, min(int(decode_slots), _lib.max_batch()) // g.num_beams)
-            eng = self._many_engine(groups * g.num_beams) if groups * g.num_beams > 4 else self.gpt
-        else:
-            eng = self._many_engine(decode_slots)
+        if g.num_beams > 1 and not (2 <= g.num_beams <= 4 and 1 <= g.top_k <= 128):
+            raise NotImplementedError("beam-sample on the device: 2 <= num_beams <= 4, 1 <= top_k <= 128")
+        # segments decode per `num_beams` class (the call's, and whatever pinned requests ask for), each class on its own engine
+        engines = {g.num_beams: self._many_engine_for(g.num_beams, decode_slots)}
+        classes = {}  # num_beams -> segments
         start = time.perf_counter()
-        plans, todo = [None] * len(requests), []
+        plans = [None] * len(requests)
         failed = {}
         text_emo = self._emo_text_vectors(requests, failed)
         for ri, rq in enumerate(requests):
@@ -733,12 +793,28 @@ class IndexTTS2:
                 spk, emo_cond = self._encode_prompts(spk_prompt, emo_prompt)
                 cl = self._conds_latent(spk, emo_cond, emo_is_spk, emo_alpha, emo_vector, rq.get("use_random", False))
                 segments = self._segments_of(rq["text"], max_text_tokens_per_segment)
-                mine = [self._segment(cl, ids, eng, g.max_mel_tokens, request=ri, index=si) for si, ids in enumerate(segments)]
-                plans[ri] = dict(spk=spk, cl=cl, segments=segments)
-                todo += mine  # only once the whole request is known to be well-formed
+                gr, pinned = self._request_generation(rq, generation_kwargs, g)
+                nb = gr.num_beams
+                if nb not in engines:
+                    engines[nb] = self._many_engine_for(nb, decode_slots)
+                eng = engines[nb]
+                if nb > 1 and eng.max_batch < nb:
+                    raise NotImplementedError(f"num_beams={nb} needs {nb} decode slots: the engine chosen for decode_slots={decode_slots} holds {eng.max_batch}")
+                # a pinned request: segment i under the request's own settings and seed, drawing from stream i
+                sampler = self._segment_sampler(gr) if pinned else None
+                mine = [self._segment(cl, ids, eng, gr.max_mel_tokens, request=ri, index=si, stream=si if pinned else None, sampler=sampler)
+                        for si, ids in enumerate(segments)]
+                plans[ri] = dict(spk=spk, cl=cl, segments=segments, seed=gr.seed if pinned else None)
+                classes.setdefault(nb, []).extend(mine)  # only once the whole request is known to be well-formed
             except Exception as e:  # this request only
                 failed[ri] = e
-        decoded = self._decode(eng, todo, g)
+        decoded, todo = {}, []
+        for nb, segs in (classes or {g.num_beams: []}).items():
+            # the run's settings (idle slots, parked groups, unpinned segments): the call's in its own class; another class holds
+            # pinned segments only and idles under the served defaults
+            gc = g if nb == g.num_beams else self._generation_args(dict(num_beams=nb))[0]
+            decoded.update(self._decode(engines[nb], segs, gc))
+            todo += segs
         t_decode = time.perf_counter() - start
         # per request: codes -> latents (a code outside the codebook fails its request only, before anything is packed); a segment
         # without codes is left out
@@ -747,7 +823,11 @@ class IndexTTS2:
                 continue
             try:
                 codes = [self._trim_codes(decoded[ri, si]) for si in range(len(plan["segments"]))]
-                plan["items"] = [self._s2mel_item(plan["cl"], seg, c, plan["spk"]) for seg, c in zip(plan["segments"], codes) if c.shape[1]]
+                kept = [si for si, c in enumerate(codes) if c.shape[1]]
+                plan["items"] = [self._s2mel_item(plan["cl"], plan["segments"][si], codes[si], plan["spk"]) for si in kept]
+                # a pinned request's audio is a function of the request: the built-in s2mel's noise comes from its seed, per segment
+                pin = plan["seed"] is not None and self.s2mel is not None
+                plan["noises"] = [self._pinned_noise(it, plan["seed"], si) if pin else None for si, it in zip(kept, plan["items"])]
             except Exception as e:  # this request only
                 failed[ri] = e
         # s2mel, IXTTS_S2MEL_BATCH=1: every surviving segment of every request in one packed solve -- an exception raised inside it
@@ -755,7 +835,8 @@ class IndexTTS2:
         live = [ri for ri in range(len(plans)) if ri not in failed]
         if self.s2mel is not None and s2mel_batching():
             try:
-                mels = iter(self._mels([it for ri in live for it in plans[ri]["items"]], None, packed=True))
+                mels = iter(self._mels([it for ri in live for it in plans[ri]["items"]], None, packed=True,
+                                       noises=[z for ri in live for z in plans[ri]["noises"]]))
                 for ri in live:
                     plans[ri]["mels"] = [next(mels) for _ in plans[ri]["items"]]
             except Exception as e:
@@ -764,7 +845,7 @@ class IndexTTS2:
         else:
             for ri in live:
                 try:
-                    plans[ri]["mels"] = self._mels(plans[ri]["items"], plans[ri]["spk"])
+                    plans[ri]["mels"] = self._mels(plans[ri]["items"], plans[ri]["spk"], noises=plans[ri]["noises"])
                 except Exception as e:  # this request only
                     failed[ri] = e
         out = []

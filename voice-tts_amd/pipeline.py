@@ -73,11 +73,11 @@ def vocode(bigvgan, mel):
     return torch.clamp(32767 * wav, -32767.0, 32767.0)
 
 
-def decode_segment(index, embeds, n_left_pad, max_new, request=0, payload=None, stream=None):
+def decode_segment(index, embeds, n_left_pad, max_new, request=0, payload=None, stream=None, sampler=None):
     """One prepared sequence as the decode schedulers take it (`scheduler.Segment`); `HotPath` and `IndexTTS2` build theirs here."""
     from .scheduler import Segment
 
-    return Segment(request, index, embeds, n_left_pad, max_new, payload, stream)
+    return Segment(request, index, embeds, n_left_pad, max_new, payload, stream, sampler)
 
 
 class HotPath:

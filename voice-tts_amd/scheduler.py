@@ -6,6 +6,12 @@ B=2 step, r01), so a worker that owns a GPU keeps its decode slots full: segment
 into free slots, all slots step together, a finished slot is handed back and refilled while the others keep going
 (continuous batching).  Greedy results do not depend on the company a sequence keeps -- every slot's arithmetic is
 its own, in a fixed order -- which `tests/test_gpu_scheduler.py` checks against one-at-a-time decoding.
+
+Sampling settings and the random stream can belong to the SEGMENT (`Segment.sampler`, `Segment.stream`): the schedulers
+then hand the engine one cfg per slot / per beam group with every decode call (`decode_slots`, `beam_decode_groups`), and a
+segment that carries both draws the same tokens whatever slot or group it lands in and whatever decodes beside it -- on one
+engine shape (wide and register engines differ in logit bits).  A run in which no segment carries either makes exactly the
+uniform calls (`decode`, `beam_decode`), where a sampling slot's stream is its slot index.
 """
 import collections
 
@@ -15,11 +21,15 @@ import numpy as np
 class Segment:
     """One text segment of one request, ready for the decode engine."""
 
-    __slots__ = ("request", "index", "embeds", "n_left_pad", "max_new", "payload", "stream")
+    __slots__ = ("request", "index", "embeds", "n_left_pad", "max_new", "payload", "stream", "sampler")
 
-    def __init__(self, request, index, embeds, n_left_pad, max_new, payload=None, stream=None):
+    def __init__(self, request, index, embeds, n_left_pad, max_new, payload=None, stream=None, sampler=None):
         self.request, self.index, self.embeds, self.n_left_pad, self.max_new, self.payload = request, index, embeds, n_left_pad, max_new, payload
-        self.stream = stream  # beam groups: the random stream this segment draws from (None: its position in the submission order)
+        # the random stream this segment draws from (None: beam groups, its position in the submission order; single slots, the
+        # index of the slot it lands in)
+        self.stream = stream
+        # its own sampler settings: keyword names of the engine's decode() / beam_decode(), over the run's **sampler (None: the run's)
+        self.sampler = sampler
 
 
 def live_stub(engine, like):
@@ -39,7 +49,8 @@ class DecodeScheduler:
     """Keeps the engine's decode slots busy with segments from a queue.
 
     engine: `GptEngine`-like object with prefill(slot, embeds, n_left_pad), decode(n_active, n_steps, **sampler) and
-    read(slot) -> (ids, finished).  `stop_token` ends a sequence (inclusive) unless `fixed_length`.
+    read(slot) -> (ids, finished); decode_slots(n_steps, cfgs, streams) too when a segment carries `sampler` or `stream`.
+    `stop_token` ends a sequence (inclusive) unless `fixed_length`.
     """
 
     def __init__(self, engine, max_batch, stop_token, sync_every=64):
@@ -50,7 +61,11 @@ class DecodeScheduler:
     def run(self, segments, on_done, fixed_length=False, **sampler):
         """Decode every segment; `on_done(segment, ids)` is called as each finishes (ids: int32 array, stop token included
         when it was produced).  Order of completion is not the order of submission."""
-        queue = collections.deque(longest_first(list(segments)))
+        segments = list(segments)
+        # per-slot settings only when a segment asks for them: else the uniform call, as ever
+        per_slot = any(getattr(s, "sampler", None) is not None or getattr(s, "stream", None) is not None for s in segments)
+        base = dict(suppress_stop=fixed_length, **sampler)
+        queue = collections.deque(longest_first(segments))
         slots = [None] * self.max_batch  # (segment, steps issued so far)
         length = [0] * self.max_batch    # rows each slot's sequence holds (a freed slot below n_active keeps stepping)
         max_seq = getattr(self.engine, "max_seq", None)
@@ -73,8 +88,15 @@ class DecodeScheduler:
                     if slots[b] is None and length[b] + steps >= max_seq - 2:
                         self.engine.prefill(b, live_stub(self.engine, slots[live[0]][0].embeds), 0)
                         length[b] = 3
-            if steps > 0:
+            if steps > 0 and per_slot:
+                # a live slot: its segment's cfg over the run's, its segment's stream; an idle one (and a segment without a stream):
+                # the run's cfg, the slot index.  Given anew with every call: a refilled slot has nothing of its previous occupant.
+                occ = [slots[b][0] if slots[b] is not None else None for b in range(n_active)]
+                self.engine.decode_slots(steps, [dict(base, **(s.sampler or {})) if s is not None else dict(base) for s in occ],
+                                         [int(s.stream) if s is not None and s.stream is not None else b for b, s in enumerate(occ)])
+            elif steps > 0:
                 self.engine.decode(n_active, steps, suppress_stop=fixed_length, **sampler)
+            if steps > 0:
                 self.stats["decode_calls"] += 1
                 self.stats["slot_steps"] += n_active * steps
                 self.stats["busy_slot_steps"] += len(live) * steps
@@ -104,8 +126,12 @@ class BeamGroupScheduler:
     in the submission order), so its tokens do not depend on the group it lands in or on its company
     (tests/test_gpu_beam_groups.py holds that bit for bit against one-group-at-a-time decoding).
 
+    A segment with `sampler` steps under its own cfg (length penalty included): the decode calls then carry one cfg per group
+    (`beam_decode_groups`); a parked group gets the run's.
+
     engine: `GptEngine`-like with prefill(slot, embeds, pad), beam_begin(num_beams, group=, rng_stream=), beam_park(group),
-    beam_decode(n_steps, groups=, **sampler), beam_read(max_new, group=) -> (ids, done, score, ...).
+    beam_decode(n_steps, groups=, **sampler), beam_read(max_new, group=) -> (ids, done, score, ...); beam_decode_groups(n_steps,
+    cfgs) too when a segment carries `sampler`.
     """
 
     def __init__(self, engine, num_beams, max_groups=None, sync_every=64):
@@ -120,6 +146,9 @@ class BeamGroupScheduler:
     def run(self, segments, on_done, fixed_length=False, **sampler):
         """Decode every segment; `on_done(segment, ids, score)` as each finishes: ids = the best hypothesis as
         `generate()` returns it (`BeamSearchScorer.finalize`: + eos when there is room)."""
+        segments = list(segments)
+        per_group = any(getattr(s, "sampler", None) is not None for s in segments)  # (streams go through beam_begin either way)
+        base = dict(suppress_stop=fixed_length, **sampler)
         # (a segment's random stream is fixed by its place in the SUBMISSION order before the queue is re-ordered: its tokens do not change)
         queue = collections.deque(longest_first([(seg, getattr(seg, "stream", None) if getattr(seg, "stream", None) is not None else i)
                                                  for i, seg in enumerate(segments)], seg_of=lambda it: it[0]))
@@ -142,8 +171,11 @@ class BeamGroupScheduler:
                 if groups[g] is None:
                     eng.beam_park(g)  # nothing queued for it: a no-op under the live ones
             steps = min([self.sync_every] + [groups[g][0].max_new - groups[g][1] for g in live])
-            if steps > 0:
+            if steps > 0 and per_group:
+                eng.beam_decode_groups(steps, [dict(base, **(groups[g][0].sampler or {})) if groups[g] is not None else dict(base) for g in range(n_groups)])
+            elif steps > 0:
                 eng.beam_decode(steps, groups=n_groups, suppress_stop=fixed_length, **sampler)
+            if steps > 0:
                 self.stats["decode_calls"] += 1
                 self.stats["group_steps"] += n_groups * steps
                 self.stats["busy_group_steps"] += len(live) * steps

@@ -199,6 +199,14 @@ int ixtts_bigvgan_arena(ixtts_bigvgan* h, void** ptr_dev, size_t* bytes);
 int ixtts_bigvgan_adopt_arena(ixtts_bigvgan* h);
 /* mel [B,num_mels,F] fp32 -> wav [B,1,F*prod(rates)] fp32, clamp(-1,1) (bigvgan.py:360-386). */
 int ixtts_bigvgan_forward(ixtts_bigvgan* h, const float* mel_dev, int B, int F, float* wav_dev, void* stream);
+/* The same generator over B rows of unequal length in one pass: mel [B,num_mels,Fmax] and wav [B,1,Fmax*prod(rates)] are padded to
+ * Fmax, row b is frames[b] frames long.  `frames_dev` is what the kernels read (each clamps it to [0, Fmax], so no table can move
+ * a load or a store outside the tensors); `frames_host` holds the same numbers for validation (0 <= frames <= Fmax, else
+ * IXTTS_ERR_ARG) and for choosing conv tiles.  Padding is never read -- it may hold anything, NaN included -- and wav_dev[b] from
+ * frames[b]*prod(rates) on is left untouched; a row of 0 frames writes nothing; B == 0 or Fmax == 0 returns IXTTS_OK.  Row b is
+ * bit-identical to ixtts_bigvgan_forward on that row alone.  Same schedule and workspace (sized for B x Fmax). */
+int ixtts_bigvgan_forward_varlen(ixtts_bigvgan* h, const float* mel_dev, const int* frames_dev, const int* frames_host, int B, int Fmax,
+                                 float* wav_dev, void* stream);
 /* Algorithmic conv FLOPs of one forward at F frames. */
 double ixtts_bigvgan_flops(const ixtts_bigvgan* h, int B, int F);
 int ixtts_bigvgan_destroy(ixtts_bigvgan* h);

@@ -96,6 +96,7 @@ SYMBOLS = {
     "ixtts_bigvgan_arena": (C.c_int, [_P, C.POINTER(_P), C.POINTER(C.c_size_t)]),
     "ixtts_bigvgan_adopt_arena": (C.c_int, [_P]),
     "ixtts_bigvgan_forward": (C.c_int, [_P, _P, C.c_int, C.c_int, _P, _P]),
+    "ixtts_bigvgan_forward_varlen": (C.c_int, [_P, _P, _P, _P, C.c_int, C.c_int, _P, _P]),
     "ixtts_bigvgan_flops": (C.c_double, [_P, C.c_int, C.c_int]),
     "ixtts_bigvgan_destroy": (C.c_int, [_P]),
     "ixtts_gpt_create": (C.c_int, [C.POINTER(_P), C.POINTER(GptCfg)]),

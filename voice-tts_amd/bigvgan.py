@@ -7,12 +7,46 @@ without weight norm), called as `bigvgan(mel_fp32[B,80,F]) -> wav[B,1,256F]`
 drop-in compatibility (the fold happens once in `load_state_dict`, row V5).
 """
 import ctypes as C
+import os
 
 import torch
 import torch.nn as nn
 
 from . import _lib
 from .weights import BIGVGAN_CFG, fold_weight_norm
+
+
+# Padded frames (rows x longest row) per batched vocoder pass (`BigVGAN.forward_many`; IXTTS_BV_BATCH_FRAMES).  The workspace grows
+# with it: at production width 11 fp32 buffers of 6144 floats per padded frame and 4 plane buffers of 6144 x 6 bytes, 418 KB per
+# padded frame -- 1.7 GB at this default (3.4 GB at 8192).  Chosen by tools/bv_batch_perf.py (profiles/bv_batch_perf.json, DESIGN.md §4.3).
+BV_BATCH_FRAMES = 4096
+
+
+def vocoder_batching():
+    """The mels of several segments through ONE vocoder pass (`BigVGAN.forward_many`) in `infer_many` and after a packed solve in
+    `infer`.  On by default (every row is bit-identical to its own `forward`); IXTTS_BV_BATCH=0: one pass per segment."""
+    return os.environ.get("IXTTS_BV_BATCH", "1") != "0"
+
+
+def vocoder_batch_frames():
+    return max(1, int(os.environ.get("IXTTS_BV_BATCH_FRAMES", str(BV_BATCH_FRAMES))))
+
+
+def plan_vocoder_batches(frames, cap):
+    """Groups of row indices for the batched vocoder pass: rows sorted by length (ties in input order), cut greedily so that a group's
+    padded size, rows x longest row, stays within `cap` frames; a single row longer than `cap` is a group of its own.  Every index
+    appears in exactly one group."""
+    order = sorted(range(len(frames)), key=lambda i: (int(frames[i]), i))
+    groups, cur = [], []
+    for i in order:
+        # (sorted ascending: the row being added is the longest of its group)
+        if cur and (len(cur) + 1) * int(frames[i]) > cap:
+            groups.append(cur)
+            cur = []
+        cur.append(i)
+    if cur:
+        groups.append(cur)
+    return groups
 
 
 class BigVGAN(nn.Module):
@@ -98,6 +132,53 @@ class BigVGAN(nn.Module):
             rc = _lib.lib().ixtts_bigvgan_forward(self._h, x.data_ptr(), B, F, wav.data_ptr(), _lib.current_stream_ptr())
         _lib.check(rc, "ixtts_bigvgan_forward")
         return wav
+
+    def forward_varlen(self, mel, frames, out=None):
+        """One pass over rows of unequal length (`ixtts_bigvgan_forward_varlen`): `mel` fp32 [B, num_mels, Fmax] on the device, row b
+        `frames[b] <= Fmax` frames long (the rest is padding and is never read) -> wav [B, 1, Fmax*total_up], zero from
+        `frames[b]*total_up` on (`out`: written in place instead, and left as it was from there on).  Row b is bit-identical to
+        `forward` on that row alone."""
+        if not self._loaded:
+            raise RuntimeError("BigVGAN: weights not loaded")
+        if mel.dtype != torch.float32 or not mel.is_cuda or mel.dim() != 3 or mel.shape[1] != self.h["num_mels"]:
+            raise RuntimeError(f"BigVGAN.forward_varlen expects a CUDA fp32 [B,{self.h['num_mels']},Fmax] mel, got {tuple(mel.shape)} {mel.dtype} {mel.device}")
+        mel = mel.contiguous()
+        B, _, Fmax = mel.shape
+        frames = [int(f) for f in frames]
+        if len(frames) != B:
+            raise RuntimeError(f"BigVGAN.forward_varlen: {len(frames)} lengths for {B} rows")
+        wav = out if out is not None else torch.zeros(B, 1, Fmax * self.total_up, device=mel.device, dtype=torch.float32)
+        if wav.shape != (B, 1, Fmax * self.total_up) or wav.dtype != torch.float32 or wav.device != mel.device or not wav.is_contiguous():
+            raise RuntimeError(f"BigVGAN.forward_varlen: out must be a contiguous fp32 [{B},1,{Fmax * self.total_up}] tensor on {mel.device}")
+        host = (C.c_int * max(B, 1))(*frames)
+        with torch.cuda.device(mel.device):
+            dev = torch.tensor(frames, dtype=torch.int32, device=mel.device)
+            rc = _lib.lib().ixtts_bigvgan_forward_varlen(self._h, mel.data_ptr(), dev.data_ptr(), host, B, Fmax, wav.data_ptr(),
+                                                         _lib.current_stream_ptr())
+        _lib.check(rc, "ixtts_bigvgan_forward_varlen")
+        return wav
+
+    def forward_many(self, mels):
+        """Mels of unequal length, fp32 [1, num_mels, F_i] on the device -> [1, 1, F_i*total_up] each, in input order: rows grouped
+        by length (`plan_vocoder_batches`, at most IXTTS_BV_BATCH_FRAMES padded frames per group), every group one padded buffer and
+        one `forward_varlen` call.  Each result is bit-identical to `forward(mel_i)`."""
+        mels = list(mels)
+        for m in mels:
+            if m.dim() != 3 or m.shape[0] != 1 or m.shape[1] != self.h["num_mels"] or m.dtype != torch.float32 or not m.is_cuda:
+                raise RuntimeError(f"BigVGAN.forward_many expects CUDA fp32 [1,{self.h['num_mels']},F] mels, got {tuple(m.shape)} {m.dtype} {m.device}")
+        out = [None] * len(mels)
+        for group in plan_vocoder_batches([m.shape[2] for m in mels], vocoder_batch_frames()):
+            frames = [mels[i].shape[2] for i in group]
+            if len(group) == 1:
+                out[group[0]] = self.forward(mels[group[0]])
+                continue
+            pad = torch.zeros(len(group), self.h["num_mels"], max(frames), device=mels[group[0]].device, dtype=torch.float32)
+            for b, i in enumerate(group):
+                pad[b, :, :frames[b]] = mels[i][0]
+            wav = self.forward_varlen(pad, frames)
+            for b, i in enumerate(group):
+                out[i] = wav[b:b + 1, :, :frames[b] * self.total_up].clone()
+        return out
 
     def __del__(self):
         try:

@@ -12,7 +12,7 @@
 // streams, and the down-filter reads LDS as conflict-free 8-byte pairs.
 //
 // Roofline: 8 B of HBM per element (read x, write y); 2 sin^2 (12 instructions each) + 24 FMA per element.
-#include "common.h"
+#include "conv.h"
 
 namespace ixtts {
 
@@ -52,20 +52,29 @@ __device__ __forceinline__ float snake(float u, float a, float inv_b) {
   }
 }
 
-template <bool FAST_SIN>
+// LENS = RowLens: rows of unequal length -- TS stays the row stride of x and y, and T, the bound of the replicate padding, of the
+// interior test and of the stores, becomes the row's own length; a tile past it leaves before anything is read (workgroup-uniform).
+// LENS = NoLens (an empty argument): every row is TS long, the kernel as it was.
+struct NoLens {};
+template <bool FAST_SIN, class LENS = NoLens>
 __global__ __launch_bounds__(AA_THREADS) void aa_snake_kernel(const float* __restrict__ x, float* __restrict__ y,
                                                                const float* __restrict__ up12,
                                                                const float* __restrict__ down12,
                                                                const float* __restrict__ log_alpha,
-                                                               const float* __restrict__ log_beta, int C, int T) {
+                                                               const float* __restrict__ log_beta, int C, int TS, LENS rl) {
   __shared__ __attribute__((aligned(16))) float xs[AA_NX];
   __shared__ __attribute__((aligned(16))) float ss[AA_NS];
 
   const int row = blockIdx.y;  // b*C + c
   const int c = row % C;
   const int t0 = blockIdx.x * AA_TILE;
-  const float* xr = x + (size_t)row * T;
-  float* yr = y + (size_t)row * T;
+  int T = TS;
+  if constexpr (std::is_same_v<LENS, RowLens>) {
+    T = row_len_vl(rl, row / C);
+    if (t0 >= T) return;
+  }
+  const float* xr = x + (size_t)row * TS;
+  float* yr = y + (size_t)row * TS;
 
   float fu[12], fd[12];
 #pragma unroll
@@ -174,20 +183,27 @@ constexpr int AP_NS = 2 * AP_TILE + 16;
 #endif
 constexpr int AP_NSUB = IXTTS_AP_NSUB;  // consecutive 256-output tiles per workgroup: tile s+1's inputs are fetched under tile s's arithmetic
 
-template <bool FAST_SIN>
+// LENS as in aa_snake_kernel (TS: row stride of x and of the planes; T: time steps of this row): the next-tile prefetch and the walk
+// over the workgroup's tiles end at the row's length
+template <bool FAST_SIN, class LENS = NoLens>
 __global__ __launch_bounds__(512) void aa_snake_planes_kernel(const float* __restrict__ x, uint4* __restrict__ xp, const float* __restrict__ up12,
                                                               const float* __restrict__ down12, const float* __restrict__ log_alpha,
-                                                              const float* __restrict__ log_beta, int C, int T) {
+                                                              const float* __restrict__ log_beta, int C, int TS, LENS rl) {
   __shared__ __attribute__((aligned(16))) float xs[8][AP_NX];
   __shared__ __attribute__((aligned(16))) float ss[8][AP_NS];
   __shared__ __attribute__((aligned(16))) float ys[2][8][AP_TILE];  // (two: tile s+1's results are written while tile s's are packed)
 
   const int lane = threadIdx.x & 63, r = threadIdx.x >> 6;  // wave r = channel r of the octet
   const int o = blockIdx.y, b = blockIdx.z;
+  int T = TS;
+  if constexpr (std::is_same_v<LENS, RowLens>) {
+    T = row_len_vl(rl, b);
+    if ((int)blockIdx.x * (AP_NSUB * AP_TILE) >= T) return;
+  }
   const int C8 = (C + 7) >> 3;
   const int c = min(o * 8 + r, C - 1);  // (an octet past the tensor's channels: its rows are written as zeros below)
   const bool live = o * 8 + r < C;
-  const float* xr = x + ((size_t)b * C + c) * T;
+  const float* xr = x + ((size_t)b * C + c) * TS;
   constexpr int NXR = (AP_NX + 63) / 64;  // staged inputs per lane and tile
 
   // a short-lived workgroup (one tile) spent its life waiting for its own first loads with only 2-4 workgroups per CU to hide it:
@@ -295,13 +311,13 @@ __global__ __launch_bounds__(512) void aa_snake_planes_kernel(const float* __res
       for (int e = 0; e < 8; ++e) v[e] = ys[sub & 1][e][threadIdx.x];
       uint4 ph, pm, pl;
       split8_bf16x3(v, ph, pm, pl);
-      uint4* dst = xp + ((size_t)b * 3 * C8 + o) * T + t0 + threadIdx.x;
+      uint4* dst = xp + ((size_t)b * 3 * C8 + o) * TS + t0 + threadIdx.x;
 #ifdef IXTTS_SNK_NOSTORE
       if (ph.x == 0x12345678u && T < 0) {
 #endif
       dst[0] = ph;
-      dst[(size_t)C8 * T] = pm;
-      dst[(size_t)2 * C8 * T] = pl;
+      dst[(size_t)C8 * TS] = pm;
+      dst[(size_t)2 * C8 * TS] = pl;
 #ifdef IXTTS_SNK_NOSTORE
       }
 #endif
@@ -310,29 +326,37 @@ __global__ __launch_bounds__(512) void aa_snake_planes_kernel(const float* __res
 }
 
 int launch_aa_snake_planes(const float* x, void* xplanes, const float* up12, const float* down12, const float* la, const float* lb, int B, int C, int T,
-                           bool fast_sin, hipStream_t st) {
+                           bool fast_sin, hipStream_t st, const RowLens& rl) {
   if (B * C == 0 || T == 0) return IXTTS_OK;
   IX_ARG(B > 0 && C > 0 && T > 0, "aa_snake_planes: bad shape B=%d C=%d T=%d", B, C, T);
   IX_ARG((C + 7) / 8 <= 65535 && B <= 65535, "aa_snake_planes: grid too large");
   dim3 grid(ceil_div(T, AP_TILE * AP_NSUB), (C + 7) / 8, B);
-  if (fast_sin)
-    hipLaunchKernelGGL(aa_snake_planes_kernel<true>, grid, dim3(512), 0, st, x, reinterpret_cast<uint4*>(xplanes), up12, down12, la, lb, C, T);
+  if (rl.lens && fast_sin)
+    hipLaunchKernelGGL((aa_snake_planes_kernel<true, RowLens>), grid, dim3(512), 0, st, x, reinterpret_cast<uint4*>(xplanes), up12, down12, la, lb, C, T, rl);
+  else if (rl.lens)
+    hipLaunchKernelGGL((aa_snake_planes_kernel<false, RowLens>), grid, dim3(512), 0, st, x, reinterpret_cast<uint4*>(xplanes), up12, down12, la, lb, C, T, rl);
+  else if (fast_sin)
+    hipLaunchKernelGGL((aa_snake_planes_kernel<true, NoLens>), grid, dim3(512), 0, st, x, reinterpret_cast<uint4*>(xplanes), up12, down12, la, lb, C, T, NoLens());
   else
-    hipLaunchKernelGGL(aa_snake_planes_kernel<false>, grid, dim3(512), 0, st, x, reinterpret_cast<uint4*>(xplanes), up12, down12, la, lb, C, T);
+    hipLaunchKernelGGL((aa_snake_planes_kernel<false, NoLens>), grid, dim3(512), 0, st, x, reinterpret_cast<uint4*>(xplanes), up12, down12, la, lb, C, T, NoLens());
   IX_HIP(hipGetLastError());
   return IXTTS_OK;
 }
 
 int launch_aa_snake(const float* x, float* y, const float* up12, const float* down12, const float* la,
-                    const float* lb, int B, int C, int T, bool fast_sin, hipStream_t st) {
+                    const float* lb, int B, int C, int T, bool fast_sin, hipStream_t st, const RowLens& rl) {
   if (B * C == 0 || T == 0) return IXTTS_OK;
   IX_ARG(B > 0 && C > 0 && T > 0, "aa_snake: bad shape B=%d C=%d T=%d", B, C, T);
   IX_ARG((long long)B * C <= 65535, "aa_snake: B*C=%lld exceeds grid.y", (long long)B * C);
   dim3 grid(ceil_div(T, AA_TILE), B * C);
-  if (fast_sin)
-    hipLaunchKernelGGL(aa_snake_kernel<true>, grid, dim3(AA_THREADS), 0, st, x, y, up12, down12, la, lb, C, T);
+  if (rl.lens && fast_sin)
+    hipLaunchKernelGGL((aa_snake_kernel<true, RowLens>), grid, dim3(AA_THREADS), 0, st, x, y, up12, down12, la, lb, C, T, rl);
+  else if (rl.lens)
+    hipLaunchKernelGGL((aa_snake_kernel<false, RowLens>), grid, dim3(AA_THREADS), 0, st, x, y, up12, down12, la, lb, C, T, rl);
+  else if (fast_sin)
+    hipLaunchKernelGGL((aa_snake_kernel<true, NoLens>), grid, dim3(AA_THREADS), 0, st, x, y, up12, down12, la, lb, C, T, NoLens());
   else
-    hipLaunchKernelGGL(aa_snake_kernel<false>, grid, dim3(AA_THREADS), 0, st, x, y, up12, down12, la, lb, C, T);
+    hipLaunchKernelGGL((aa_snake_kernel<false, NoLens>), grid, dim3(AA_THREADS), 0, st, x, y, up12, down12, la, lb, C, T, NoLens());
   IX_HIP(hipGetLastError());
   return IXTTS_OK;
 }

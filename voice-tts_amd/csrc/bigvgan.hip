@@ -341,22 +341,36 @@ extern "C" int ixtts_bigvgan_adopt_arena(ixtts_bigvgan* h) {
   return IXTTS_OK;
 }
 
-static int run_act(ixtts_bigvgan* h, const std::string& name, const float* x, float* y, int B, int T, hipStream_t st) {
+// Rows of unequal length (ixtts_bigvgan_forward_varlen): frames per row on the device (what the kernels read) and on the host (tile
+// scoring), in a [B][C][fmax * up] layout.  dev == nullptr: every row is fmax frames long.
+struct VarLen {
+  const int* dev = nullptr;
+  const int* host = nullptr;
+  int fmax = 0;
+  // the table as the element-wise and Snake passes take it, at a stage of T = fmax * up time steps per padded row
+  RowLens rows(int T) const {
+    RowLens rl;
+    if (dev) rl.lens = dev, rl.lens_max = fmax, rl.mul = T / fmax;
+    return rl;
+  }
+};
+
+static int run_act(ixtts_bigvgan* h, const std::string& name, const float* x, float* y, int B, int T, hipStream_t st, const VarLen& vl) {
   const ActDesc& a = h->acts.at(name);
   const float* f = h->arena + h->filt_off;
-  return launch_aa_snake(x, y, f, f, h->arena + a.a_off, h->arena + a.b_off, B, a.C, T, h->cfg.fast_sin != 0, st);
+  return launch_aa_snake(x, y, f, f, h->arena + a.a_off, h->arena + a.b_off, B, a.C, T, h->cfg.fast_sin != 0, st, vl.rows(T));
 }
 
 // the activation written as the next conv's x planes (x3 mode)
-static int run_act_planes(ixtts_bigvgan* h, const std::string& name, const float* x, void* xp, int B, int T, hipStream_t st) {
+static int run_act_planes(ixtts_bigvgan* h, const std::string& name, const float* x, void* xp, int B, int T, hipStream_t st, const VarLen& vl) {
   const ActDesc& a = h->acts.at(name);
   const float* f = h->arena + h->filt_off;
-  return launch_aa_snake_planes(x, xp, f, f, h->arena + a.a_off, h->arena + a.b_off, B, a.C, T, h->cfg.fast_sin != 0, st);
+  return launch_aa_snake_planes(x, xp, f, f, h->arena + a.a_off, h->arena + a.b_off, B, a.C, T, h->cfg.fast_sin != 0, st, vl.rows(T));
 }
 
 // x: [B][Cin][Tin] fp32, or (x3 mode) the planes of that tensor
 static int run_conv(ixtts_bigvgan* h, const std::string& name, const float* x, float* y, const float* res,
-                    const float* accum, int div3, int B, int Tin, hipStream_t st, const float* accum2 = nullptr) {
+                    const float* accum, int div3, int B, int Tin, hipStream_t st, const VarLen& vl, const float* accum2 = nullptr) {
   const ConvDesc& d = h->convs.at(name);
   ConvParams p;
   memset(&p, 0, sizeof(p));
@@ -395,6 +409,13 @@ static int run_conv(ixtts_bigvgan* h, const std::string& name, const float* x, f
     p.Nq = Tin + p.ntap;  // q up to Tin-1+ (ntap-1) still touches valid inputs; extra column is masked
     p.nphase = d.stride;
   }
+  if (vl.dev) {
+    p.lens = vl.dev;
+    p.lens_host = vl.host;
+    p.lens_max = vl.fmax;
+    p.lens_in = p.Tin / vl.fmax;
+    p.lens_out = p.Tout / vl.fmax;
+  }
   static const bool timing = getenv("IXTTS_BV_TIMING") != nullptr;  // developer table: per conv shape, time and TFLOP/s
   auto launch = [&]() { return h->x3 ? launch_conv1d_x3(p, st) : launch_conv1d(p, st); };
   if (!timing) return launch();
@@ -428,11 +449,8 @@ static int run_conv(ixtts_bigvgan* h, const std::string& name, const float* x, f
   return rc;
 }
 
-extern "C" int ixtts_bigvgan_forward(ixtts_bigvgan* h, const float* mel, int B, int F, float* wav, void* stream) {
-  IX_ARG(h && (mel || F == 0) && (wav || F == 0), "bigvgan_forward: null argument");
-  if (!h->finalized) { set_error("bigvgan_forward: handle not finalized"); return IXTTS_ERR_STATE; }
-  IX_ARG(B >= 0 && F >= 0, "bigvgan_forward: negative shape");
-  if (B == 0 || F == 0) return IXTTS_OK;
+// the generator over B rows of F frames (vl.dev == nullptr) or of vl's frames in rows padded to F = vl.fmax
+static int forward_rows(ixtts_bigvgan* h, const float* mel, int B, int F, float* wav, void* stream, const VarLen& vl) {
   hipStream_t st = (hipStream_t)stream;
   IX_TRY(ensure_workspace(h, B, F));
   float *XS = h->buf[0], *X = h->buf[1];
@@ -449,19 +467,19 @@ extern "C" int ixtts_bigvgan_forward(ixtts_bigvgan* h, const float* mel, int B, 
   }
   // conv input of a resblock conv: the Snake pass writes it -- fp32 rows for conv1d.hip, the x planes for conv1d_x3.hip
   auto act_to = [&](const std::string& name, const float* src, float* f32dst, void* planes, int T_, hipStream_t s_) {
-    return h->x3 ? run_act_planes(h, name, src, planes, B, T_, s_) : run_act(h, name, src, f32dst, B, T_, s_);
+    return h->x3 ? run_act_planes(h, name, src, planes, B, T_, s_, vl) : run_act(h, name, src, f32dst, B, T_, s_, vl);
   };
   // conv input that no Snake pass produces (the mel, a stage output): split pass in x3 mode
   auto conv_in = [&](const float* src, int C_, int T_) -> const float* {
     if (!h->x3) return src;
-    launch_split_planes(src, h->pbuf[3], B, C_, T_, st);
+    launch_split_planes(src, h->pbuf[3], B, C_, T_, st, vl.rows(T_));
     return reinterpret_cast<const float*>(h->pbuf[3]);
   };
-  IX_TRY(run_conv(h, "conv_pre", conv_in(mel, c.num_mels, F), XS, nullptr, nullptr, 0, B, F, st));
+  IX_TRY(run_conv(h, "conv_pre", conv_in(mel, c.num_mels, F), XS, nullptr, nullptr, 0, B, F, st, vl));
   int T = F;
   int ch = c.upsample_initial_channel;
   for (int i = 0; i < c.n_stages; ++i) {
-    IX_TRY(run_conv(h, "ups." + std::to_string(i) + ".0", conv_in(XS, ch, T), X, nullptr, nullptr, 0, B, T, st));
+    IX_TRY(run_conv(h, "ups." + std::to_string(i) + ".0", conv_in(XS, ch, T), X, nullptr, nullptr, 0, B, T, st, vl));
     T *= c.upsample_rates[i];
     ch /= 2;
     if (conc) IX_HIP(hipEventRecord(h->ev_fork, st));
@@ -476,25 +494,56 @@ extern "C" int ixtts_bigvgan_forward(ixtts_bigvgan* h, const float* mel, int B, 
       const float* cur = X;
       for (int m = 0; m < 3; ++m) {
         IX_TRY(act_to(p + ".activations." + std::to_string(2 * m) + ".act", cur, T1j, h->pbuf[j], T, bs));
-        IX_TRY(run_conv(h, p + ".convs1." + std::to_string(m), Aj, T2j, nullptr, nullptr, 0, B, T, bs));
+        IX_TRY(run_conv(h, p + ".convs1." + std::to_string(m), Aj, T2j, nullptr, nullptr, 0, B, T, bs, vl));
         IX_TRY(act_to(p + ".activations." + std::to_string(2 * m + 1) + ".act", T2j, T1j, h->pbuf[j], T, bs));
         if (m < 2 || !last) {
-          IX_TRY(run_conv(h, p + ".convs2." + std::to_string(m), Aj, Rj, cur, nullptr, 0, B, T, bs));
+          IX_TRY(run_conv(h, p + ".convs2." + std::to_string(m), Aj, Rj, cur, nullptr, 0, B, T, bs, vl));
           cur = Rj;
         } else {
           // xs = r0 ; xs += r1 ; x = (xs + r2) / 3      (bigvgan.py:369-375)
           if (conc)
             for (int k = 0; k < 2; ++k) IX_HIP(hipStreamWaitEvent(st, h->ev_join[k], 0));
-          IX_TRY(run_conv(h, p + ".convs2." + std::to_string(m), Aj, XS, cur, h->buf[2], 1, B, T, st, h->buf[5]));
+          IX_TRY(run_conv(h, p + ".convs2." + std::to_string(m), Aj, XS, cur, h->buf[2], 1, B, T, st, vl, h->buf[5]));
         }
       }
       if (conc && !last) IX_HIP(hipEventRecord(h->ev_join[j], bs));
     }
   }
-  IX_TRY(run_act(h, "activation_post.act", XS, T1, B, T, st));
+  IX_TRY(run_act(h, "activation_post.act", XS, T1, B, T, st, vl));
   const ConvDesc& cp = h->convs.at("conv_post");
-  IX_TRY(launch_conv_post(T1, h->arena + cp.w_off, nullptr, wav, B, cp.Cin, T, st));
+  IX_TRY(launch_conv_post(T1, h->arena + cp.w_off, nullptr, wav, B, cp.Cin, T, st, vl.rows(T)));
   return IXTTS_OK;
+}
+
+extern "C" int ixtts_bigvgan_forward(ixtts_bigvgan* h, const float* mel, int B, int F, float* wav, void* stream) {
+  IX_ARG(h && (mel || F == 0) && (wav || F == 0), "bigvgan_forward: null argument");
+  if (!h->finalized) { set_error("bigvgan_forward: handle not finalized"); return IXTTS_ERR_STATE; }
+  IX_ARG(B >= 0 && F >= 0, "bigvgan_forward: negative shape");
+  if (B == 0 || F == 0) return IXTTS_OK;
+  return forward_rows(h, mel, B, F, wav, stream, VarLen());
+}
+
+// Row b is frames[b] <= Fmax frames long inside tensors padded to Fmax: the same schedule and workspace as ixtts_bigvgan_forward on
+// [B][..][Fmax], every kernel taking its bounds from frames_dev (clamped to [0, Fmax] there, so a table that disagrees with
+// frames_host cannot move a load or a store outside the allocation).  Nothing past a row's length is read or written.
+extern "C" int ixtts_bigvgan_forward_varlen(ixtts_bigvgan* h, const float* mel, const int* frames_dev, const int* frames_host, int B, int Fmax,
+                                            float* wav, void* stream) {
+  IX_ARG(h, "bigvgan_forward_varlen: null handle");
+  if (!h->finalized) { set_error("bigvgan_forward_varlen: handle not finalized"); return IXTTS_ERR_STATE; }
+  IX_ARG(B >= 0 && Fmax >= 0, "bigvgan_forward_varlen: negative shape");
+  if (B == 0 || Fmax == 0) return IXTTS_OK;
+  IX_ARG(mel && wav && frames_dev && frames_host, "bigvgan_forward_varlen: null argument");
+  bool any = false;
+  for (int b = 0; b < B; ++b) {
+    IX_ARG(frames_host[b] >= 0 && frames_host[b] <= Fmax, "bigvgan_forward_varlen: frames[%d] = %d outside [0, %d]", b, frames_host[b], Fmax);
+    any = any || frames_host[b] > 0;
+  }
+  if (!any) return IXTTS_OK;
+  VarLen vl;
+  vl.dev = frames_dev;
+  vl.host = frames_host;
+  vl.fmax = Fmax;
+  return forward_rows(h, mel, B, Fmax, wav, stream, vl);
 }
 
 extern "C" double ixtts_bigvgan_flops(const ixtts_bigvgan* h, int B, int F) {

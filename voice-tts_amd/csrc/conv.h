@@ -20,14 +20,35 @@ struct ConvParams {
   int nphase;           // 1 for Conv1d, stride for ConvTranspose1d
   int div3;             // divide by 3 (mean of the stage's 3 resblocks, bigvgan.py:375)
   int n_tiles, m_tiles; // filled by the launcher
+  // ---- rows of unequal length in a padded [B][C][Tmax] layout (the kernels' VL instantiations; null / 0 otherwise).  Tin, Tout stay the
+  // row strides; row b is frames_b = clamp(lens[b], 0, lens_max) frames long: Tin_b = frames_b * lens_in, Tout_b = frames_b *
+  // lens_out, Nq_b = Tin_b + (Nq - Tin), and nothing at or past those is read or written.
+  const int* lens;       // [B] frames per row, device
+  const int* lens_host;  // the same on the host: tile scoring only, never dereferenced by a kernel
+  int lens_max, lens_in, lens_out;
 };
+
+// Bounds of row b of a varlen conv (workgroup-uniform: one scalar load).  An empty row has no columns at all.
+struct ConvRow {
+  int Tin, Tout, Nq;
+};
+__device__ __forceinline__ ConvRow conv_row_vl(const ConvParams& p, int b) {
+  const int f = min(max(p.lens[b], 0), p.lens_max);
+  ConvRow r;
+  r.Tin = f * p.lens_in;
+  r.Tout = f * p.lens_out;
+  r.Nq = f > 0 ? r.Tin + (p.Nq - p.Tin) : 0;
+  return r;
+}
 
 // ---- epilogue shared by conv1d.hip and conv1d_x3.hip: a wave's MT x NT accumulator tiles of 32 x 32 (register r of lane l =
 // output channel mrow0 + 32i + (r&3) + 8(r>>2) + 4(l>>5), column qcol0 + 32j + (l&31)) -> y, with bias, residual, the 3-way resblock
 // accumulate and /3 fused
 typedef float conv_f32x16 __attribute__((ext_vector_type(16)));
 template <int MT, int NT>
-__device__ __forceinline__ void conv_epilogue(const ConvParams& p, const conv_f32x16 (&acc)[MT][NT], int mrow0, int qcol0, int b, int phase, int l31, int lh) {
+__device__ __forceinline__ void conv_epilogue(const ConvParams& p, const conv_f32x16 (&acc)[MT][NT], int mrow0, int qcol0, int b, int phase, int l31, int lh,
+                                              int Nq, int Tout) {
+  // Nq, Tout: the bounds of this row (p.Nq, p.Tout unless the rows have lengths of their own); p.Tout stays the row stride
   // ---- epilogue: bias, residual, 3-way accumulate, /3.  Every operand load is unconditional and issued before the first
   // store of its 32x32 block (absent operands and out-of-range elements read the zero page / a clamped element): loads
   // under the bounds branch were waited for one by one, 64+ dependent round trips per lane.
@@ -47,8 +68,8 @@ __device__ __forceinline__ void conv_epilogue(const ConvParams& p, const conv_f3
     for (int j = 0; j < NT; ++j) {
       const int q = qcol0 + j * 32 + l31;
       const int t = q * p.os + ophase;
-      const bool tv = (q < p.Nq) && (t >= 0) && (t < p.Tout);
-      const int tc = min(max(t, 0), p.Tout - 1);
+      const bool tv = (q < Nq) && (t >= 0) && (t < Tout);
+      const int tc = min(max(t, 0), Tout - 1);
       float rv[16], av[16], av2[16];
 #pragma unroll
       for (int r = 0; r < 16; ++r) {
@@ -77,13 +98,20 @@ int launch_conv1d(const ConvParams& p, hipStream_t st);
 // the same operator with x and the weights as three bf16 planes each (conv1d_x3.hip): p.x = x planes, p.wp = weight planes
 int launch_conv1d_x3(const ConvParams& p, hipStream_t st);
 int conv_x3_cout_pad(int Cout);
-int launch_split_planes(const float* x, void* xplanes, int B, int C, int T, hipStream_t st);
-int launch_conv_post(const float* x, const float* w, const float* bias, float* y, int B, int C, int T, hipStream_t st);
+// Rows of unequal length for the element-wise and Snake passes: row b holds clamp(lens[b], 0, lens_max) * mul time steps of its
+// T (T stays the row stride); lens == nullptr: every row is T long.
+struct RowLens {
+  const int* lens = nullptr;  // [B], device
+  int lens_max = 0, mul = 0;
+};
+__device__ __forceinline__ int row_len_vl(const RowLens& rl, int b) { return min(max(rl.lens[b], 0), rl.lens_max) * rl.mul; }
+int launch_split_planes(const float* x, void* xplanes, int B, int C, int T, hipStream_t st, const RowLens& rl = RowLens());
+int launch_conv_post(const float* x, const float* w, const float* bias, float* y, int B, int C, int T, hipStream_t st, const RowLens& rl = RowLens());
 int conv_tile_bm(int Cout);
 int launch_aa_snake(const float* x, float* y, const float* up12, const float* down12, const float* la,
-                    const float* lb, int B, int C, int T, bool fast_sin, hipStream_t st);
+                    const float* lb, int B, int C, int T, bool fast_sin, hipStream_t st, const RowLens& rl = RowLens());
 // the same activation, written as the x planes of conv1d_x3.hip
 int launch_aa_snake_planes(const float* x, void* xplanes, const float* up12, const float* down12, const float* la, const float* lb, int B, int C, int T,
-                           bool fast_sin, hipStream_t st);
+                           bool fast_sin, hipStream_t st, const RowLens& rl = RowLens());
 
 }  // namespace ixtts

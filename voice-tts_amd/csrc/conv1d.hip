@@ -34,7 +34,8 @@ constexpr int CG = 8;   // input channels per weight group (one float4 per lane 
 // holding its A operand for the 4 consecutive k-steps of a channel group; a half-wave reads 512 contiguous bytes.
 // They stream from L2 (the XCD-aware tile map keeps one co-slice per XCD) straight into registers, one tap ahead;
 // only the x tile (+dilation halo) lives in LDS.
-template <int MT, int NT, int WM, int WN, int CKG = 4, bool RAGGED = true>
+// VL: rows of unequal length (ConvParams::lens); an instantiation of its own, so that the equal-length kernels stay as they were
+template <int MT, int NT, int WM, int WN, int CKG = 4, bool RAGGED = true, bool VL = false>
 __global__ __launch_bounds__(256, (MT == 1 ? 3 : 2)) void conv1d_mfma_kernel(ConvParams p) {
   static_assert(CKG == 3 || CKG == 4, "three or four 8-channel groups per chunk");
   constexpr int BM = 32 * MT * WM;
@@ -55,6 +56,14 @@ __global__ __launch_bounds__(256, (MT == 1 ? 3 : 2)) void conv1d_mfma_kernel(Con
   const int b = blockIdx.y;
   const int m0 = m_tile * BM;
   const int q0 = n_tile * BN;
+  // bounds of this row; the row strides stay p.Tin / p.Tout.  (b, q0 are workgroup-uniform: a tile past the row's last column
+  // leaves before the first barrier)
+  int Tin = p.Tin, Tout = p.Tout, Nq = p.Nq;
+  if constexpr (VL) {
+    const ConvRow row = conv_row_vl(p, b);
+    Tin = row.Tin, Tout = row.Tout, Nq = row.Nq;
+    if (q0 >= Nq) return;
+  }
   const int adil = p.dil < 0 ? -p.dil : p.dil;
   const int span = (p.ntap - 1) * adil;
   const int XW = BN + span;
@@ -98,7 +107,7 @@ __global__ __launch_bounds__(256, (MT == 1 ? 3 : 2)) void conv1d_mfma_kernel(Con
     for (int pc = 0; pc < np; ++pc) {
       const int cs = (pc < np - 1) ? pc * 64 : XW - 64;
       const int t = lo + cs + lane;
-      const bool tvalid = t >= 0 && t < p.Tin;
+      const bool tvalid = t >= 0 && t < Tin;
 #pragma unroll
       for (int r = 0; r < 8; ++r) {
         const int c = c0 + r;
@@ -183,18 +192,20 @@ __global__ __launch_bounds__(256, (MT == 1 ? 3 : 2)) void conv1d_mfma_kernel(Con
   for (int g = 0; g < nchunks; ++g) chunk_step(g, Xs + (g & 1) * bufsz, Xs + ((g + 1) & 1) * bufsz);
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // the surplus copy of the last iteration, before the workgroup's LDS is released
 
-  conv_epilogue<MT, NT>(p, acc, m0 + wm * (32 * MT), q0 + wn * (32 * NT), b, phase, l31, lh);
+  conv_epilogue<MT, NT>(p, acc, m0 + wm * (32 * MT), q0 + wn * (32 * NT), b, phase, l31, lh, Nq, Tout);
 }
 
-template <int MT, int NT, int WM, int WN, int CKG = 4, bool RAGGED = true>
+template <int MT, int NT, int WM, int WN, int CKG, bool RAGGED, bool VL>
 static int launch_cfg_r(const ConvParams& p0, hipStream_t st);
 
 template <int MT, int NT, int WM, int WN, int CKG = 4>
 static int launch_cfg(const ConvParams& p0, hipStream_t st) {
-  return (p0.Cin_pad / CG) % CKG == 0 ? launch_cfg_r<MT, NT, WM, WN, CKG, false>(p0, st) : launch_cfg_r<MT, NT, WM, WN, CKG, true>(p0, st);
+  const bool whole = (p0.Cin_pad / CG) % CKG == 0;
+  if (p0.lens) return whole ? launch_cfg_r<MT, NT, WM, WN, CKG, false, true>(p0, st) : launch_cfg_r<MT, NT, WM, WN, CKG, true, true>(p0, st);
+  return whole ? launch_cfg_r<MT, NT, WM, WN, CKG, false, false>(p0, st) : launch_cfg_r<MT, NT, WM, WN, CKG, true, false>(p0, st);
 }
 
-template <int MT, int NT, int WM, int WN, int CKG, bool RAGGED>
+template <int MT, int NT, int WM, int WN, int CKG, bool RAGGED, bool VL>
 static int launch_cfg_r(const ConvParams& p0, hipStream_t st) {
   ConvParams p = p0;
   constexpr int BM = 32 * MT * WM, BN = 32 * NT * WN;
@@ -206,7 +217,7 @@ static int launch_cfg_r(const ConvParams& p0, hipStream_t st) {
   size_t smem = (size_t)(2 * CKG * CG * XWP) * sizeof(float);  // two x-tile buffers
   IX_ARG(smem <= 160 * 1024, "conv: LDS tile %zu B too large", smem);
   IX_ARG(BN + (p.ntap - 1) * adil <= 512, "conv: x tile of %d columns exceeds the staging bound (512)", BN + (p.ntap - 1) * adil);
-  auto kern = conv1d_mfma_kernel<MT, NT, WM, WN, CKG, RAGGED>;
+  auto kern = conv1d_mfma_kernel<MT, NT, WM, WN, CKG, RAGGED, VL>;
   if (smem > 64 * 1024) {
     static bool done = false;
     if (!done) {
@@ -280,10 +291,38 @@ __global__ __launch_bounds__(256) void conv_post_kernel(const float* __restrict_
   y[(size_t)b * T + t] = fminf(fmaxf(acc, -1.0f), 1.0f);
 }
 
-int launch_conv_post(const float* x, const float* w, const float* bias, float* y, int B, int C, int T, hipStream_t st) {
+// The same for rows of unequal length: row b is Tb time steps of its T (T stays the row stride), the zero padding starts at Tb and
+// nothing is written from there on.  (A kernel of its own and not a shared body: the compiler allocates the kernel above
+// differently once its text is an inlined function.)
+__global__ __launch_bounds__(256) void conv_post_vl_kernel(const float* __restrict__ x, const float* __restrict__ w, const float* __restrict__ bias,
+                                                            float* __restrict__ y, int C, int T, RowLens rl) {
+  extern __shared__ float ws[];  // [C][7]
+  for (int i = threadIdx.x; i < C * 7; i += blockDim.x) ws[i] = w[i];
+  __syncthreads();
+  const int b = blockIdx.y;
+  const int Tb = row_len_vl(rl, b);
+  const int t = blockIdx.x * blockDim.x + threadIdx.x;
+  if (t >= Tb) return;
+  const float* xb = x + (size_t)b * C * T;
+  float acc = 0.f;
+  for (int c = 0; c < C; ++c) {
+    const float* xr = xb + (size_t)c * T;
+#pragma unroll
+    for (int k = 0; k < 7; ++k) {
+      int ti = t + k - 3;
+      float v = (ti >= 0 && ti < Tb) ? xr[ti] : 0.f;
+      acc = fmaf(ws[c * 7 + k], v, acc);
+    }
+  }
+  if (bias) acc += bias[0];
+  y[(size_t)b * T + t] = fminf(fmaxf(acc, -1.0f), 1.0f);
+}
+
+int launch_conv_post(const float* x, const float* w, const float* bias, float* y, int B, int C, int T, hipStream_t st, const RowLens& rl) {
   if (B == 0 || T == 0) return IXTTS_OK;
   dim3 grid(ceil_div(T, 256), B);
-  hipLaunchKernelGGL(conv_post_kernel, grid, dim3(256), C * 7 * sizeof(float), st, x, w, bias, y, C, T);
+  if (rl.lens) hipLaunchKernelGGL(conv_post_vl_kernel, grid, dim3(256), C * 7 * sizeof(float), st, x, w, bias, y, C, T, rl);
+  else hipLaunchKernelGGL(conv_post_kernel, grid, dim3(256), C * 7 * sizeof(float), st, x, w, bias, y, C, T);
   IX_HIP(hipGetLastError());
   return IXTTS_OK;
 }

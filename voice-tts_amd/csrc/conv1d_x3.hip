@@ -23,7 +23,8 @@ namespace ixtts {
 typedef conv_f32x16 cx_f32x16;
 typedef __bf16 cx_bf16x8 __attribute__((ext_vector_type(8)));
 
-template <int MT, int NT, int WM, int WN>
+// VL: rows of unequal length (ConvParams::lens); an instantiation of its own, so that the equal-length kernels stay as they were
+template <int MT, int NT, int WM, int WN, bool VL = false>
 __global__ __launch_bounds__(256, 2) void conv1d_x3_kernel(ConvParams p) {
   constexpr int BM = 32 * MT * WM;
   constexpr int BN = 32 * NT * WN;
@@ -43,6 +44,14 @@ __global__ __launch_bounds__(256, 2) void conv1d_x3_kernel(ConvParams p) {
   const int b = blockIdx.y;
   const int m0 = m_tile * BM;
   const int q0 = n_tile * BN;
+  // bounds of this row; the row strides stay p.Tin / p.Tout.  (b, q0 are workgroup-uniform: a tile past the row's last column
+  // leaves before the first barrier)
+  int Tin = p.Tin, Tout = p.Tout, Nq = p.Nq;
+  if constexpr (VL) {
+    const ConvRow row = conv_row_vl(p, b);
+    Tin = row.Tin, Tout = row.Tout, Nq = row.Nq;
+    if (q0 >= Nq) return;
+  }
   const int adil = p.dil < 0 ? -p.dil : p.dil;
   const int span = (p.ntap - 1) * adil;
   const int XW = BN + span;
@@ -89,7 +98,7 @@ __global__ __launch_bounds__(256, 2) void conv1d_x3_kernel(ConvParams p) {
       for (int pc = 0; pc < np; ++pc) {
         const int cs = (pc < np - 1) ? pc * 64 : XW - 64;
         const int t = lo + cs + lane;
-        const uint4* src = (t >= 0 && t < p.Tin && oc < C8) ? srow + t : zero;
+        const uint4* src = (t >= 0 && t < Tin && oc < C8) ? srow + t : zero;
         __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)src, (__attribute__((address_space(3))) void*)(drow + cs), 16, 0, 0);
       }
     }
@@ -171,11 +180,19 @@ __global__ __launch_bounds__(256, 2) void conv1d_x3_kernel(ConvParams p) {
   const int bufsz = 12 * XW;  // (a conv of at most 32 input channels has one chunk and is given one buffer: twice the workgroups per CU)
   for (int g = 0; g < nchunks; ++g) chunk_step(g, Xq + (g & 1) * bufsz, Xq + ((g + 1) & 1) * bufsz);
 
-  conv_epilogue<MT, NT>(p, acc, m0 + wm * (32 * MT), q0 + wn * (32 * NT), b, phase, l31, lh);
+  conv_epilogue<MT, NT>(p, acc, m0 + wm * (32 * MT), q0 + wn * (32 * NT), b, phase, l31, lh, Nq, Tout);
 }
+
+template <int MT, int NT, int WM, int WN, bool VL>
+static int launch_x3_cfg_v(const ConvParams& p0, hipStream_t st);
 
 template <int MT, int NT, int WM, int WN>
 static int launch_x3_cfg(const ConvParams& p0, hipStream_t st) {
+  return p0.lens ? launch_x3_cfg_v<MT, NT, WM, WN, true>(p0, st) : launch_x3_cfg_v<MT, NT, WM, WN, false>(p0, st);
+}
+
+template <int MT, int NT, int WM, int WN, bool VL>
+static int launch_x3_cfg_v(const ConvParams& p0, hipStream_t st) {
   ConvParams p = p0;
   constexpr int BM = 32 * MT * WM, BN = 32 * NT * WN;
   p.m_tiles = ceil_div(p.Cout, BM);
@@ -185,7 +202,7 @@ static int launch_x3_cfg(const ConvParams& p0, hipStream_t st) {
   const int XW = BN + (p.ntap - 1) * adil;
   const size_t smem = (size_t)(p.Cin_pad > 32 ? 2 : 1) * 12 * XW * 16;  // two x-tile buffers of 12 rows (one when there is a single chunk)
   IX_ARG(smem <= 160 * 1024, "conv_x3: LDS tile %zu B too large", smem);
-  auto kern = conv1d_x3_kernel<MT, NT, WM, WN>;
+  auto kern = conv1d_x3_kernel<MT, NT, WM, WN, VL>;
   if (smem > 64 * 1024) {
     static bool done = false;
     if (!done) {
@@ -209,10 +226,23 @@ static double x3_tile_score(const ConvParams& p, int BM, int BN, int max_occ, do
   const int adil = p.dil < 0 ? -p.dil : p.dil;
   const size_t smem = (size_t)(p.Cin_pad > 32 ? 2 : 1) * 12 * (BN + (p.ntap - 1) * adil) * 16;
   const int occ = std::max(1, std::min(max_occ, (int)((160 * 1024) / (smem + 512))));
-  const double wgs = (double)ceil_div(p.Cout, BM) * ceil_div(p.Nq, BN) * p.B * p.nphase;
+  // column tiles and columns over all rows.  Rows of unequal length: the sums over the rows' own extents (a tile past a row's end
+  // returns at once and is counted neither as a workgroup nor as work)
+  double ntiles = (double)ceil_div(p.Nq, BN) * p.B, ncols = (double)p.Nq * p.B;
+  if (p.lens_host) {
+    ntiles = ncols = 0.0;
+    for (int b = 0; b < p.B; ++b) {
+      const int f = std::min(std::max(p.lens_host[b], 0), p.lens_max);
+      const int nq = f > 0 ? f * p.lens_in + (p.Nq - p.Tin) : 0;
+      ntiles += ceil_div(nq, BN);
+      ncols += nq;
+    }
+    if (ntiles == 0.0) return 0.0;
+  }
+  const double wgs = (double)ceil_div(p.Cout, BM) * ntiles * p.nphase;
   const double slots = 256.0 * occ;
   const double rounds = (double)(((long long)wgs + (long long)slots - 1) / (long long)slots);
-  const double useful = (double)p.Cout * p.Nq * p.B * p.nphase / (wgs * BM * BN);
+  const double useful = (double)p.Cout * ncols * p.nphase / (wgs * BM * BN);
   return useful * wgs / (rounds * slots) * pref;
 }
 
@@ -239,10 +269,11 @@ int launch_conv1d_x3(const ConvParams& p, hipStream_t st) {
 // the transposed convs read).  One (octet, time step) per thread: eight strided 4-byte reads (coalesced across the wave),
 // three 16-byte writes.
 
-__global__ __launch_bounds__(256) void split_planes_kernel(const float* __restrict__ x, uint4* __restrict__ xp, int C, int T) {
+// Tb: time steps of row b (T is the row stride)
+__device__ __forceinline__ void split_planes_body(const float* __restrict__ x, uint4* __restrict__ xp, int C, int T, int Tb) {
   const int C8 = (C + 7) >> 3;
   const int t = blockIdx.x * 256 + threadIdx.x, o = blockIdx.y, b = blockIdx.z;
-  if (t >= T) return;
+  if (t >= Tb) return;
   const float* xb = x + (size_t)b * C * T;
   float v[8];
 #pragma unroll
@@ -255,10 +286,20 @@ __global__ __launch_bounds__(256) void split_planes_kernel(const float* __restri
   dst[(size_t)2 * C8 * T] = pl;
 }
 
-int launch_split_planes(const float* x, void* xp, int B, int C, int T, hipStream_t st) {
+__global__ __launch_bounds__(256) void split_planes_kernel(const float* __restrict__ x, uint4* __restrict__ xp, int C, int T) {
+  split_planes_body(x, xp, C, T, T);
+}
+
+__global__ __launch_bounds__(256) void split_planes_vl_kernel(const float* __restrict__ x, uint4* __restrict__ xp, int C, int T, RowLens rl) {
+  split_planes_body(x, xp, C, T, row_len_vl(rl, blockIdx.z));
+}
+
+int launch_split_planes(const float* x, void* xp, int B, int C, int T, hipStream_t st, const RowLens& rl) {
   if (B * C == 0 || T == 0) return IXTTS_OK;
   IX_ARG((C + 7) / 8 <= 65535 && B <= 65535, "split_planes: grid too large");
-  hipLaunchKernelGGL(split_planes_kernel, dim3(ceil_div(T, 256), (C + 7) / 8, B), dim3(256), 0, st, x, reinterpret_cast<uint4*>(xp), C, T);
+  const dim3 grid(ceil_div(T, 256), (C + 7) / 8, B);
+  if (rl.lens) hipLaunchKernelGGL(split_planes_vl_kernel, grid, dim3(256), 0, st, x, reinterpret_cast<uint4*>(xp), C, T, rl);
+  else hipLaunchKernelGGL(split_planes_kernel, grid, dim3(256), 0, st, x, reinterpret_cast<uint4*>(xp), C, T);
   IX_HIP(hipGetLastError());
   return IXTTS_OK;
 }

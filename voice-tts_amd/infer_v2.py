@@ -27,7 +27,7 @@ import torch
 
 from .bigvgan import BigVGAN
 from .gpt_engine import GptEngine, resolve_gpt_dtype
-from .pipeline import conds_latent, decode_segment, latent_prefix, prepare_gpt_inputs, vocode
+from .pipeline import conds_latent, decode_segment, latent_prefix, prepare_gpt_inputs, vocode, vocode_many
 from .weights import BIGVGAN_CFG, GPT_CFG, load_bigvgan_checkpoint, load_gpt_checkpoint
 
 logger = logging.getLogger("indextts.infer_v2")
@@ -848,13 +848,22 @@ class IndexTTS2:
                     plans[ri]["mels"] = self._mels(plans[ri]["items"], plans[ri]["spk"], noises=plans[ri]["noises"])
                 except Exception as e:  # this request only
                     failed[ri] = e
+        # vocoder: the mels of every surviving request in batched passes (`vocode_many`; IXTTS_BV_BATCH=0, or an injected vocoder:
+        # mel after mel).  A mel that raises comes back as its exception and fails its own request only.
+        live = [ri for ri in range(len(plans)) if ri not in failed]
+        pcm = iter(vocode_many(self.bigvgan, [mel for ri in live for mel in plans[ri]["mels"]]))
+        for ri in live:
+            plans[ri]["pcm"] = [next(pcm) for _ in plans[ri]["mels"]]
         out = []
         for ri, plan in enumerate(plans):
             if ri in failed:
                 out.append(failed[ri])
                 continue
             try:
-                wavs = [vocode(self.bigvgan, mel).cpu() for mel in plan["mels"]]
+                for w in plan["pcm"]:
+                    if isinstance(w, Exception):
+                        raise w
+                wavs = [w.cpu() for w in plan["pcm"]]
                 if not wavs:
                     out.append(None)
                     continue
@@ -968,7 +977,11 @@ class IndexTTS2:
             torch.cuda.synchronize(self.device)
             s2mel_time += time.perf_counter() - m0
             m0 = time.perf_counter()
-            wavs = [vocode(self.bigvgan, mel).cpu() for mel in mels]  # (.cpu() waits for the vocoder)
+            wavs = []
+            for w in vocode_many(self.bigvgan, mels):  # one batched pass (IXTTS_BV_BATCH=0: mel after mel)
+                if isinstance(w, Exception):
+                    raise w
+                wavs.append(w.cpu())  # (.cpu() waits for the vocoder)
             bigvgan_time += time.perf_counter() - m0
         end_time = time.perf_counter()
         if not wavs:

@@ -73,6 +73,36 @@ def vocode(bigvgan, mel):
     return torch.clamp(32767 * wav, -32767.0, 32767.0)
 
 
+def vocode_many(bigvgan, mels):
+    """`vocode` for the mels of several segments ([1, 80, F_i], lengths unequal) -> one fp32 [1, T_i] per mel, in input order, or the
+    EXCEPTION that mel raised.  A vocoder with `forward_many` (the built-in `BigVGAN`) takes them in batched passes; when such a pass
+    raises, its mels are redone one at a time, so the exception lands only on the mel that caused it.  Any other vocoder (an
+    injected stage, a test stub), or IXTTS_BV_BATCH=0: one `vocode` per mel."""
+    from .bigvgan import plan_vocoder_batches, vocoder_batch_frames, vocoder_batching
+
+    mels = list(mels)
+
+    def one(mel):
+        try:
+            return vocode(bigvgan, mel)
+        except Exception as e:  # this mel only
+            return e
+
+    if not hasattr(bigvgan, "forward_many") or not vocoder_batching() or len(mels) < 2:
+        return [one(mel) for mel in mels]
+    out = [None] * len(mels)
+    # the groups `forward_many` would cut itself, cut here: one call and one failure domain per group
+    for group in plan_vocoder_batches([mel.shape[-1] for mel in mels], vocoder_batch_frames()):
+        try:
+            wavs = bigvgan.forward_many([mels[i].to(bigvgan.device_, torch.float32) for i in group])
+            for i, w in zip(group, wavs):
+                out[i] = torch.clamp(32767 * w.squeeze(1), -32767.0, 32767.0)
+        except Exception:
+            for i in group:
+                out[i] = one(mels[i])
+    return out
+
+
 def decode_segment(index, embeds, n_left_pad, max_new, request=0, payload=None, stream=None, sampler=None):
     """One prepared sequence as the decode schedulers take it (`scheduler.Segment`); `HotPath` and `IndexTTS2` build theirs here."""
     from .scheduler import Segment
@@ -232,6 +262,10 @@ class HotPath:
     def vocode(self, mel):
         """-> fp32 [1, T] scaled to +-32767; see the module-level `vocode`."""
         return vocode(self.bigvgan, mel)
+
+    def vocode_many(self, mels):
+        """One fp32 [1, T_i] (or the exception it raised) per mel; see the module-level `vocode_many`."""
+        return vocode_many(self.bigvgan, mels)
 
 
 def audio_seconds(n_codes_per_segment, interval_silence_ms=200):

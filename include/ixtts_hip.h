@@ -248,6 +248,12 @@ typedef struct ixtts_gpt_cfg {
   int weight_dtype;    /* IXTTS_DTYPE_F32 (parity mode) | IXTTS_DTYPE_BF16 (throughput mode) | IXTTS_DTYPE_F16 (see above) */
 } ixtts_gpt_cfg;
 
+#define IXTTS_NGRAM_MAX 8 /* largest no_repeat_ngram_size */
+
+/* Token selection follows `_get_logits_processor` (transformers_generation_utils.py:900-1049), in its order:
+ *   [suppress_stop] -> RepetitionPenalty -> NoRepeatNGram -> MinNewTokens -> SuppressTokens -> SuppressTokensAtBegin -> [typical]
+ *   -> Temperature -> TopK -> TopP -> MinP -> softmax + multinomial | argmax
+ * The warpers (Temperature .. MinP) run when sampling only: not in greedy decoding, not in beam search proper. */
 typedef struct ixtts_sampler_cfg {
   float repetition_penalty; /* 10.0 (infer_v2.py:605); 1.0 disables                         */
   float temperature;        /* 0.8; ignored when do_sample == 0                              */
@@ -263,6 +269,17 @@ typedef struct ixtts_sampler_cfg {
                                (model_v2.py:717-722, utils/typical_sampling.py) after the repetition penalty; 0: off */
   float length_penalty;     /* beam mode: hypothesis score = sum_logprobs / generated_len ** length_penalty
                                (transformers_beam_search.py:947-951,989-1006); 0.0 is the served default (infer_v2.py:603) */
+  /* The constraints `generate()` builds from plain keywords (transformers_generation_utils.py:902-1049); 0 = off.  Like every field
+     they belong to the slot / the beam group.  The two id lists of the family are state of the sequence: ixtts_gpt_set_bans. */
+  int min_new_tokens;       /* MinNewTokensLengthLogitsProcessor: the stop token is -inf while fewer tokens than this have been
+                               generated; more than can be generated is no error (the sequence runs to its cap); >= 0 */
+  int no_repeat_ngram_size; /* NoRepeatNGramLogitsProcessor over the history HF sees -- the fake prompt ids [1]*(P-1) + [start_mel]
+                               and the generated tokens (in beam mode each beam's own reordered history): the token that followed an
+                               earlier occurrence of the last n-1 tokens is -inf; 1 bans every id of the history;
+                               0..IXTTS_NGRAM_MAX */
+  float min_p;              /* MinPLogitsWarper, sampling (and beam-sample) only, after TopP: ids whose probability over the remaining
+                               scores is below min_p * the largest are removed, the best min_tokens_to_keep (1; 2 with beams)
+                               never; 0..1 */
 } ixtts_sampler_cfg;
 
 typedef struct ixtts_gpt ixtts_gpt;
@@ -309,6 +326,13 @@ int ixtts_gpt_read_logits(ixtts_gpt* h, int b, float* logits_host, void* stream)
 /* Probability vector [n_mel_codes] the last do_sample step drew from for slot b (after penalty,
  * temperature, top-k, top-p, softmax; zeros for removed ids).  Parity-test hook. */
 int ixtts_gpt_read_probs(ixtts_gpt* h, int b, float* probs_host, void* stream);
+/* `suppress_tokens` / `begin_suppress_tokens` of generate() for the sequence in `slot` (SuppressTokensLogitsProcessor,
+ * SuppressTokensAtBeginLogitsProcessor): always_host[n_always] ids are -inf at every step, first_host[n_first] at the first
+ * generated token only.  The lists REPLACE the slot's earlier ones; ixtts_gpt_prefill of the slot clears them, so call this after
+ * the slot's prefill and before its first decode step.  In beam mode the lists of the group's first slot hold for all its
+ * beams.  Stream-ordered (the ids are copied before the call returns); an id outside 0..n_mel_codes-1 returns IXTTS_ERR_ARG. */
+int ixtts_gpt_set_bans(ixtts_gpt* h, int slot, const int32_t* always_host, int n_always, const int32_t* first_host, int n_first,
+                       void* stream);
 /* Teacher forcing for parity tests: overrides the NEXT token chosen for slot b. */
 int ixtts_gpt_force_next(ixtts_gpt* h, int b, int32_t token, void* stream);
 

@@ -36,8 +36,11 @@ class SamplerCfg(C.Structure):
         ("repetition_penalty", C.c_float), ("temperature", C.c_float), ("top_k", C.c_int),
         ("top_p", C.c_float), ("do_sample", C.c_int), ("suppress_stop", C.c_int), ("seed", C.c_uint64),
         ("typical_mass", C.c_float), ("length_penalty", C.c_float),
+        ("min_new_tokens", C.c_int), ("no_repeat_ngram_size", C.c_int), ("min_p", C.c_float),
     ]
 
+
+NGRAM_MAX = 8  # IXTTS_NGRAM_MAX
 
 QWEN_TOPK_MAX = 64  # IXTTS_QWEN_TOPK_MAX
 QWEN_MAX_EOS = 8
@@ -122,6 +125,7 @@ SYMBOLS = {
     "ixtts_gpt_beam_force_group": (C.c_int, [_P, C.c_int, _P, C.c_int, _P]),
     "ixtts_gpt_read_probs": (C.c_int, [_P, C.c_int, _P, _P]),
     "ixtts_gpt_force_next": (C.c_int, [_P, C.c_int, C.c_int32, _P]),
+    "ixtts_gpt_set_bans": (C.c_int, [_P, C.c_int, _P, C.c_int, _P, C.c_int, _P]),
     "ixtts_gpt_latent": (C.c_int, [_P, _P, C.c_int, _P, C.c_int, _P, _P]),
     "ixtts_gpt_bench_gemv": (C.c_int, [_P, C.c_int, C.c_int, C.c_int, _P]),
     "ixtts_gpt_step_bytes": (C.c_double, [_P, C.c_int, C.c_int]),

@@ -79,8 +79,8 @@ __device__ __forceinline__ BeamArgs beam_group_view(const BeamArgs& in, int g) {
   return a;
 }
 
-// Phase A, one workgroup per beam: log_softmax -> penalty -> temperature -> TopK (min keep 2) -> TopP (min keep 2); the
-// survivors go to global memory sorted by score.  (As one workgroup looping over the beams, with the TopP sums on one
+// Phase A, one workgroup per beam: log_softmax -> penalty -> n-gram / min-new-tokens / token bans -> temperature -> TopK -> TopP ->
+// MinP (min keep 2 each); the survivors go to global memory sorted by score.  (As one workgroup looping over the beams, with the TopP sums on one
 // thread, the whole step took 164 us at 3 beams.)
 __global__ __launch_bounds__(1024) void beam_cand_kernel(BeamArgs a) {
   __shared__ float red[16];
@@ -95,16 +95,21 @@ __global__ __launch_bounds__(1024) void beam_cand_kernel(BeamArgs a) {
   // every load whose address is known at entry, up front and unconditionally
   const float* lg = s.logits + (size_t)b * V;
   const uint8_t* seen = s.seen + (size_t)b * V;
+  const uint8_t* bans = s.bans + (size_t)(b / a.NB * a.NB) * V;  // the group's ban flags: those of its first slot
+  const int32_t* gtok = s.tokens + (size_t)b * s.max_new;       // this beam's own (reordered) history
   float vals[SAMP_PT];
-  uint8_t sn[SAMP_PT];
+  uint8_t sn[SAMP_PT], bn[SAMP_PT];
 #pragma unroll
   for (int i = 0; i < SAMP_PT; ++i) {
     const int v = min((int)threadIdx.x + i * 1024, V - 1);
     vals[i] = lg[v];
     sn[i] = seen[v];
+    bn[i] = bans[v];
   }
+  const int32_t ht0 = gtok[min((int)threadIdx.x, s.max_new - 1)], ht1 = gtok[min((int)threadIdx.x + 1024, s.max_new - 1)];
   const ixtts_sampler_cfg cfg = s.cfg[b];  // the host writes a group's cfg to each of its slots
   const int done = a.done[b / a.NB];  // (b is the engine slot: beam b % NB of group b / NB)
+  const int st_gen = s.gen_count[b], st_prompt = s.prompt_len[b];
   __builtin_amdgcn_sched_barrier(0);
   if (done) return;  // hypotheses complete: HF leaves the loop here; later graph replays are no-ops
   DBG_TS(1);
@@ -125,6 +130,8 @@ __global__ __launch_bounds__(1024) void beam_cand_kernel(BeamArgs a) {
 #pragma unroll
     for (int i = 0; i < SAMP_PT; ++i) se += (threadIdx.x + i * 1024 < V) ? expf(vals[i] - mx) : 0.f;
     const float lse = mx + logf(block_sum_1024(se, red));
+    const bool no_stop = cfg.suppress_stop || st_gen < cfg.min_new_tokens;
+    const unsigned int ban_mask = st_gen == 0 ? 3u : 1u;
     DBG_TS(2);
 #pragma unroll
     for (int i = 0; i < SAMP_PT; ++i) {
@@ -132,10 +139,14 @@ __global__ __launch_bounds__(1024) void beam_cand_kernel(BeamArgs a) {
       float x = -INFINITY;
       if (v < V) {
         x = vals[i] - lse;  // log_softmax
-        if (cfg.suppress_stop && v == s.stop) x = -INFINITY;
+        if ((no_stop && v == s.stop) || (bn[i] & ban_mask)) x = -INFINITY;  // MinNewTokens, SuppressTokens(AtBegin): -inf commutes with the penalty
         if (sn[i] && theta != 1.0f) x = (x < 0.f) ? x * theta : x / theta;
       }
       vals[i] = x;
+    }
+    if (cfg.no_repeat_ngram_size > 0) {  // NoRepeatNGram over this beam's history
+      __shared__ NgramScratch ng;
+      ngram_ban_1024<SAMP_PT>(vals, gtok, ht0, ht1, min(st_gen, s.max_new), st_prompt, cfg.no_repeat_ngram_size, s.start, ng);
     }
     if (cfg.typical_mass > 0.f) {  // custom processor: after the penalty, before the warpers; min_tokens_to_keep = 2 with beams
       __shared__ TypicalScratch typ;
@@ -149,7 +160,8 @@ __global__ __launch_bounds__(1024) void beam_cand_kernel(BeamArgs a) {
     DBG_TS(4);
     if (threadIdx.x < 64) {  // TopP (never removes the top min_tokens_to_keep = 2) and the survivors' way out, by wave 0
       float Z;
-      const int keep = sampling ? topp_wave0(sort_v, n, cfg.top_p, 2, ev, qv, &Z) : n;
+      int keep = sampling ? topp_wave0(sort_v, n, cfg.top_p, 2, ev, qv, &Z) : n;
+      if (sampling && cfg.min_p > 0.f) keep = minp_wave0(ev, keep, cfg.min_p, 2);  // MinP: beam-sample only, after TopP
       const int lane = threadIdx.x;
       if (lane == 0) a.cand_n[b] = keep;
       if (lane < n) {

@@ -81,6 +81,8 @@ struct ixtts_gpt {
       *forced = nullptr;
   int32_t* tokens = nullptr;
   uint8_t* seen = nullptr;
+  uint8_t* bans = nullptr;         // [slots][V] ixtts_gpt_set_bans: bit 0 = id banned at every step, bit 1 = at the first generated token
+  std::vector<uint8_t> bans_host;  // [slots][V] what set_bans stages for its async copy
   // sampler settings and random stream of every slot, at fixed device addresses (the captured step graphs read them in place;
   // each decode call refreshes them with an async copy on its stream).  Beam mode: group g's cfg sits at each of its slots.
   ixtts_sampler_cfg* d_samp = nullptr;  // [MAXB]

@@ -251,6 +251,7 @@ static SamplerState make_sampler_state(ixtts_gpt* h) {
   SamplerState s;
   s.logits = h->logits;
   s.seen = h->seen;
+  s.bans = h->bans;
   s.tokens = h->tokens;
   s.gen_count = h->gen_count;
   s.cur_len = h->cur_len;
@@ -267,6 +268,7 @@ static SamplerState make_sampler_state(ixtts_gpt* h) {
   s.max_new = h->smax;
   s.n_pos = h->cfg.n_mel_pos;
   s.stop = h->cfg.stop_mel_token;
+  s.start = h->cfg.start_mel_token;
   s.slot0 = 0;
   s.probs_out = h->probs;
   return s;
@@ -520,6 +522,7 @@ extern "C" int ixtts_gpt_create(ixtts_gpt** out, const ixtts_gpt_cfg* c) {
   ok &= hipMalloc(&h->probs, (size_t)S * V * 4) == hipSuccess;
   h->scratch_floats = (size_t)FF * D;
   ok &= hipMalloc(&h->scratch, h->scratch_floats * 4) == hipSuccess;
+  ok &= hipMalloc(&h->bans, (size_t)S * V) == hipSuccess;  // (after everything older: no other buffer's address moves)
   if (!ok) return fail("state");
   hipMemset(h->cur_len, 0, S * 4);
   hipMemset(h->gen_count, 0, S * 4);
@@ -528,6 +531,8 @@ extern "C" int ixtts_gpt_create(ixtts_gpt** out, const ixtts_gpt_cfg* c) {
   hipMemset(h->finished, 0, S * 4);
   hipMemset(h->forced, 0xff, S * 4);
   hipMemset(h->seen, 0, (size_t)S * V);
+  hipMemset(h->bans, 0, (size_t)S * V);
+  h->bans_host.assign((size_t)S * V, 0);
   hipMemset(h->logits, 0, (size_t)S * V * 4);
   {  // every beam group starts parked (done): a group below a stepping one that was never begun is a no-op in the beam kernels
     int ones[MAXG];
@@ -766,6 +771,7 @@ extern "C" int ixtts_gpt_prefill(ixtts_gpt* h, int b, const float* embeds, int n
   IX_HIP(hipMemsetAsync(h->seen + (size_t)b * V, 0, V, st));
   IX_HIP(hipMemsetAsync(h->seen + (size_t)b * V + 1, 1, 1, st));
   IX_HIP(hipMemsetAsync(h->seen + (size_t)b * V + h->cfg.start_mel_token, 1, 1, st));
+  IX_HIP(hipMemsetAsync(h->bans + (size_t)b * V, 0, V, st));  // a refilled slot inherits no bans: ixtts_gpt_set_bans comes after the prefill
   IX_HIP(hipMemsetAsync(h->gen_count + b, 0, 4, st));
   IX_HIP(hipMemsetAsync(h->finished + b, 0, 4, st));
   IX_HIP(hipMemsetAsync(h->forced + b, 0xff, 4, st));
@@ -786,6 +792,23 @@ extern "C" int ixtts_gpt_prefill(ixtts_gpt* h, int b, const float* embeds, int n
   h->hc = h->h;
   IX_TRY(do_head(h, 1, b, nullptr, st));
   IX_HIP(hipGetLastError());
+  return IXTTS_OK;
+}
+
+// suppress_tokens / begin_suppress_tokens of the sequence in `slot`: one flag byte per id (bit 0 always, bit 1 at the first generated
+// token), staged in the handle's own host copy and sent down the caller's stream.  The step graphs read the flags in place.
+extern "C" int ixtts_gpt_set_bans(ixtts_gpt* h, int slot, const int32_t* always_host, int n_always, const int32_t* first_host, int n_first, void* stream) {
+  NEED_READY(h, "gpt_set_bans");
+  IX_ARG(slot >= 0 && slot < h->cfg.max_batch, "gpt_set_bans: slot %d out of range", slot);
+  IX_ARG(n_always >= 0 && n_first >= 0 && (always_host || n_always == 0) && (first_host || n_first == 0), "gpt_set_bans: slot %d: bad id lists", slot);
+  const int V = h->V;
+  for (int i = 0; i < n_always; ++i) IX_ARG(always_host[i] >= 0 && always_host[i] < V, "gpt_set_bans: slot %d: suppressed id %d outside 0..%d", slot, always_host[i], V - 1);
+  for (int i = 0; i < n_first; ++i) IX_ARG(first_host[i] >= 0 && first_host[i] < V, "gpt_set_bans: slot %d: begin-suppressed id %d outside 0..%d", slot, first_host[i], V - 1);
+  uint8_t* stage = h->bans_host.data() + (size_t)slot * V;
+  memset(stage, 0, V);
+  for (int i = 0; i < n_always; ++i) stage[always_host[i]] |= 1u;
+  for (int i = 0; i < n_first; ++i) stage[first_host[i]] |= 2u;
+  IX_HIP(hipMemcpyAsync(h->bans + (size_t)slot * V, stage, V, hipMemcpyHostToDevice, (hipStream_t)stream));
   return IXTTS_OK;
 }
 
@@ -834,15 +857,28 @@ static int upload_sampler(ixtts_gpt* h, int n, const ixtts_sampler_cfg* uni, con
   return IXTTS_OK;
 }
 
+// The constraint fields of one sampler cfg (the same check for a slot's and a group's): nullptr, or what is wrong with it.
+static const char* constraint_error(const ixtts_sampler_cfg& c) {
+  if (c.min_new_tokens < 0) return "min_new_tokens must be >= 0";
+  if (c.no_repeat_ngram_size < 0 || c.no_repeat_ngram_size > IXTTS_NGRAM_MAX) return "no_repeat_ngram_size outside 0..IXTTS_NGRAM_MAX";
+  if (!(c.min_p >= 0.f && c.min_p <= 1.f)) return "min_p outside 0..1";
+  return nullptr;
+}
+
 static int decode_impl(ixtts_gpt* h, int n_active, int n_steps, const ixtts_sampler_cfg* uni, const ixtts_sampler_cfg* per, const uint32_t* streams,
                        hipStream_t st, const char* who) {
   IX_ARG(n_active >= 1 && n_active <= h->cfg.max_batch, "%s: n_active %d", who, n_active);
   IX_ARG(n_steps >= 0, "%s: n_steps %d", who, n_steps);
   if (per) {
-    for (int b = 0; b < n_active; ++b)
+    for (int b = 0; b < n_active; ++b) {
       if (per[b].do_sample) IX_ARG(per[b].temperature > 0.f && per[b].top_p > 0.f, "%s: slot %d: temperature and top_p must be positive", who, b);
-  } else if (uni->do_sample) {
-    IX_ARG(uni->temperature > 0.f && uni->top_p > 0.f, "%s: temperature and top_p must be positive", who);
+      const char* bad = constraint_error(per[b]);
+      IX_ARG(!bad, "%s: slot %d: %s", who, b, bad);
+    }
+  } else {
+    if (uni->do_sample) IX_ARG(uni->temperature > 0.f && uni->top_p > 0.f, "%s: temperature and top_p must be positive", who);
+    const char* bad = constraint_error(*uni);
+    IX_ARG(!bad, "%s: %s", who, bad);
   }
   IX_ARG(h->V <= 1024 * SAMP_PT, "%s: vocabulary %d exceeds the sampler tile", who, h->V);
   for (int b = 0; b < n_active; ++b) {
@@ -974,12 +1010,17 @@ static int beam_decode_impl(ixtts_gpt* h, int n_groups, int n_steps, const ixtts
   IX_ARG(n_groups == 1 || h->wide, "gpt_beam_decode: several groups step together on the wide engines only (max_batch > %d)", MAXB_REG);
   // do_sample == 0 is beam search proper: the warpers do not run (generation_utils.py:1020), their settings are not looked at
   if (per) {
-    for (int g = 0; g < n_groups; ++g)
+    for (int g = 0; g < n_groups; ++g) {
       IX_ARG(!per[g].do_sample || (per[g].top_k >= 1 && per[g].top_k <= SAMP_MAXK && per[g].temperature > 0.f && per[g].top_p > 0.f),
              "gpt_beam_decode: group %d: 1 <= top_k <= %d, positive temperature/top_p", g, SAMP_MAXK);
+      const char* bad = constraint_error(per[g]);
+      IX_ARG(!bad, "gpt_beam_decode: group %d: %s", g, bad);
+    }
   } else {
     IX_ARG(!uni->do_sample || (uni->top_k >= 1 && uni->top_k <= SAMP_MAXK && uni->temperature > 0.f && uni->top_p > 0.f),
            "gpt_beam_decode: 1 <= top_k <= %d, positive temperature/top_p", SAMP_MAXK);
+    const char* bad = constraint_error(*uni);
+    IX_ARG(!bad, "gpt_beam_decode: %s", bad);
   }
   int ctx0 = 0, live = 0;
   for (int g = 0; g < n_groups; ++g) {
@@ -1256,7 +1297,7 @@ extern "C" int ixtts_gpt_destroy(ixtts_gpt* h) {
   if (h->cap_stream) hipStreamDestroy(h->cap_stream);
   if (h->arena_borrowed) h->arena = nullptr;  // the owner frees it
   void* ptrs[] = {h->arena, h->stage, h->kc, h->vc, h->h, h->q, h->ff, h->att, h->part, h->logits, h->rowbuf, h->cur_len, h->gen_count,
-                  h->prompt_len, h->valid_from, h->finished, h->forced, h->tokens, h->seen, h->d_samp, h->d_rng, h->probs, h->scratch, h->beam_scores, h->hyp_score, h->hyp_worst, h->beam_src, h->hyp_len,
+                  h->prompt_len, h->valid_from, h->finished, h->forced, h->tokens, h->seen, h->bans, h->d_samp, h->d_rng, h->probs, h->scratch, h->beam_scores, h->hyp_score, h->hyp_worst, h->beam_src, h->hyp_len,
                   h->n_hyp, h->beam_done, h->beam_forced_flag, h->beam_forced, h->hyp_tok, h->beam_cand_v, h->beam_cand_i, h->beam_cand_n, h->beam_lcp, h->beam_stream,
                   h->rx, h->rxn, h->rq, h->ratt, h->rff, h->h2, h->wprx, h->mlp_part, h->mlp_ctr, h->fold_overflow};
   for (void* p : ptrs)

@@ -1336,6 +1336,10 @@ struct SamplerState {
   const unsigned int* rng_stream;  // [slots] the random stream a sampling slot draws from (a property of the sequence, not of the slot it sits in)
   float* probs_out;     // optional [slots][V]: the processed probability vector (tests), or null
   int V, D, max_new, n_pos, stop, slot0;
+  // (what the constraints added sits behind the older fields: those keep their places among the preloaded kernel arguments)
+  int start;            // start_mel_token: the last id of the fake prompt (the n-gram ban's history)
+  const uint8_t* bans;  // [slots][V] ixtts_gpt_set_bans: bit 0 = id banned at every step, bit 1 = at the first generated token (beam
+                        // mode: the group's first slot holds the group's)
 };
 
 // float -> uint key with the same ordering (ascending)
@@ -1777,11 +1781,64 @@ __device__ __forceinline__ int topp_wave0(const float* sort_v, int n, float top_
   return keep;
 }
 
+// MinPLogitsWarper over the `keep` survivors whose softmax numerators topp_wave0 left in ev (descending), by wave 0 alone: a
+// survivor goes when its probability over the survivors is below min_p * the largest; the first min_keep always stay.  The
+// probabilities descend, so those that stay are a prefix: returns its length.
+__device__ __forceinline__ int minp_wave0(const float* ev, int keep, float min_p, int min_keep) {
+  const int lane = threadIdx.x;
+  const float Z = seq_sum_lds(ev, keep);
+  const float thr = min_p * (ev[0] / Z);  // probs < min_p * probs.amax()
+  const bool k0 = lane < keep && (lane < min_keep || !(ev[lane] / Z < thr));
+  const bool k1 = lane + 64 < keep && (lane + 64 < min_keep || !(ev[lane + 64] / Z < thr));
+  return (int)__popcll(__ballot(k0)) + (int)__popcll(__ballot(k1));
+}
+
+// NoRepeatNGramLogitsProcessor.  The history is the one HF sees: the fake prompt ids [1] * (P - 1) + [start] and the G generated
+// tokens; position k counts from the first generated token (k = -1: start, k < -1: 1).  Every window of n positions ending at e
+// whose first n - 1 tokens equal the history's last n - 1 bans its own last token.  The windows that lie wholly inside the ones
+// (e <= -2) are all alike, so e = -2 stands for them: at most G + 2 windows, one per thread and round.
+constexpr int NGRAM_LDS = 2048;  // generated tokens held in LDS (two per thread, loaded at kernel entry); later ones are read from memory
+struct NgramScratch {
+  int32_t tok[NGRAM_LDS];
+  unsigned int bits[(1024 * SAMP_PT + 31) / 32];  // one bit per id: banned
+};
+
+// Call with the whole workgroup of 1024 threads and a wave-uniform n >= 1; t0 / t1 = gtok[threadIdx.x], gtok[threadIdx.x + 1024]
+// (clamped loads: only indices below G are used).  vals[i] belongs to id threadIdx.x + i * 1024.
+template <int PT>
+__device__ __forceinline__ void ngram_ban_1024(float (&vals)[PT], const int32_t* gtok, int32_t t0, int32_t t1, int G, int P, int n, int start_tok,
+                                               NgramScratch& ng) {
+  const int t = threadIdx.x;
+  if (P + G < n) return;  // no complete n-gram yet (wave-uniform)
+  if (t < G) ng.tok[t] = t0;
+  if (t + 1024 < G) ng.tok[t + 1024] = t1;
+  if (t < (int)(sizeof(ng.bits) / sizeof(ng.bits[0]))) ng.bits[t] = 0u;
+  __syncthreads();
+  auto hist = [&](int k) -> int32_t { return k < -1 ? 1 : k == -1 ? start_tok : k < NGRAM_LDS ? ng.tok[k] : gtok[k]; };
+  const int e_lo = max(n - 1 - P, -2);
+  for (int e = e_lo + t; e < G; e += 1024) {
+    bool match = true;
+    for (int i = 0; i < n - 1; ++i) match = match && hist(e - n + 1 + i) == hist(G - n + 1 + i);
+    if (match) {
+      const unsigned int id = (unsigned int)hist(e);
+      if (id < 1024u * PT) atomicOr(&ng.bits[id >> 5], 1u << (id & 31u));
+    }
+  }
+  __syncthreads();
+#pragma unroll
+  for (int i = 0; i < PT; ++i) {
+    const unsigned int v = t + i * 1024;
+    if ((ng.bits[v >> 5] >> (v & 31u)) & 1u) vals[i] = -INFINITY;
+  }
+}
+
 #ifdef IXTTS_ENGINE_TU  // non-template kernels: compiled into gpt_engine.hip only
 
-// Processor chain in `_get_logits_processor` order (generation_utils.py:900-901,1020-1044):
-// [suppress] -> RepetitionPenalty -> Temperature -> TopK (ties with the k-th value kept) -> TopP -> softmax ->
-// multinomial(1)  |  argmax when do_sample == 0.
+// Processor chain in `_get_logits_processor` order (generation_utils.py:900-1049):
+// [suppress] -> RepetitionPenalty -> NoRepeatNGram -> MinNewTokens -> SuppressTokens -> SuppressTokensAtBegin -> [typical] ->
+// Temperature -> TopK (ties with the k-th value kept) -> TopP -> MinP -> softmax -> multinomial(1)  |  argmax when do_sample == 0.
+// The stages that only write -inf commute with the penalty, so the stop-token and ban-flag ones ride in its loop; the n-gram
+// scan, like MinP, sits behind a workgroup-uniform test of its cfg field: a slot without it executes none of it.
 __global__ __launch_bounds__(1024) void sampler_kernel(SamplerState s) {
   __shared__ float bv[16];
   __shared__ int bi[16];
@@ -1795,14 +1852,19 @@ __global__ __launch_bounds__(1024) void sampler_kernel(SamplerState s) {
   // configuration, the slot's counters -- one memory round trip instead of a chain of dependent ones
   const float* lg = s.logits + (size_t)slot * s.V;
   const uint8_t* seen = s.seen + (size_t)slot * s.V;
+  const uint8_t* bans = s.bans + (size_t)slot * s.V;
+  const int32_t* gtok = s.tokens + (size_t)slot * s.max_new;
   float raw[SAMP_PT];
-  uint8_t sn[SAMP_PT];
+  uint8_t sn[SAMP_PT], bn[SAMP_PT];
 #pragma unroll
   for (int i = 0; i < SAMP_PT; ++i) {
     const int v = min((int)threadIdx.x + i * 1024, s.V - 1);
     raw[i] = lg[v];
     sn[i] = seen[v];
+    bn[i] = bans[v];
   }
+  // the generated tokens the n-gram scan compares (two per thread; it reads what lies past them itself)
+  const int32_t ht0 = gtok[min((int)threadIdx.x, s.max_new - 1)], ht1 = gtok[min((int)threadIdx.x + 1024, s.max_new - 1)];
   const ixtts_sampler_cfg cfg = s.cfg[slot];
   const unsigned int st_stream = s.rng_stream[slot];
   const int st_finished = s.finished[slot], st_forced = s.forced[slot], st_gen = s.gen_count[slot], st_prompt = s.prompt_len[slot];
@@ -1816,6 +1878,9 @@ __global__ __launch_bounds__(1024) void sampler_kernel(SamplerState s) {
   const bool sampling = cfg.do_sample != 0;
   const float inv_t = (sampling && cfg.temperature > 0.f) ? 1.0f / cfg.temperature : 1.0f;
 
+  // MinNewTokensLengthLogitsProcessor: no stop token before min_new_tokens tokens; the ban flags: bit 0 always, bit 1 at the first token
+  const bool no_stop = cfg.suppress_stop || st_gen < cfg.min_new_tokens;
+  const unsigned int ban_mask = st_gen == 0 ? 3u : 1u;
   float vals[SAMP_PT];
 #pragma unroll
   for (int i = 0; i < SAMP_PT; ++i) {
@@ -1823,10 +1888,14 @@ __global__ __launch_bounds__(1024) void sampler_kernel(SamplerState s) {
     float x = -INFINITY;
     if (v < s.V) {
       x = raw[i];
-      if (cfg.suppress_stop && v == s.stop) x = -INFINITY;
+      if ((no_stop && v == s.stop) || (bn[i] & ban_mask)) x = -INFINITY;
       if (sn[i] && theta != 1.0f) x = (x < 0.f) ? x * theta : x / theta;  // RepetitionPenaltyLogitsProcessor
     }
     vals[i] = x;
+  }
+  if (cfg.no_repeat_ngram_size > 0) {
+    __shared__ NgramScratch ng;
+    ngram_ban_1024<SAMP_PT>(vals, gtok, ht0, ht1, min(st_gen, s.max_new), st_prompt, cfg.no_repeat_ngram_size, s.start, ng);
   }
   if (cfg.typical_mass > 0.f) {  // custom processor of inference_speech(typical_sampling=True): after the penalty, before the warpers
     __shared__ TypicalScratch typ;
@@ -1954,6 +2023,18 @@ __global__ __launch_bounds__(1024) void sampler_kernel(SamplerState s) {
       for (int i = 0; i < SAMP_PT; ++i)
         if (key[i] < tau && key[i] != kmax) e[i] = 0.f;
     }
+    if (cfg.min_p > 0.f) {
+      // ---- MinP: probabilities over what is left; below min_p * the largest goes.  The largest is the maximum's, numerator 1
+      // (TopK and TopP never remove it), and it stays (min_tokens_to_keep = 1).
+      float sk = 0.f;
+#pragma unroll
+      for (int i = 0; i < SAMP_PT; ++i) sk += e[i];
+      const float Zk = block_sum_1024(sk, gs.red);
+      const float thr = cfg.min_p * (1.0f / Zk);
+#pragma unroll
+      for (int i = 0; i < SAMP_PT; ++i)
+        if (e[i] / Zk < thr) e[i] = 0.f;
+    }
     // ---- multinomial(1): inverse CDF over the kept tokens in (thread, register) order -- a fixed order, so a fixed stream
     float mine = 0.f;
 #pragma unroll
@@ -2010,7 +2091,8 @@ __global__ __launch_bounds__(1024) void sampler_kernel(SamplerState s) {
     if (threadIdx.x < 64 && n > 0) {
       // ---- TopP over the survivors (keep >= 1), then multinomial(1) by inverse CDF over the kept ones
       float Z;
-      const int keep = topp_wave0(sort_v, n, cfg.top_p, 1, ev, qv, &Z);
+      int keep = topp_wave0(sort_v, n, cfg.top_p, 1, ev, qv, &Z);
+      if (cfg.min_p > 0.f) keep = minp_wave0(ev, keep, cfg.min_p, 1);
       const float Zk = seq_sum_lds(ev, keep);
       const float u = uniform01(cfg.seed, st_stream, (unsigned int)st_gen) * Zk;
       float c = 0.f;

@@ -44,6 +44,47 @@ def resolve_gpt_dtype(use_fp16, gpt_dtype=None, env=None):
 GPT_TENSOR_PREFIXES = ("gpt.h.", "gpt.ln_f.", "final_norm.", "mel_head.", "mel_embedding.", "mel_pos_embedding.")
 
 
+CONSTRAINT_KEYS = ("min_new_tokens", "min_length", "no_repeat_ngram_size", "suppress_tokens", "begin_suppress_tokens", "min_p")
+
+
+def generation_constraints(kwargs, prompt_len=None):
+    """The constraint keywords of HF `generate()` out of `kwargs` (popped; None counts as not given) -> (cfg, bans): `cfg` holds
+    the engine's keyword names `min_new_tokens`, `no_repeat_ngram_size`, `min_p` -- only those that were given and are not off --
+    and `bans` is `(suppress_tokens, begin_suppress_tokens)` as tuples of ints, or None when neither list holds an id.
+    `min_length=L` means `min_new_tokens = max(0, L - prompt_len)`; `min_new_tokens` wins when both are given
+    (generation_utils.py:1445-1453).  With `prompt_len=None` (a caller whose segments differ in prompt length) a surviving
+    `min_length` is handed back under its own name for `resolve_min_length`."""
+    got = {k: kwargs.pop(k) for k in CONSTRAINT_KEYS if k in kwargs}
+    got = {k: v for k, v in got.items() if v is not None}
+    cfg = {}
+    if "min_new_tokens" in got:
+        if int(got["min_new_tokens"]):
+            cfg["min_new_tokens"] = int(got["min_new_tokens"])
+    elif "min_length" in got:
+        if prompt_len is None:
+            cfg["min_length"] = int(got["min_length"])
+        elif int(got["min_length"]) - int(prompt_len) > 0:
+            cfg["min_new_tokens"] = int(got["min_length"]) - int(prompt_len)
+    if int(got.get("no_repeat_ngram_size", 0)):
+        cfg["no_repeat_ngram_size"] = int(got["no_repeat_ngram_size"])
+    if float(got.get("min_p", 0.0)) != 0.0:
+        cfg["min_p"] = float(got["min_p"])
+    lists = tuple(tuple(int(t) for t in np.asarray(got.get(k, ()), dtype=np.int64).reshape(-1)) for k in ("suppress_tokens", "begin_suppress_tokens"))
+    return cfg, (lists if lists[0] or lists[1] else None)
+
+
+def resolve_min_length(cfg, prompt_len):
+    """`cfg` of `generation_constraints(..., prompt_len=None)` for a sequence whose prompt holds `prompt_len` ids: `min_length`
+    turned into that sequence's `min_new_tokens` (left out when it asks for nothing)."""
+    if "min_length" not in cfg:
+        return cfg
+    out = {k: v for k, v in cfg.items() if k != "min_length"}
+    m = int(cfg["min_length"]) - int(prompt_len)
+    if m > 0:
+        out["min_new_tokens"] = m
+    return out
+
+
 class GptEngine:
     def __init__(self, cfg=None, dtype="f32", max_seq=2048, max_batch=1, device=None):
         code = _dtype_code(dtype)
@@ -122,16 +163,19 @@ class GptEngine:
         self._keep = e  # keep alive until the stream has consumed it
 
     def decode(self, n_active, n_steps, repetition_penalty=10.0, temperature=1.0, top_k=0, top_p=1.0,
-               do_sample=False, suppress_stop=False, seed=0, typical_mass=0.0):
-        sc = _lib.SamplerCfg(repetition_penalty, temperature, top_k, top_p, int(do_sample), int(suppress_stop), seed, float(typical_mass), 0.0)
+               do_sample=False, suppress_stop=False, seed=0, typical_mass=0.0, min_new_tokens=0, no_repeat_ngram_size=0, min_p=0.0):
+        """`min_new_tokens`, `no_repeat_ngram_size`, `min_p`: the processors HF `generate()` builds from the keywords of the same
+        names (0 = off; `min_p` acts when sampling only); the two id lists of the family belong to the slot: `set_bans`."""
+        sc = _lib.SamplerCfg(repetition_penalty, temperature, top_k, top_p, int(do_sample), int(suppress_stop), seed, float(typical_mass), 0.0,
+                             int(min_new_tokens), int(no_repeat_ngram_size), float(min_p))
         with torch.cuda.device(self.device):
             rc = _lib.lib().ixtts_gpt_decode(self._h, n_active, n_steps, C.byref(sc), self._stream())
         _lib.check(rc, "ixtts_gpt_decode")
 
     _DECODE_KEYS = dict(repetition_penalty=10.0, temperature=1.0, top_k=0, top_p=1.0, do_sample=False, suppress_stop=False, seed=0,
-                        typical_mass=0.0)
+                        typical_mass=0.0, min_new_tokens=0, no_repeat_ngram_size=0, min_p=0.0)
     _BEAM_KEYS = dict(repetition_penalty=10.0, temperature=0.8, top_k=30, top_p=0.8, suppress_stop=False, seed=0, typical_mass=0.0,
-                      length_penalty=0.0, do_sample=True)
+                      length_penalty=0.0, do_sample=True, min_new_tokens=0, no_repeat_ngram_size=0, min_p=0.0)
 
     @staticmethod
     def _sampler_array(cfgs, defaults, what):
@@ -143,7 +187,8 @@ class GptEngine:
                 raise TypeError(f"{what}: entry {i} has unexpected keys {sorted(unknown)}")
             v = {**defaults, **cfg}
             arr[i] = _lib.SamplerCfg(v["repetition_penalty"], v["temperature"], int(v["top_k"]), v["top_p"], int(bool(v["do_sample"])),
-                                     int(bool(v["suppress_stop"])), int(v["seed"]), float(v["typical_mass"]), float(v.get("length_penalty", 0.0)))
+                                     int(bool(v["suppress_stop"])), int(v["seed"]), float(v["typical_mass"]), float(v.get("length_penalty", 0.0)),
+                                     int(v["min_new_tokens"]), int(v["no_repeat_ngram_size"]), float(v["min_p"]))
         return arr
 
     def decode_slots(self, n_steps, cfgs, streams=None):
@@ -180,6 +225,17 @@ class GptEngine:
             _lib.check(_lib.lib().ixtts_gpt_read_probs(self._h, slot, out.ctypes.data, self._stream()), "ixtts_gpt_read_probs")
         return out
 
+    def set_bans(self, slot, suppress_tokens=(), begin_suppress_tokens=()):
+        """`suppress_tokens` (ids banned at every step) and `begin_suppress_tokens` (at the first generated token only) of the
+        sequence in `slot`, as HF `generate()` takes them.  Call it after the slot's `prefill` (which clears them) and before its
+        first decode step; with beams, on the group's first slot.  An id outside the vocabulary raises IxttsError."""
+        a = np.ascontiguousarray(np.asarray(list(suppress_tokens), dtype=np.int64).astype(np.int32).reshape(-1))
+        f = np.ascontiguousarray(np.asarray(list(begin_suppress_tokens), dtype=np.int64).astype(np.int32).reshape(-1))
+        with torch.cuda.device(self.device):
+            rc = _lib.lib().ixtts_gpt_set_bans(self._h, int(slot), a.ctypes.data if a.size else None, a.size, f.ctypes.data if f.size else None, f.size,
+                                               self._stream())
+        _lib.check(rc, "ixtts_gpt_set_bans")
+
     def force_next(self, slot, token):
         with torch.cuda.device(self.device):
             _lib.check(_lib.lib().ixtts_gpt_force_next(self._h, slot, int(token), self._stream()), "ixtts_gpt_force_next")
@@ -196,9 +252,11 @@ class GptEngine:
             _lib.check(_lib.lib().ixtts_gpt_beam_park_group(self._h, int(group), self._stream()), "ixtts_gpt_beam_park_group")
 
     def beam_decode(self, n_steps, repetition_penalty=10.0, temperature=0.8, top_k=30, top_p=0.8, suppress_stop=False, seed=0, typical_mass=0.0,
-                    length_penalty=0.0, groups=1, do_sample=True):
-        """`do_sample=False`: beam search proper -- the joint top 2 * num_beams instead of the multinomial draw, no warpers."""
-        sc = _lib.SamplerCfg(repetition_penalty, temperature, top_k, top_p, int(bool(do_sample)), int(suppress_stop), seed, float(typical_mass), float(length_penalty))
+                    length_penalty=0.0, groups=1, do_sample=True, min_new_tokens=0, no_repeat_ngram_size=0, min_p=0.0):
+        """`do_sample=False`: beam search proper -- the joint top 2 * num_beams instead of the multinomial draw, no warpers (`min_p`
+        is one of them).  `no_repeat_ngram_size` looks at each beam's own history."""
+        sc = _lib.SamplerCfg(repetition_penalty, temperature, top_k, top_p, int(bool(do_sample)), int(suppress_stop), seed, float(typical_mass), float(length_penalty),
+                             int(min_new_tokens), int(no_repeat_ngram_size), float(min_p))
         self._lp = [float(length_penalty)] * int(groups)  # per group
         with torch.cuda.device(self.device):
             _lib.check(_lib.lib().ixtts_gpt_beam_decode_groups(self._h, int(groups), n_steps, C.byref(sc), self._stream()), "ixtts_gpt_beam_decode_groups")
@@ -269,6 +327,8 @@ class GptEngine:
         # the one custom processor inference_speech ever builds is TypicalLogitsWarper(mass=typical_mass) (model_v2.py:717-722):
         # it runs on the device; anything else has no kernel
         typical_mass = float(unused.pop("typical_mass", 0.0)) if unused.pop("typical_sampling", False) else 0.0
+        # the constraints HF builds from plain keywords (generation_utils.py:902-1049): scalars into the sampler cfg, id lists onto the slot
+        cons, bans = generation_constraints(unused, inputs.shape[1])
         for proc in (logits_processor or []):
             if type(proc).__name__ == "TypicalLogitsWarper" and hasattr(proc, "mass"):
                 typical_mass = float(proc.mass)
@@ -297,6 +357,8 @@ class GptEngine:
         # the mel position table bounds what can be embedded (inference_speech's own default cap: max_mel_tokens - 1, model_v2.py:699-703)
         max_new = max(0, min(max_new, self.max_seq - P - 2, self.cfg["max_mel_tokens"] - 1))
         self.prefill(0, emb, n_pad)
+        if bans is not None:
+            self.set_bans(0, *bans)
         if num_beams != 1:
             # served default: 3-beam beam-sample (infer_v2.py:598-605,641-658); do_sample=False: beam search (generation_utils.py:3520-3524)
             self.beam_begin(num_beams)
@@ -306,7 +368,7 @@ class GptEngine:
                 n = min(sync_every, max_new - done_steps)
                 self.beam_decode(n, repetition_penalty=repetition_penalty, temperature=temperature, top_k=top_k, top_p=top_p,
                                  suppress_stop=suppress_stop, seed=int(unused.get("seed", 0)), typical_mass=typical_mass, length_penalty=length_penalty,
-                                 do_sample=do_sample)
+                                 do_sample=do_sample, **cons)
                 done_steps += n
                 ids, fin = self.beam_read(max_new)[:2]
             out = torch.cat([inputs.reshape(1, -1).to(torch.long).cpu(), torch.from_numpy(ids.astype(np.int64)).reshape(1, -1)], dim=1)
@@ -316,12 +378,14 @@ class GptEngine:
             # (the slot index is part of the counter-based RNG); rows are right-padded with pad_token_id as HF pads finished rows
             for b in range(1, nret):
                 self.prefill(b, emb, n_pad)
+                if bans is not None:
+                    self.set_bans(b, *bans)
             done, fins = 0, [False] * nret
             rows = [np.zeros(0, np.int32)] * nret
             while done < max_new and not all(fins):
                 n = min(sync_every, max_new - done)
                 self.decode(nret, n, repetition_penalty=repetition_penalty, temperature=temperature, top_k=top_k, top_p=top_p,
-                            do_sample=not greedy, suppress_stop=suppress_stop, seed=int(unused.get("seed", 0)), typical_mass=typical_mass)
+                            do_sample=not greedy, suppress_stop=suppress_stop, seed=int(unused.get("seed", 0)), typical_mass=typical_mass, **cons)
                 done += n
                 for b in range(nret):
                     rows[b], fins[b] = self.read(b)
@@ -338,7 +402,7 @@ class GptEngine:
         while done < max_new and not fin:
             n = min(sync_every, max_new - done)
             self.decode(1, n, repetition_penalty=repetition_penalty, temperature=temperature, top_k=top_k, top_p=top_p,
-                        do_sample=not greedy, suppress_stop=suppress_stop, seed=int(unused.get("seed", 0)), typical_mass=typical_mass)
+                        do_sample=not greedy, suppress_stop=suppress_stop, seed=int(unused.get("seed", 0)), typical_mass=typical_mass, **cons)
             done += n
             ids, fin = self.read(0)
         ids = ids[:max_new]

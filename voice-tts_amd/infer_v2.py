@@ -26,7 +26,7 @@ import numpy as np
 import torch
 
 from .bigvgan import BigVGAN
-from .gpt_engine import GptEngine, resolve_gpt_dtype
+from .gpt_engine import GptEngine, generation_constraints, resolve_gpt_dtype, resolve_min_length
 from .pipeline import conds_latent, decode_segment, latent_prefix, prepare_gpt_inputs, vocode, vocode_many
 from .weights import BIGVGAN_CFG, GPT_CFG, load_bigvgan_checkpoint, load_gpt_checkpoint
 
@@ -553,7 +553,7 @@ class IndexTTS2:
     def _generation_args(self, generation_kwargs):
         """Generation kwargs and their defaults (infer_v2.py:598-606) -> (namespace of the parsed values, the kwargs left over);
         do_sample is popped and then forced True (:648).  `typical_mass` and `seed` are read for the schedulers and stay among the
-        leftovers, which `infer` forwards to `gpt.generate`."""
+        leftovers, which `infer` forwards to `gpt.generate`; so do the constraint keywords, which `_generation_constraints` parses."""
         rest = dict(generation_kwargs)
         rest.pop("do_sample", True)
         g = SimpleNamespace(top_p=rest.pop("top_p", 0.8), top_k=rest.pop("top_k", 30), temperature=rest.pop("temperature", 0.8),
@@ -562,6 +562,29 @@ class IndexTTS2:
                             typical_mass=float(rest.get("typical_mass", 0.9)) if rest.get("typical_sampling") else 0.0,
                             seed=int(rest.get("seed", 0)))
         return g, rest
+
+    def _generation_constraints(self, rest):
+        """The constraint keywords of HF `generate()` among the leftovers of `_generation_args` -- `min_new_tokens`, `min_length`,
+        `no_repeat_ngram_size`, `suppress_tokens`, `begin_suppress_tokens`, `min_p` -- for the segments the schedulers decode ->
+        (cfg, bans) or None when none is set: `cfg` under the engine's keyword names (`Segment.sampler`; a `min_length` stays under
+        its own name until `_segment` knows the segment's prompt length: min_new_tokens = max(0, min_length - P), and
+        `min_new_tokens` wins over it), `bans` = (suppress_tokens, begin_suppress_tokens) or None (`Segment.bans`).  `rest` is left
+        alone: `gpt.generate` parses the same keywords itself.  A value the engine would refuse raises ValueError here, where it
+        fails its own request only."""
+        from . import _lib
+
+        cfg, bans = generation_constraints(dict(rest))
+        if cfg.get("min_new_tokens", 0) < 0:
+            raise ValueError(f"generation: min_new_tokens {cfg['min_new_tokens']} is negative")
+        if not 0 <= cfg.get("no_repeat_ngram_size", 0) <= _lib.NGRAM_MAX:
+            raise ValueError(f"generation: no_repeat_ngram_size {cfg['no_repeat_ngram_size']} outside 0..{_lib.NGRAM_MAX}")
+        if not 0.0 <= cfg.get("min_p", 0.0) <= 1.0:
+            raise ValueError(f"generation: min_p {cfg['min_p']} outside 0..1")
+        V = int(self.gpt_cfg["number_mel_codes"])
+        for t in (bans or ((), ()))[0] + (bans or ((), ()))[1]:
+            if not 0 <= t < V:
+                raise ValueError(f"generation: suppressed id {t} outside 0..{V - 1}")
+        return (cfg, bans) if cfg or bans is not None else None
 
     def _no_qwen_emo(self):
         return NotImplementedError(
@@ -627,32 +650,42 @@ class IndexTTS2:
         return [self.tokenizer.convert_tokens_to_ids(sent) for sent in
                 self.tokenizer.split_segments(text_tokens_list, max_text_tokens_per_segment, quick_streaming_tokens=quick_streaming_tokens)]
 
-    def _segment(self, conds_latent, ids, engine, max_mel_tokens, request=0, index=0, payload=None, stream=None, sampler=None):
-        """One segment's text ids -> what the schedulers decode; `max_new` is taken against the engine that will decode it."""
+    def _segment(self, conds_latent, ids, engine, max_mel_tokens, request=0, index=0, payload=None, stream=None, sampler=None, constraints=None):
+        """One segment's text ids -> what the schedulers decode; `max_new` is taken against the engine that will decode it.
+        `constraints`: what `_generation_constraints` returned -- its scalars join the segment's sampler settings (a sampler of its
+        own only when there is something to set), its id lists become the segment's bans."""
         embeds, n_pad, P = prepare_gpt_inputs(self.gpt_cfg, self.text_embedding, self.text_pos_embedding, conds_latent, ids)
         max_new = max(0, min(max_mel_tokens, engine.max_seq - P - 2, self.gpt_cfg["max_mel_tokens"] - 1))
-        return decode_segment(index, embeds, n_pad, max_new, request, payload, stream, sampler)
+        bans = None
+        if constraints is not None:
+            cfg = resolve_min_length(constraints[0], P)
+            if cfg:
+                sampler = {**(sampler or {}), **cfg}
+            bans = constraints[1]
+        return decode_segment(index, embeds, n_pad, max_new, request, payload, stream, sampler, bans)
 
     # what a request's `generation` dict may hold (infer_many): `infer`'s generation kwargs, parsed by `_generation_args`
     GENERATION_KEYS = ("top_p", "top_k", "temperature", "repetition_penalty", "length_penalty", "max_mel_tokens", "typical_sampling",
-                       "typical_mass", "seed", "num_beams")
+                       "typical_mass", "seed", "num_beams", "min_new_tokens", "min_length", "no_repeat_ngram_size", "suppress_tokens",
+                       "begin_suppress_tokens", "min_p")
 
     def _request_generation(self, rq, generation_kwargs, g):
-        """-> (generation namespace of this request, pinned): a request with a `generation` dict overrides the call's kwargs with
-        it and is PINNED -- its settings, seed and random streams are its own; one without it takes the call's (`g`)."""
+        """-> (generation namespace of this request, pinned, its constraints): a request with a `generation` dict overrides the
+        call's kwargs with it and is PINNED -- its settings, seed and random streams are its own; one without it takes the call's
+        (`g`).  The constraints are `_generation_constraints` of the same merged kwargs."""
         if "generation" not in rq:
-            return g, False
+            return g, False, self._generation_constraints(self._generation_args(generation_kwargs)[1])
         gen = dict(rq["generation"] or {})
         for k in gen:
             if k not in self.GENERATION_KEYS:
                 raise ValueError(f"generation: unknown key {k!r} (known: {', '.join(self.GENERATION_KEYS)})")
-        gr, _ = self._generation_args({**generation_kwargs, **gen})
+        gr, rest = self._generation_args({**generation_kwargs, **gen})
         gr.num_beams = int(gr.num_beams)
         if gr.num_beams < 1:
             raise ValueError(f"generation: num_beams {gr.num_beams}")
         if gr.num_beams > 1 and not (2 <= gr.num_beams <= 4 and 1 <= gr.top_k <= 128):
             raise NotImplementedError("beam-sample on the device: 2 <= num_beams <= 4, 1 <= top_k <= 128")
-        return gr, True
+        return gr, True, self._generation_constraints(rest)
 
     @staticmethod
     def _segment_sampler(g):
@@ -757,8 +790,11 @@ class IndexTTS2:
         floor(decode_slots / num_beams) groups step together; `num_beams=1` samples without beams, one slot per segment (argmax
         when `top_k == 1`).
 
+        The constraint keywords of HF `generate()` -- `min_new_tokens`, `min_length`, `no_repeat_ngram_size`, `suppress_tokens`,
+        `begin_suppress_tokens`, `min_p` -- hold for every segment of the call, as they do in `infer`.
+
         A request may carry `generation`, a dict with any of `GENERATION_KEYS` (top_p, top_k, temperature, repetition_penalty,
-        length_penalty, max_mel_tokens, typical_sampling, typical_mass, seed, num_beams): it overrides the call's kwargs for that
+        length_penalty, max_mel_tokens, typical_sampling, typical_mass, seed, num_beams and the six constraint keywords): it overrides the call's kwargs for that
         request, and the request is PINNED (even with `{}`): segment i decodes under the request's settings and seed from random
         stream i, and the built-in s2mel's noise comes from (seed, i).  Its codes and PCM are then a function of the request
         alone -- bit-identical alone or in any batch, in any order -- at a given `decode_slots` (the engine's shape: wide and
@@ -793,7 +829,7 @@ class IndexTTS2:
                 spk, emo_cond = self._encode_prompts(spk_prompt, emo_prompt)
                 cl = self._conds_latent(spk, emo_cond, emo_is_spk, emo_alpha, emo_vector, rq.get("use_random", False))
                 segments = self._segments_of(rq["text"], max_text_tokens_per_segment)
-                gr, pinned = self._request_generation(rq, generation_kwargs, g)
+                gr, pinned, cons = self._request_generation(rq, generation_kwargs, g)
                 nb = gr.num_beams
                 if nb not in engines:
                     engines[nb] = self._many_engine_for(nb, decode_slots)
@@ -802,7 +838,8 @@ class IndexTTS2:
                     raise NotImplementedError(f"num_beams={nb} needs {nb} decode slots: the engine chosen for decode_slots={decode_slots} holds {eng.max_batch}")
                 # a pinned request: segment i under the request's own settings and seed, drawing from stream i
                 sampler = self._segment_sampler(gr) if pinned else None
-                mine = [self._segment(cl, ids, eng, gr.max_mel_tokens, request=ri, index=si, stream=si if pinned else None, sampler=sampler)
+                mine = [self._segment(cl, ids, eng, gr.max_mel_tokens, request=ri, index=si, stream=si if pinned else None, sampler=sampler,
+                                      constraints=cons)
                         for si, ids in enumerate(segments)]
                 plans[ri] = dict(spk=spk, cl=cl, segments=segments, seed=gr.seed if pinned else None)
                 classes.setdefault(nb, []).extend(mine)  # only once the whole request is known to be well-formed
@@ -918,7 +955,8 @@ class IndexTTS2:
         pre = None
         if eng is not None:
             beams = g.num_beams > 1
-            pre = self._decode(eng, [self._segment(cl, ids, eng, g.max_mel_tokens, index=i, stream=i if beams else None)
+            cons = self._generation_constraints(rest)  # (the one-segment path below hands `rest` to gpt.generate, which parses them itself)
+            pre = self._decode(eng, [self._segment(cl, ids, eng, g.max_mel_tokens, index=i, stream=i if beams else None, constraints=cons)
                                      for i, ids in enumerate(segments)], g)
         gpt_gen_time += time.perf_counter() - m0
         # several segments, whole audio at the end, IXTTS_S2MEL_BATCH=1: their CFM solves run as ONE packed solve (default: segment

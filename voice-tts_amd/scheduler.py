@@ -21,15 +21,18 @@ import numpy as np
 class Segment:
     """One text segment of one request, ready for the decode engine."""
 
-    __slots__ = ("request", "index", "embeds", "n_left_pad", "max_new", "payload", "stream", "sampler")
+    __slots__ = ("request", "index", "embeds", "n_left_pad", "max_new", "payload", "stream", "sampler", "bans")
 
-    def __init__(self, request, index, embeds, n_left_pad, max_new, payload=None, stream=None, sampler=None):
+    def __init__(self, request, index, embeds, n_left_pad, max_new, payload=None, stream=None, sampler=None, bans=None):
         self.request, self.index, self.embeds, self.n_left_pad, self.max_new, self.payload = request, index, embeds, n_left_pad, max_new, payload
         # the random stream this segment draws from (None: beam groups, its position in the submission order; single slots, the
         # index of the slot it lands in)
         self.stream = stream
         # its own sampler settings: keyword names of the engine's decode() / beam_decode(), over the run's **sampler (None: the run's)
         self.sampler = sampler
+        # (suppress_tokens, begin_suppress_tokens) of HF generate(): ids banned at every step / at the first generated token.  They are
+        # state of the slot the segment lands in: the schedulers call engine.set_bans right after its prefill (None: no call)
+        self.bans = bans
 
 
 def live_stub(engine, like):
@@ -49,7 +52,8 @@ class DecodeScheduler:
     """Keeps the engine's decode slots busy with segments from a queue.
 
     engine: `GptEngine`-like object with prefill(slot, embeds, n_left_pad), decode(n_active, n_steps, **sampler) and
-    read(slot) -> (ids, finished); decode_slots(n_steps, cfgs, streams) too when a segment carries `sampler` or `stream`.
+    read(slot) -> (ids, finished); decode_slots(n_steps, cfgs, streams) too when a segment carries `sampler` or `stream`, and
+    set_bans(slot, suppress_tokens, begin_suppress_tokens) when one carries `bans`.
     `stop_token` ends a sequence (inclusive) unless `fixed_length`.
     """
 
@@ -75,6 +79,8 @@ class DecodeScheduler:
                 if slots[b] is None and queue and b <= primed:
                     seg = queue.popleft()
                     self.engine.prefill(b, seg.embeds, seg.n_left_pad)
+                    if getattr(seg, "bans", None) is not None:
+                        self.engine.set_bans(b, *seg.bans)
                     if b < primed:
                         self.stats["refills"] += 1
                     primed = max(primed, b + 1)
@@ -131,7 +137,7 @@ class BeamGroupScheduler:
 
     engine: `GptEngine`-like with prefill(slot, embeds, pad), beam_begin(num_beams, group=, rng_stream=), beam_park(group),
     beam_decode(n_steps, groups=, **sampler), beam_read(max_new, group=) -> (ids, done, score, ...); beam_decode_groups(n_steps,
-    cfgs) too when a segment carries `sampler`.
+    cfgs) too when a segment carries `sampler`, set_bans(slot, ...) when one carries `bans`.
     """
 
     def __init__(self, engine, num_beams, max_groups=None, sync_every=64):
@@ -160,6 +166,8 @@ class BeamGroupScheduler:
                 if groups[g] is None and queue and g <= begun:
                     seg, stream = queue.popleft()
                     eng.prefill(g * nb, seg.embeds, seg.n_left_pad)
+                    if getattr(seg, "bans", None) is not None:
+                        eng.set_bans(g * nb, *seg.bans)  # the group's: the flags of its first slot hold for all its beams
                     eng.beam_begin(nb, group=g, rng_stream=stream)
                     if g < begun:
                         self.stats["refills"] += 1

@@ -248,12 +248,15 @@ typedef struct ixtts_gpt_cfg {
   int weight_dtype;    /* IXTTS_DTYPE_F32 (parity mode) | IXTTS_DTYPE_BF16 (throughput mode) | IXTTS_DTYPE_F16 (see above) */
 } ixtts_gpt_cfg;
 
-#define IXTTS_NGRAM_MAX 8 /* largest no_repeat_ngram_size */
+#define IXTTS_NGRAM_MAX 8     /* largest no_repeat_ngram_size */
+#define IXTTS_SEQ_BIAS_MAX 64 /* entries of a sequence's bias table: `sequence_bias` and `bad_words_ids` share it */
+#define IXTTS_SEQ_BIAS_LEN 8  /* ids per entry */
 
-/* Token selection follows `_get_logits_processor` (transformers_generation_utils.py:900-1049), in its order:
- *   [suppress_stop] -> RepetitionPenalty -> NoRepeatNGram -> MinNewTokens -> SuppressTokens -> SuppressTokensAtBegin -> [typical]
- *   -> Temperature -> TopK -> TopP -> MinP -> softmax + multinomial | argmax
- * The warpers (Temperature .. MinP) run when sampling only: not in greedy decoding, not in beam search proper. */
+/* Token selection follows `_get_logits_processor` (transformers_generation_utils.py:862-1069), in its order:
+ *   [suppress_stop] -> SequenceBias -> RepetitionPenalty -> NoRepeatNGram -> NoBadWords -> MinNewTokens -> ForcedEOS
+ *   -> ExponentialDecayLengthPenalty -> SuppressTokens -> SuppressTokensAtBegin -> [typical]
+ *   -> Temperature -> TopK -> TopP -> MinP -> EpsilonCutoff -> EtaCutoff -> LogitNormalization -> softmax + multinomial | argmax
+ * The warpers (Temperature .. EtaCutoff) run when sampling only: not in greedy decoding, not in beam search proper. */
 typedef struct ixtts_sampler_cfg {
   float repetition_penalty; /* 10.0 (infer_v2.py:605); 1.0 disables                         */
   float temperature;        /* 0.8; ignored when do_sample == 0                              */
@@ -280,6 +283,23 @@ typedef struct ixtts_sampler_cfg {
   float min_p;              /* MinPLogitsWarper, sampling (and beam-sample) only, after TopP: ids whose probability over the remaining
                                scores is below min_p * the largest are removed, the best min_tokens_to_keep (1; 2 with beams)
                                never; 0..1 */
+  /* The rest of that family (transformers_generation_utils.py:862-1069); 0 = off, so a caller that zero-fills them gets none of it.
+     The table of biased sequences and the forced ids are state of the sequence: ixtts_gpt_set_sequence_bias, ixtts_gpt_set_forced_eos. */
+  int exp_decay_start;      /* ExponentialDecayLengthPenalty(start_index, factor): once MORE than exp_decay_start tokens have been */
+  double exp_decay_factor;  /* generated, score[stop] += |score[stop]| * (factor ** (generated - start) - 1); the power is taken in fp64
+                               as HF takes it in Python floats, so the factor is a double; a stop score of -inf stays -inf.
+                               factor 0: off; start >= 0, factor > 0 */
+  float epsilon_cutoff;     /* EpsilonLogitsWarper, sampling only, after MinP: ids whose probability over the remaining scores is
+                               below epsilon are removed, the best min_tokens_to_keep (1; 2 with beams) never; [0, 1) */
+  float eta_cutoff;         /* EtaLogitsWarper, after it: the same with the threshold min(eta, sqrt(eta) * exp(-entropy)); [0, 1) */
+  int renormalize_logits;   /* LogitNormalization, last: the scores become their own log_softmax.  Without beams that changes neither
+                               tokens nor ixtts_gpt_read_probs; with beams each beam's candidate scores are shifted by the logsumexp
+                               over that beam's surviving scores (beam search proper: over its whole processed row) */
+  int forced_eos_step;      /* ForcedEOSTokenLogitsProcessor: when the forced_eos_step-th generated token is chosen (HF: the token at
+                               position max_length - 1, so forced_eos_step = max_length - prompt length) every score is -inf and the
+                               ids of ixtts_gpt_set_forced_eos are 0; SuppressTokens still runs after it.  >= 0 */
+  int n_seq_bias;           /* filled in by the engine (entries of the slot's / the group's table); whatever the caller writes here
+                               is ignored */
 } ixtts_sampler_cfg;
 
 typedef struct ixtts_gpt ixtts_gpt;
@@ -333,6 +353,20 @@ int ixtts_gpt_read_probs(ixtts_gpt* h, int b, float* probs_host, void* stream);
  * beams.  Stream-ordered (the ids are copied before the call returns); an id outside 0..n_mel_codes-1 returns IXTTS_ERR_ARG. */
 int ixtts_gpt_set_bans(ixtts_gpt* h, int slot, const int32_t* always_host, int n_always, const int32_t* first_host, int n_first,
                        void* stream);
+/* `sequence_bias` and `bad_words_ids` of generate() for the sequence in `slot` (SequenceBiasLogitsProcessor,
+ * NoBadWordsLogitsProcessor): n entries, entry e = the lens_host[e] ids (1..IXTTS_SEQ_BIAS_LEN) that follow those of the entries
+ * before it in ids_flat_host, and biases_host[e] (a bad word: -INFINITY; NaN is refused).  A one-id entry adds its bias to that id
+ * at every step; a longer one adds it to its last id when the history HF sees -- [1]*(P-1) + [start_mel], then the generated
+ * tokens; with beams each beam's own -- ends with its other ids; an entry longer than the history is ignored; entries that end in
+ * one id add up.  The bias lands BEFORE the repetition penalty.  n = 0..IXTTS_SEQ_BIAS_MAX; the table REPLACES the slot's earlier
+ * one and ixtts_gpt_prefill of the slot clears it, so call this after the prefill; with beams the table of the group's first
+ * slot holds for all its beams.  Stream-ordered (copied before the call returns); IXTTS_ERR_ARG names the slot and the limit. */
+int ixtts_gpt_set_sequence_bias(ixtts_gpt* h, int slot, const int32_t* ids_flat_host, const int32_t* lens_host, const float* biases_host,
+                                int n, void* stream);
+/* `forced_eos_token_id` of generate() for the sequence in `slot`: the ids that ixtts_sampler_cfg.forced_eos_step leaves at 0.
+ * Replaces the slot's earlier ones, cleared by ixtts_gpt_prefill, the group's first slot with beams -- as ixtts_gpt_set_bans,
+ * whose two lists it leaves alone (and which leaves these alone). */
+int ixtts_gpt_set_forced_eos(ixtts_gpt* h, int slot, const int32_t* ids_host, int n, void* stream);
 /* Teacher forcing for parity tests: overrides the NEXT token chosen for slot b. */
 int ixtts_gpt_force_next(ixtts_gpt* h, int b, int32_t token, void* stream);
 

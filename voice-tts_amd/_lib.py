@@ -37,10 +37,14 @@ class SamplerCfg(C.Structure):
         ("top_p", C.c_float), ("do_sample", C.c_int), ("suppress_stop", C.c_int), ("seed", C.c_uint64),
         ("typical_mass", C.c_float), ("length_penalty", C.c_float),
         ("min_new_tokens", C.c_int), ("no_repeat_ngram_size", C.c_int), ("min_p", C.c_float),
+        ("exp_decay_start", C.c_int), ("exp_decay_factor", C.c_double), ("epsilon_cutoff", C.c_float), ("eta_cutoff", C.c_float),
+        ("renormalize_logits", C.c_int), ("forced_eos_step", C.c_int), ("n_seq_bias", C.c_int),  # n_seq_bias: the engine fills it in
     ]
 
 
 NGRAM_MAX = 8  # IXTTS_NGRAM_MAX
+SEQ_BIAS_MAX = 64  # IXTTS_SEQ_BIAS_MAX
+SEQ_BIAS_LEN = 8  # IXTTS_SEQ_BIAS_LEN
 
 QWEN_TOPK_MAX = 64  # IXTTS_QWEN_TOPK_MAX
 QWEN_MAX_EOS = 8
@@ -126,6 +130,8 @@ SYMBOLS = {
     "ixtts_gpt_read_probs": (C.c_int, [_P, C.c_int, _P, _P]),
     "ixtts_gpt_force_next": (C.c_int, [_P, C.c_int, C.c_int32, _P]),
     "ixtts_gpt_set_bans": (C.c_int, [_P, C.c_int, _P, C.c_int, _P, C.c_int, _P]),
+    "ixtts_gpt_set_sequence_bias": (C.c_int, [_P, C.c_int, _P, _P, _P, C.c_int, _P]),
+    "ixtts_gpt_set_forced_eos": (C.c_int, [_P, C.c_int, _P, C.c_int, _P]),
     "ixtts_gpt_latent": (C.c_int, [_P, _P, C.c_int, _P, C.c_int, _P, _P]),
     "ixtts_gpt_bench_gemv": (C.c_int, [_P, C.c_int, C.c_int, C.c_int, _P]),
     "ixtts_gpt_step_bytes": (C.c_double, [_P, C.c_int, C.c_int]),

@@ -177,4 +177,12 @@ __device__ __forceinline__ void split8_bf16x3(const float (&v)[8], uint4& ph, ui
   pl = make_uint4(pk(l[1], l[0]), pk(l[3], l[2]), pk(l[5], l[4]), pk(l[7], l[6]));
 }
 
+
+// One entry of a sequence's bias table (sequence_bias / bad_words_ids): `len` ids and the bias their completion earns.
+struct SeqBiasEntry {
+  int32_t len;
+  int32_t ids[IXTTS_SEQ_BIAS_LEN];
+  float bias;
+};
+
 }  // namespace ixtts

@@ -79,12 +79,14 @@ __device__ __forceinline__ BeamArgs beam_group_view(const BeamArgs& in, int g) {
   return a;
 }
 
-// Phase A, one workgroup per beam: log_softmax -> penalty -> n-gram / min-new-tokens / token bans -> temperature -> TopK -> TopP ->
-// MinP (min keep 2 each); the survivors go to global memory sorted by score.  (As one workgroup looping over the beams, with the TopP sums on one
+// Phase A, one workgroup per beam: log_softmax -> sequence biases / bad words -> penalty -> n-gram / min-new-tokens / token bans ->
+// forced eos -> exponential decay -> temperature -> TopK -> TopP -> MinP -> epsilon / eta cutoff (min keep 2 each) ->
+// renormalisation; the survivors go to global memory sorted by score.  (As one workgroup looping over the beams, with the TopP sums on one
 // thread, the whole step took 164 us at 3 beams.)
 __global__ __launch_bounds__(1024) void beam_cand_kernel(BeamArgs a) {
   __shared__ float red[16];
-  __shared__ TopkScratch tk;
+  __shared__ SamplerScratch scr;
+  TopkScratch& tk = scr.sel.tk;
   __shared__ float sort_v[SAMP_MAXK], ev[SAMP_MAXK], qv[SAMP_MAXK];
   __shared__ int sort_i[SAMP_MAXK];
 
@@ -129,7 +131,14 @@ __global__ __launch_bounds__(1024) void beam_cand_kernel(BeamArgs a) {
     float se = 0.f;
 #pragma unroll
     for (int i = 0; i < SAMP_PT; ++i) se += (threadIdx.x + i * 1024 < V) ? expf(vals[i] - mx) : 0.f;
-    const float lse = mx + logf(block_sum_1024(se, red));
+    float lse = mx + logf(block_sum_1024(se, red));
+    if (cfg.n_seq_bias > 0) {  // SequenceBias (and the bad words) on the log-probabilities, ahead of the penalty; the group's table, this beam's history
+#pragma unroll
+      for (int i = 0; i < SAMP_PT; ++i) vals[i] -= lse;
+      lse = 0.f;
+      seq_bias_1024<SAMP_PT>(vals, s.seq_bias + (size_t)(b / a.NB * a.NB) * IXTTS_SEQ_BIAS_MAX, min(cfg.n_seq_bias, IXTTS_SEQ_BIAS_MAX), gtok,
+                             min(st_gen, s.max_new), st_prompt, s.start, scr.sb);
+    }
     const bool no_stop = cfg.suppress_stop || st_gen < cfg.min_new_tokens;
     const unsigned int ban_mask = st_gen == 0 ? 3u : 1u;
     DBG_TS(2);
@@ -145,12 +154,24 @@ __global__ __launch_bounds__(1024) void beam_cand_kernel(BeamArgs a) {
       vals[i] = x;
     }
     if (cfg.no_repeat_ngram_size > 0) {  // NoRepeatNGram over this beam's history
-      __shared__ NgramScratch ng;
-      ngram_ban_1024<SAMP_PT>(vals, gtok, ht0, ht1, min(st_gen, s.max_new), st_prompt, cfg.no_repeat_ngram_size, s.start, ng);
+      ngram_ban_1024<SAMP_PT>(vals, gtok, ht0, ht1, min(st_gen, s.max_new), st_prompt, cfg.no_repeat_ngram_size, s.start, scr.ng);
+      __syncthreads();  // (the scan's LDS is the selects' too)
     }
-    if (cfg.typical_mass > 0.f) {  // custom processor: after the penalty, before the warpers; min_tokens_to_keep = 2 with beams
-      __shared__ TypicalScratch typ;
-      typical_filter_1024<SAMP_PT>(vals, V, cfg.typical_mass, 2, typ);
+    if (cfg.forced_eos_step > 0 && st_gen + 1 == cfg.forced_eos_step) forced_eos_1024<SAMP_PT>(vals, bans, V, ban_mask);
+    if (cfg.exp_decay_factor > 0.0 && st_gen > cfg.exp_decay_start) exp_decay_1024<SAMP_PT>(vals, s.stop, cfg.exp_decay_factor, st_gen - cfg.exp_decay_start);
+    if (cfg.typical_mass > 0.f)  // custom processor: after the penalty, before the warpers; min_tokens_to_keep = 2 with beams
+      typical_filter_1024<SAMP_PT>(vals, V, cfg.typical_mass, 2, scr.sel.typ);
+    if (cfg.renormalize_logits && !sampling) {  // LogitNormalization in beam search proper: log_softmax of the whole processed row
+      float m2 = -INFINITY;
+#pragma unroll
+      for (int i = 0; i < SAMP_PT; ++i) m2 = fmaxf(m2, vals[i]);
+      m2 = block_max_1024(m2, red);
+      float s2 = 0.f;
+#pragma unroll
+      for (int i = 0; i < SAMP_PT; ++i) s2 += vals[i] > -INFINITY ? expf(vals[i] - m2) : 0.f;
+      const float lse2 = m2 + logf(block_sum_1024(s2, red));
+#pragma unroll
+      for (int i = 0; i < SAMP_PT; ++i) vals[i] -= lse2;
     }
 #pragma unroll
     for (int i = 0; i < SAMP_PT; ++i) vals[i] *= inv_t;
@@ -162,14 +183,17 @@ __global__ __launch_bounds__(1024) void beam_cand_kernel(BeamArgs a) {
       float Z;
       int keep = sampling ? topp_wave0(sort_v, n, cfg.top_p, 2, ev, qv, &Z) : n;
       if (sampling && cfg.min_p > 0.f) keep = minp_wave0(ev, keep, cfg.min_p, 2);  // MinP: beam-sample only, after TopP
+      if (sampling && (cfg.epsilon_cutoff > 0.f || cfg.eta_cutoff > 0.f)) keep = eps_eta_wave0(sort_v, ev, keep, cfg.epsilon_cutoff, cfg.eta_cutoff, 2);
+      // LogitNormalization in beam-sample: log_softmax over the survivors
+      const float shift = (sampling && cfg.renormalize_logits && keep > 0) ? sort_v[0] + logf(seq_sum_lds(ev, keep)) : 0.f;
       const int lane = threadIdx.x;
       if (lane == 0) a.cand_n[b] = keep;
       if (lane < n) {
-        a.cand_v[b * SAMP_MAXK + lane] = sort_v[lane];
+        a.cand_v[b * SAMP_MAXK + lane] = sort_v[lane] - shift;
         a.cand_i[b * SAMP_MAXK + lane] = sort_i[lane];
       }
       if (lane + 64 < n) {
-        a.cand_v[b * SAMP_MAXK + lane + 64] = sort_v[lane + 64];
+        a.cand_v[b * SAMP_MAXK + lane + 64] = sort_v[lane + 64] - shift;
         a.cand_i[b * SAMP_MAXK + lane + 64] = sort_i[lane + 64];
       }
       DBG_TS(5);

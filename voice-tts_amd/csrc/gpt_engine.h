@@ -81,8 +81,11 @@ struct ixtts_gpt {
       *forced = nullptr;
   int32_t* tokens = nullptr;
   uint8_t* seen = nullptr;
-  uint8_t* bans = nullptr;         // [slots][V] ixtts_gpt_set_bans: bit 0 = id banned at every step, bit 1 = at the first generated token
+  uint8_t* bans = nullptr;         // [slots][V] ixtts_gpt_set_bans: bit 0 = id banned at every step, bit 1 = at the first generated token, bit 2 = forced eos id
   std::vector<uint8_t> bans_host;  // [slots][V] what set_bans stages for its async copy
+  ixtts::SeqBiasEntry* seq_bias = nullptr;        // [slots][IXTTS_SEQ_BIAS_MAX] ixtts_gpt_set_sequence_bias: the table of each sequence
+  std::vector<ixtts::SeqBiasEntry> seq_bias_host;  // its staging copy
+  std::vector<int> seq_bias_n;              // [slots] entries that count (0 after a prefill); rides to the device in the slot's sampler cfg
   // sampler settings and random stream of every slot, at fixed device addresses (the captured step graphs read them in place;
   // each decode call refreshes them with an async copy on its stream).  Beam mode: group g's cfg sits at each of its slots.
   ixtts_sampler_cfg* d_samp = nullptr;  // [MAXB]

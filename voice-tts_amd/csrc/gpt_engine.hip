@@ -252,6 +252,7 @@ static SamplerState make_sampler_state(ixtts_gpt* h) {
   s.logits = h->logits;
   s.seen = h->seen;
   s.bans = h->bans;
+  s.seq_bias = h->seq_bias;
   s.tokens = h->tokens;
   s.gen_count = h->gen_count;
   s.cur_len = h->cur_len;
@@ -523,6 +524,7 @@ extern "C" int ixtts_gpt_create(ixtts_gpt** out, const ixtts_gpt_cfg* c) {
   h->scratch_floats = (size_t)FF * D;
   ok &= hipMalloc(&h->scratch, h->scratch_floats * 4) == hipSuccess;
   ok &= hipMalloc(&h->bans, (size_t)S * V) == hipSuccess;  // (after everything older: no other buffer's address moves)
+  ok &= hipMalloc(&h->seq_bias, (size_t)S * IXTTS_SEQ_BIAS_MAX * sizeof(SeqBiasEntry)) == hipSuccess;
   if (!ok) return fail("state");
   hipMemset(h->cur_len, 0, S * 4);
   hipMemset(h->gen_count, 0, S * 4);
@@ -533,6 +535,9 @@ extern "C" int ixtts_gpt_create(ixtts_gpt** out, const ixtts_gpt_cfg* c) {
   hipMemset(h->seen, 0, (size_t)S * V);
   hipMemset(h->bans, 0, (size_t)S * V);
   h->bans_host.assign((size_t)S * V, 0);
+  hipMemset(h->seq_bias, 0, (size_t)S * IXTTS_SEQ_BIAS_MAX * sizeof(SeqBiasEntry));
+  h->seq_bias_host.assign((size_t)S * IXTTS_SEQ_BIAS_MAX, SeqBiasEntry{});
+  h->seq_bias_n.assign(S, 0);
   hipMemset(h->logits, 0, (size_t)S * V * 4);
   {  // every beam group starts parked (done): a group below a stepping one that was never begun is a no-op in the beam kernels
     int ones[MAXG];
@@ -772,6 +777,8 @@ extern "C" int ixtts_gpt_prefill(ixtts_gpt* h, int b, const float* embeds, int n
   IX_HIP(hipMemsetAsync(h->seen + (size_t)b * V + 1, 1, 1, st));
   IX_HIP(hipMemsetAsync(h->seen + (size_t)b * V + h->cfg.start_mel_token, 1, 1, st));
   IX_HIP(hipMemsetAsync(h->bans + (size_t)b * V, 0, V, st));  // a refilled slot inherits no bans: ixtts_gpt_set_bans comes after the prefill
+  memset(h->bans_host.data() + (size_t)b * V, 0, V);           // (nor forced ids, which set_bans and set_forced_eos keep for each other)
+  h->seq_bias_n[b] = 0;                                        // nor a bias table: the count rides in the sampler cfg of the next decode call
   IX_HIP(hipMemsetAsync(h->gen_count + b, 0, 4, st));
   IX_HIP(hipMemsetAsync(h->finished + b, 0, 4, st));
   IX_HIP(hipMemsetAsync(h->forced + b, 0xff, 4, st));
@@ -805,10 +812,57 @@ extern "C" int ixtts_gpt_set_bans(ixtts_gpt* h, int slot, const int32_t* always_
   for (int i = 0; i < n_always; ++i) IX_ARG(always_host[i] >= 0 && always_host[i] < V, "gpt_set_bans: slot %d: suppressed id %d outside 0..%d", slot, always_host[i], V - 1);
   for (int i = 0; i < n_first; ++i) IX_ARG(first_host[i] >= 0 && first_host[i] < V, "gpt_set_bans: slot %d: begin-suppressed id %d outside 0..%d", slot, first_host[i], V - 1);
   uint8_t* stage = h->bans_host.data() + (size_t)slot * V;
-  memset(stage, 0, V);
+  for (int v = 0; v < V; ++v) stage[v] &= 4u;  // (bit 2 is ixtts_gpt_set_forced_eos's)
   for (int i = 0; i < n_always; ++i) stage[always_host[i]] |= 1u;
   for (int i = 0; i < n_first; ++i) stage[first_host[i]] |= 2u;
   IX_HIP(hipMemcpyAsync(h->bans + (size_t)slot * V, stage, V, hipMemcpyHostToDevice, (hipStream_t)stream));
+  return IXTTS_OK;
+}
+
+// forced_eos_token_id of the sequence in `slot`: bit 2 of the same flag bytes.
+extern "C" int ixtts_gpt_set_forced_eos(ixtts_gpt* h, int slot, const int32_t* ids_host, int n, void* stream) {
+  NEED_READY(h, "gpt_set_forced_eos");
+  IX_ARG(slot >= 0 && slot < h->cfg.max_batch, "gpt_set_forced_eos: slot %d out of range", slot);
+  IX_ARG(n >= 0 && (ids_host || n == 0), "gpt_set_forced_eos: slot %d: bad id list", slot);
+  const int V = h->V;
+  for (int i = 0; i < n; ++i) IX_ARG(ids_host[i] >= 0 && ids_host[i] < V, "gpt_set_forced_eos: slot %d: forced id %d outside 0..%d", slot, ids_host[i], V - 1);
+  uint8_t* stage = h->bans_host.data() + (size_t)slot * V;
+  for (int v = 0; v < V; ++v) stage[v] &= 3u;
+  for (int i = 0; i < n; ++i) stage[ids_host[i]] |= 4u;
+  IX_HIP(hipMemcpyAsync(h->bans + (size_t)slot * V, stage, V, hipMemcpyHostToDevice, (hipStream_t)stream));
+  return IXTTS_OK;
+}
+
+// sequence_bias / bad_words_ids of the sequence in `slot`: the table goes down the caller's stream, its length into the sampler
+// cfg of every later decode call (upload_sampler), where the kernels find it without a load of its own.
+extern "C" int ixtts_gpt_set_sequence_bias(ixtts_gpt* h, int slot, const int32_t* ids_flat_host, const int32_t* lens_host, const float* biases_host, int n,
+                                           void* stream) {
+  NEED_READY(h, "gpt_set_sequence_bias");
+  IX_ARG(slot >= 0 && slot < h->cfg.max_batch, "gpt_set_sequence_bias: slot %d out of range", slot);
+  IX_ARG(n >= 0 && n <= IXTTS_SEQ_BIAS_MAX, "gpt_set_sequence_bias: slot %d: %d entries exceed IXTTS_SEQ_BIAS_MAX = %d", slot, n, IXTTS_SEQ_BIAS_MAX);
+  IX_ARG(n == 0 || (ids_flat_host && lens_host && biases_host), "gpt_set_sequence_bias: slot %d: null table", slot);
+  const int V = h->V;
+  SeqBiasEntry* stage = h->seq_bias_host.data() + (size_t)slot * IXTTS_SEQ_BIAS_MAX;
+  int at = 0;
+  for (int e = 0; e < n; ++e) {  // (all of it checked before anything is written)
+    IX_ARG(lens_host[e] >= 1 && lens_host[e] <= IXTTS_SEQ_BIAS_LEN, "gpt_set_sequence_bias: slot %d: entry %d holds %d ids (1..IXTTS_SEQ_BIAS_LEN = %d)", slot, e,
+           lens_host[e], IXTTS_SEQ_BIAS_LEN);
+    IX_ARG(biases_host[e] == biases_host[e], "gpt_set_sequence_bias: slot %d: entry %d: bias is NaN", slot, e);
+    for (int j = 0; j < lens_host[e]; ++j)
+      IX_ARG(ids_flat_host[at + j] >= 0 && ids_flat_host[at + j] < V, "gpt_set_sequence_bias: slot %d: entry %d: id %d outside 0..%d", slot, e, ids_flat_host[at + j], V - 1);
+    at += lens_host[e];
+  }
+  at = 0;
+  for (int e = 0; e < n; ++e) {
+    SeqBiasEntry en{};
+    en.len = lens_host[e];
+    for (int j = 0; j < en.len; ++j) en.ids[j] = ids_flat_host[at + j];
+    en.bias = biases_host[e];
+    stage[e] = en;
+    at += en.len;
+  }
+  if (n) IX_HIP(hipMemcpyAsync(h->seq_bias + (size_t)slot * IXTTS_SEQ_BIAS_MAX, stage, (size_t)n * sizeof(SeqBiasEntry), hipMemcpyHostToDevice, (hipStream_t)stream));
+  h->seq_bias_n[slot] = n;
   return IXTTS_OK;
 }
 
@@ -846,10 +900,12 @@ static int pick_bucket(const ixtts_gpt* h, int ctx) {
 // Sampler settings and random streams to their fixed device addresses, ahead of the graph launches on the same stream (the
 // captured graphs read them in place: no configuration is baked into a graph).  `per` == nullptr: the uniform case -- `*uni` at
 // EVERY slot of the engine, stream = slot index.
-static int upload_sampler(ixtts_gpt* h, int n, const ixtts_sampler_cfg* uni, const ixtts_sampler_cfg* per, const uint32_t* streams, hipStream_t st) {
+// `group`: slots per beam group (1 without beams) -- a slot's cfg carries the length of the bias table of its group's first slot.
+static int upload_sampler(ixtts_gpt* h, int n, const ixtts_sampler_cfg* uni, const ixtts_sampler_cfg* per, const uint32_t* streams, hipStream_t st, int group = 1) {
   const int fill = per ? n : h->cfg.max_batch;
   for (int b = 0; b < fill; ++b) {
     h->samp_host[b] = per ? per[b] : *uni;
+    h->samp_host[b].n_seq_bias = h->seq_bias_n[b / group * group];
     h->rng_host[b] = (per && streams) ? streams[b] : (unsigned int)b;
   }
   IX_HIP(hipMemcpyAsync(h->d_samp, h->samp_host, (size_t)fill * sizeof(ixtts_sampler_cfg), hipMemcpyHostToDevice, st));
@@ -862,6 +918,11 @@ static const char* constraint_error(const ixtts_sampler_cfg& c) {
   if (c.min_new_tokens < 0) return "min_new_tokens must be >= 0";
   if (c.no_repeat_ngram_size < 0 || c.no_repeat_ngram_size > IXTTS_NGRAM_MAX) return "no_repeat_ngram_size outside 0..IXTTS_NGRAM_MAX";
   if (!(c.min_p >= 0.f && c.min_p <= 1.f)) return "min_p outside 0..1";
+  if (c.exp_decay_start < 0 || !(c.exp_decay_factor >= 0.0) || c.exp_decay_factor > 1.7e308)
+    return "exponential decay: start_index must be >= 0 and the factor positive and finite";
+  if (!(c.epsilon_cutoff >= 0.f && c.epsilon_cutoff < 1.f)) return "epsilon_cutoff outside [0, 1)";
+  if (!(c.eta_cutoff >= 0.f && c.eta_cutoff < 1.f)) return "eta_cutoff outside [0, 1)";
+  if (c.forced_eos_step < 0) return "forced_eos_step must be >= 0";
   return nullptr;
 }
 
@@ -1043,9 +1104,9 @@ static int beam_decode_impl(ixtts_gpt* h, int n_groups, int n_steps, const ixtts
   if (per) {  // group g's entry at each of its slots (gpt_beam.hip reads it there; beam_read takes its length penalty from the first)
     ixtts_sampler_cfg slots[MAXB];
     for (int b = 0; b < n_groups * nb; ++b) slots[b] = per[b / nb];
-    IX_TRY(upload_sampler(h, n_groups * nb, nullptr, slots, nullptr, st));  // (copied into h->samp_host before the async copy reads it)
+    IX_TRY(upload_sampler(h, n_groups * nb, nullptr, slots, nullptr, st, nb));  // (copied into h->samp_host before the async copy reads it)
   } else {
-    IX_TRY(upload_sampler(h, 0, uni, nullptr, nullptr, st));
+    IX_TRY(upload_sampler(h, 0, uni, nullptr, nullptr, st, nb));
   }
   h->beam_groups = n_groups;
   for (int done = 0; done < n_steps;) {
@@ -1297,7 +1358,7 @@ extern "C" int ixtts_gpt_destroy(ixtts_gpt* h) {
   if (h->cap_stream) hipStreamDestroy(h->cap_stream);
   if (h->arena_borrowed) h->arena = nullptr;  // the owner frees it
   void* ptrs[] = {h->arena, h->stage, h->kc, h->vc, h->h, h->q, h->ff, h->att, h->part, h->logits, h->rowbuf, h->cur_len, h->gen_count,
-                  h->prompt_len, h->valid_from, h->finished, h->forced, h->tokens, h->seen, h->bans, h->d_samp, h->d_rng, h->probs, h->scratch, h->beam_scores, h->hyp_score, h->hyp_worst, h->beam_src, h->hyp_len,
+                  h->prompt_len, h->valid_from, h->finished, h->forced, h->tokens, h->seen, h->bans, h->seq_bias, h->d_samp, h->d_rng, h->probs, h->scratch, h->beam_scores, h->hyp_score, h->hyp_worst, h->beam_src, h->hyp_len,
                   h->n_hyp, h->beam_done, h->beam_forced_flag, h->beam_forced, h->hyp_tok, h->beam_cand_v, h->beam_cand_i, h->beam_cand_n, h->beam_lcp, h->beam_stream,
                   h->rx, h->rxn, h->rq, h->ratt, h->rff, h->h2, h->wprx, h->mlp_part, h->mlp_ctr, h->fold_overflow};
   for (void* p : ptrs)

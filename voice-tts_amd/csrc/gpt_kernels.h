@@ -1339,7 +1339,8 @@ struct SamplerState {
   // (what the constraints added sits behind the older fields: those keep their places among the preloaded kernel arguments)
   int start;            // start_mel_token: the last id of the fake prompt (the n-gram ban's history)
   const uint8_t* bans;  // [slots][V] ixtts_gpt_set_bans: bit 0 = id banned at every step, bit 1 = at the first generated token (beam
-                        // mode: the group's first slot holds the group's)
+                        // mode: the group's first slot holds the group's); bit 2 = a forced eos id (ixtts_gpt_set_forced_eos)
+  const SeqBiasEntry* seq_bias;  // [slots][IXTTS_SEQ_BIAS_MAX] ixtts_gpt_set_sequence_bias; cfg.n_seq_bias of them count
 };
 
 // float -> uint key with the same ordering (ascending)
@@ -1832,18 +1833,149 @@ __device__ __forceinline__ void ngram_ban_1024(float (&vals)[PT], const int32_t*
   }
 }
 
+// SequenceBiasLogitsProcessor and NoBadWordsLogitsProcessor (a bias of -inf) over the n entries of the sequence's table.  Wave 0
+// tests them all at once: lane e compares entry e's leading ids with the history's tail, read from `gtok` itself (the fake
+// prompt in closed form, as above: position k < -1 holds 1, k == -1 the start token); an entry longer than the history P + G is
+// ignored, a one-id entry always matches.  The matches go to the owning threads through LDS; biases that end in one id add up
+// among themselves first, as HF builds its bias row, and then join the score.  x[i] belongs to id threadIdx.x + i * 1024.
+struct SeqBiasScratch {
+  int32_t id[IXTTS_SEQ_BIAS_MAX];  // the id entry e biases at this step, or -1
+  float bias[IXTTS_SEQ_BIAS_MAX];
+};
+static_assert(IXTTS_SEQ_BIAS_MAX == 64, "seq_bias_1024 holds one entry per lane of wave 0");
+
+// Call with the whole workgroup and a workgroup-uniform 1 <= n <= IXTTS_SEQ_BIAS_MAX; synchronised on return (sb may be reused).
+template <int PT>
+__device__ __forceinline__ void seq_bias_1024(float (&x)[PT], const SeqBiasEntry* tab, int n, const int32_t* gtok, int G, int P, int start_tok,
+                                              SeqBiasScratch& sb) {
+  const int t = threadIdx.x;
+  if (t < IXTTS_SEQ_BIAS_MAX) {
+    int id = -1;
+    float bias = 0.f;
+    if (t < n) {
+      const SeqBiasEntry e = tab[t];
+      const int L = e.len;
+      bool match = L >= 1 && L <= IXTTS_SEQ_BIAS_LEN && L <= P + G;
+      int last = -1;
+#pragma unroll
+      for (int j = 0; j < IXTTS_SEQ_BIAS_LEN; ++j) {
+        if (j == L - 1) last = e.ids[j];
+        if (match && j < L - 1) {
+          const int k = G - (L - 1) + j;  // the history position id j must sit at
+          const int32_t hk = k < -1 ? 1 : k == -1 ? start_tok : gtok[k];
+          match = hk == e.ids[j];
+        }
+      }
+      if (match) {
+        id = last;
+        bias = e.bias;
+      }
+    }
+    sb.id[t] = id;
+    sb.bias[t] = bias;
+  }
+  __syncthreads();
+  float add[PT];
+#pragma unroll
+  for (int i = 0; i < PT; ++i) add[i] = 0.f;
+  for (int j = 0; j < n; ++j) {
+    const int id = sb.id[j];
+    if (id >= 0 && (id & 1023) == t) {
+      const float bj = sb.bias[j];
+#pragma unroll
+      for (int i = 0; i < PT; ++i)
+        if (i == (id >> 10)) add[i] += bj;
+    }
+  }
+#pragma unroll
+  for (int i = 0; i < PT; ++i) x[i] += add[i];
+  __syncthreads();
+}
+
+// ForcedEOSTokenLogitsProcessor at its step: every score -inf, the forced ids (bit 2 of the slot's flag bytes) 0 -- and
+// SuppressTokens / SuppressTokensAtBegin, which follow it in the chain and rode in the penalty loop before it, once more.  The
+// flags are read again here: the step comes once in a sequence's life, and the registers that held them are long free.
+template <int PT>
+__device__ __forceinline__ void forced_eos_1024(float (&vals)[PT], const uint8_t* flags, int V, unsigned int ban_mask) {
+#pragma unroll
+  for (int i = 0; i < PT; ++i) {
+    const int v = threadIdx.x + i * 1024;
+    const unsigned int f = flags[min(v, V - 1)];
+    vals[i] = (v < V && (f & 4u) && !(f & ban_mask)) ? 0.f : -INFINITY;
+  }
+}
+
+// ExponentialDecayLengthPenalty past its start: score[stop] += |score[stop]| * (factor ** n - 1), n = generated - start_index >= 1.
+// HF takes the power in Python floats and multiplies an fp32 tensor by it: fp64 pow on the one lane that owns the stop id, the
+// factor rounded to fp32, then an fp32 product and an fp32 sum (no fused multiply-add).  A stop score of -inf stays -inf.
+template <int PT>
+__device__ __forceinline__ void exp_decay_1024(float (&vals)[PT], int stop, double factor, int n) {
+  if ((int)threadIdx.x == (stop & 1023)) {
+    const float m = (float)(pow(factor, (double)n) - 1.0);
+#pragma unroll
+    for (int i = 0; i < PT; ++i)
+      if (i == (stop >> 10) && vals[i] > -INFINITY) vals[i] = __fadd_rn(vals[i], __fmul_rn(fabsf(vals[i]), m));
+  }
+}
+
+// EpsilonLogitsWarper, then EtaLogitsWarper (either off at 0), over the `keep` survivors whose scores sit in sort_v and whose
+// softmax numerators in ev (both descending), by wave 0 alone: a survivor goes when its probability over the survivors is below
+// the threshold -- epsilon, or min(eta, sqrt(eta) * exp(-entropy of that softmax)) -- unless its score reaches the min_keep-th
+// best.  Eta looks at what epsilon left.  Those that stay are a prefix: returns its length.
+__device__ __forceinline__ int eps_eta_wave0(const float* sort_v, const float* ev, int keep, float epsilon, float eta, int min_keep) {
+  const int lane = threadIdx.x;
+  if (keep <= 0) return keep;
+  const float vk = sort_v[min(min_keep, keep) - 1];
+  const float v0 = sort_v[lane], v1 = sort_v[lane + 64], e0 = ev[lane], e1 = ev[lane + 64];
+  if (epsilon > 0.f) {
+    const float Z = seq_sum_lds(ev, keep);
+    const bool k0 = lane < keep && !(e0 / Z < epsilon && v0 < vk);
+    const bool k1 = lane + 64 < keep && !(e1 / Z < epsilon && v1 < vk);
+    keep = (int)__popcll(__ballot(k0)) + (int)__popcll(__ballot(k1));
+  }
+  if (eta > 0.f) {
+    const float Z = seq_sum_lds(ev, keep);
+    const float lz = logf(Z), mx = sort_v[0];
+    float h = lane < keep ? (e0 / Z) * (v0 - mx - lz) : 0.f;  // p * log p
+    h += lane + 64 < keep ? (e1 / Z) * (v1 - mx - lz) : 0.f;
+    const float thr = fminf(eta, sqrtf(eta) * expf(wave_sum(h)));
+    const bool k0 = lane < keep && !(e0 / Z < thr && v0 < vk);
+    const bool k1 = lane + 64 < keep && !(e1 / Z < thr && v1 < vk);
+    keep = (int)__popcll(__ballot(k0)) + (int)__popcll(__ballot(k1));
+  }
+  return keep;
+}
+
+// What the stages of one sampling workgroup keep in LDS.  The table match, the n-gram scan and the pair (top-k select, typical /
+// whole-vocabulary sums) are never live at the same time -- each ends on a barrier before the next begins -- so they share one
+// piece of LDS instead of three.
+union SamplerScratch {
+  struct {
+    TopkScratch tk;
+    TypicalScratch typ;
+  } sel;
+  NgramScratch ng;
+  SeqBiasScratch sb;
+};
+
 #ifdef IXTTS_ENGINE_TU  // non-template kernels: compiled into gpt_engine.hip only
 
-// Processor chain in `_get_logits_processor` order (generation_utils.py:900-1049):
-// [suppress] -> RepetitionPenalty -> NoRepeatNGram -> MinNewTokens -> SuppressTokens -> SuppressTokensAtBegin -> [typical] ->
-// Temperature -> TopK (ties with the k-th value kept) -> TopP -> MinP -> softmax -> multinomial(1)  |  argmax when do_sample == 0.
-// The stages that only write -inf commute with the penalty, so the stop-token and ban-flag ones ride in its loop; the n-gram
-// scan, like MinP, sits behind a workgroup-uniform test of its cfg field: a slot without it executes none of it.
+// Processor chain in `_get_logits_processor` order (generation_utils.py:862-1069):
+// [suppress] -> SequenceBias -> RepetitionPenalty -> NoRepeatNGram -> NoBadWords -> MinNewTokens -> ForcedEOS ->
+// ExponentialDecayLengthPenalty -> SuppressTokens -> SuppressTokensAtBegin -> [typical] -> Temperature -> TopK (ties with the
+// k-th value kept) -> TopP -> MinP -> EpsilonCutoff -> EtaCutoff -> LogitNormalization -> softmax -> multinomial(1)  |  argmax
+// when do_sample == 0.
+// The stages that only write -inf commute with the penalty, so the stop-token and ban-flag ones ride in its loop, and the bad
+// words (biases of -inf) go onto the row with the finite biases, ahead of it; ForcedEOS, which overwrites what came before it,
+// repeats the ban flags that follow it.  LogitNormalization shifts the row by a constant, which the softmax and the argmax do not
+// see: nothing to do here.  Every stage but the penalty loop sits behind a workgroup-uniform test of a cfg field: a slot
+// without it executes none of it.
 __global__ __launch_bounds__(1024) void sampler_kernel(SamplerState s) {
   __shared__ float bv[16];
   __shared__ int bi[16];
   __shared__ int tok_s;
-  __shared__ TopkScratch tk;
+  __shared__ SamplerScratch scr;
+  TopkScratch& tk = scr.sel.tk;
   __shared__ float sort_v[SAMP_MAXK];
   __shared__ int sort_i[SAMP_MAXK];
 
@@ -1881,6 +2013,10 @@ __global__ __launch_bounds__(1024) void sampler_kernel(SamplerState s) {
   // MinNewTokensLengthLogitsProcessor: no stop token before min_new_tokens tokens; the ban flags: bit 0 always, bit 1 at the first token
   const bool no_stop = cfg.suppress_stop || st_gen < cfg.min_new_tokens;
   const unsigned int ban_mask = st_gen == 0 ? 3u : 1u;
+  // SequenceBias (and the bad words): onto the raw row, the penalty looks at the sign of the biased score
+  if (cfg.n_seq_bias > 0)
+    seq_bias_1024<SAMP_PT>(raw, s.seq_bias + (size_t)slot * IXTTS_SEQ_BIAS_MAX, min(cfg.n_seq_bias, IXTTS_SEQ_BIAS_MAX), gtok, min(st_gen, s.max_new),
+                           st_prompt, s.start, scr.sb);
   float vals[SAMP_PT];
 #pragma unroll
   for (int i = 0; i < SAMP_PT; ++i) {
@@ -1894,13 +2030,13 @@ __global__ __launch_bounds__(1024) void sampler_kernel(SamplerState s) {
     vals[i] = x;
   }
   if (cfg.no_repeat_ngram_size > 0) {
-    __shared__ NgramScratch ng;
-    ngram_ban_1024<SAMP_PT>(vals, gtok, ht0, ht1, min(st_gen, s.max_new), st_prompt, cfg.no_repeat_ngram_size, s.start, ng);
+    ngram_ban_1024<SAMP_PT>(vals, gtok, ht0, ht1, min(st_gen, s.max_new), st_prompt, cfg.no_repeat_ngram_size, s.start, scr.ng);
+    __syncthreads();  // (the scan's LDS is the selects' too)
   }
-  if (cfg.typical_mass > 0.f) {  // custom processor of inference_speech(typical_sampling=True): after the penalty, before the warpers
-    __shared__ TypicalScratch typ;
-    typical_filter_1024<SAMP_PT>(vals, s.V, cfg.typical_mass, 1, typ);
-  }
+  if (cfg.forced_eos_step > 0 && st_gen + 1 == cfg.forced_eos_step) forced_eos_1024<SAMP_PT>(vals, bans, s.V, ban_mask);
+  if (cfg.exp_decay_factor > 0.0 && st_gen > cfg.exp_decay_start) exp_decay_1024<SAMP_PT>(vals, s.stop, cfg.exp_decay_factor, st_gen - cfg.exp_decay_start);
+  if (cfg.typical_mass > 0.f)  // custom processor of inference_speech(typical_sampling=True): after the penalty, before the warpers
+    typical_filter_1024<SAMP_PT>(vals, s.V, cfg.typical_mass, 1, scr.sel.typ);
   float best = -INFINITY;
   int besti = 0x7fffffff;
 #pragma unroll
@@ -1947,7 +2083,7 @@ __global__ __launch_bounds__(1024) void sampler_kernel(SamplerState s) {
   if (general) {
     // ---- top_k = 0 ("off": HF builds no TopK warper), top_k > 128 or >= V: no survivor list -- the filters become thresholds on
     // the whole vocabulary and the draw an inverse CDF over it.  TopK: the k-th largest key by the same 4-pass radix select.
-    __shared__ TypicalScratch gs;
+    TypicalScratch& gs = scr.sel.typ;  // (the typical filter is through with it)
     __shared__ int pick_s;
     if (cfg.top_k > 0 && cfg.top_k < s.V) {
       unsigned int key[SAMP_PT];
@@ -2035,6 +2171,31 @@ __global__ __launch_bounds__(1024) void sampler_kernel(SamplerState s) {
       for (int i = 0; i < SAMP_PT; ++i)
         if (e[i] / Zk < thr) e[i] = 0.f;
     }
+    if (cfg.epsilon_cutoff > 0.f) {
+      // ---- EpsilonCutoff: probabilities over what is left; below epsilon goes, a score that reaches the largest never
+      float sk = 0.f;
+#pragma unroll
+      for (int i = 0; i < SAMP_PT; ++i) sk += e[i];
+      const float Zk = block_sum_1024(sk, gs.red);
+#pragma unroll
+      for (int i = 0; i < SAMP_PT; ++i)
+        if (e[i] / Zk < cfg.epsilon_cutoff && vals[i] < mx) e[i] = 0.f;
+    }
+    if (cfg.eta_cutoff > 0.f) {
+      // ---- EtaCutoff: the same with min(eta, sqrt(eta) * exp(-H)), H the entropy of that distribution (removed ids add 0)
+      float sk = 0.f;
+#pragma unroll
+      for (int i = 0; i < SAMP_PT; ++i) sk += e[i];
+      const float Zk = block_sum_1024(sk, gs.red);
+      const float lz = logf(Zk);
+      float hh = 0.f;
+#pragma unroll
+      for (int i = 0; i < SAMP_PT; ++i) hh += e[i] > 0.f ? (e[i] / Zk) * (vals[i] - mx - lz) : 0.f;  // p * log p
+      const float thr = fminf(cfg.eta_cutoff, sqrtf(cfg.eta_cutoff) * expf(block_sum_1024(hh, gs.red)));
+#pragma unroll
+      for (int i = 0; i < SAMP_PT; ++i)
+        if (e[i] / Zk < thr && vals[i] < mx) e[i] = 0.f;
+    }
     // ---- multinomial(1): inverse CDF over the kept tokens in (thread, register) order -- a fixed order, so a fixed stream
     float mine = 0.f;
 #pragma unroll
@@ -2093,6 +2254,7 @@ __global__ __launch_bounds__(1024) void sampler_kernel(SamplerState s) {
       float Z;
       int keep = topp_wave0(sort_v, n, cfg.top_p, 1, ev, qv, &Z);
       if (cfg.min_p > 0.f) keep = minp_wave0(ev, keep, cfg.min_p, 1);
+      if (cfg.epsilon_cutoff > 0.f || cfg.eta_cutoff > 0.f) keep = eps_eta_wave0(sort_v, ev, keep, cfg.epsilon_cutoff, cfg.eta_cutoff, 1);
       const float Zk = seq_sum_lds(ev, keep);
       const float u = uniform01(cfg.seed, st_stream, (unsigned int)st_gen) * Zk;
       float c = 0.f;

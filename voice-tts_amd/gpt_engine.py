@@ -85,6 +85,103 @@ def resolve_min_length(cfg, prompt_len):
     return out
 
 
+PROCESSOR_KEYS = ("sequence_bias", "bad_words_ids", "forced_eos_token_id", "exponential_decay_length_penalty", "epsilon_cutoff", "eta_cutoff",
+                  "renormalize_logits")
+
+
+def _is_id(t):
+    return isinstance(t, (int, np.integer)) and not isinstance(t, bool) and t >= 0
+
+
+def sequence_bias_table(sequence_bias=None, bad_words_ids=None, eos_token_id=None, vocab=None):
+    """`sequence_bias` ({tuple(ids): float} or HF's list form [[[ids], bias], ...]) and `bad_words_ids` ([[ids], ...]) of HF
+    `generate()` -> the sequence's table for `ixtts_gpt_set_sequence_bias`: a list of (ids tuple, bias), the biased sequences
+    first, then the bad words with a bias of -inf (entries equal to `[eos_token_id]` dropped, as NoBadWordsLogitsProcessor
+    drops them).  None = not given.  Checked as HF checks them (SequenceBiasLogitsProcessor._validate_arguments,
+    NoBadWordsLogitsProcessor._validate_arguments), ids against `vocab` too, and against the table's limits: ValueError."""
+    table = []
+    if sequence_bias is not None:
+        sb = sequence_bias
+        if not isinstance(sb, (dict, list)) or len(sb) == 0:
+            raise ValueError(f"`sequence_bias` has to be a non-empty dictionary, or non-empty list of lists but is {sb}.")
+        if isinstance(sb, list):
+            for item in sb:
+                if not (isinstance(item, (list, tuple)) and len(item) == 2 and isinstance(item[0], (list, tuple))):
+                    raise ValueError(f"Each element in `sequence_bias` has to be a list of a non-empty list of ids and a float, but is {item}.")
+            sb = {tuple(item[0]): item[1] for item in sb}
+        for ids, bias in sb.items():
+            if not isinstance(ids, tuple) or len(ids) == 0 or not all(_is_id(t) for t in ids):
+                raise ValueError(f"Each sequence in `sequence_bias` has to be a non-empty tuple of non-negative integers, but is {ids}.")
+            if not isinstance(bias, (float, np.floating)) or bias != bias:
+                raise ValueError(f"`sequence_bias` has to hold floats as biases, but {ids} has {bias!r}.")
+            table.append((tuple(int(t) for t in ids), float(bias)))
+    if bad_words_ids is not None:
+        bw = bad_words_ids
+        if not isinstance(bw, list) or len(bw) == 0:
+            raise ValueError(f"`bad_words_ids` has to be a non-empty list, but is {bw}.")
+        if any(not isinstance(w, list) for w in bw):
+            raise ValueError(f"`bad_words_ids` has to be a list of lists, but is {bw}.")
+        if any(len(w) == 0 or not all(_is_id(t) for t in w) for w in bw):
+            raise ValueError(f"Each list in `bad_words_ids` has to be a non-empty list of non-negative integers, but is {bw}.")
+        eos = eos_token_id.tolist() if torch.is_tensor(eos_token_id) else eos_token_id
+        eos = [] if eos is None else [int(e) for e in np.asarray(eos).reshape(-1)]
+        words = {tuple(int(t) for t in w): None for w in bw if all(list(w) != [e] for e in eos)}
+        table.extend((w, float("-inf")) for w in words)
+    if len(table) > _lib.SEQ_BIAS_MAX:
+        raise ValueError(f"`sequence_bias` and `bad_words_ids` hold {len(table)} sequences together: the table of a sequence holds at most "
+                         f"IXTTS_SEQ_BIAS_MAX = {_lib.SEQ_BIAS_MAX}")
+    for ids, _ in table:
+        if len(ids) > _lib.SEQ_BIAS_LEN:
+            raise ValueError(f"sequence {ids} holds {len(ids)} ids: at most IXTTS_SEQ_BIAS_LEN = {_lib.SEQ_BIAS_LEN}")
+        if vocab is not None and any(t >= vocab for t in ids):
+            raise ValueError(f"sequence {ids}: id outside 0..{int(vocab) - 1}")
+    return table
+
+
+def generation_processors(kwargs, eos_token_id, vocab=None):
+    """The other processor keywords of HF `generate()` out of `kwargs` (popped; None counts as not given) -- `sequence_bias`,
+    `bad_words_ids`, `forced_eos_token_id`, `exponential_decay_length_penalty`, `epsilon_cutoff`, `eta_cutoff`,
+    `renormalize_logits` -> (cfg, state).  `cfg` holds the engine's keyword names `exp_decay_start`, `exp_decay_factor`,
+    `epsilon_cutoff`, `eta_cutoff`, `renormalize_logits` -- only those that were given and are not off.  `state` is what belongs
+    to the sequence's slot, or None: a dict with `table` (`sequence_bias_table`'s list, for `set_sequence_bias`) and `forced_eos`
+    (the forced ids, for `set_forced_eos`; the step they are forced at, `forced_eos_step` = the sequence's own max_new, is the
+    caller's to add to the cfg).  `vocab`: ids must lie below it.  A bad value raises ValueError, as HF's classes do."""
+    got = {k: kwargs.pop(k) for k in PROCESSOR_KEYS if k in kwargs}
+    got = {k: v for k, v in got.items() if v is not None}
+    cfg = {}
+    for k in ("epsilon_cutoff", "eta_cutoff"):
+        if k in got:
+            v = float(got[k])
+            if not 0.0 <= v < 1.0:
+                raise ValueError(f"`{k}` has to be a float >= 0 (off) and < 1, but is {got[k]}")
+            if v > 0.0:
+                cfg[k] = v
+    if "exponential_decay_length_penalty" in got:
+        pen = got["exponential_decay_length_penalty"]
+        if not isinstance(pen, (tuple, list)) or len(pen) != 2:
+            raise ValueError(f"`exponential_decay_length_penalty` has to be (start_index, decay_factor), but is {pen}")
+        start, factor = pen
+        if not _is_id(start):
+            raise ValueError(f"`exponential_decay_length_penalty`: start_index has to be an integer >= 0, but is {start!r}")
+        if isinstance(factor, bool) or not isinstance(factor, (int, float, np.integer, np.floating)) or not 0.0 < float(factor) < float("inf"):
+            raise ValueError(f"`exponential_decay_length_penalty`: decay_factor has to be a finite number > 0, but is {factor!r}")
+        cfg["exp_decay_start"], cfg["exp_decay_factor"] = int(start), float(factor)
+    if got.get("renormalize_logits") is True:  # (`is True`, as generation_utils.py:1068 tests it)
+        cfg["renormalize_logits"] = True
+    table = sequence_bias_table(got.get("sequence_bias"), got.get("bad_words_ids"), eos_token_id, vocab)
+    forced = ()
+    if "forced_eos_token_id" in got:
+        f = got["forced_eos_token_id"]
+        f = [f] if isinstance(f, (int, np.integer)) and not isinstance(f, bool) else f
+        if not isinstance(f, (list, tuple)) or len(f) == 0 or not all(_is_id(t) for t in f):
+            raise ValueError(f"`forced_eos_token_id` has to be a non-negative integer or a non-empty list of them, but is {got['forced_eos_token_id']}")
+        if vocab is not None and any(t >= vocab for t in f):
+            raise ValueError(f"`forced_eos_token_id` {list(f)}: id outside 0..{int(vocab) - 1}")
+        forced = tuple(int(t) for t in f)
+    state = dict(table=table, forced_eos=forced) if table or forced else None
+    return cfg, state
+
+
 class GptEngine:
     def __init__(self, cfg=None, dtype="f32", max_seq=2048, max_batch=1, device=None):
         code = _dtype_code(dtype)
@@ -162,20 +259,40 @@ class GptEngine:
         _lib.check(rc, "ixtts_gpt_prefill")
         self._keep = e  # keep alive until the stream has consumed it
 
+    @staticmethod
+    def _sampler_cfg(v):
+        """One SamplerCfg from a dict with every keyword of `decode()` / `beam_decode()` (`length_penalty` may be missing)."""
+        return _lib.SamplerCfg(v["repetition_penalty"], v["temperature"], int(v["top_k"]), v["top_p"], int(bool(v["do_sample"])),
+                               int(bool(v["suppress_stop"])), int(v["seed"]), float(v["typical_mass"]), float(v.get("length_penalty", 0.0)),
+                               int(v["min_new_tokens"]), int(v["no_repeat_ngram_size"]), float(v["min_p"]),
+                               int(v["exp_decay_start"]), float(v["exp_decay_factor"]), float(v["epsilon_cutoff"]), float(v["eta_cutoff"]),
+                               int(bool(v["renormalize_logits"])), int(v["forced_eos_step"]), 0)
+
     def decode(self, n_active, n_steps, repetition_penalty=10.0, temperature=1.0, top_k=0, top_p=1.0,
-               do_sample=False, suppress_stop=False, seed=0, typical_mass=0.0, min_new_tokens=0, no_repeat_ngram_size=0, min_p=0.0):
+               do_sample=False, suppress_stop=False, seed=0, typical_mass=0.0, min_new_tokens=0, no_repeat_ngram_size=0, min_p=0.0,
+               exp_decay_start=0, exp_decay_factor=0.0, epsilon_cutoff=0.0, eta_cutoff=0.0, renormalize_logits=False, forced_eos_step=0):
         """`min_new_tokens`, `no_repeat_ngram_size`, `min_p`: the processors HF `generate()` builds from the keywords of the same
-        names (0 = off; `min_p` acts when sampling only); the two id lists of the family belong to the slot: `set_bans`."""
-        sc = _lib.SamplerCfg(repetition_penalty, temperature, top_k, top_p, int(do_sample), int(suppress_stop), seed, float(typical_mass), 0.0,
-                             int(min_new_tokens), int(no_repeat_ngram_size), float(min_p))
+        names (0 = off; `min_p` acts when sampling only); the two id lists of the family belong to the slot: `set_bans`.
+        `exp_decay_start`, `exp_decay_factor`: `exponential_decay_length_penalty=(start_index, factor)` (factor 0 = off);
+        `epsilon_cutoff`, `eta_cutoff`: the two truncation samplers (sampling only); `renormalize_logits` (no effect without
+        beams); `forced_eos_step=N`: the N-th generated token is one of the slot's forced ids (`set_forced_eos`; HF's
+        `forced_eos_token_id` with N = max_length - prompt length).  The table of `sequence_bias` / `bad_words_ids` belongs to the
+        slot: `set_sequence_bias`."""
+        sc = self._sampler_cfg(dict(repetition_penalty=repetition_penalty, temperature=temperature, top_k=top_k, top_p=top_p, do_sample=do_sample,
+                                    suppress_stop=suppress_stop, seed=seed, typical_mass=typical_mass, min_new_tokens=min_new_tokens,
+                                    no_repeat_ngram_size=no_repeat_ngram_size, min_p=min_p, exp_decay_start=exp_decay_start,
+                                    exp_decay_factor=exp_decay_factor, epsilon_cutoff=epsilon_cutoff, eta_cutoff=eta_cutoff,
+                                    renormalize_logits=renormalize_logits, forced_eos_step=forced_eos_step))
         with torch.cuda.device(self.device):
             rc = _lib.lib().ixtts_gpt_decode(self._h, n_active, n_steps, C.byref(sc), self._stream())
         _lib.check(rc, "ixtts_gpt_decode")
 
     _DECODE_KEYS = dict(repetition_penalty=10.0, temperature=1.0, top_k=0, top_p=1.0, do_sample=False, suppress_stop=False, seed=0,
-                        typical_mass=0.0, min_new_tokens=0, no_repeat_ngram_size=0, min_p=0.0)
+                        typical_mass=0.0, min_new_tokens=0, no_repeat_ngram_size=0, min_p=0.0, exp_decay_start=0, exp_decay_factor=0.0,
+                        epsilon_cutoff=0.0, eta_cutoff=0.0, renormalize_logits=False, forced_eos_step=0)
     _BEAM_KEYS = dict(repetition_penalty=10.0, temperature=0.8, top_k=30, top_p=0.8, suppress_stop=False, seed=0, typical_mass=0.0,
-                      length_penalty=0.0, do_sample=True, min_new_tokens=0, no_repeat_ngram_size=0, min_p=0.0)
+                      length_penalty=0.0, do_sample=True, min_new_tokens=0, no_repeat_ngram_size=0, min_p=0.0, exp_decay_start=0,
+                      exp_decay_factor=0.0, epsilon_cutoff=0.0, eta_cutoff=0.0, renormalize_logits=False, forced_eos_step=0)
 
     @staticmethod
     def _sampler_array(cfgs, defaults, what):
@@ -186,9 +303,7 @@ class GptEngine:
             if unknown:
                 raise TypeError(f"{what}: entry {i} has unexpected keys {sorted(unknown)}")
             v = {**defaults, **cfg}
-            arr[i] = _lib.SamplerCfg(v["repetition_penalty"], v["temperature"], int(v["top_k"]), v["top_p"], int(bool(v["do_sample"])),
-                                     int(bool(v["suppress_stop"])), int(v["seed"]), float(v["typical_mass"]), float(v.get("length_penalty", 0.0)),
-                                     int(v["min_new_tokens"]), int(v["no_repeat_ngram_size"]), float(v["min_p"]))
+            arr[i] = GptEngine._sampler_cfg(v)
         return arr
 
     def decode_slots(self, n_steps, cfgs, streams=None):
@@ -236,6 +351,52 @@ class GptEngine:
                                                self._stream())
         _lib.check(rc, "ixtts_gpt_set_bans")
 
+    def set_sequence_bias(self, slot, sequence_bias=None, bad_words_ids=None):
+        """`sequence_bias` ({tuple(ids): float} or [[[ids], bias], ...]) and `bad_words_ids` ([[ids], ...]) of the sequence in
+        `slot`, as HF `generate()` takes them -- or a table `sequence_bias_table` made already (a list of (ids tuple, bias)) as
+        `sequence_bias`.  They share one table of at most 64 sequences of at most 8 ids; a bad word equal to [stop token] is
+        dropped.  Call it after the slot's `prefill` (which clears the table) and before its first decode step; with beams, on
+        the group's first slot.  ValueError for what HF refuses and for the limits."""
+        made = isinstance(sequence_bias, list) and bad_words_ids is None and all(isinstance(e, tuple) and len(e) == 2 and isinstance(e[0], tuple) for e in sequence_bias)
+        try:
+            if made:  # (the same checks; entries on one sequence, a bias and a bad word, stay two entries)
+                table = list(sequence_bias)
+                sequence_bias_table(dict(table) or None, None, None, self.V)
+                if len(table) > _lib.SEQ_BIAS_MAX:
+                    raise ValueError(f"{len(table)} sequences: the table of a sequence holds at most IXTTS_SEQ_BIAS_MAX = {_lib.SEQ_BIAS_MAX}")
+            else:
+                table = sequence_bias_table(sequence_bias, bad_words_ids, self.cfg["stop_mel_token"], self.V)
+        except ValueError as e:
+            raise ValueError(f"slot {slot}: {e}") from None
+        flat = np.ascontiguousarray(np.asarray([t for ids, _ in table for t in ids], dtype=np.int32))
+        lens = np.ascontiguousarray(np.asarray([len(ids) for ids, _ in table], dtype=np.int32))
+        bias = np.ascontiguousarray(np.asarray([b for _, b in table], dtype=np.float32))
+        with torch.cuda.device(self.device):
+            rc = _lib.lib().ixtts_gpt_set_sequence_bias(self._h, int(slot), flat.ctypes.data if flat.size else None, lens.ctypes.data if lens.size else None,
+                                                        bias.ctypes.data if bias.size else None, len(table), self._stream())
+        _lib.check(rc, "ixtts_gpt_set_sequence_bias")
+
+    def set_forced_eos(self, slot, forced_eos_token_id=()):
+        """`forced_eos_token_id` (an id or a list of ids) of the sequence in `slot`: what the `forced_eos_step`-th generated token
+        is forced to.  After the slot's `prefill`, which clears it; with beams, on the group's first slot."""
+        f = forced_eos_token_id
+        f = [f] if isinstance(f, (int, np.integer)) else list(f)
+        if not all(_is_id(t) and t < self.V for t in f):
+            raise ValueError(f"slot {slot}: forced_eos_token_id {f}: ids must lie in 0..{self.V - 1}")
+        a = np.ascontiguousarray(np.asarray(f, dtype=np.int32).reshape(-1))
+        with torch.cuda.device(self.device):
+            rc = _lib.lib().ixtts_gpt_set_forced_eos(self._h, int(slot), a.ctypes.data if a.size else None, a.size, self._stream())
+        _lib.check(rc, "ixtts_gpt_set_forced_eos")
+
+    def set_processors(self, slot, state):
+        """What `generation_processors` returned as `state`, onto `slot` (after its prefill)."""
+        if state is None:
+            return
+        if state.get("table"):
+            self.set_sequence_bias(slot, list(state["table"]))
+        if state.get("forced_eos"):
+            self.set_forced_eos(slot, state["forced_eos"])
+
     def force_next(self, slot, token):
         with torch.cuda.device(self.device):
             _lib.check(_lib.lib().ixtts_gpt_force_next(self._h, slot, int(token), self._stream()), "ixtts_gpt_force_next")
@@ -252,11 +413,17 @@ class GptEngine:
             _lib.check(_lib.lib().ixtts_gpt_beam_park_group(self._h, int(group), self._stream()), "ixtts_gpt_beam_park_group")
 
     def beam_decode(self, n_steps, repetition_penalty=10.0, temperature=0.8, top_k=30, top_p=0.8, suppress_stop=False, seed=0, typical_mass=0.0,
-                    length_penalty=0.0, groups=1, do_sample=True, min_new_tokens=0, no_repeat_ngram_size=0, min_p=0.0):
-        """`do_sample=False`: beam search proper -- the joint top 2 * num_beams instead of the multinomial draw, no warpers (`min_p`
-        is one of them).  `no_repeat_ngram_size` looks at each beam's own history."""
-        sc = _lib.SamplerCfg(repetition_penalty, temperature, top_k, top_p, int(bool(do_sample)), int(suppress_stop), seed, float(typical_mass), float(length_penalty),
-                             int(min_new_tokens), int(no_repeat_ngram_size), float(min_p))
+                    length_penalty=0.0, groups=1, do_sample=True, min_new_tokens=0, no_repeat_ngram_size=0, min_p=0.0,
+                    exp_decay_start=0, exp_decay_factor=0.0, epsilon_cutoff=0.0, eta_cutoff=0.0, renormalize_logits=False, forced_eos_step=0):
+        """`do_sample=False`: beam search proper -- the joint top 2 * num_beams instead of the multinomial draw, no warpers (`min_p`,
+        `epsilon_cutoff` and `eta_cutoff` are three of them).  `no_repeat_ngram_size` and the table of `set_sequence_bias` look at
+        each beam's own history.  `renormalize_logits` shifts each beam's candidate scores by the logsumexp over its surviving
+        scores (beam search proper: over its whole processed row)."""
+        sc = self._sampler_cfg(dict(repetition_penalty=repetition_penalty, temperature=temperature, top_k=top_k, top_p=top_p, do_sample=do_sample,
+                                    suppress_stop=suppress_stop, seed=seed, typical_mass=typical_mass, length_penalty=length_penalty,
+                                    min_new_tokens=min_new_tokens, no_repeat_ngram_size=no_repeat_ngram_size, min_p=min_p,
+                                    exp_decay_start=exp_decay_start, exp_decay_factor=exp_decay_factor, epsilon_cutoff=epsilon_cutoff,
+                                    eta_cutoff=eta_cutoff, renormalize_logits=renormalize_logits, forced_eos_step=forced_eos_step))
         self._lp = [float(length_penalty)] * int(groups)  # per group
         with torch.cuda.device(self.device):
             _lib.check(_lib.lib().ixtts_gpt_beam_decode_groups(self._h, int(groups), n_steps, C.byref(sc), self._stream()), "ixtts_gpt_beam_decode_groups")
@@ -329,6 +496,9 @@ class GptEngine:
         typical_mass = float(unused.pop("typical_mass", 0.0)) if unused.pop("typical_sampling", False) else 0.0
         # the constraints HF builds from plain keywords (generation_utils.py:902-1049): scalars into the sampler cfg, id lists onto the slot
         cons, bans = generation_constraints(unused, inputs.shape[1])
+        # the rest of that family (generation_utils.py:862-1069): scalars into the cfg, the table and the forced ids onto the slot
+        procs, pstate = generation_processors(unused, eos_token_id if eos_token_id is not None else self.cfg["stop_mel_token"], self.V)
+        cons = {**cons, **procs}
         for proc in (logits_processor or []):
             if type(proc).__name__ == "TypicalLogitsWarper" and hasattr(proc, "mass"):
                 typical_mass = float(proc.mass)
@@ -356,9 +526,14 @@ class GptEngine:
         max_new = (max_length - P) if max_length is not None else (self.max_seq - P - 2)
         # the mel position table bounds what can be embedded (inference_speech's own default cap: max_mel_tokens - 1, model_v2.py:699-703)
         max_new = max(0, min(max_new, self.max_seq - P - 2, self.cfg["max_mel_tokens"] - 1))
+        if pstate is not None and pstate["forced_eos"] and max_new >= 1:
+            # ForcedEOSTokenLogitsProcessor(max_length, ids): the token at position max_length - 1 = P + max_new - 1, the last one this
+            # call can generate
+            cons["forced_eos_step"] = max_new
         self.prefill(0, emb, n_pad)
         if bans is not None:
             self.set_bans(0, *bans)
+        self.set_processors(0, pstate)
         if num_beams != 1:
             # served default: 3-beam beam-sample (infer_v2.py:598-605,641-658); do_sample=False: beam search (generation_utils.py:3520-3524)
             self.beam_begin(num_beams)
@@ -380,6 +555,7 @@ class GptEngine:
                 self.prefill(b, emb, n_pad)
                 if bans is not None:
                     self.set_bans(b, *bans)
+                self.set_processors(b, pstate)
             done, fins = 0, [False] * nret
             rows = [np.zeros(0, np.int32)] * nret
             while done < max_new and not all(fins):

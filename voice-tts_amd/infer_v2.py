@@ -26,7 +26,7 @@ import numpy as np
 import torch
 
 from .bigvgan import BigVGAN
-from .gpt_engine import GptEngine, generation_constraints, resolve_gpt_dtype, resolve_min_length
+from .gpt_engine import GptEngine, generation_constraints, generation_processors, resolve_gpt_dtype, resolve_min_length
 from .pipeline import conds_latent, decode_segment, latent_prefix, prepare_gpt_inputs, vocode, vocode_many
 from .weights import BIGVGAN_CFG, GPT_CFG, load_bigvgan_checkpoint, load_gpt_checkpoint
 
@@ -586,6 +586,17 @@ class IndexTTS2:
                 raise ValueError(f"generation: suppressed id {t} outside 0..{V - 1}")
         return (cfg, bans) if cfg or bans is not None else None
 
+    def _generation_processors(self, kwargs):
+        """The other processor keywords of HF `generate()` among `kwargs` (a call's generation kwargs, a request's merged ones or
+        the leftovers of `_generation_args`; left alone) -- `sequence_bias`, `bad_words_ids`, `forced_eos_token_id`,
+        `exponential_decay_length_penalty`, `epsilon_cutoff`, `eta_cutoff`, `renormalize_logits` -- for the segments the schedulers
+        decode -> (cfg, state) as `gpt_engine.generation_processors` returns them, or None when none is set: `cfg` joins
+        `Segment.sampler`, `state` (the table of biased sequences and the forced ids) becomes `Segment.processors`; the step the
+        forced ids are forced at is each segment's own `max_new` (`_segment`).  A bad value raises ValueError here, where it fails
+        its own request only."""
+        cfg, state = generation_processors(dict(kwargs), int(self.gpt_cfg["stop_mel_token"]), int(self.gpt_cfg["number_mel_codes"]))
+        return (cfg, state) if cfg or state is not None else None
+
     def _no_qwen_emo(self):
         return NotImplementedError(
             f"use_emo_text needs the Qwen emotion model: no directory at model_dir/qwen_emo_path "
@@ -650,10 +661,13 @@ class IndexTTS2:
         return [self.tokenizer.convert_tokens_to_ids(sent) for sent in
                 self.tokenizer.split_segments(text_tokens_list, max_text_tokens_per_segment, quick_streaming_tokens=quick_streaming_tokens)]
 
-    def _segment(self, conds_latent, ids, engine, max_mel_tokens, request=0, index=0, payload=None, stream=None, sampler=None, constraints=None):
+    def _segment(self, conds_latent, ids, engine, max_mel_tokens, request=0, index=0, payload=None, stream=None, sampler=None, constraints=None,
+                 processors=None):
         """One segment's text ids -> what the schedulers decode; `max_new` is taken against the engine that will decode it.
         `constraints`: what `_generation_constraints` returned -- its scalars join the segment's sampler settings (a sampler of its
-        own only when there is something to set), its id lists become the segment's bans."""
+        own only when there is something to set), its id lists become the segment's bans.  `processors`: what
+        `_generation_processors` returned, likewise -- and forced eos ids are forced at this segment's own cap,
+        `forced_eos_step = max_new` (ForcedEOSTokenLogitsProcessor's max_length = P + max_new)."""
         embeds, n_pad, P = prepare_gpt_inputs(self.gpt_cfg, self.text_embedding, self.text_pos_embedding, conds_latent, ids)
         max_new = max(0, min(max_mel_tokens, engine.max_seq - P - 2, self.gpt_cfg["max_mel_tokens"] - 1))
         bans = None
@@ -662,12 +676,20 @@ class IndexTTS2:
             if cfg:
                 sampler = {**(sampler or {}), **cfg}
             bans = constraints[1]
-        return decode_segment(index, embeds, n_pad, max_new, request, payload, stream, sampler, bans)
+        state = None
+        if processors is not None:
+            cfg, state = processors
+            if state is not None and state["forced_eos"] and max_new >= 1:
+                cfg = {**cfg, "forced_eos_step": max_new}
+            if cfg:
+                sampler = {**(sampler or {}), **cfg}
+        return decode_segment(index, embeds, n_pad, max_new, request, payload, stream, sampler, bans, state)
 
     # what a request's `generation` dict may hold (infer_many): `infer`'s generation kwargs, parsed by `_generation_args`
     GENERATION_KEYS = ("top_p", "top_k", "temperature", "repetition_penalty", "length_penalty", "max_mel_tokens", "typical_sampling",
                        "typical_mass", "seed", "num_beams", "min_new_tokens", "min_length", "no_repeat_ngram_size", "suppress_tokens",
-                       "begin_suppress_tokens", "min_p")
+                       "begin_suppress_tokens", "min_p", "sequence_bias", "bad_words_ids", "forced_eos_token_id",
+                       "exponential_decay_length_penalty", "epsilon_cutoff", "eta_cutoff", "renormalize_logits")
 
     def _request_generation(self, rq, generation_kwargs, g):
         """-> (generation namespace of this request, pinned, its constraints): a request with a `generation` dict overrides the
@@ -791,10 +813,13 @@ class IndexTTS2:
         when `top_k == 1`).
 
         The constraint keywords of HF `generate()` -- `min_new_tokens`, `min_length`, `no_repeat_ngram_size`, `suppress_tokens`,
-        `begin_suppress_tokens`, `min_p` -- hold for every segment of the call, as they do in `infer`.
+        `begin_suppress_tokens`, `min_p` -- and the processor keywords -- `sequence_bias`, `bad_words_ids`, `forced_eos_token_id`,
+        `exponential_decay_length_penalty`, `epsilon_cutoff`, `eta_cutoff`, `renormalize_logits` -- hold for every segment of the call,
+        as they do in `infer`.
 
         A request may carry `generation`, a dict with any of `GENERATION_KEYS` (top_p, top_k, temperature, repetition_penalty,
-        length_penalty, max_mel_tokens, typical_sampling, typical_mass, seed, num_beams and the six constraint keywords): it overrides the call's kwargs for that
+        length_penalty, max_mel_tokens, typical_sampling, typical_mass, seed, num_beams, the six constraint keywords and the seven processor keywords;
+        `sequence_bias` in HF's list form [[[ids], bias], ...], which survives JSON): it overrides the call's kwargs for that
         request, and the request is PINNED (even with `{}`): segment i decodes under the request's settings and seed from random
         stream i, and the built-in s2mel's noise comes from (seed, i).  Its codes and PCM are then a function of the request
         alone -- bit-identical alone or in any batch, in any order -- at a given `decode_slots` (the engine's shape: wide and
@@ -830,6 +855,7 @@ class IndexTTS2:
                 cl = self._conds_latent(spk, emo_cond, emo_is_spk, emo_alpha, emo_vector, rq.get("use_random", False))
                 segments = self._segments_of(rq["text"], max_text_tokens_per_segment)
                 gr, pinned, cons = self._request_generation(rq, generation_kwargs, g)
+                procs = self._generation_processors({**generation_kwargs, **(rq.get("generation") or {})})
                 nb = gr.num_beams
                 if nb not in engines:
                     engines[nb] = self._many_engine_for(nb, decode_slots)
@@ -839,7 +865,7 @@ class IndexTTS2:
                 # a pinned request: segment i under the request's own settings and seed, drawing from stream i
                 sampler = self._segment_sampler(gr) if pinned else None
                 mine = [self._segment(cl, ids, eng, gr.max_mel_tokens, request=ri, index=si, stream=si if pinned else None, sampler=sampler,
-                                      constraints=cons)
+                                      constraints=cons, processors=procs)
                         for si, ids in enumerate(segments)]
                 plans[ri] = dict(spk=spk, cl=cl, segments=segments, seed=gr.seed if pinned else None)
                 classes.setdefault(nb, []).extend(mine)  # only once the whole request is known to be well-formed
@@ -956,7 +982,8 @@ class IndexTTS2:
         if eng is not None:
             beams = g.num_beams > 1
             cons = self._generation_constraints(rest)  # (the one-segment path below hands `rest` to gpt.generate, which parses them itself)
-            pre = self._decode(eng, [self._segment(cl, ids, eng, g.max_mel_tokens, index=i, stream=i if beams else None, constraints=cons)
+            procs = self._generation_processors(rest)
+            pre = self._decode(eng, [self._segment(cl, ids, eng, g.max_mel_tokens, index=i, stream=i if beams else None, constraints=cons, processors=procs)
                                      for i, ids in enumerate(segments)], g)
         gpt_gen_time += time.perf_counter() - m0
         # several segments, whole audio at the end, IXTTS_S2MEL_BATCH=1: their CFM solves run as ONE packed solve (default: segment

@@ -103,11 +103,11 @@ def vocode_many(bigvgan, mels):
     return out
 
 
-def decode_segment(index, embeds, n_left_pad, max_new, request=0, payload=None, stream=None, sampler=None, bans=None):
+def decode_segment(index, embeds, n_left_pad, max_new, request=0, payload=None, stream=None, sampler=None, bans=None, processors=None):
     """One prepared sequence as the decode schedulers take it (`scheduler.Segment`); `HotPath` and `IndexTTS2` build theirs here."""
     from .scheduler import Segment
 
-    return Segment(request, index, embeds, n_left_pad, max_new, payload, stream, sampler, bans)
+    return Segment(request, index, embeds, n_left_pad, max_new, payload, stream, sampler, bans, processors)
 
 
 class HotPath:

@@ -21,9 +21,9 @@ import numpy as np
 class Segment:
     """One text segment of one request, ready for the decode engine."""
 
-    __slots__ = ("request", "index", "embeds", "n_left_pad", "max_new", "payload", "stream", "sampler", "bans")
+    __slots__ = ("request", "index", "embeds", "n_left_pad", "max_new", "payload", "stream", "sampler", "bans", "processors")
 
-    def __init__(self, request, index, embeds, n_left_pad, max_new, payload=None, stream=None, sampler=None, bans=None):
+    def __init__(self, request, index, embeds, n_left_pad, max_new, payload=None, stream=None, sampler=None, bans=None, processors=None):
         self.request, self.index, self.embeds, self.n_left_pad, self.max_new, self.payload = request, index, embeds, n_left_pad, max_new, payload
         # the random stream this segment draws from (None: beam groups, its position in the submission order; single slots, the
         # index of the slot it lands in)
@@ -33,6 +33,9 @@ class Segment:
         # (suppress_tokens, begin_suppress_tokens) of HF generate(): ids banned at every step / at the first generated token.  They are
         # state of the slot the segment lands in: the schedulers call engine.set_bans right after its prefill (None: no call)
         self.bans = bans
+        # the rest of that slot state, what gpt_engine.generation_processors returned as `state`: the table of sequence_bias /
+        # bad_words_ids and the forced eos ids; the schedulers call engine.set_processors beside set_bans (None: no call)
+        self.processors = processors
 
 
 def live_stub(engine, like):
@@ -53,7 +56,8 @@ class DecodeScheduler:
 
     engine: `GptEngine`-like object with prefill(slot, embeds, n_left_pad), decode(n_active, n_steps, **sampler) and
     read(slot) -> (ids, finished); decode_slots(n_steps, cfgs, streams) too when a segment carries `sampler` or `stream`, and
-    set_bans(slot, suppress_tokens, begin_suppress_tokens) when one carries `bans`.
+    set_bans(slot, suppress_tokens, begin_suppress_tokens) when one carries `bans`, set_processors(slot, state) when one carries
+    `processors`.
     `stop_token` ends a sequence (inclusive) unless `fixed_length`.
     """
 
@@ -81,6 +85,8 @@ class DecodeScheduler:
                     self.engine.prefill(b, seg.embeds, seg.n_left_pad)
                     if getattr(seg, "bans", None) is not None:
                         self.engine.set_bans(b, *seg.bans)
+                    if getattr(seg, "processors", None) is not None:
+                        self.engine.set_processors(b, seg.processors)
                     if b < primed:
                         self.stats["refills"] += 1
                     primed = max(primed, b + 1)
@@ -137,7 +143,8 @@ class BeamGroupScheduler:
 
     engine: `GptEngine`-like with prefill(slot, embeds, pad), beam_begin(num_beams, group=, rng_stream=), beam_park(group),
     beam_decode(n_steps, groups=, **sampler), beam_read(max_new, group=) -> (ids, done, score, ...); beam_decode_groups(n_steps,
-    cfgs) too when a segment carries `sampler`, set_bans(slot, ...) when one carries `bans`.
+    cfgs) too when a segment carries `sampler`, set_bans(slot, ...) when one carries `bans`, set_processors(slot, state) when one
+    carries `processors`.
     """
 
     def __init__(self, engine, num_beams, max_groups=None, sync_every=64):
@@ -168,6 +175,8 @@ class BeamGroupScheduler:
                     eng.prefill(g * nb, seg.embeds, seg.n_left_pad)
                     if getattr(seg, "bans", None) is not None:
                         eng.set_bans(g * nb, *seg.bans)  # the group's: the flags of its first slot hold for all its beams
+                    if getattr(seg, "processors", None) is not None:
+                        eng.set_processors(g * nb, seg.processors)  # the group's too
                     eng.beam_begin(nb, group=g, rng_stream=stream)
                     if g < begun:
                         self.stats["refills"] += 1

@@ -244,7 +244,7 @@ typedef struct ixtts_gpt_cfg {
   int start_mel_token; /* 8192 */
   int stop_mel_token;  /* 8193 */
   int max_seq;         /* KV-cache capacity per sequence (prompt + generated) */
-  int max_batch;       /* concurrent sequences (1 greedy; beams / segment batching later) */
+  int max_batch;       /* concurrent sequences: 1..ixtts_gpt_max_batch_for(weight_dtype) (32 for bf16 / f16, 16 for f32) */
   int weight_dtype;    /* IXTTS_DTYPE_F32 (parity mode) | IXTTS_DTYPE_BF16 (throughput mode) | IXTTS_DTYPE_F16 (see above) */
 } ixtts_gpt_cfg;
 
@@ -389,7 +389,7 @@ int ixtts_gpt_beam_force(ixtts_gpt* h, const int32_t* picks_host, int n, void* s
  * `_beam_search` over num_beams sequences.  Here the segments of a request (or of several requests) decode TOGETHER: group g
  * owns slots g*num_beams .. g*num_beams+num_beams-1 and its own scorer state (beam scores, hypotheses, done flag, forced
  * draws), the weights are read once per step for all groups.  An engine of up to 4 slots holds one group (the calls above ==
- * group 0); a wide engine (max_batch 5..16, either weight type) holds floor(max_batch / num_beams) of them.  A group's tokens do not depend
+ * group 0); a wide engine (max_batch 5..16, or up to 32 with bf16 / f16 weights) holds floor(max_batch / num_beams) of them.  A group's tokens do not depend
  * on which other groups step with it.  Usage per segment: ixtts_gpt_prefill(h, g*num_beams, ...) ->
  * ixtts_gpt_beam_begin_group(h, g, num_beams, rng_stream) (rng_stream selects the group's random stream: 0 is the stream
  * ixtts_gpt_beam_begin uses, so segment i decoded with rng_stream i draws the same numbers in any group) -> repeated
@@ -420,8 +420,12 @@ int ixtts_gpt_bench_gemv(ixtts_gpt* h, int which, int layer, int batch, void* st
 /* Algorithmic HBM bytes of one decode step at batch B and context S. */
 double ixtts_gpt_step_bytes(const ixtts_gpt* h, int B, int S);
 
-/* Largest `max_batch` (decode slots decoded together, weights read once per step for all of them) this build supports. */
+/* Largest `max_batch` (decode slots decoded together, weights read once per step for all of them) that EVERY weight type of this
+ * build supports: 16. */
 int ixtts_gpt_max_batch(void);
+/* The same for one weight type: 32 for IXTTS_DTYPE_BF16 and IXTTS_DTYPE_F16 (steps of 17..32 sequences serve two blocks of 16
+ * columns from one weight stream), 16 for IXTTS_DTYPE_F32, 0 for anything else.  ixtts_gpt_create refuses more. */
+int ixtts_gpt_max_batch_for(int weight_dtype);
 
 int ixtts_gpt_destroy(ixtts_gpt* h);
 

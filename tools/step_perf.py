@@ -2,7 +2,7 @@
 
     python tools/step_perf.py [--dtype {bf16,f16,f32}]... [--repeat N] [B ...]
 
-B = 1..4 run on the register GEMVs, 5..16 on the wide (matrix-core) engine.  With no argument: bf16, B = 2 and 3, one line
+B = 1..4 run on the register GEMVs, 5..16 (5..32 for bf16 / f16) on the wide (matrix-core) engine.  With no argument: bf16, B = 2 and 3, one line
 per B.  `--dtype` may be given several times: the engines of one B are then timed ALTERNATELY, `--repeat N` rounds of 800
 steps each, every round printed (an A/B in one process, same clocks, same neighbours)."""
 import argparse, sys, time, torch

@@ -136,6 +136,7 @@ SYMBOLS = {
     "ixtts_gpt_bench_gemv": (C.c_int, [_P, C.c_int, C.c_int, C.c_int, _P]),
     "ixtts_gpt_step_bytes": (C.c_double, [_P, C.c_int, C.c_int]),
     "ixtts_gpt_max_batch": (C.c_int, []),
+    "ixtts_gpt_max_batch_for": (C.c_int, [C.c_int]),
     "ixtts_gpt_destroy": (C.c_int, [_P]),
     "ixtts_qwen_create": (C.c_int, [C.POINTER(_P), C.POINTER(QwenCfg)]),
     "ixtts_qwen_set_tensor": (C.c_int, [_P, C.c_char_p, _P, C.POINTER(C.c_int64), C.c_int]),
@@ -195,8 +196,21 @@ def check(rc, what=""):
 
 
 def max_batch():
-    """Decode slots the engine can step together (a build constant of libixtts_hip.so)."""
+    """Decode slots an engine of ANY weight type can step together (a build constant of libixtts_hip.so): 16."""
     return int(lib().ixtts_gpt_max_batch())
+
+
+_DTYPE_CODES = {"f32": 0, "bf16": 1, "f16": 2}  # IXTTS_DTYPE_*
+
+
+def max_batch_for(dtype):
+    """Decode slots an engine of weight type `dtype` ("f32" | "bf16" | "f16", or the IXTTS_DTYPE_* code) can step together:
+    32 for the 16-bit types, 16 for fp32."""
+    if isinstance(dtype, str):
+        if dtype not in _DTYPE_CODES:
+            raise ValueError(f"max_batch_for: unknown weight type {dtype!r}")
+        dtype = _DTYPE_CODES[dtype]
+    return int(lib().ixtts_gpt_max_batch_for(int(dtype)))
 
 
 def current_stream_ptr():

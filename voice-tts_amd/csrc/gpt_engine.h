@@ -8,7 +8,8 @@
 
 namespace ixtts {
 
-constexpr int MAXB = 16;       // decode slots stepped together: 1..4 on the register GEMVs, 5..16 ("wide" engines) on the matrix cores (gpt_wide.h)
+constexpr int MAXB = 32;       // decode slots stepped together: 1..4 on the register GEMVs, 5..32 ("wide" engines) on the matrix cores (gpt_wide.h)
+constexpr int MAXB_F32 = 16;   // fp32 weights stop here (one column block; a 32-slot fp32 K/V cache would be 16 GB): what every weight type holds
 constexpr int MAXB_REG = 4;
 constexpr int STEPS_PER_GRAPH = 8;
 // beam-sample (gpt_beam.hip): beams per group, groups stepping together (group g owns slots g*NB .. g*NB+NB-1), and the strides
@@ -125,7 +126,7 @@ struct ixtts_gpt {
   float* beam_cand_v = nullptr;  // [MAXB][SAMP_MAXK] per-beam survivors of a step (gpt_beam.hip)
   int *beam_cand_i = nullptr, *beam_cand_n = nullptr;
   bool beam_every_row = false;  // IXTTS_BEAM_REORDER=full: move every generated row at each reorder (A/B test of the shared-prefix bookkeeping)
-  int* beam_lcp = nullptr;  // [MAXB*MAXB] leading generated K/V rows known identical between two beams' slots, then [MAXB] first row to copy
+  int* beam_lcp = nullptr;  // [MAXG][BEAM_LCP_STRIDE] per group: leading generated K/V rows known identical between two beams' slots, then the first row to copy
   hipGraphExec_t beam_exec[ixtts::MAXG + 1][ixtts::NBKT + 1] = {}, beam_multi_exec[ixtts::MAXG + 1][ixtts::NBKT + 1] = {};  // per (groups, bucket)
   int beam_exec_nb = 0;
   // batched-rows workspace (prefill / latent): [max_seq][D] x4 + [max_seq][4D]

@@ -305,7 +305,8 @@ static void launch_sampler(ixtts_gpt* h, int n_active, hipStream_t st) {
 
 
 // ------------------------------------------------------------------------------------ wide engines (gpt_wide.h)
-// max_batch > 4, either weight type.  Rows per workgroup (RP0 + RP1) make one workgroup per CU at model_dim 1280:
+// max_batch > 4, any weight type; 17..32 slots on the 16-bit types only, where a step of more than 16 sequences takes the
+// two-block form of gemv_wide_kernel and a step of at most 16 the one-block kernels.  Rows per workgroup (RP0 + RP1) make one workgroup per CU at model_dim 1280:
 //   bf16 (v_mfma_f32_16x16x32_bf16) and fp16 (v_mfma_f32_16x16x32_f16, the same kernel on the other element type):
 //   15 / 5 / 16 + 4 / 5 / 16 + 16 for QKV / out-proj / FC / MLP-out / head, 4 waves each;
 //   fp32 (v_mfma_f32_16x16x4_f32):   15 / 5 / 16 + 4 / 5 (8 waves, K walked in 4 phases) / 16 + 16 -- the same split: a row is
@@ -315,9 +316,16 @@ template <typename WT, typename KVT, int K, int INP, int EPI, int NW, int RP0, i
 static int launch_wide(const void* wt, const void* xin, const float* bias, void* out, int N, int B, int slot0, int out_stride, ixtts_gpt* h,
                        void* kc, void* vc, const float* ln_w, const float* ln_b, hipStream_t st) {
   constexpr int NT = RP1 > 0 ? 2 : 1;
+  if (B < 1 || B > (std::is_same<WT, float>::value ? WIDE_COLS : 2 * WIDE_COLS)) {
+    set_error("wide launch: batch %d outside what the weight type steps together", B);
+    return IXTTS_ERR_ARG;
+  }
   if constexpr (std::is_same<WT, float>::value) {
     hipLaunchKernelGGL((gemv_wide_f32_kernel<K, NT, INP, EPI, KVT, NW, RP0, RP1>), dim3(ceil_div(N, RP0 + RP1)), dim3(64 * NW), 0, st,
                        reinterpret_cast<const float*>(wt), xin, bias, out, N, B, slot0, out_stride, h->smax, kc, vc, (const int*)h->cur_len, h->H, ln_w, ln_b);
+  } else if (B > WIDE_COLS) {  // 17..32 sequences: two column blocks on the one weight stream
+    hipLaunchKernelGGL((gemv_wide_kernel<WT, K, NT, INP, EPI, KVT, NW, RP0, RP1, 2>), dim3(ceil_div(N, RP0 + RP1)), dim3(64 * NW), 0, st,
+                       reinterpret_cast<const WT*>(wt), xin, bias, out, N, B, slot0, out_stride, h->smax, kc, vc, (const int*)h->cur_len, h->H, ln_w, ln_b);
   } else {
     hipLaunchKernelGGL((gemv_wide_kernel<WT, K, NT, INP, EPI, KVT, NW, RP0, RP1>), dim3(ceil_div(N, RP0 + RP1)), dim3(64 * NW), 0, st,
                        reinterpret_cast<const WT*>(wt), xin, bias, out, N, B, slot0, out_stride, h->smax, kc, vc, (const int*)h->cur_len, h->H, ln_w, ln_b);
@@ -411,9 +419,13 @@ extern "C" int ixtts_gpt_create(ixtts_gpt** out, const ixtts_gpt_cfg* c) {
   IX_ARG(c->model_dim == 1280 || c->model_dim == 128, "gpt_create: model_dim %d has no kernel instantiation (1280 | 128)", c->model_dim);
   IX_ARG(c->heads * HD == c->model_dim, "gpt_create: head dim must be 64 (heads %d, dim %d)", c->heads, c->model_dim);
   IX_ARG(c->layers > 0 && c->n_mel_codes > 0 && c->n_mel_pos > 2 && c->max_seq > 8, "gpt_create: bad sizes");
-  IX_ARG(c->max_batch >= 1 && c->max_batch <= MAXB, "gpt_create: max_batch %d (1..%d)", c->max_batch, MAXB);
   IX_ARG(c->weight_dtype == IXTTS_DTYPE_F32 || c->weight_dtype == IXTTS_DTYPE_BF16 || c->weight_dtype == IXTTS_DTYPE_F16,
          "gpt_create: weight_dtype %d (IXTTS_DTYPE_F32 | IXTTS_DTYPE_BF16 | IXTTS_DTYPE_F16)", c->weight_dtype);
+  {
+    const int lim = ixtts_gpt_max_batch_for(c->weight_dtype);
+    IX_ARG(c->max_batch >= 1 && c->max_batch <= lim, "gpt_create: max_batch %d (1..%d for %s weights)", c->max_batch, lim,
+           c->weight_dtype == IXTTS_DTYPE_F32 ? "f32" : c->weight_dtype == IXTTS_DTYPE_F16 ? "f16" : "bf16");
+  }
   IX_ARG(c->start_mel_token >= 0 && c->start_mel_token < c->n_mel_codes && c->stop_mel_token >= 0 && c->stop_mel_token < c->n_mel_codes, "gpt_create: start/stop token out of range");
   auto* h = new (std::nothrow) ixtts_gpt();
   if (!h) return IXTTS_ERR_NOMEM;
@@ -975,7 +987,7 @@ extern "C" int ixtts_gpt_decode_slots(ixtts_gpt* h, int n_active, int n_steps, c
 
 // ------------------------------------------------------------------------------------ beam-sample
 // Group g = the beams of ONE prompt, in slots g*NB .. g*NB+NB-1.  Engines of up to 4 slots hold one group (register GEMVs);
-// wide engines (5..16 slots) hold floor(max_batch / NB) groups that step together: the text segments of a request, or
+// wide engines (5..32 slots) hold floor(max_batch / NB) groups that step together: the text segments of a request, or
 // of several requests, each with its own scorer state (the reference decodes them one after another, infer_v2.py:616).
 static int beam_begin_impl(ixtts_gpt* h, int g, int num_beams, unsigned long long stream_id, hipStream_t st) {
   IX_ARG(num_beams >= 2 && num_beams <= BEAM_MAX, "gpt_beam_begin: num_beams %d (2..%d)", num_beams, BEAM_MAX);
@@ -1330,7 +1342,12 @@ extern "C" int ixtts_gpt_bench_gemv(ixtts_gpt* h, int which, int layer, int batc
   return do_gemv_which(h, which, layer, batch, (hipStream_t)stream);
 }
 
-extern "C" int ixtts_gpt_max_batch(void) { return MAXB; }
+extern "C" int ixtts_gpt_max_batch(void) { return MAXB_F32; }  // what holds for every weight type
+
+extern "C" int ixtts_gpt_max_batch_for(int weight_dtype) {
+  if (weight_dtype == IXTTS_DTYPE_BF16 || weight_dtype == IXTTS_DTYPE_F16) return MAXB;
+  return weight_dtype == IXTTS_DTYPE_F32 ? MAXB_F32 : 0;
+}
 
 extern "C" double ixtts_gpt_step_bytes(const ixtts_gpt* h, int B, int S) {
   if (!h) return 0.0;

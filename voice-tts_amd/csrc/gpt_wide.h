@@ -1,4 +1,5 @@
-// gpt_wide.h -- the decode-step GEMVs for WIDE batches (5..16 sequences stepped together) on the matrix cores: gemv_wide_kernel for
+// gpt_wide.h -- the decode-step GEMVs for WIDE batches (5..16 sequences stepped together; 17..32 as two column blocks on one
+// weight stream, 16-bit weights only: NB below) on the matrix cores: gemv_wide_kernel for
 // bf16 weights (described first) and, as a second instantiation of the same template, fp16 weights (WideEl<f16>:
 // v_mfma_f32_16x16x32_f16, same lane maps, same row splits); gemv_wide_f32_kernel for fp32 weights (the parity mode; at the end of the file).
 //
@@ -26,6 +27,8 @@
 //
 // Reference arithmetic: indextts/gpt/transformers_gpt2.py:480-667 (block), :1164 (ln_f); model_v2.py:53,185 (final_norm + mel_head).
 #pragma once
+#include <type_traits>
+
 #include "gpt_kernels.h"
 
 namespace ixtts {
@@ -46,9 +49,23 @@ template <>
 struct WideEl<bf16> {
   typedef wbf16x8 vec8;
   static constexpr bool LO_SCALED = false;
+  // How the one-block kernel of this element type has always been contracted by the compiler, which the two-block kernel spells
+  // out (its own code is contracted differently around the jump, and a column must get the one-block kernel's bits):
+  // MEAN_CONTRACTED: `x -= sum * (1 / K)` of the LayerNorm is one fma(-sum, 1 / K, x) per element (fp16: every instantiation;
+  // bf16: none, the subtraction is packed two to an instruction first).  split_scaled: see there.
+  static constexpr bool MEAN_CONTRACTED = false;
   __device__ static __forceinline__ void split(float x, vec8& hi, vec8& lo, int j) {
     hi[j] = (__bf16)x;
     lo[j] = (__bf16)(x - (float)hi[j]);
+  }
+  // the split of the normalised activation x * rstd as the ONE-block kernel computes it: there the compiler contracts the
+  // `x *= rstd` of the LayerNorm into the remainder of `split` -- lo = bf16(fma(x, rstd, -hi)), the remainder of the unrounded
+  // product -- in every instantiation (its ISA holds no v_sub_f32 for these).  Around the two-block kernel's jump it contracts only
+  // some of them, so that kernel spells the fused form out (the one-block kernel keeps the source it has always been compiled
+  // from: same instructions as ever).  tests/test_gpu_wide32.py holds the two to the same bits at model_dim 128 and 1280.
+  __device__ static __forceinline__ void split_scaled(float x, float rstd, vec8& hi, vec8& lo, int j) {
+    hi[j] = (__bf16)(x * rstd);
+    lo[j] = (__bf16)__builtin_fmaf(x, rstd, -(float)hi[j]);
   }
   __device__ static __forceinline__ wf32x4 mfma(const vec8& a, const vec8& b, const wf32x4& c) { return __builtin_amdgcn_mfma_f32_16x16x32_bf16(a, b, c, 0, 0, 0); }
 };
@@ -56,6 +73,7 @@ template <>
 struct WideEl<f16> {
   typedef wf16x8 vec8;
   static constexpr bool LO_SCALED = true;
+  static constexpr bool MEAN_CONTRACTED = true;
   static constexpr float LO_SCALE = 2048.0f, LO_INV = 1.0f / 2048.0f;
   __device__ static __forceinline__ void split(float x, vec8& hi, vec8& lo, int j) {
     // one clamp serves both parts: the remainder of the CLAMPED value is at most half an ulp of hi (<= 16), 32768 after scaling
@@ -63,11 +81,13 @@ struct WideEl<f16> {
     hi[j] = (f16)xc;
     lo[j] = (f16)((xc - (float)hi[j]) * LO_SCALE);
   }
+  // (the clamp sits between the product and the remainder: nothing here for the compiler to contract)
+  __device__ static __forceinline__ void split_scaled(float x, float rstd, vec8& hi, vec8& lo, int j) { split(x * rstd, hi, lo, j); }
   __device__ static __forceinline__ wf32x4 mfma(const vec8& a, const vec8& b, const wf32x4& c) { return __builtin_amdgcn_mfma_f32_16x16x32_f16(a, b, c, 0, 0, 0); }
 };
 
 enum { WIN_LN = 0, WIN_LN2 = 1, WIN_PLAIN = 2, WIN_FF = 3 };
-constexpr int WIDE_COLS = 16;  // sequence slots a wide launch can carry (the N of the MFMA)
+constexpr int WIDE_COLS = 16;  // sequence slots one column block of a wide launch carries (the N of the MFMA)
 
 // sum over the 4 lanes that hold one sequence in a wave (lanes c, c+16, c+32, c+48), every one of them gets it; fixed order
 __device__ __forceinline__ float seq_sum4(float v) {
@@ -101,13 +121,24 @@ __device__ __forceinline__ uint4 row_shl4(const uint4& v) {
 // with few rows would waste most of every 16-row weight load (5 rows x 64 B per wave-instruction instead of 1 KiB), so its
 // loads are PACKED: 16 / RP k-steps per instruction, lane (m, g) fetching row m % RP of k-step pack m / RP, and the fragment of
 // pack p is moved into place with a DPP row shift (4 v_mov_dpp) when its MFMA is issued.
-template <typename ET, int K, int NT, int INP, int EPI, typename KVT, int NW, int RP0, int RP1>
+//
+// NB: column blocks served from the one weight stream.  NB == 1 is the kernel of the engines of up to 16 slots: B <= 16 columns
+// at slots slot0 .. slot0 + B - 1.  NB == 2 (engines of 17..32 slots stepping B = 17..32 sequences) keeps the weight fragments
+// resident and walks two blocks one after the other -- block 0 = slots slot0 .. slot0 + 15, block 1 = slots slot0 + 16 ..
+// slot0 + B - 1 -- each through the very same staging, LayerNorm, hi + lo split, MFMA order, part[] sum and epilogue, so a
+// column's arithmetic is that of the one-block kernel whatever block it sits in.  Block 1's activations (L2 hits: the launch
+// before has just written them) are requested as soon as block 0's MFMAs have consumed block 0's, and arrive under block 0's
+// K-partial exchange and epilogue; the registers are those of one block at a time.  The second pass is a jump back over the
+// block's code (`next_block`), taken only when NB == 2: with NB == 1 there is no loop, no lambda and no helper for the compiler
+// to see, and the instantiation is instruction for instruction the kernel it was before NB existed.
+template <typename ET, int K, int NT, int INP, int EPI, typename KVT, int NW, int RP0, int RP1, int NB = 1>
 __global__ __launch_bounds__(64 * NW) void gemv_wide_kernel(const ET* __restrict__ wt, const void* __restrict__ xin, const float* __restrict__ bias, void* out,
                                                         int N, int B, int slot0, int out_stride, int smax, void* kcache, void* vcache,
                                                         const int* __restrict__ cur_len, int heads, const float* __restrict__ ln_w,
                                                         const float* __restrict__ ln_b) {
   static_assert(K % (32 * NW) == 0, "K is dealt to the waves in 32-element k-steps");
   static_assert(NW == 4 || INP == WIN_FF, "the in-register staging of fp32 activations is laid out for 4 waves");
+  static_assert(NB == 1 || NB == 2, "one or two column blocks");
   constexpr int NI = K / (32 * NW);  // k-steps per wave = 8-float chunks per staging thread
   constexpr int NPASS = INP == WIN_LN ? 1 : (INP == WIN_LN2 ? 2 : 0);
   static_assert(RP0 >= 1 && RP0 <= 16 && RP1 >= 0 && RP1 <= 16 && (NT == 2) == (RP1 > 0), "rows per tile");
@@ -119,168 +150,204 @@ __global__ __launch_bounds__(64 * NW) void gemv_wide_kernel(const ET* __restrict
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int c = lane & 15, g = lane >> 4;
   const int row0 = blockIdx.x * (RP0 + RP1);
-  const int slot_c = slot0 + min(c, B - 1);  // columns beyond the batch repeat the last sequence (finite, never stored)
+  // columns of block `blk`: its first slot and how many of its 16 columns carry a sequence (columns beyond that repeat the
+  // block's last sequence: finite, never stored)
+#define IX_BLK_SLOT0(blk) (slot0 + (blk) * WIDE_COLS)
+#define IX_BLK_COLS(blk) (NB == 1 ? B : ((blk) == 0 ? WIDE_COLS : B - WIDE_COLS))
 
   // ---- 1. activations of this lane: chunk (4 wave + g) + 16 i of sequence c  ==  k-step wave + 4 i, elements 8 g .. 8 g + 7
   float x[INP == WIN_FF ? 1 : NI][8];
   float lw[NPASS == 2 ? NI : 1][8], lb[NPASS == 2 ? NI : 1][8];
   uint4 braw[INP == WIN_FF ? NI : 1];
-  if constexpr (INP == WIN_FF) {
-    const ET* xb = reinterpret_cast<const ET*>(xin) + (size_t)slot_c * K + g * 8;
-#pragma unroll
-    for (int i = 0; i < NI; ++i) braw[i] = *reinterpret_cast<const uint4*>(xb + (wave + NW * i) * 32);
-  } else {
-    const float* xb = reinterpret_cast<const float*>(xin) + (size_t)slot_c * K + g * 8;
-#pragma unroll
-    for (int i = 0; i < NI; ++i) {
-      const int k0 = (wave + NW * i) * 32;
-      const float4 t0 = *reinterpret_cast<const float4*>(xb + k0), t1 = *reinterpret_cast<const float4*>(xb + k0 + 4);
-      x[i][0] = t0.x; x[i][1] = t0.y; x[i][2] = t0.z; x[i][3] = t0.w; x[i][4] = t1.x; x[i][5] = t1.y; x[i][6] = t1.z; x[i][7] = t1.w;
-      if constexpr (NPASS == 2) {  // explicit affine of the first norm (ln_f); the second norm's affine is folded into W
-        const float4 w0 = *reinterpret_cast<const float4*>(ln_w + k0 + g * 8), w1 = *reinterpret_cast<const float4*>(ln_w + k0 + g * 8 + 4);
-        const float4 b0 = *reinterpret_cast<const float4*>(ln_b + k0 + g * 8), b1 = *reinterpret_cast<const float4*>(ln_b + k0 + g * 8 + 4);
-        lw[i][0] = w0.x; lw[i][1] = w0.y; lw[i][2] = w0.z; lw[i][3] = w0.w; lw[i][4] = w1.x; lw[i][5] = w1.y; lw[i][6] = w1.z; lw[i][7] = w1.w;
-        lb[i][0] = b0.x; lb[i][1] = b0.y; lb[i][2] = b0.z; lb[i][3] = b0.w; lb[i][4] = b1.x; lb[i][5] = b1.y; lb[i][6] = b1.z; lb[i][7] = b1.w;
-      }
-    }
+// (a macro, not a helper: arrays handed to a function or a lambda by reference change the one-block kernel's instruction schedule)
+#define IX_WIDE_LOAD_X(SLOT_C) \
+  {                                                                                                                                                \
+    const int slot_c = (SLOT_C);                                                                                                                   \
+    if constexpr (INP == WIN_FF) {                                                                                                                 \
+      const ET* xb = reinterpret_cast<const ET*>(xin) + (size_t)slot_c * K + g * 8;                                                                \
+      _Pragma("unroll") for (int i = 0; i < NI; ++i) braw[i] = *reinterpret_cast<const uint4*>(xb + (wave + NW * i) * 32);                         \
+    } else {                                                                                                                                       \
+      const float* xb = reinterpret_cast<const float*>(xin) + (size_t)slot_c * K + g * 8;                                                          \
+      _Pragma("unroll") for (int i = 0; i < NI; ++i) {                                                                                             \
+        const int k0 = (wave + NW * i) * 32;                                                                                                       \
+        const float4 t0 = *reinterpret_cast<const float4*>(xb + k0), t1 = *reinterpret_cast<const float4*>(xb + k0 + 4);                           \
+        x[i][0] = t0.x; x[i][1] = t0.y; x[i][2] = t0.z; x[i][3] = t0.w; x[i][4] = t1.x; x[i][5] = t1.y; x[i][6] = t1.z; x[i][7] = t1.w;            \
+        if constexpr (NPASS == 2) { /* explicit affine of the first norm (ln_f); the second norm's affine is folded into W */                      \
+          const float4 w0 = *reinterpret_cast<const float4*>(ln_w + k0 + g * 8), w1 = *reinterpret_cast<const float4*>(ln_w + k0 + g * 8 + 4);     \
+          const float4 b0 = *reinterpret_cast<const float4*>(ln_b + k0 + g * 8), b1 = *reinterpret_cast<const float4*>(ln_b + k0 + g * 8 + 4);     \
+          lw[i][0] = w0.x; lw[i][1] = w0.y; lw[i][2] = w0.z; lw[i][3] = w0.w; lw[i][4] = w1.x; lw[i][5] = w1.y; lw[i][6] = w1.z; lw[i][7] = w1.w;  \
+          lb[i][0] = b0.x; lb[i][1] = b0.y; lb[i][2] = b0.z; lb[i][3] = b0.w; lb[i][4] = b1.x; lb[i][5] = b1.y; lb[i][6] = b1.z; lb[i][7] = b1.w;  \
+        }                                                                                                                                          \
+      }                                                                                                                                            \
+    }                                                                                                                                              \
   }
+  IX_WIDE_LOAD_X(IX_BLK_SLOT0(0) + min(c, IX_BLK_COLS(0) - 1))
   __builtin_amdgcn_sched_barrier(0);
-  // ---- 2. epilogue operands: thread (m = tid >> 4, n = tid & 15) finishes row 16 t + m of sequence n
   const int em = (tid >> 4) & 15, en = tid & 15;  // (threads 256.. of an 8-wave workgroup mirror 0..255 and store nothing)
-  const int eslot = slot0 + min(en, B - 1);
-  float pre_bias[NT], pre_res[NT];
-  int pre_pos = 0;
-#pragma unroll
-  for (int t = 0; t < NT; ++t) {
-    const int n = min(row0 + (t == 0 ? 0 : RP0) + min(em, (t == 0 ? RP0 : RP1) - 1), N - 1);
-    pre_bias[t] = bias[n];
-    pre_res[t] = 0.f;
-    if constexpr (EPI == EPI_RESID) pre_res[t] = reinterpret_cast<const float*>(out)[(size_t)eslot * out_stride + n];
-  }
-  if constexpr (EPI == EPI_QKV) pre_pos = cur_len[eslot];
-  __builtin_amdgcn_sched_barrier(0);
-  // ---- 3. weight stream: load j of tile t = k-steps j KP .. j KP + KP - 1 of the rows of that tile (rows / packs beyond the
-  // range repeat a valid address; their products land in accumulator rows nobody reads)
   uint4 a[NT][NLM];
-#pragma unroll
-  for (int t = 0; t < NT; ++t) {
-    const int RP = t == 0 ? RP0 : RP1, KP = t == 0 ? KP0 : KP1, NL = t == 0 ? NL0 : NL1;
-    const int pk = min(c / RP, KP - 1);
-    const ET* wrow = wt + (size_t)min(row0 + (t == 0 ? 0 : RP0) + c % RP, N - 1) * K + g * 8;
-#pragma unroll
-    for (int j = 0; j < NL; ++j) a[t][j] = load_w16<false>(wrow + (wave + NW * min(j * KP + pk, NI - 1)) * 32);
-  }
-  __builtin_amdgcn_sched_barrier(0);
-  // ---- 4. LayerNorm of sequence c over its 16 threads (4 lanes in each of the 4 waves), in registers
-#pragma unroll
-  for (int pass = 0; pass < NPASS; ++pass) {
-    float s = 0.f;
-#pragma unroll
-    for (int i = 0; i < NI; ++i) s += ((x[i][0] + x[i][1]) + (x[i][2] + x[i][3])) + ((x[i][4] + x[i][5]) + (x[i][6] + x[i][7]));
-    const float mean = seq_block_sum(s, red[2 * pass], wave, lane) * (1.0f / K);
-    float q = 0.f;
-#pragma unroll
-    for (int i = 0; i < NI; ++i)
-#pragma unroll
-      for (int j = 0; j < 8; ++j) {
-        x[i][j] -= mean;
-        q = fmaf(x[i][j], x[i][j], q);
-      }
-    const float rstd = 1.0f / sqrtf(seq_block_sum(q, red[2 * pass + 1], wave, lane) * (1.0f / K) + 1e-5f);
-#pragma unroll
-    for (int i = 0; i < NI; ++i)
-#pragma unroll
-      for (int j = 0; j < 8; ++j) {
-        x[i][j] *= rstd;
-        if (NPASS == 2 && pass == 0) x[i][j] = fmaf(x[i][j], lw[i][j], lb[i][j]);
-      }
-  }
-  // ---- 5. matrix cores: acc[t] (rows 4 g .. 4 g + 3 of tile t, sequence c) += W fragment . (hi + lo) activations
-  using EL = WideEl<ET>;
-  typedef typename EL::vec8 vec8;
-  constexpr bool LO2 = EL::LO_SCALED && INP != WIN_FF;  // the lo products have an accumulator of their own
-  wf32x4 acc[NT], accl[LO2 ? NT : 1];
-#pragma unroll
-  for (int t = 0; t < NT; ++t) acc[t] = wf32x4{0.f, 0.f, 0.f, 0.f};
-  if constexpr (LO2) {
-#pragma unroll
-    for (int t = 0; t < NT; ++t) accl[t] = wf32x4{0.f, 0.f, 0.f, 0.f};
-  }
-#pragma unroll
-  for (int i = 0; i < NI; ++i) {
-    vec8 bh, bl;
-    if constexpr (INP == WIN_FF) {
-      bh = __builtin_bit_cast(vec8, braw[i]);
-    } else {
-#pragma unroll
-      for (int j = 0; j < 8; ++j) EL::split(x[i][j], bh, bl, j);
-    }
+  int blk = 0;
+next_block: {
+    const int Bb = IX_BLK_COLS(blk);
+    if (NB == 2 && blk > 0) __syncthreads();  // every thread is done with the block before's red[] and part[]
+    // ---- 2. epilogue operands: thread (m = tid >> 4, n = tid & 15) finishes row 16 t + m of sequence n
+    const int eslot = IX_BLK_SLOT0(blk) + min(en, Bb - 1);
+    float pre_bias[NT], pre_res[NT];
+    int pre_pos = 0;
 #pragma unroll
     for (int t = 0; t < NT; ++t) {
-      constexpr int dummy = 0;
-      (void)dummy;
-      const int KP = t == 0 ? KP0 : KP1;
-      uint4 raw;
-      // (i, t are compile-time after unrolling: the switch folds to one shift)
-      switch ((i % KP) * (t == 0 ? RP0 : RP1)) {
-        case 0: raw = a[t][i / KP]; break;
-        case 1: raw = row_shl4<1>(a[t][i / KP]); break;
-        case 2: raw = row_shl4<2>(a[t][i / KP]); break;
-        case 3: raw = row_shl4<3>(a[t][i / KP]); break;
-        case 4: raw = row_shl4<4>(a[t][i / KP]); break;
-        case 5: raw = row_shl4<5>(a[t][i / KP]); break;
-        case 6: raw = row_shl4<6>(a[t][i / KP]); break;
-        case 7: raw = row_shl4<7>(a[t][i / KP]); break;
-        case 8: raw = row_shl4<8>(a[t][i / KP]); break;
-        case 9: raw = row_shl4<9>(a[t][i / KP]); break;
-        case 10: raw = row_shl4<10>(a[t][i / KP]); break;
-        case 11: raw = row_shl4<11>(a[t][i / KP]); break;
-        case 12: raw = row_shl4<12>(a[t][i / KP]); break;
-        case 13: raw = row_shl4<13>(a[t][i / KP]); break;
-        case 14: raw = row_shl4<14>(a[t][i / KP]); break;
-        default: raw = row_shl4<15>(a[t][i / KP]); break;
-      }
-      const vec8 af = __builtin_bit_cast(vec8, raw);
-      acc[t] = EL::mfma(af, bh, acc[t]);
-      if constexpr (LO2) accl[t] = EL::mfma(af, bl, accl[t]);
-      else if constexpr (INP != WIN_FF) acc[t] = EL::mfma(af, bl, acc[t]);
+      const int n = min(row0 + (t == 0 ? 0 : RP0) + min(em, (t == 0 ? RP0 : RP1) - 1), N - 1);
+      pre_bias[t] = bias[n];
+      pre_res[t] = 0.f;
+      if constexpr (EPI == EPI_RESID) pre_res[t] = reinterpret_cast<const float*>(out)[(size_t)eslot * out_stride + n];
     }
-  }
-  if constexpr (LO2) {
+    if constexpr (EPI == EPI_QKV) pre_pos = cur_len[eslot];
+    __builtin_amdgcn_sched_barrier(0);
+    // ---- 3. weight stream (once, ahead of block 0): load j of tile t = k-steps j KP .. j KP + KP - 1 of the rows of that tile
+    // (rows / packs beyond the range repeat a valid address; their products land in accumulator rows nobody reads)
+    if (blk == 0) {
 #pragma unroll
-    for (int t = 0; t < NT; ++t)
+      for (int t = 0; t < NT; ++t) {
+        const int RP = t == 0 ? RP0 : RP1, KP = t == 0 ? KP0 : KP1, NL = t == 0 ? NL0 : NL1;
+        const int pk = min(c / RP, KP - 1);
+        const ET* wrow = wt + (size_t)min(row0 + (t == 0 ? 0 : RP0) + c % RP, N - 1) * K + g * 8;
 #pragma unroll
-      for (int j = 0; j < 4; ++j) acc[t][j] = fmaf(accl[t][j], WideEl<f16>::LO_INV, acc[t][j]);
-  }
-  // ---- 6. the 4 K-partials through LDS (fixed order), then the epilogue of (row 16 t + em, sequence en)
+        for (int j = 0; j < NL; ++j) a[t][j] = load_w16<false>(wrow + (wave + NW * min(j * KP + pk, NI - 1)) * 32);
+      }
+    }
+    __builtin_amdgcn_sched_barrier(0);
+    // ---- 4. LayerNorm of sequence c over its 16 threads (4 lanes in each of the 4 waves), in registers
+    float rstd_last = 1.0f;
 #pragma unroll
-  for (int t = 0; t < NT; ++t) *reinterpret_cast<float4*>(&part[wave][t][lane][0]) = make_float4(acc[t][0], acc[t][1], acc[t][2], acc[t][3]);
-  __syncthreads();
-  const int src_lane = (em >> 2) * 16 + en, src_j = em & 3;  // C/D map: col = lane & 15, row = (lane >> 4) * 4 + j
+    for (int pass = 0; pass < NPASS; ++pass) {
+      float s = 0.f;
 #pragma unroll
-  for (int t = 0; t < NT; ++t) {
-    const int n = row0 + (t == 0 ? 0 : RP0) + em;  // accumulator row em of tile t
-    if (tid < 256 && em < (t == 0 ? RP0 : RP1) && n < N && en < B) {
-      float v = (part[0][t][src_lane][src_j] + part[1][t][src_lane][src_j]) + (part[2][t][src_lane][src_j] + part[3][t][src_lane][src_j]);
-      if constexpr (NW == 8) v += (part[4][t][src_lane][src_j] + part[5][t][src_lane][src_j]) + (part[6][t][src_lane][src_j] + part[7][t][src_lane][src_j]);
-      v += pre_bias[t];
-      if constexpr (EPI == EPI_RESID) {
-        reinterpret_cast<float*>(out)[(size_t)eslot * out_stride + n] = pre_res[t] + v;
-      } else if constexpr (EPI == EPI_GELU) {
-        store_kv(reinterpret_cast<ET*>(out) + (size_t)eslot * out_stride + n, gelu_new_f(v));  // ff travels in the weights' type (fp16: saturating)
-      } else if constexpr (EPI == EPI_LOGITS) {
-        reinterpret_cast<float*>(out)[(size_t)eslot * out_stride + n] = v;
-      } else {  // EPI_QKV: q -> buffer, k / v -> cache at position cur_len[slot]  (K == model_dim here)
-        if (n < K) {
+      for (int i = 0; i < NI; ++i) s += ((x[i][0] + x[i][1]) + (x[i][2] + x[i][3])) + ((x[i][4] + x[i][5]) + (x[i][6] + x[i][7]));
+      const float ssum = seq_block_sum(s, red[2 * pass], wave, lane);
+      const float mean = ssum * (1.0f / K);
+      float q = 0.f;
+#pragma unroll
+      for (int i = 0; i < NI; ++i)
+#pragma unroll
+        for (int j = 0; j < 8; ++j) {
+          if constexpr (NB == 2 && WideEl<ET>::MEAN_CONTRACTED) x[i][j] = __builtin_fmaf(-ssum, 1.0f / K, x[i][j]);  // (see WideEl)
+          else x[i][j] -= mean;
+          q = fmaf(x[i][j], x[i][j], q);
+        }
+      const float rstd = 1.0f / sqrtf(seq_block_sum(q, red[2 * pass + 1], wave, lane) * (1.0f / K) + 1e-5f);
+      if (NB == 2 && pass + 1 == NPASS) {  // two blocks: the last norm's scale goes into the hi + lo split below (split_scaled)
+        rstd_last = rstd;
+      } else {
+#pragma unroll
+        for (int i = 0; i < NI; ++i)
+#pragma unroll
+          for (int j = 0; j < 8; ++j) {
+            x[i][j] *= rstd;
+            if (NPASS == 2 && pass == 0) x[i][j] = fmaf(x[i][j], lw[i][j], lb[i][j]);
+          }
+      }
+    }
+    // ---- 5. matrix cores: acc[t] (rows 4 g .. 4 g + 3 of tile t, sequence c) += W fragment . (hi + lo) activations
+    using EL = WideEl<ET>;
+    typedef typename EL::vec8 vec8;
+    constexpr bool LO2 = EL::LO_SCALED && INP != WIN_FF;  // the lo products have an accumulator of their own
+    wf32x4 acc[NT], accl[LO2 ? NT : 1];
+#pragma unroll
+    for (int t = 0; t < NT; ++t) acc[t] = wf32x4{0.f, 0.f, 0.f, 0.f};
+    if constexpr (LO2) {
+#pragma unroll
+      for (int t = 0; t < NT; ++t) accl[t] = wf32x4{0.f, 0.f, 0.f, 0.f};
+    }
+#pragma unroll
+    for (int i = 0; i < NI; ++i) {
+      vec8 bh, bl;
+      if constexpr (INP == WIN_FF) {
+        bh = __builtin_bit_cast(vec8, braw[i]);
+      } else {
+#pragma unroll
+        for (int j = 0; j < 8; ++j) {
+          if constexpr (NB == 2 && NPASS > 0) EL::split_scaled(x[i][j], rstd_last, bh, bl, j);
+          else EL::split(x[i][j], bh, bl, j);
+        }
+      }
+#pragma unroll
+      for (int t = 0; t < NT; ++t) {
+        const int KP = t == 0 ? KP0 : KP1;
+        // (i, t are compile-time after unrolling: the switch folds to one shift)
+        uint4 raw;
+        switch ((i % KP) * (t == 0 ? RP0 : RP1)) {
+          case 0: raw = a[t][i / KP]; break;
+          case 1: raw = row_shl4<1>(a[t][i / KP]); break;
+          case 2: raw = row_shl4<2>(a[t][i / KP]); break;
+          case 3: raw = row_shl4<3>(a[t][i / KP]); break;
+          case 4: raw = row_shl4<4>(a[t][i / KP]); break;
+          case 5: raw = row_shl4<5>(a[t][i / KP]); break;
+          case 6: raw = row_shl4<6>(a[t][i / KP]); break;
+          case 7: raw = row_shl4<7>(a[t][i / KP]); break;
+          case 8: raw = row_shl4<8>(a[t][i / KP]); break;
+          case 9: raw = row_shl4<9>(a[t][i / KP]); break;
+          case 10: raw = row_shl4<10>(a[t][i / KP]); break;
+          case 11: raw = row_shl4<11>(a[t][i / KP]); break;
+          case 12: raw = row_shl4<12>(a[t][i / KP]); break;
+          case 13: raw = row_shl4<13>(a[t][i / KP]); break;
+          case 14: raw = row_shl4<14>(a[t][i / KP]); break;
+          default: raw = row_shl4<15>(a[t][i / KP]); break;
+        }
+        const vec8 af = __builtin_bit_cast(vec8, raw);
+        acc[t] = EL::mfma(af, bh, acc[t]);
+        if constexpr (LO2) accl[t] = EL::mfma(af, bl, accl[t]);
+        else if constexpr (INP != WIN_FF) acc[t] = EL::mfma(af, bl, acc[t]);
+      }
+    }
+    if constexpr (LO2) {
+#pragma unroll
+      for (int t = 0; t < NT; ++t)
+#pragma unroll
+        for (int j = 0; j < 4; ++j) acc[t][j] = fmaf(accl[t][j], WideEl<f16>::LO_INV, acc[t][j]);
+    }
+    if (NB == 2 && blk == 0) {  // the next block's activations: in flight under this block's K-partial exchange and epilogue
+      __builtin_amdgcn_sched_barrier(0);
+      IX_WIDE_LOAD_X(IX_BLK_SLOT0(1) + min(c, IX_BLK_COLS(1) - 1))
+      __builtin_amdgcn_sched_barrier(0);
+    }
+    // ---- 6. the 4 K-partials through LDS (fixed order), then the epilogue of (row 16 t + em, sequence en)
+#pragma unroll
+    for (int t = 0; t < NT; ++t) *reinterpret_cast<float4*>(&part[wave][t][lane][0]) = make_float4(acc[t][0], acc[t][1], acc[t][2], acc[t][3]);
+    __syncthreads();
+    const int src_lane = (em >> 2) * 16 + en, src_j = em & 3;  // C/D map: col = lane & 15, row = (lane >> 4) * 4 + j
+#pragma unroll
+    for (int t = 0; t < NT; ++t) {
+      const int n = row0 + (t == 0 ? 0 : RP0) + em;  // accumulator row em of tile t
+      if (tid < 256 && em < (t == 0 ? RP0 : RP1) && n < N && en < Bb) {
+        float v = (part[0][t][src_lane][src_j] + part[1][t][src_lane][src_j]) + (part[2][t][src_lane][src_j] + part[3][t][src_lane][src_j]);
+        if constexpr (NW == 8) v += (part[4][t][src_lane][src_j] + part[5][t][src_lane][src_j]) + (part[6][t][src_lane][src_j] + part[7][t][src_lane][src_j]);
+        v += pre_bias[t];
+        if constexpr (EPI == EPI_RESID) {
+          reinterpret_cast<float*>(out)[(size_t)eslot * out_stride + n] = pre_res[t] + v;
+        } else if constexpr (EPI == EPI_GELU) {
+          store_kv(reinterpret_cast<ET*>(out) + (size_t)eslot * out_stride + n, gelu_new_f(v));  // ff travels in the weights' type (fp16: saturating)
+        } else if constexpr (EPI == EPI_LOGITS) {
           reinterpret_cast<float*>(out)[(size_t)eslot * out_stride + n] = v;
-        } else {
-          const int which = n / K, cc = n - which * K;
-          KVT* cache = reinterpret_cast<KVT*>(which == 1 ? kcache : vcache);
-          store_kv(cache + (((size_t)eslot * heads + cc / HD) * smax + pre_pos) * HD + cc % HD, v);
+        } else {  // EPI_QKV: q -> buffer, k / v -> cache at position cur_len[slot]  (K == model_dim here)
+          if (n < K) {
+            reinterpret_cast<float*>(out)[(size_t)eslot * out_stride + n] = v;
+          } else {
+            const int which = n / K, cc = n - which * K;
+            KVT* cache = reinterpret_cast<KVT*>(which == 1 ? kcache : vcache);
+            store_kv(cache + (((size_t)eslot * heads + cc / HD) * smax + pre_pos) * HD + cc % HD, v);
+          }
         }
       }
     }
   }
+  if constexpr (NB == 2) {
+    if (blk == 0) {
+      blk = 1;
+      goto next_block;
+    }
+  }
+#undef IX_WIDE_LOAD_X
+#undef IX_BLK_SLOT0
+#undef IX_BLK_COLS
 }
 
 // ------------------------------------------------------------------------------------------------------------------------

@@ -484,10 +484,10 @@ class IndexTTS2:
     # ------------------------------------------------------------------ decode engines beside `self.gpt` (infer_many, beam groups)
     def _many_engine(self, slots):
         """A second decode engine whose slots are shared by the segments of several requests (wide MFMA GEMVs above 4 slots,
-        on the bf16, fp16 or fp32 matrix cores by the model's GPT weight type)."""
+        on the bf16, fp16 or fp32 matrix cores by the model's GPT weight type: up to 32 slots for the 16-bit types, 16 for fp32)."""
         from . import _lib
 
-        slots = max(1, min(int(slots), _lib.max_batch()))
+        slots = max(1, min(int(slots), _lib.max_batch_for(self.gpt_dtype)))
         if slots not in self._engines:
             # a second engine SHAPE over the same device weights (ixtts_gpt_share_arena): it costs its KV cache only
             eng = GptEngine(self.gpt_cfg, dtype=self.gpt_dtype, max_seq=self.gpt.max_seq, max_batch=slots, device=self.device)
@@ -495,21 +495,22 @@ class IndexTTS2:
         return self._engines[slots]
 
     def _beam_group_engine(self, num_beams, n_segments):
-        """The engine several beam groups step together on: wide (5..16 slots on the matrix cores, bf16 or fp32 by the model's
-        precision) when there is more than one segment to decode, else None (one group at a time on the register engine, as the
+        """The engine several beam groups step together on: wide (5..32 slots on the matrix cores for a bf16 or fp16 model, 5..16
+        for an fp32 one) when there is more than one segment to decode, else None (one group at a time on the register engine, as the
         reference decodes: segment after segment).  `IXTTS_BEAM_GROUPS` caps the groups (0 / 1: off); a bf16 or fp16 model defaults to 5,
         an fp32 model joins the groups only when the variable is set."""
         from . import _lib
 
         cap = int(os.environ.get("IXTTS_BEAM_GROUPS", "5"))
-        groups = min(cap, _lib.max_batch() // num_beams, n_segments)
+        most = _lib.max_batch_for(self.gpt_dtype) // num_beams  # 10 groups of 3 beams on a 16-bit model, 5 on an fp32 one
+        groups = min(cap, most, n_segments)
         # An fp32 model takes this path only when IXTTS_BEAM_GROUPS is set explicitly: the fp32 wide step has no recorded timing
         # against the register engine yet (DESIGN.md 4.1b), and the second engine's fp32 K/V cache is 8 GB at max_seq 2048.
         if self.gpt_dtype == "f32" and "IXTTS_BEAM_GROUPS" not in os.environ:
             return None
         if groups < 2 or groups * num_beams <= 4:
             return None
-        want = min(cap, _lib.max_batch() // num_beams) * num_beams  # one engine shape per worker, whatever the request's segment count
+        want = min(cap, most) * num_beams  # one engine shape per worker, whatever the request's segment count
         eng = self._many_engine(want)
         return eng if eng.max_batch >= 2 * num_beams else None
 
@@ -726,7 +727,7 @@ class IndexTTS2:
         from . import _lib
 
         if num_beams > 1:
-            groups = max(1, min(int(decode_slots), _lib.max_batch()) // num_beams)
+            groups = max(1, min(int(decode_slots), _lib.max_batch_for(self.gpt_dtype)) // num_beams)
             return self._many_engine(groups * num_beams) if groups * num_beams > 4 else self.gpt
         return self._many_engine(decode_slots)
 
@@ -810,7 +811,7 @@ class IndexTTS2:
         `emo_text` (the emotion from text, as in `infer`; the emotion texts of the whole batch are decoded together).  Generation
         kwargs and defaults are `infer`'s: with `num_beams > 1` (the served default, 3) every segment is a beam GROUP and
         floor(decode_slots / num_beams) groups step together; `num_beams=1` samples without beams, one slot per segment (argmax
-        when `top_k == 1`).
+        when `top_k == 1`).  `decode_slots` goes up to 32 on a bf16 / fp16 model and up to 16 on an fp32 one (more is clamped).
 
         The constraint keywords of HF `generate()` -- `min_new_tokens`, `min_length`, `no_repeat_ngram_size`, `suppress_tokens`,
         `begin_suppress_tokens`, `min_p` -- and the processor keywords -- `sequence_bias`, `bad_words_ids`, `forced_eos_token_id`,
@@ -822,8 +823,8 @@ class IndexTTS2:
         `sequence_bias` in HF's list form [[[ids], bias], ...], which survives JSON): it overrides the call's kwargs for that
         request, and the request is PINNED (even with `{}`): segment i decodes under the request's settings and seed from random
         stream i, and the built-in s2mel's noise comes from (seed, i).  Its codes and PCM are then a function of the request
-        alone -- bit-identical alone or in any batch, in any order -- at a given `decode_slots` (the engine's shape: wide and
-        register engines differ in logit bits) and outside IXTTS_S2MEL_BATCH=1 (the packed solve reassociates with its pack).
+        alone -- bit-identical alone or in any batch, in any order -- on every wide engine (`decode_slots` 5..32: the bits are the
+        same on all of them; only the register engines of up to 4 slots differ in logit bits) and outside IXTTS_S2MEL_BATCH=1 (the packed solve reassociates with its pack).
         `num_beams` may differ between requests: each value decodes as its own class, one after another.  An unknown key, or a
         `num_beams` the engine chosen for `decode_slots` cannot hold, fails that request only.  Requests without the key behave
         as ever: the call's settings, streams by slot / submission order, noise from the default generator.

@@ -79,6 +79,18 @@ int ixtts_attn_full_varlen_f32(const float* q_dev, const float* k_dev, const flo
                                int total_tiles, int n_work, int H, int head_dim, long stride_t, long stride_h, long ostride_t, long ostride_h,
                                float scale, void* workspace_dev, size_t workspace_bytes, void* stream);
 
+/* ixtts_attn_full_rope_f32 / ixtts_attn_full_rope_varlen_f32: the two entries above with RoPE (gpt_fast/model.py:289-301,348-360) of
+ * q and k inside: q and k arrive UNROTATED (and are left so), the keys are rotated as they are split into planes, the queries as they
+ * are loaded, v is untouched.  cos_sin_dev [positions][32] (cos, sin) pairs, 16-byte aligned, position = row within the sequence
+ * (rope_rows >= T; varlen: it covers the longest sequence).  Bit for bit ixtts_rope_qk_f32 (/ _varlen_f32) on q and k followed by
+ * the entry above.  Split-product build only: workspace_dev is required, and IXTTS_ATTN_FULL=f32 is refused. */
+int ixtts_attn_full_rope_f32(const float* q_dev, const float* k_dev, const float* v_dev, float* out_dev, const float* cos_sin_dev, int rope_rows,
+                             int B, int H, int T, int head_dim, long stride_b, long stride_t, long stride_h, long ostride_b, long ostride_t,
+                             long ostride_h, float scale, void* workspace_dev, size_t workspace_bytes, void* stream);
+int ixtts_attn_full_rope_varlen_f32(const float* q_dev, const float* k_dev, const float* v_dev, float* out_dev, const float* cos_sin_dev,
+                                    const int* table_dev, int nseq, int total_tiles, int n_work, int H, int head_dim, long stride_t, long stride_h,
+                                    long ostride_t, long ostride_h, float scale, void* workspace_dev, size_t workspace_bytes, void* stream);
+
 /* Row N1 helpers -- the element/row chains between the DiT's GEMMs, one fp32 pass each (csrc/dit_ops.hip).
  *
  * ixtts_adaln_rmsnorm_f32  replaces AdaptiveLayerNorm.forward over RMSNorm (gpt_fast/model.py:18-37,362-372):
@@ -125,6 +137,15 @@ int ixtts_wn_gate_rows_varlen_f32(const float* a_dev, const float* g_dev, float*
                                   long g_stride, int g_offset, void* stream);
 int ixtts_reflect_halo_rows_varlen_f32(float* p_dev, const int* seq_off_dev, int nseq, int C, int left, int right, void* stream);
 
+/* AdaLN-RMSNorm whose output goes straight to a split-product GEMM: the same rows as ixtts_adaln_rmsnorm_f32 (/ _varlen_f32), written
+ * as the bf16 planes that ixtts_gemm_x6_split would make of them -- byte for byte, the zero rows up to ixtts_gemm_x6_rows_padded(rows)
+ * included -- instead of as fp32 (which is not written).  planes_dev: (H/16) * 6 * rows_padded * 16 bytes, 128-byte aligned; H a
+ * multiple of 64, at most 1024. */
+int ixtts_adaln_rmsnorm_planes_f32(const float* x_dev, const float* wb_dev, const float* g_dev, void* planes_dev, int B, int T, int H, float eps,
+                                   void* stream);
+int ixtts_adaln_rmsnorm_planes_varlen_f32(const float* x_dev, const float* wb_dev, const float* g_dev, void* planes_dev, const int* seq_off_dev,
+                                          int nseq, long rows, int H, float eps, void* stream);
+
 /* Row N1 -- the linear layers of the s2mel DiT / WaveNet: C[M][N] (+)= A[M][K] . W[N][K]^T + bias, fp32 in and out
  * replaces: `nn.Linear` / 1x1 and k-tap Conv1d of indextts/s2mel/modules/gpt_fast/model.py:242-326 (wqkv, wo, w1 | w3, w2),
  *   wavenet.py:103-174 (in_layers as one row-shifted GEMM per tap, res_skip_layers), diffusion_transformer.py:186-257 (merge / skip
@@ -146,6 +167,13 @@ long ixtts_gemm_x6_rows_padded(long rows);
 int ixtts_gemm_x6_split(const float* a_dev, long lda, void* planes_dev, long rows, int K, void* stream);
 int ixtts_gemm_x6_f32(const void* a_planes_dev, long rows_total, long row0, const void* packed_dev, const float* bias_dev, float* c_dev, long ldc,
                       int M, int N, int K, int accumulate, int tile, void* stream);
+/* ixtts_gemm_x6_split_halo (/ _varlen): ixtts_gemm_x6_split of a reflect-padded row buffer (rows = whole sequences of left + T + right
+ * rows; varlen: sequence s = rows [seq_off[s], seq_off[s+1]), its own halo rows included, rows = seq_off[nseq]) that reads every halo
+ * row from the interior row it mirrors: the planes of ixtts_reflect_halo_rows_f32 (/ _varlen_f32) followed by ixtts_gemm_x6_split,
+ * without the refresh -- the fp32 halo rows are neither read nor written. */
+int ixtts_gemm_x6_split_halo(const float* a_dev, long lda, void* planes_dev, long rows, int K, int T, int left, int right, void* stream);
+int ixtts_gemm_x6_split_halo_varlen(const float* a_dev, long lda, void* planes_dev, long rows, int K, const int* seq_off_dev, int nseq, int left,
+                                    int right, void* stream);
 /* ixtts_gemm_x6_pair_f32: the same GEMM with a pair epilogue, over weights packed with their two halves interleaved in 32-row blocks
  * (rows 64q .. 64q + 31 = rows 32q .. of the first half, 64q + 32 .. 64q + 63 = the same rows of the second; bias_dev [N] likewise):
  * C[M][N/2] = f(a, b), a / b = the two halves' results + bias; epilogue 1 = silu(a) * b (SwiGLU), 2 = tanh(a + g_a) * sigmoid(b + g_b)

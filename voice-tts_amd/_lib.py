@@ -76,6 +76,10 @@ SYMBOLS = {
     "ixtts_attn_full_varlen_workspace_bytes": (C.c_size_t, [C.c_int, C.c_int, C.c_int]),
     "ixtts_attn_full_varlen_f32": (C.c_int, [_P, _P, _P, _P, _P, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_long, C.c_long, C.c_long, C.c_long,
                                              C.c_float, _P, C.c_size_t, _P]),
+    "ixtts_attn_full_rope_f32": (C.c_int, [_P, _P, _P, _P, _P, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_long, C.c_long, C.c_long, C.c_long,
+                                           C.c_long, C.c_long, C.c_float, _P, C.c_size_t, _P]),
+    "ixtts_attn_full_rope_varlen_f32": (C.c_int, [_P, _P, _P, _P, _P, _P, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_long, C.c_long, C.c_long,
+                                                  C.c_long, C.c_float, _P, C.c_size_t, _P]),
     "ixtts_adaln_rmsnorm_f32": (C.c_int, [_P, _P, _P, _P, C.c_int, C.c_int, C.c_int, C.c_float, _P]),
     "ixtts_ln_modulate_f32": (C.c_int, [_P, _P, _P, C.c_int, C.c_int, C.c_int, C.c_float, _P]),
     "ixtts_rope_qk_f32": (C.c_int, [_P, _P, C.c_int, C.c_int, C.c_int, C.c_int, _P]),
@@ -88,6 +92,10 @@ SYMBOLS = {
     "ixtts_rope_qk_varlen_f32": (C.c_int, [_P, _P, _P, C.c_int, C.c_long, C.c_int, C.c_int, _P]),
     "ixtts_wn_gate_rows_varlen_f32": (C.c_int, [_P, _P, _P, C.c_long, C.c_int, _P, C.c_int, C.c_long, C.c_int, _P]),
     "ixtts_reflect_halo_rows_varlen_f32": (C.c_int, [_P, _P, C.c_int, C.c_int, C.c_int, C.c_int, _P]),
+    "ixtts_adaln_rmsnorm_planes_f32": (C.c_int, [_P, _P, _P, _P, C.c_int, C.c_int, C.c_int, C.c_float, _P]),
+    "ixtts_adaln_rmsnorm_planes_varlen_f32": (C.c_int, [_P, _P, _P, _P, _P, C.c_int, C.c_long, C.c_int, C.c_float, _P]),
+    "ixtts_gemm_x6_split_halo": (C.c_int, [_P, C.c_long, _P, C.c_long, C.c_int, C.c_int, C.c_int, C.c_int, _P]),
+    "ixtts_gemm_x6_split_halo_varlen": (C.c_int, [_P, C.c_long, _P, C.c_long, C.c_int, _P, C.c_int, C.c_int, C.c_int, _P]),
     "ixtts_gemm_x6_packed_bytes": (C.c_size_t, [C.c_int, C.c_int]),
     "ixtts_gemm_x6_pack": (C.c_int, [_P, _P, C.c_int, C.c_int, _P]),
     "ixtts_gemm_x6_rows_padded": (C.c_long, [C.c_long]),

@@ -26,11 +26,15 @@ struct AttnFullArgs {
   // packed (ragged) sequences, attn_full_x3 only (B = 1, T unused): vl_tab = [seq_off n+1 | tile_off n+1 | (seq, 128-query block) pairs]
   const int* vl_tab;
   int vl_n, vl_tiles;  // sequences, key tiles of all of them (tile_off[n])
+  // attn_full_x3 only: RoPE table [position][32] (cos, sin), position = row within the sequence; q and k arrive unrotated and are
+  // rotated as they are split (the K planes pass, the Q load), v is untouched.  Null: q and k are taken as they are.
+  const float2* rope;
 };
 
 // bytes of K / V planes the x3 build keeps per call: [B*H][tiles][2 (K, V)][3 planes][512 units] x 16 B
 size_t attn_full_x3_plane_bytes(int B, int H, int T);
 // split pass + attention (+ partials for the caller's merge when a.ws_o is set); planes = attn_full_x3_plane_bytes() of scratch
+// (a.rope set: the instantiations that rotate q and k -- bit for bit rope_qk_kernel on q and k, then the same call without a.rope)
 int launch_attn_full_x3(const AttnFullArgs& a, void* planes, bool split, hipStream_t st);
 // the same over packed sequences: queries of sequence s see the keys of sequence s only; n_work (sequence, query block) items
 int launch_attn_full_x3_varlen(const AttnFullArgs& a, void* planes, int n_work, hipStream_t st);

@@ -221,9 +221,10 @@ extern "C" size_t ixtts_attn_full_workspace_bytes(int B, int H, int T) {
   return attn_partials_bytes(B, H, T) + ixtts::attn_full_x3_plane_bytes(B, H, T);
 }
 
-extern "C" int ixtts_attn_full_f32(const float* q_dev, const float* k_dev, const float* v_dev, float* out_dev, int B, int H, int T,
-                                   int head_dim, long stride_b, long stride_t, long stride_h, long ostride_b, long ostride_t,
-                                   long ostride_h, float scale, void* workspace_dev, size_t workspace_bytes, void* stream) {
+// rope_dev: null, or the (cos, sin) table of ixtts_attn_full_rope_f32
+static int attn_full_run(const float* q_dev, const float* k_dev, const float* v_dev, float* out_dev, const float* rope_dev, int B, int H, int T, int head_dim,
+                         long stride_b, long stride_t, long stride_h, long ostride_b, long ostride_t, long ostride_h, float scale, void* workspace_dev,
+                         size_t workspace_bytes, void* stream) {
   using namespace ixtts;
   IX_ARG(q_dev && k_dev && v_dev && out_dev, "attn_full: null pointer");
   IX_ARG(head_dim == AF_D, "attn_full: head_dim %d (only 64 is built)", head_dim);
@@ -236,6 +237,7 @@ extern "C" int ixtts_attn_full_f32(const float* q_dev, const float* k_dev, const
   a.B = B; a.H = H; a.T = T; a.scale = scale;
   a.ws_o = a.ws_ml = nullptr;
   a.vl_tab = nullptr; a.vl_n = a.vl_tiles = 0;
+  a.rope = reinterpret_cast<const float2*>(rope_dev);
   hipStream_t st = (hipStream_t)stream;
   const int qblocks = ceil_div(T, AF_WAVES * AF_QW);
   // split the keys when the un-split grid cannot give every SIMD two waves and the caller brought the workspace
@@ -246,6 +248,7 @@ extern "C" int ixtts_attn_full_f32(const float* q_dev, const float* k_dev, const
   const char* mode = getenv("IXTTS_ATTN_FULL");  // (read per call: the parity tests run both builds in one process)
   const bool x3 = !(mode && strcmp(mode, "f32") == 0);
   const bool use_x3 = x3 && have_ws;
+  IX_ARG(!rope_dev || use_x3, "attn_full_rope: only the split-product build rotates (it needs the workspace, and IXTTS_ATTN_FULL unset or x3)");
   if (split) {
     a.ws_o = reinterpret_cast<float*>(workspace_dev);
     a.ws_ml = a.ws_o + (size_t)(use_x3 ? AX_KSPLIT : AF_KSPLIT) * B * H * T * AF_D;
@@ -270,14 +273,30 @@ extern "C" int ixtts_attn_full_f32(const float* q_dev, const float* k_dev, const
   return IXTTS_OK;
 }
 
+extern "C" int ixtts_attn_full_f32(const float* q_dev, const float* k_dev, const float* v_dev, float* out_dev, int B, int H, int T,
+                                   int head_dim, long stride_b, long stride_t, long stride_h, long ostride_b, long ostride_t,
+                                   long ostride_h, float scale, void* workspace_dev, size_t workspace_bytes, void* stream) {
+  return attn_full_run(q_dev, k_dev, v_dev, out_dev, nullptr, B, H, T, head_dim, stride_b, stride_t, stride_h, ostride_b, ostride_t, ostride_h, scale,
+                       workspace_dev, workspace_bytes, stream);
+}
+
+extern "C" int ixtts_attn_full_rope_f32(const float* q_dev, const float* k_dev, const float* v_dev, float* out_dev, const float* cos_sin_dev, int rope_rows,
+                                        int B, int H, int T, int head_dim, long stride_b, long stride_t, long stride_h, long ostride_b, long ostride_t,
+                                        long ostride_h, float scale, void* workspace_dev, size_t workspace_bytes, void* stream) {
+  IX_ARG(cos_sin_dev && rope_rows >= T && (reinterpret_cast<uintptr_t>(cos_sin_dev) & 15) == 0,
+         "attn_full_rope: the (cos, sin) table must be 16-byte aligned and cover T=%d positions (it has %d)", T, rope_rows);
+  return attn_full_run(q_dev, k_dev, v_dev, out_dev, cos_sin_dev, B, H, T, head_dim, stride_b, stride_t, stride_h, ostride_b, ostride_t, ostride_h, scale,
+                       workspace_dev, workspace_bytes, stream);
+}
+
 extern "C" size_t ixtts_attn_full_varlen_workspace_bytes(int nseq, int H, int total_tiles) {
   if (nseq <= 0 || H <= 0 || total_tiles <= 0) return 0;
   return (size_t)H * total_tiles * 2 * 3 * 8 * 64 * 16;  // K / V planes only: this entry never splits the key range
 }
 
-extern "C" int ixtts_attn_full_varlen_f32(const float* q_dev, const float* k_dev, const float* v_dev, float* out_dev, const int* table_dev, int nseq,
-                                          int total_tiles, int n_work, int H, int head_dim, long stride_t, long stride_h, long ostride_t, long ostride_h,
-                                          float scale, void* workspace_dev, size_t workspace_bytes, void* stream) {
+static int attn_full_varlen_run(const float* q_dev, const float* k_dev, const float* v_dev, float* out_dev, const float* rope_dev, const int* table_dev,
+                                int nseq, int total_tiles, int n_work, int H, int head_dim, long stride_t, long stride_h, long ostride_t, long ostride_h,
+                                float scale, void* workspace_dev, size_t workspace_bytes, void* stream) {
   using namespace ixtts;
   IX_ARG(q_dev && k_dev && v_dev && out_dev && table_dev, "attn_full_varlen: null pointer");
   IX_ARG(head_dim == AF_D, "attn_full_varlen: head_dim %d (only 64 is built)", head_dim);
@@ -293,5 +312,21 @@ extern "C" int ixtts_attn_full_varlen_f32(const float* q_dev, const float* k_dev
   a.B = 1; a.H = H; a.T = 0; a.scale = scale;
   a.ws_o = a.ws_ml = nullptr;
   a.vl_tab = table_dev; a.vl_n = nseq; a.vl_tiles = total_tiles;
+  a.rope = reinterpret_cast<const float2*>(rope_dev);
   return launch_attn_full_x3_varlen(a, workspace_dev, n_work, (hipStream_t)stream);
+}
+
+extern "C" int ixtts_attn_full_varlen_f32(const float* q_dev, const float* k_dev, const float* v_dev, float* out_dev, const int* table_dev, int nseq,
+                                          int total_tiles, int n_work, int H, int head_dim, long stride_t, long stride_h, long ostride_t, long ostride_h,
+                                          float scale, void* workspace_dev, size_t workspace_bytes, void* stream) {
+  return attn_full_varlen_run(q_dev, k_dev, v_dev, out_dev, nullptr, table_dev, nseq, total_tiles, n_work, H, head_dim, stride_t, stride_h, ostride_t, ostride_h,
+                              scale, workspace_dev, workspace_bytes, stream);
+}
+
+extern "C" int ixtts_attn_full_rope_varlen_f32(const float* q_dev, const float* k_dev, const float* v_dev, float* out_dev, const float* cos_sin_dev,
+                                               const int* table_dev, int nseq, int total_tiles, int n_work, int H, int head_dim, long stride_t, long stride_h,
+                                               long ostride_t, long ostride_h, float scale, void* workspace_dev, size_t workspace_bytes, void* stream) {
+  IX_ARG(cos_sin_dev && (reinterpret_cast<uintptr_t>(cos_sin_dev) & 15) == 0, "attn_full_rope_varlen: the (cos, sin) table must be 16-byte aligned");
+  return attn_full_varlen_run(q_dev, k_dev, v_dev, out_dev, cos_sin_dev, table_dev, nseq, total_tiles, n_work, H, head_dim, stride_t, stride_h, ostride_t,
+                              ostride_h, scale, workspace_dev, workspace_bytes, stream);
 }

@@ -37,7 +37,8 @@ size_t attn_full_x3_plane_bytes(int B, int H, int T) {
 //   V block  [plane][unit 8 = (j, u, kh)][d 64]: element e = key 32j + 16u + 8(e>>2) + 4kh + (e&3) of one d
 // Keys at or beyond T are written as zeros (their scores are masked in the attention kernel).
 // VL (packed sequences): blockIdx.x is a tile of all sequences' tiles; sequence s's tiles sit at tile_off[s] of head h's run
-template <bool VL>
+// ROPE: the keys arrive unrotated; the 4 pairs of a (key, oct) are rotated by a.rope[key's position] before the split
+template <bool VL, bool ROPE = false>
 __global__ __launch_bounds__(256) void attn_kv_planes_kernel(AttnFullArgs a, uint4* __restrict__ planes) {
   int tile = blockIdx.x, T = a.T;
   const float *kb, *vb;
@@ -66,7 +67,15 @@ __global__ __launch_bounds__(256) void attn_kv_planes_kernel(AttnFullArgs a, uin
     const int t = t0 + key;
     float v[8];
     const float4* src = reinterpret_cast<const float4*>(kb + (long)min(t, T - 1) * a.st + 8 * oct);
-    const float4 x0 = src[0], x1 = src[1];
+    float4 x0 = src[0], x1 = src[1];
+    if constexpr (ROPE) {
+      const float4* f = reinterpret_cast<const float4*>(a.rope + (long)min(t, T - 1) * (AF_D / 2) + 4 * oct);
+      const float4 f01 = f[0], f23 = f[1];
+      const float2 r0 = rope_rotate(x0.x, x0.y, make_float2(f01.x, f01.y)), r1 = rope_rotate(x0.z, x0.w, make_float2(f01.z, f01.w));
+      const float2 r2 = rope_rotate(x1.x, x1.y, make_float2(f23.x, f23.y)), r3 = rope_rotate(x1.z, x1.w, make_float2(f23.z, f23.w));
+      x0 = make_float4(r0.x, r0.y, r1.x, r1.y);
+      x1 = make_float4(r2.x, r2.y, r3.x, r3.y);
+    }
     const bool live = t < T;
     v[0] = live ? x0.x : 0.f; v[1] = live ? x0.y : 0.f; v[2] = live ? x0.z : 0.f; v[3] = live ? x0.w : 0.f;
     v[4] = live ? x1.x : 0.f; v[5] = live ? x1.y : 0.f; v[6] = live ? x1.z : 0.f; v[7] = live ? x1.w : 0.f;
@@ -97,7 +106,8 @@ __global__ __launch_bounds__(256) void attn_kv_planes_kernel(AttnFullArgs a, uin
 
 // VL (packed sequences, KSPLIT 1): blockIdx.x is a work item (sequence s, 128-query block), blockIdx.y the head; the queries and keys
 // are those of sequence s, its key tiles start at tile_off[s] of the head's run of planes
-template <int KSPLIT, bool VL = false>
+// ROPE: the queries arrive unrotated; a lane rotates its query's pairs by a.rope[query's position] before the scaling and the split
+template <int KSPLIT, bool VL = false, bool ROPE = false>
 __global__ __launch_bounds__(AX_WAVES * 64, 3) void attn_full_x3_kernel(AttnFullArgs a, const uint4* __restrict__ planes) {
   __shared__ uint4 Ks[AX_TILE_UNITS];  // [plane][oct][key]
   __shared__ uint4 Vs[AX_TILE_UNITS];  // [plane][unit][d]
@@ -135,7 +145,15 @@ __global__ __launch_bounds__(AX_WAVES * 64, 3) void attn_full_x3_kernel(AttnFull
     const float qs = a.scale * 1.4426950408889634f;
 #pragma unroll
     for (int s = 0; s < 4; ++s) {
-      const float4 x0 = *reinterpret_cast<const float4*>(qrow + 16 * s), x1 = *reinterpret_cast<const float4*>(qrow + 16 * s + 4);
+      float4 x0 = *reinterpret_cast<const float4*>(qrow + 16 * s), x1 = *reinterpret_cast<const float4*>(qrow + 16 * s + 4);
+      if constexpr (ROPE) {
+        const float4* f = reinterpret_cast<const float4*>(a.rope + (long)qi * (AF_D / 2) + 8 * s + 4 * lh);
+        const float4 f01 = f[0], f23 = f[1];
+        const float2 r0 = rope_rotate(x0.x, x0.y, make_float2(f01.x, f01.y)), r1 = rope_rotate(x0.z, x0.w, make_float2(f01.z, f01.w));
+        const float2 r2 = rope_rotate(x1.x, x1.y, make_float2(f23.x, f23.y)), r3 = rope_rotate(x1.z, x1.w, make_float2(f23.z, f23.w));
+        x0 = make_float4(r0.x, r0.y, r1.x, r1.y);
+        x1 = make_float4(r2.x, r2.y, r3.x, r3.y);
+      }
       const float v[8] = {x0.x * qs, x0.y * qs, x0.z * qs, x0.w * qs, x1.x * qs, x1.y * qs, x1.z * qs, x1.w * qs};
       split8_bf16x3(v, qp[s][0], qp[s][1], qp[s][2]);
     }
@@ -294,6 +312,13 @@ int launch_attn_full_x3(const AttnFullArgs& a, void* planes, bool split, hipStre
   const int n_tiles = ceil_div(a.T, AF_KT);
   const int qblocks = ceil_div(a.T, AX_WAVES * AF_QW);
   uint4* pl = reinterpret_cast<uint4*>(planes);
+  if (a.rope) {
+    hipLaunchKernelGGL((attn_kv_planes_kernel<false, true>), dim3(n_tiles, a.B * a.H), dim3(256), 0, st, a, pl);
+    if (split) hipLaunchKernelGGL((attn_full_x3_kernel<AX_KSPLIT, false, true>), dim3(qblocks, a.B * a.H, AX_KSPLIT), dim3(AX_WAVES * 64), 0, st, a, (const uint4*)pl);
+    else hipLaunchKernelGGL((attn_full_x3_kernel<1, false, true>), dim3(qblocks, a.B * a.H), dim3(AX_WAVES * 64), 0, st, a, (const uint4*)pl);
+    IX_HIP(hipGetLastError());
+    return IXTTS_OK;
+  }
   hipLaunchKernelGGL(attn_kv_planes_kernel<false>, dim3(n_tiles, a.B * a.H), dim3(256), 0, st, a, pl);
   if (split) hipLaunchKernelGGL(attn_full_x3_kernel<AX_KSPLIT>, dim3(qblocks, a.B * a.H, AX_KSPLIT), dim3(AX_WAVES * 64), 0, st, a, (const uint4*)pl);
   else hipLaunchKernelGGL(attn_full_x3_kernel<1>, dim3(qblocks, a.B * a.H), dim3(AX_WAVES * 64), 0, st, a, (const uint4*)pl);
@@ -305,6 +330,12 @@ int launch_attn_full_x3(const AttnFullArgs& a, void* planes, bool split, hipStre
 // heads, so short sequences leave no idle workgroups.  No key-range split: the grid holds every sequence's query blocks.
 int launch_attn_full_x3_varlen(const AttnFullArgs& a, void* planes, int n_work, hipStream_t st) {
   uint4* pl = reinterpret_cast<uint4*>(planes);
+  if (a.rope) {
+    hipLaunchKernelGGL((attn_kv_planes_kernel<true, true>), dim3(a.vl_tiles, a.H), dim3(256), 0, st, a, pl);
+    hipLaunchKernelGGL((attn_full_x3_kernel<1, true, true>), dim3(n_work, a.H), dim3(AX_WAVES * 64), 0, st, a, (const uint4*)pl);
+    IX_HIP(hipGetLastError());
+    return IXTTS_OK;
+  }
   hipLaunchKernelGGL(attn_kv_planes_kernel<true>, dim3(a.vl_tiles, a.H), dim3(256), 0, st, a, pl);
   hipLaunchKernelGGL((attn_full_x3_kernel<1, true>), dim3(n_work, a.H), dim3(AX_WAVES * 64), 0, st, a, (const uint4*)pl);
   IX_HIP(hipGetLastError());

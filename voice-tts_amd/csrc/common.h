@@ -59,6 +59,13 @@ __device__ __forceinline__ int seq_of_row(const int* __restrict__ off, int n, lo
   return lo;
 }
 
+// RoPE of one pair: (x + i y) (cos + i sin), f = (cos, sin).  The roundings are those `rope_qk_kernel` (dit_ops.hip) has always been
+// compiled to -- the sine product rounded on its own, the cosine product fused with the sum -- written out so that every kernel that
+// rotates (rope_qk_kernel, and the K split and Q load of attn_full_x3.hip) gives the same bits whatever the compiler contracts.
+__device__ __forceinline__ float2 rope_rotate(float x, float y, float2 f) {
+  return make_float2(__fmaf_rn(x, f.x, -__fmul_rn(y, f.y)), __fmaf_rn(y, f.x, __fmul_rn(x, f.y)));
+}
+
 __device__ __forceinline__ float lo_bf16(unsigned int w) { return __uint_as_float(w << 16); }
 __device__ __forceinline__ float hi_bf16(unsigned int w) { return __uint_as_float(w & 0xffff0000u); }
 

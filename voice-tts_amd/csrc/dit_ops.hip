@@ -13,13 +13,43 @@ namespace ixtts {
 
 constexpr int ROW_NV = 8;  // float4 per lane: rows up to 64 * 8 * 4 = 2048 floats
 
+// PLANES form of row_norm_mod_kernel: 8 rows per workgroup.  The waves leave their output rows in LDS (row stride H + 4 floats) instead
+// of global memory; this pass then writes them as the bf16 planes [H/16][3][2][Mpad] of gemm_x6.hip, one (row, k-octet) unit per
+// thread and plane, the 8 rows of a unit contiguous across lanes (full 128-byte lines).  Same values through the same split8_bf16x3
+// as `ixtts_gemm_x6_split` over the fp32 output: the same bytes.
+constexpr int NORM_PLANES_ROWS = 8;
+__device__ __forceinline__ void norm_planes_store(const float* tile, uint4* __restrict__ planes, long row0, int H, long Mpad) {
+  __syncthreads();
+  const int S = H + 4;
+  for (int idx = threadIdx.x; idx < H; idx += 64 * NORM_PLANES_ROWS) {  // 8 rows x H / 8 octets
+    const int r = idx & 7, o = idx >> 3;
+    const float4 a = *reinterpret_cast<const float4*>(tile + r * S + 8 * o), b = *reinterpret_cast<const float4*>(tile + r * S + 8 * o + 4);
+    const float v[8] = {a.x, a.y, a.z, a.w, b.x, b.y, b.z, b.w};
+    uint4 ph, pm, pl;
+    split8_bf16x3(v, ph, pm, pl);
+    const int gk = o >> 1, kh = o & 1;
+    uint4* base = planes + ((long)gk * 6) * Mpad + row0 + r;
+    base[(long)(0 * 2 + kh) * Mpad] = ph;
+    base[(long)(1 * 2 + kh) * Mpad] = pm;
+    base[(long)(2 * 2 + kh) * Mpad] = pl;
+  }
+}
+
 // one wavefront per row; the row lives in registers between the statistics and the output pass
-template <bool CENTER>
-__global__ __launch_bounds__(256) void row_norm_mod_kernel(const float* __restrict__ x, const float* __restrict__ mw, const float* __restrict__ mb,
-                                                           const float* __restrict__ g, float* __restrict__ out, long rows, int T, int H, long mstride,
-                                                           float eps, float wadd, const int* __restrict__ seq_off = nullptr, int nseq = 0) {
-  const long row = (long)blockIdx.x * 4 + (threadIdx.x >> 6);
-  if (row >= rows) return;
+// PLANES: `out` is the plane buffer of Mpad rows (the launch covers all of them: rows >= `rows` are written as zeros), see above
+template <bool CENTER, bool PLANES = false>
+__global__ __launch_bounds__(PLANES ? 64 * NORM_PLANES_ROWS : 256) void row_norm_mod_kernel(
+    const float* __restrict__ x, const float* __restrict__ mw, const float* __restrict__ mb, const float* __restrict__ g, float* __restrict__ out, long rows, int T,
+    int H, long mstride, float eps, float wadd, const int* __restrict__ seq_off = nullptr, int nseq = 0, long Mpad = 0) {
+  extern __shared__ float4 norm_tile[];  // PLANES: [8][H / 4 + 1]
+  const long row = (long)blockIdx.x * (PLANES ? NORM_PLANES_ROWS : 4) + (threadIdx.x >> 6);
+  if (row >= rows) {
+    if constexpr (PLANES) {
+      for (int c = threadIdx.x & 63; c < (H >> 2); c += 64) norm_tile[(threadIdx.x >> 6) * ((H >> 2) + 1) + c] = make_float4(0.f, 0.f, 0.f, 0.f);
+      norm_planes_store(reinterpret_cast<const float*>(norm_tile), reinterpret_cast<uint4*>(out), (long)blockIdx.x * NORM_PLANES_ROWS, H, Mpad);
+    }
+    return;
+  }
   const int lane = threadIdx.x & 63;
   const int H4 = H >> 2;
   const float4* xr = reinterpret_cast<const float4*>(x + row * H);
@@ -86,9 +116,13 @@ __global__ __launch_bounds__(256) void row_norm_mod_kernel(const float* __restri
         const float4 gg = g4[c];
         n.x *= gg.x; n.y *= gg.y; n.z *= gg.z; n.w *= gg.w;
       }
-      o4[c] = make_float4(fmaf(w.x + wadd, n.x, b.x), fmaf(w.y + wadd, n.y, b.y), fmaf(w.z + wadd, n.z, b.z), fmaf(w.w + wadd, n.w, b.w));
+      const float4 o = make_float4(fmaf(w.x + wadd, n.x, b.x), fmaf(w.y + wadd, n.y, b.y), fmaf(w.z + wadd, n.z, b.z), fmaf(w.w + wadd, n.w, b.w));
+      if constexpr (PLANES) norm_tile[(threadIdx.x >> 6) * (H4 + 1) + c] = o;
+      else o4[c] = o;
     }
   }
+  if constexpr (PLANES)
+    norm_planes_store(reinterpret_cast<const float*>(norm_tile), reinterpret_cast<uint4*>(out), (long)blockIdx.x * NORM_PLANES_ROWS, H, Mpad);
 }
 
 // qkv [rows][3H]; q = cols [0,H), k = cols [H,2H); pair i of head h sits at h*hd + 2i, +1; table [T][hd/2] (cos, sin)
@@ -106,7 +140,8 @@ __global__ __launch_bounds__(256) void rope_qk_kernel(float* __restrict__ qkv, c
   float4* ptr = reinterpret_cast<float4*>(qkv + row * 3 * H + col);
   const float4 v = *ptr;
   const float2 f0 = tab[(long)t * (hd >> 1) + p], f1 = tab[(long)t * (hd >> 1) + p + 1];
-  *ptr = make_float4(v.x * f0.x - v.y * f0.y, v.y * f0.x + v.x * f0.y, v.z * f1.x - v.w * f1.y, v.w * f1.x + v.z * f1.y);
+  const float2 r0 = rope_rotate(v.x, v.y, f0), r1 = rope_rotate(v.z, v.w, f1);
+  *ptr = make_float4(r0.x, r0.y, r1.x, r1.y);
 }
 
 __global__ __launch_bounds__(256) void swiglu_kernel(const float* __restrict__ u, float* __restrict__ out, long rows, int Fd) {
@@ -205,6 +240,25 @@ extern "C" int ixtts_adaln_rmsnorm_f32(const float* x_dev, const float* wb_dev, 
   return IXTTS_OK;
 }
 
+// The same norm, written as the gemm_x6 planes of its output (what ixtts_gemm_x6_split makes of it), every padded row included
+static int launch_adaln_rmsnorm_planes(const float* x_dev, const float* wb_dev, const float* g_dev, void* planes_dev, long rows, int T, int H, float eps,
+                                       const int* seq_off_dev, int nseq, void* stream) {
+  const long Mpad = ixtts_gemm_x6_rows_padded(rows);
+  const size_t lds = (size_t)NORM_PLANES_ROWS * (H / 4 + 1) * sizeof(float4);
+  hipLaunchKernelGGL((row_norm_mod_kernel<false, true>), dim3((unsigned)(Mpad / NORM_PLANES_ROWS)), dim3(64 * NORM_PLANES_ROWS), lds, (hipStream_t)stream, x_dev,
+                     wb_dev, wb_dev + H, g_dev, reinterpret_cast<float*>(planes_dev), rows, T, H, (long)2 * H, eps, 0.0f, seq_off_dev, nseq, Mpad);
+  IX_HIP(hipGetLastError());
+  return IXTTS_OK;
+}
+
+extern "C" int ixtts_adaln_rmsnorm_planes_f32(const float* x_dev, const float* wb_dev, const float* g_dev, void* planes_dev, int B, int T, int H, float eps,
+                                              void* stream) {
+  IX_ARG(x_dev && wb_dev && g_dev && planes_dev, "adaln_rmsnorm_planes: null pointer");
+  IX_ARG(B > 0 && T > 0 && H > 0 && H % 64 == 0 && H <= 1024, "adaln_rmsnorm_planes: bad shape B=%d T=%d H=%d (H a multiple of 64, at most 1024)", B, T, H);
+  IX_ARG((reinterpret_cast<uintptr_t>(planes_dev) & 127) == 0, "adaln_rmsnorm_planes: planes must be 128-byte aligned");
+  return launch_adaln_rmsnorm_planes(x_dev, wb_dev, g_dev, planes_dev, (long)B * T, T, H, eps, nullptr, 0, stream);
+}
+
 extern "C" int ixtts_ln_modulate_f32(const float* x_dev, const float* shift_scale_dev, float* out_dev, int B, int T, int H, float eps, void* stream) {
   IX_ARG(x_dev && shift_scale_dev && out_dev, "ln_modulate: null pointer");
   IX_ARG(B > 0 && T > 0 && H > 0 && H % 4 == 0 && H <= 64 * ROW_NV * 4, "ln_modulate: bad shape B=%d T=%d H=%d", B, T, H);
@@ -277,6 +331,15 @@ extern "C" int ixtts_adaln_rmsnorm_varlen_f32(const float* x_dev, const float* w
                      rows, 1, H, (long)2 * H, eps, 0.0f, seq_off_dev, nseq);
   IX_HIP(hipGetLastError());
   return IXTTS_OK;
+}
+
+extern "C" int ixtts_adaln_rmsnorm_planes_varlen_f32(const float* x_dev, const float* wb_dev, const float* g_dev, void* planes_dev, const int* seq_off_dev,
+                                                     int nseq, long rows, int H, float eps, void* stream) {
+  IX_ARG(x_dev && wb_dev && g_dev && planes_dev && seq_off_dev, "adaln_rmsnorm_planes_varlen: null pointer");
+  IX_ARG(nseq > 0 && rows > 0 && H > 0 && H % 64 == 0 && H <= 1024, "adaln_rmsnorm_planes_varlen: bad shape nseq=%d rows=%ld H=%d (H a multiple of 64, at most 1024)",
+         nseq, rows, H);
+  IX_ARG((reinterpret_cast<uintptr_t>(planes_dev) & 127) == 0, "adaln_rmsnorm_planes_varlen: planes must be 128-byte aligned");
+  return launch_adaln_rmsnorm_planes(x_dev, wb_dev, g_dev, planes_dev, rows, 1, H, eps, seq_off_dev, nseq, stream);
 }
 
 extern "C" int ixtts_ln_modulate_varlen_f32(const float* x_dev, const float* shift_scale_dev, float* out_dev, const int* seq_off_dev, int nseq, long rows, int H,

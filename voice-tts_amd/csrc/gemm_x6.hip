@@ -11,7 +11,8 @@
 //   * the WEIGHTS are split once at load (`ixtts_gemm_x6_pack`) into planes [k/16][plane 3][k-half 2][N_pad] of 16-byte units
 //     (eight consecutive k of one output feature = the B operand of a lane);
 //   * the ACTIVATIONS are split into the same layout [k/16][3][2][M_pad] by a small pass (`ixtts_gemm_x6_split`: one coalesced read of
-//     the fp32 rows, 6 B per element written) -- a producer that writes the planes itself saves that pass;
+//     the fp32 rows, 6 B per element written) -- a producer that writes the planes itself saves that pass (the AdaLN norm in front
+//     of [w1; w3] does: dit_ops.hip, `ixtts_adaln_rmsnorm_planes_f32`);
 //   * both are copied global -> LDS by LDS-DMA into a 4-stage ring, THREE 16-deep steps ahead of the MFMAs: with one step of cover
 //     (the first version) every barrier waited out a full L2 / Infinity-Cache round trip and the kernel ran at the library's speed;
 //   * the blockIdx -> tile map gives each XCD a contiguous run of tiles, row-tile major: the tiles of one XCD share their A rows in
@@ -49,7 +50,32 @@ __global__ void gemm_x6_pack_kernel(const float* __restrict__ w, uint4* __restri
 
 // Activations A [M][K] (row stride lda) -> the same packed planes [K/16][3][2][Mpad] units, rows >= M zero.  One workgroup = 64 rows x
 // 64 k: coalesced 256-byte row reads into an LDS tile, then one (row, k-octet) unit per thread and plane, rows contiguous across lanes.
-__global__ __launch_bounds__(256) void gemm_x6_split_kernel(const float* __restrict__ a, long lda, uint4* __restrict__ out, int M, int K, long Mpad) {
+// HALO (the WaveNet's reflect-padded row buffers): a halo row is read from the interior row that `reflect_halo_rows_kernel` would have
+// copied into it, so the planes equal halo refresh + split without the refresh.  1: sequences of hleft + hT + hright rows back to back;
+// 2: packed, sequence s = rows [hoff[s], hoff[s+1]) with its own halo rows (one too short to reflect is read as it is, as the refresh
+// leaves it).
+template <int HALO>
+__device__ __forceinline__ long split_src_row(long rr, int hT, int hleft, int hright, const int* __restrict__ hoff, int hn) {
+  if constexpr (HALO == 0) return rr;
+  long o0;
+  int T = hT;
+  if constexpr (HALO == 1) {
+    o0 = rr / (hleft + hT + hright) * (hleft + hT + hright);
+  } else {
+    const int s = seq_of_row(hoff, hn, rr);
+    o0 = hoff[s];
+    T = hoff[s + 1] - (int)o0 - hleft - hright;
+    if (T <= hleft || T <= hright) return rr;
+  }
+  const int h = (int)(rr - o0);
+  if (h < hleft) return o0 + 2 * hleft - h;                          // halo row hleft-1-i <- interior row i+1
+  if (h >= hleft + T && h < hleft + T + hright) return o0 + 2 * (hleft + T) - 2 - h;  // halo row hleft+T+i <- interior row T-2-i
+  return rr;
+}
+
+template <int HALO = 0>
+__global__ __launch_bounds__(256) void gemm_x6_split_kernel(const float* __restrict__ a, long lda, uint4* __restrict__ out, int M, int K, long Mpad, int hT = 0,
+                                                            int hleft = 0, int hright = 0, const int* __restrict__ hoff = nullptr, int hn = 0) {
   __shared__ float tile[64][65];
   const int r0 = blockIdx.x * 64, k0 = blockIdx.y * 64;
   const int t = threadIdx.x;
@@ -57,7 +83,7 @@ __global__ __launch_bounds__(256) void gemm_x6_split_kernel(const float* __restr
   for (int i = 0; i < 4; ++i) {
     const int r = (t >> 4) + 16 * i, kq = t & 15;
     float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
-    if (r0 + r < M) v = *reinterpret_cast<const float4*>(a + (long)(r0 + r) * lda + k0 + 4 * kq);
+    if (r0 + r < M) v = *reinterpret_cast<const float4*>(a + split_src_row<HALO>(r0 + r, hT, hleft, hright, hoff, hn) * lda + k0 + 4 * kq);
     tile[r][4 * kq + 0] = v.x; tile[r][4 * kq + 1] = v.y; tile[r][4 * kq + 2] = v.z; tile[r][4 * kq + 3] = v.w;
   }
   __syncthreads();
@@ -415,8 +441,32 @@ extern "C" int ixtts_gemm_x6_split(const float* a_dev, long lda, void* planes_de
   IX_ARG(a_dev && planes_dev && rows > 0 && K > 0 && K % 64 == 0, "gemm_x6_split: bad argument (K must be a multiple of 64)");
   IX_ARG(lda >= K && lda % 4 == 0 && (reinterpret_cast<uintptr_t>(a_dev) & 15) == 0, "gemm_x6_split: rows must be 16-byte aligned (lda %ld)", lda);
   const long Mpad = ixtts_gemm_x6_rows_padded(rows);
-  hipLaunchKernelGGL(gemm_x6_split_kernel, dim3((unsigned)(Mpad / 64), K / 64), dim3(256), 0, (hipStream_t)stream, a_dev, lda,
+  hipLaunchKernelGGL(gemm_x6_split_kernel<0>, dim3((unsigned)(Mpad / 64), K / 64), dim3(256), 0, (hipStream_t)stream, a_dev, lda,
                      reinterpret_cast<uint4*>(planes_dev), (int)rows, K, Mpad);
+  IX_HIP(hipGetLastError());
+  return IXTTS_OK;
+}
+
+extern "C" int ixtts_gemm_x6_split_halo(const float* a_dev, long lda, void* planes_dev, long rows, int K, int T, int left, int right, void* stream) {
+  IX_ARG(a_dev && planes_dev && rows > 0 && K > 0 && K % 64 == 0, "gemm_x6_split_halo: bad argument (K must be a multiple of 64)");
+  IX_ARG(lda >= K && lda % 4 == 0 && (reinterpret_cast<uintptr_t>(a_dev) & 15) == 0, "gemm_x6_split_halo: rows must be 16-byte aligned (lda %ld)", lda);
+  IX_ARG(left >= 0 && right >= 0 && T > left && T > right && rows % (left + T + right) == 0,
+         "gemm_x6_split_halo: bad shape rows=%ld T=%d left=%d right=%d (rows = whole sequences of left + T + right)", rows, T, left, right);
+  const long Mpad = ixtts_gemm_x6_rows_padded(rows);
+  hipLaunchKernelGGL(gemm_x6_split_kernel<1>, dim3((unsigned)(Mpad / 64), K / 64), dim3(256), 0, (hipStream_t)stream, a_dev, lda,
+                     reinterpret_cast<uint4*>(planes_dev), (int)rows, K, Mpad, T, left, right);
+  IX_HIP(hipGetLastError());
+  return IXTTS_OK;
+}
+
+extern "C" int ixtts_gemm_x6_split_halo_varlen(const float* a_dev, long lda, void* planes_dev, long rows, int K, const int* seq_off_dev, int nseq, int left,
+                                               int right, void* stream) {
+  IX_ARG(a_dev && planes_dev && seq_off_dev && rows > 0 && K > 0 && K % 64 == 0, "gemm_x6_split_halo_varlen: bad argument (K must be a multiple of 64)");
+  IX_ARG(lda >= K && lda % 4 == 0 && (reinterpret_cast<uintptr_t>(a_dev) & 15) == 0, "gemm_x6_split_halo_varlen: rows must be 16-byte aligned (lda %ld)", lda);
+  IX_ARG(nseq > 0 && left >= 0 && right >= 0, "gemm_x6_split_halo_varlen: bad shape nseq=%d left=%d right=%d", nseq, left, right);
+  const long Mpad = ixtts_gemm_x6_rows_padded(rows);
+  hipLaunchKernelGGL(gemm_x6_split_kernel<2>, dim3((unsigned)(Mpad / 64), K / 64), dim3(256), 0, (hipStream_t)stream, a_dev, lda,
+                     reinterpret_cast<uint4*>(planes_dev), (int)rows, K, Mpad, 0, left, right, seq_off_dev, nseq);
   IX_HIP(hipGetLastError());
   return IXTTS_OK;
 }

@@ -3,6 +3,7 @@ fp32 GEMM.  `PackedLinear` holds a weight matrix split once into the bf16 planes
 rows into the same planes (one small pass; several GEMMs over the same input -- or over row-shifted windows of it, the taps of a
 Conv1d -- share it); `linear(x, pl, ...)` = `F.linear` / `addmm_`.  Device tensors only (the CPU leg of the glue keeps torch's GEMM)."""
 import ctypes as C
+import os
 
 import torch
 
@@ -44,21 +45,46 @@ def usable(x, K):
         (x.dim() == 1 or (x.stride(-2) % 4 == 0 and x.stride(-2) >= K))
 
 
-def split(x, slot=0):
+def fused():
+    """Whether the s2mel glue passes ride in their neighbours: the AdaLN norm in front of [w1; w3] writes the planes itself, the
+    WaveNet split reads its halo rows from their mirror rows, the attention rotates q and k as it splits them.
+    `IXTTS_S2MEL_FUSED=0` takes the separate passes (A/B runs, tests) -- the same bytes either way."""
+    return os.environ.get("IXTTS_S2MEL_FUSED", "1") != "0"
+
+
+def planes_buffer(rows, K, device, slot=0):
+    """The scratch buffer `split` would put the planes of [rows, K] into."""
+    nbytes = (K // 16) * 6 * int(_lib.lib().ixtts_gemm_x6_rows_padded(rows)) * 16
+    key = (device, nbytes, slot)
+    buf = _POOL.get(key)
+    if buf is None:
+        buf = _POOL[key] = torch.empty(nbytes, dtype=torch.uint8, device=device)
+    return buf
+
+
+def split(x, slot=0, halo=None):
     """x [..., K] fp32 (contiguous, or a 2-D view with one row stride) -> Planes.  `slot` names the scratch buffer: planes made with
-    the same (size, slot) overwrite each other."""
+    the same (size, slot) overwrite each other.  halo: x is a reflect-padded row buffer whose halo rows are taken from the interior
+    rows they mirror, whatever they hold (the planes of `reflect_halo_rows` + split) -- (T, left, right) for sequences of
+    left + T + right rows back to back, (pack, left, right) for a pack of padded sequences (`.tab` int32 device offsets, `.n`)."""
     K = int(x.shape[-1])
     if x.dim() != 2:
         x = x.reshape(-1, K) if x.is_contiguous() else x.contiguous().reshape(-1, K)
     rows, lda = int(x.shape[0]), int(x.stride(0))
     L = _lib.lib()
-    nbytes = (K // 16) * 6 * int(L.ixtts_gemm_x6_rows_padded(rows)) * 16
-    key = (x.device, nbytes, slot)
-    buf = _POOL.get(key)
-    if buf is None:
-        buf = _POOL[key] = torch.empty(nbytes, dtype=torch.uint8, device=x.device)
+    buf = planes_buffer(rows, K, x.device, slot)
     with torch.cuda.device(x.device):
-        _lib.check(L.ixtts_gemm_x6_split(x.data_ptr(), lda, buf.data_ptr(), rows, K, _lib.current_stream_ptr()), "ixtts_gemm_x6_split")
+        if halo is None:
+            _lib.check(L.ixtts_gemm_x6_split(x.data_ptr(), lda, buf.data_ptr(), rows, K, _lib.current_stream_ptr()), "ixtts_gemm_x6_split")
+        elif isinstance(halo[0], int):
+            T, left, right = halo
+            _lib.check(L.ixtts_gemm_x6_split_halo(x.data_ptr(), lda, buf.data_ptr(), rows, K, T, left, right, _lib.current_stream_ptr()),
+                       "ixtts_gemm_x6_split_halo")
+        else:
+            pk, left, right = halo
+            assert rows == pk.rows and min(pk.lens) - left - right > max(left, right)
+            _lib.check(L.ixtts_gemm_x6_split_halo_varlen(x.data_ptr(), lda, buf.data_ptr(), rows, K, pk.tab.data_ptr(), pk.n, left, right,
+                                                         _lib.current_stream_ptr()), "ixtts_gemm_x6_split_halo_varlen")
     return Planes(buf, rows, K)
 
 

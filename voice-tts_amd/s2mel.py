@@ -120,9 +120,11 @@ def _pad_reflect(x, left, right):
     return y[..., : y.shape[-1] - extra]
 
 
-def attn_full(q, k, v, scale=None):
+def attn_full(q, k, v, scale=None, rope=None):
     """softmax(scale * q k^T) v for q, k, v [B, T, h, 64] fp32 CUDA tensors (any strides with d contiguous) through
-    libixtts_hip.so's fp32-MFMA flash kernel (csrc/attn_full.hip); returns [B, T, h, 64] contiguous."""
+    libixtts_hip.so's fp32-MFMA flash kernel (csrc/attn_full.hip); returns [B, T, h, 64] contiguous.
+    rope: complex64 [>= T, 32] -- q and k come unrotated and the kernel rotates them as it splits them (csrc/attn_full_x3.hip; not
+    with IXTTS_ATTN_FULL=f32): the bits of `ixtts_rope_qk_f32` followed by this call without `rope`."""
     import ctypes as C
 
     from . import _lib
@@ -137,10 +139,16 @@ def attn_full(q, k, v, scale=None):
     nws = L.ixtts_attn_full_workspace_bytes(B, Hh, T)
     ws = torch.empty(nws, device=q.device, dtype=torch.uint8)  # scratch for the key-split partials (caching allocator: no hipMalloc)
     with torch.cuda.device(q.device):
-        rc = L.ixtts_attn_full_f32(q.data_ptr(), k.data_ptr(), v.data_ptr(), out.data_ptr(), B, Hh, T, d, q.stride(0), q.stride(1),
-                                   q.stride(2), out.stride(0), out.stride(1), out.stride(2), C.c_float(sc), ws.data_ptr(), nws,
-                                   _lib.current_stream_ptr())
-    _lib.check(rc, "ixtts_attn_full_f32")
+        if rope is not None:
+            assert rope.dtype == torch.complex64 and rope.is_contiguous() and rope.shape[0] >= T and rope.shape[1] == d // 2
+            rc = L.ixtts_attn_full_rope_f32(q.data_ptr(), k.data_ptr(), v.data_ptr(), out.data_ptr(), torch.view_as_real(rope).data_ptr(), rope.shape[0], B, Hh,
+                                            T, d, q.stride(0), q.stride(1), q.stride(2), out.stride(0), out.stride(1), out.stride(2), C.c_float(sc),
+                                            ws.data_ptr(), nws, _lib.current_stream_ptr())
+        else:
+            rc = L.ixtts_attn_full_f32(q.data_ptr(), k.data_ptr(), v.data_ptr(), out.data_ptr(), B, Hh, T, d, q.stride(0), q.stride(1),
+                                       q.stride(2), out.stride(0), out.stride(1), out.stride(2), C.c_float(sc), ws.data_ptr(), nws,
+                                       _lib.current_stream_ptr())
+    _lib.check(rc, "ixtts_attn_full_rope_f32" if rope is not None else "ixtts_attn_full_f32")
     return out
 
 
@@ -170,6 +178,25 @@ def adaln_rmsnorm(x, wb, g, eps=1e-5):
         return out
     w, b = wb[:, None, :H], wb[:, None, H:]
     return torch.addcmul(b, w, F.rms_norm(x, (H,), g, eps))
+
+
+def adaln_rmsnorm_planes(x, wb, g, eps=1e-5, pk=None):
+    """`adaln_rmsnorm` (pk: `adaln_rmsnorm_packed`) for a consumer that is a split-product GEMM: the norm's rows as `G.Planes`, written
+    by the norm kernel itself -- the bytes `G.split` makes of the fp32 rows, which are not written.  Device only; H % 64 == 0."""
+    import ctypes as C
+
+    H = x.shape[-1]
+    rows = x.numel() // H
+    x, wb = x.contiguous(), wb.contiguous()
+    buf = G.planes_buffer(rows, H, x.device)
+    with torch.cuda.device(x.device):
+        if pk is None:
+            B, T, _ = x.shape
+            _hip_call("ixtts_adaln_rmsnorm_planes_f32", x.data_ptr(), wb.data_ptr(), g.data_ptr(), buf.data_ptr(), B, T, H, C.c_float(eps))
+        else:
+            _hip_call("ixtts_adaln_rmsnorm_planes_varlen_f32", x.data_ptr(), wb.data_ptr(), g.data_ptr(), buf.data_ptr(), pk.tab.data_ptr(), pk.n, rows, H,
+                      C.c_float(eps))
+    return G.Planes(buf, rows, H)
 
 
 def ln_modulate(x, ss, eps=1e-6):
@@ -322,9 +349,10 @@ def rope_qk_packed(qkv, fc, pk, head_dim):
     return out
 
 
-def attn_full_packed(q, k, v, pk, scale=None):
+def attn_full_packed(q, k, v, pk, scale=None, rope=None):
     """softmax(scale q k^T) v per sequence of a pack: q, k, v [rows, h, 64] strided views (d contiguous, one row stride) of device fp32
-    rows; queries of sequence s see the keys of sequence s only (csrc/attn_full_x3.hip, varlen entry).  Returns [rows, h, 64]."""
+    rows; queries of sequence s see the keys of sequence s only (csrc/attn_full_x3.hip, varlen entry).  Returns [rows, h, 64].
+    rope: as `attn_full` (positions restart at 0 in each sequence; the table covers the longest)."""
     import ctypes as C
 
     from . import _lib
@@ -339,9 +367,16 @@ def attn_full_packed(q, k, v, pk, scale=None):
     nws = L.ixtts_attn_full_varlen_workspace_bytes(pk.n, Hh, pk.tiles)
     ws = torch.empty(nws, device=q.device, dtype=torch.uint8)
     with torch.cuda.device(q.device):
-        rc = L.ixtts_attn_full_varlen_f32(q.data_ptr(), k.data_ptr(), v.data_ptr(), out.data_ptr(), pk.tab.data_ptr(), pk.n, pk.tiles, pk.n_work, Hh, d,
-                                          q.stride(0), q.stride(1), out.stride(0), out.stride(1), C.c_float(sc), ws.data_ptr(), nws, _lib.current_stream_ptr())
-    _lib.check(rc, "ixtts_attn_full_varlen_f32")
+        if rope is not None:
+            assert rope.dtype == torch.complex64 and rope.is_contiguous() and rope.shape[0] >= max(pk.lens) and rope.shape[1] == d // 2
+            rc = L.ixtts_attn_full_rope_varlen_f32(q.data_ptr(), k.data_ptr(), v.data_ptr(), out.data_ptr(), torch.view_as_real(rope).data_ptr(),
+                                                   pk.tab.data_ptr(), pk.n, pk.tiles, pk.n_work, Hh, d, q.stride(0), q.stride(1), out.stride(0), out.stride(1),
+                                                   C.c_float(sc), ws.data_ptr(), nws, _lib.current_stream_ptr())
+        else:
+            rc = L.ixtts_attn_full_varlen_f32(q.data_ptr(), k.data_ptr(), v.data_ptr(), out.data_ptr(), pk.tab.data_ptr(), pk.n, pk.tiles, pk.n_work, Hh, d,
+                                              q.stride(0), q.stride(1), out.stride(0), out.stride(1), C.c_float(sc), ws.data_ptr(), nws,
+                                              _lib.current_stream_ptr())
+    _lib.check(rc, "ixtts_attn_full_rope_varlen_f32" if rope is not None else "ixtts_attn_full_varlen_f32")
     return out
 
 
@@ -484,6 +519,7 @@ class S2Mel:
         half = 128
         self.t_freqs = torch.exp(-math.log(10000.0) * torch.arange(half, dtype=torch.float32) / half).to(self.device).to(dtype)
         self._rope = None
+        self._t_consts = {}  # (n_timesteps, step, batch), name -> what a DiT evaluation derives from t alone (`_t_const`)
         # derived weights (exact re-arrangements: concatenations / column splits of the reference's matrices)
         W, C_, L = self.W, cfg["in_channels"], cfg["depth"]
         t = "cfm.estimator.transformer."
@@ -571,6 +607,19 @@ class S2Mel:
         h = F.silu(_lin(emb, self.W, prefix + ".mlp.0"))
         return _lin(h, self.W, prefix + ".mlp.2")
 
+    def _t_const(self, tkey, name, fn):
+        """`fn()`, computed once per (tkey, name): the pieces of a DiT evaluation that depend on the Euler step's t alone -- the two
+        timestep embeddings, the AdaLN (weight | bias) slabs, the WaveNet's cond_layer output, the final layer's (shift | scale).
+        t_span = linspace(0, 1, n + 1) does not depend on the request, so they are constants of tkey = (n_timesteps, step, batch) for
+        this model's weights, device and dtype: the same calls on the same inputs, made once (25 steps x ~0.3 MB at production width).
+        Consumers only read them.  tkey None, or IXTTS_S2MEL_TCACHE=0: computed every time."""
+        if tkey is None or os.environ.get("IXTTS_S2MEL_TCACHE", "1") == "0":
+            return fn()
+        v = self._t_consts.get((tkey, name))
+        if v is None:
+            v = self._t_consts[(tkey, name)] = fn()
+        return v
+
     def _rope_cache(self, T):
         if self._rope is None or self._rope.shape[0] < T:
             n = self.head_dim
@@ -593,10 +642,13 @@ class S2Mel:
         H, nh, hd = self.cfg["hidden_dim"], self.cfg["num_heads"], self.head_dim
         fc = self._rope_cache(T)
         if mask is None and hd == 64 and qkv.is_cuda:
-            # in-place rotation on the GEMM output, then the fp32-MFMA flash kernel on strided views of it: no copies
+            v4 = qkv.view(B, T, 3, nh, hd)
+            if G.fused() and fc.dtype == torch.complex64 and os.environ.get("IXTTS_ATTN_FULL", "x3") != "f32":
+                # the flash kernel on strided views of the GEMM output rotates q and k as it splits them: no rotation pass, no copies
+                return attn_full(v4[:, :, 0], v4[:, :, 1], v4[:, :, 2], rope=fc).reshape(B * T, H)
+            # in-place rotation on the GEMM output, then the flash kernel on strided views of it
             with torch.cuda.device(qkv.device):
                 _hip_call("ixtts_rope_qk_f32", qkv.data_ptr(), torch.view_as_real(fc).data_ptr(), B, T, H, hd)
-            v4 = qkv.view(B, T, 3, nh, hd)
             return attn_full(v4[:, :, 0], v4[:, :, 1], v4[:, :, 2]).reshape(B * T, H)
         q, k, v = qkv.view(B, T, 3 * H).split([H, H, H], dim=-1)
         q = self._rotary(q.reshape(B, T, nh, hd), fc)
@@ -605,16 +657,17 @@ class S2Mel:
         y = F.scaled_dot_product_attention(q.transpose(1, 2), k.transpose(1, 2), v.transpose(1, 2), attn_mask=mask, dropout_p=0.0)
         return y.transpose(1, 2).reshape(B * T, H)
 
-    def _transformer(self, x, c, mask):
+    def _transformer(self, x, c, mask, tkey=None):
         """Transformer.forward with U-ViT skips (gpt_fast/model.py:167-207): x [B,T,H], c [B,H] -> [B,T,H].  Residual adds
         ride in the GEMM epilogues (addmm), [w1; w3] is one GEMM, the skip concat is two accumulated GEMMs."""
         W, cfg = self.W, self.cfg
         B, T, H = x.shape
         L = cfg["depth"]
         # (weight | bias) of every AdaLN, one contiguous [B, 2H] slab per norm
-        wb_all = F.linear(c, self.proj_w, self.proj_b).view(B, 2 * L + 1, 2 * H).transpose(0, 1).contiguous()
+        wb_all = self._t_const(tkey, "wb_all", lambda: F.linear(c, self.proj_w, self.proj_b).view(B, 2 * L + 1, 2 * H).transpose(0, 1).contiguous())
         x = x.reshape(B * T, H)
         x6 = x.is_cuda and self._x6(self.x6_w13)
+        fuse = G.fused() and H % 64 == 0 and H <= 1024
         skips = []
         for i in range(L):
             p = f"cfm.estimator.transformer.layers.{i}."
@@ -625,8 +678,11 @@ class S2Mel:
             y = self._attention(F.linear(a.view(B * T, H), W[p + "attention.wqkv.weight"]), B, T, mask)
             # residuals accumulate in place where the input is private (layer inputs 1..L/2 are also the saved U-ViT skips)
             h = torch.addmm(x, y, W[p + "attention.wo.weight"].t()) if 0 < i <= L // 2 else x.addmm_(y, W[p + "attention.wo.weight"].t())
-            f = adaln_rmsnorm(h.view(B, T, H), wb_all[2 * i + 1], W[p + "ffn_norm.norm.weight"]).view(B * T, H)
-            u = G.pair_linear(f, self.x6_w13[i], G.SWIGLU) if x6 else swiglu(F.linear(f, self.w13[i]))
+            if x6 and fuse:  # the norm writes the planes [w1; w3] reads
+                u = G.pair_linear(adaln_rmsnorm_planes(h.view(B, T, H), wb_all[2 * i + 1], W[p + "ffn_norm.norm.weight"]), self.x6_w13[i], G.SWIGLU)
+            else:
+                f = adaln_rmsnorm(h.view(B, T, H), wb_all[2 * i + 1], W[p + "ffn_norm.norm.weight"]).view(B * T, H)
+                u = G.pair_linear(f, self.x6_w13[i], G.SWIGLU) if x6 else swiglu(F.linear(f, self.w13[i]))
             x = h.addmm_(u, W[p + "feed_forward.w2.weight"].t())
             if i < L // 2:
                 skips.append(x)
@@ -692,19 +748,20 @@ class S2Mel:
             out = torch.bmm(r2, acts) if out is None else out.baddbmm_(r2, acts)
         return out
 
-    def _wavenet_rows(self, h, g):
+    def _wavenet_rows(self, h, g, tkey=None):
         """The same network with sequences as ROWS (h [B,T,C], dilation 1): every conv is a row-major GEMM `X W^T` (the
         library's fast layout; the channel-major form above runs them at 0.6x the rate).  The B sequences sit in one
         reflect-padded buffer [B, T+k-1, C]; tap j of the k-tap conv is that buffer, flattened, shifted by j rows, so ONE
         GEMM per tap covers all sequences -- the k-1 rows that straddle two sequences are computed and never read (their
-        residual update lands in padding rows, which are refreshed before the next layer reads them).
+        residual update lands in padding rows, which are refreshed before the next layer reads them -- or, on the split-product GEMM,
+        never read: its split takes each padding row from the interior row it mirrors).
         Returns the skip sum [B,T,C] (a strided view) WITHOUT `wn_out_bias`."""
         W, cfg = self.W, self.cfg
         Hw, nl, k = cfg["wavenet_hidden"], cfg["wavenet_layers"], cfg["wavenet_kernel"]
         assert cfg["wavenet_dilation_rate"] == 1
         B, T_, _ = h.shape
         p = "cfm.estimator.wavenet."
-        g = F.linear(g, W[p + "cond_layer.conv.conv.weight"][:, :, 0], W[p + "cond_layer.conv.conv.bias"])
+        g = self._t_const(tkey, "wn_cond", lambda: F.linear(g, W[p + "cond_layer.conv.conv.weight"][:, :, 0], W[p + "cond_layer.conv.conv.bias"]))
         tot = k - 1
         right = tot // 2
         left = tot - right
@@ -716,11 +773,15 @@ class S2Mel:
         centre = P2[left:left + M]  # the input row under output row r
         out = torch.empty(B * Tp, Hw, device=h.device, dtype=h.dtype)
         x6 = self._x6(self.x6_wn)
+        fuse = G.fused()
         for i in range(nl):
-            reflect_halo_rows(P, T_, left, right)
-            if x6:  # the k taps + bias + gate: one GEMM over one split of the padded rows
-                acts = G.pair_linear(G.split(P2), self.x6_wn[i], G.GATE, taps=k, gate=g, gate_off=i * 2 * Hw, rows_per_batch=Tp)
+            if x6:  # the k taps + bias + gate: one GEMM over one split of the padded rows, which reads halo rows from their mirror rows
+                if not fuse:
+                    reflect_halo_rows(P, T_, left, right)
+                acts = G.pair_linear(G.split(P2, halo=(T_, left, right) if fuse else None), self.x6_wn[i], G.GATE, taps=k, gate=g, gate_off=i * 2 * Hw,
+                                     rows_per_batch=Tp)
             else:
+                reflect_halo_rows(P, T_, left, right)
                 acc = torch.addmm(self.wn_bin[i], P2[:M], self.wn_taps[i][0].t())
                 for j in range(1, k):
                     acc.addmm_(P2[j:j + M], self.wn_taps[i][j].t())
@@ -753,21 +814,25 @@ class S2Mel:
                 attn_mask = attn_mask.expand(B, 1, T, T)
         return dict(B=B, T=T, base=base, x_mask=x_mask.to(base.dtype), attn_mask=attn_mask, full=full)
 
-    def dit_step(self, ctx, x, t, out_from=0):
+    def dit_step(self, ctx, x, t, out_from=0, tkey=None):
         """The (x, t)-dependent part of DiT.forward (diffusion_transformer.py:186-257).  x [B,80,T] or [1,80,T] shared by
         the whole batch (the CFG stack feeds the same x to both branches); t [B].
 
         out_from > 0: the caller only uses frames [out_from, T) of the result (the CFM solver zeroes the prompt frames of x
         after every step).  After the transformer nothing mixes frames except the WaveNet's k-tap convs, so the head runs on
         frames [out_from - halo, T) only, halo = the WaveNet's receptive field; the returned tensor covers [out_from, T) and
-        equals the full computation there."""
+        equals the full computation there.
+
+        tkey: names t among the values the solver visits (`_t_const`); what depends on t alone is then computed once per model."""
         W, cfg = self.W, self.cfg
         e = "cfm.estimator."
         B, T, base = ctx["B"], ctx["T"], ctx["base"]
         xt = x.transpose(1, 2)  # [Bx,T,80]
-        t1 = self._t_embed(t, e + "t_embedder")
+        if tkey is not None:
+            tkey = tuple(tkey) + (int(t.shape[0]),)
+        t1 = self._t_const(tkey, "t1", lambda: self._t_embed(t, e + "t_embedder"))
         x_in = base + F.linear(xt, self.merge_x)  # broadcasts a shared x over the batch
-        x_res = self._transformer(x_in, t1, ctx["attn_mask"])
+        x_res = self._transformer(x_in, t1, ctx["attn_mask"], tkey)
         halo = sum((cfg["wavenet_kernel"] - 1) * cfg["wavenet_dilation_rate"] ** i for i in range(cfg["wavenet_layers"])) // 2 + 1
         lo = max(0, out_from - halo) if (ctx["full"] and out_from > 0) else 0
         if lo > 0:
@@ -777,17 +842,17 @@ class S2Mel:
             extend_tuned_gemms(T, Th)
         x_res = F.linear(x_res, self.skipl_res, W[e + "skip_linear.bias"]) + F.linear(xt, self.skipl_x)
         h = _lin(x_res, W, e + "conv1")
-        t2 = self._t_embed(t, e + "t_embedder2")
+        t2 = self._t_const(tkey, "t2", lambda: self._t_embed(t, e + "t_embedder2"))
         gemm_form = h.is_cuda and ctx["full"] and Th > 2 * cfg["wavenet_kernel"] * cfg["wavenet_dilation_rate"] ** (cfg["wavenet_layers"] - 1)
         if gemm_form and cfg["wavenet_dilation_rate"] == 1:
-            h = self._wavenet_rows(h, t2) + F.linear(x_res, W[e + "res_projection.weight"], W[e + "res_projection.bias"] + self.wn_out_bias)
+            h = self._wavenet_rows(h, t2, tkey) + F.linear(x_res, W[e + "res_projection.weight"], W[e + "res_projection.bias"] + self.wn_out_bias)
         elif gemm_form:
             h = self._wavenet_gemm(h.transpose(1, 2), t2).transpose(1, 2) + F.linear(x_res, W[e + "res_projection.weight"],
                                                                                      W[e + "res_projection.bias"] + self.wn_out_bias)
         else:
             mask = ctx["x_mask"][:, :, lo:] if lo > 0 else ctx["x_mask"]
             h = self._wavenet(h.transpose(1, 2), mask, t2, ctx["full"]).transpose(1, 2) + _lin(x_res, W, e + "res_projection")
-        ss = _lin(F.silu(t1), W, e + "final_layer.adaLN_modulation.1")
+        ss = self._t_const(tkey, "final_ss", lambda: _lin(F.silu(t1), W, e + "final_layer.adaLN_modulation.1"))
         h = ln_modulate(h, ss)
         h = _lin(h, W, e + "final_layer.linear").transpose(1, 2)
         out = conv1d(h, W[e + "conv2.weight"], W[e + "conv2.bias"])
@@ -822,10 +887,10 @@ class S2Mel:
         for step in range(1, len(t_span)):
             dt = t_span[step] - t_span[step - 1]
             if inference_cfg_rate > 0:
-                d = self.dit_step(ctx, x, torch.stack([t, t]), out_from=skip)
+                d = self.dit_step(ctx, x, torch.stack([t, t]), out_from=skip, tkey=(n_timesteps, step))
                 dphi = (1.0 + inference_cfg_rate) * d[0:1] - inference_cfg_rate * d[1:2]
             else:
-                dphi = self.dit_step(ctx, x, t.expand(B), out_from=skip)
+                dphi = self.dit_step(ctx, x, t.expand(B), out_from=skip, tkey=(n_timesteps, step))
             if skip > 0:
                 x[:, :, skip:] += dt * dphi
             else:
@@ -852,8 +917,11 @@ class S2Mel:
         its limits are not met (head_dim != 64, IXTTS_ATTN_FULL=f32) -- the single-sequence path, same result."""
         H, nh, hd = self.cfg["hidden_dim"], self.cfg["num_heads"], self.head_dim
         if qkv.is_cuda and hd == 64 and os.environ.get("IXTTS_ATTN_FULL", "x3") != "f32":
-            rope_qk_packed(qkv, self._rope_cache(max(pk.lens)), pk, hd)
+            fc = self._rope_cache(max(pk.lens))
             v4 = qkv.view(pk.rows, 3, nh, hd)
+            if G.fused() and fc.dtype == torch.complex64:
+                return attn_full_packed(v4[:, 0], v4[:, 1], v4[:, 2], pk, rope=fc).view(pk.rows, H)
+            rope_qk_packed(qkv, fc, pk, hd)
             return attn_full_packed(v4[:, 0], v4[:, 1], v4[:, 2], pk).view(pk.rows, H)
         out = torch.empty(pk.rows, H, device=qkv.device, dtype=qkv.dtype)
         if qkv.is_cuda:
@@ -875,6 +943,7 @@ class S2Mel:
         H, L = cfg["hidden_dim"], cfg["depth"]
         wb_all = F.linear(c, self.proj_w, self.proj_b).view(pk.n, 2 * L + 1, 2 * H).transpose(0, 1).contiguous()
         x6 = x.is_cuda and self._x6(self.x6_w13)
+        fuse = G.fused() and H % 64 == 0 and H <= 1024
         skips = []
         for i in range(L):
             p = f"cfm.estimator.transformer.layers.{i}."
@@ -884,8 +953,11 @@ class S2Mel:
             a = adaln_rmsnorm_packed(x, wb_all[2 * i], W[p + "attention_norm.norm.weight"], pk)
             y = self._attention_packed(F.linear(a, W[p + "attention.wqkv.weight"]), pk)
             h = torch.addmm(x, y, W[p + "attention.wo.weight"].t()) if 0 < i <= L // 2 else x.addmm_(y, W[p + "attention.wo.weight"].t())
-            f = adaln_rmsnorm_packed(h, wb_all[2 * i + 1], W[p + "ffn_norm.norm.weight"], pk)
-            u = G.pair_linear(f, self.x6_w13[i], G.SWIGLU) if x6 else swiglu(F.linear(f, self.w13[i]))
+            if x6 and fuse:
+                u = G.pair_linear(adaln_rmsnorm_planes(h, wb_all[2 * i + 1], W[p + "ffn_norm.norm.weight"], pk=pk), self.x6_w13[i], G.SWIGLU)
+            else:
+                f = adaln_rmsnorm_packed(h, wb_all[2 * i + 1], W[p + "ffn_norm.norm.weight"], pk)
+                u = G.pair_linear(f, self.x6_w13[i], G.SWIGLU) if x6 else swiglu(F.linear(f, self.w13[i]))
             x = h.addmm_(u, W[p + "feed_forward.w2.weight"].t())
             if i < L // 2:
                 skips.append(x)
@@ -910,11 +982,15 @@ class S2Mel:
         centre = P2[left:left + M]
         out = torch.empty(pp.rows, Hw, device=h.device, dtype=h.dtype)
         x6 = h.is_cuda and self._x6(self.x6_wn)
+        fuse = G.fused()
         for i in range(nl):
-            reflect_halo_rows_packed(P2, pp, left, right)
             if x6:
-                acts = G.pair_linear(G.split(P2), self.x6_wn[i], G.GATE, taps=k, gate=g, gate_off=i * 2 * Hw, seq_off=pp)
+                if not fuse:
+                    reflect_halo_rows_packed(P2, pp, left, right)
+                acts = G.pair_linear(G.split(P2, halo=(pp, left, right) if fuse else None), self.x6_wn[i], G.GATE, taps=k, gate=g, gate_off=i * 2 * Hw,
+                                     seq_off=pp)
             else:
+                reflect_halo_rows_packed(P2, pp, left, right)
                 acc = torch.addmm(self.wn_bin[i], P2[:M], self.wn_taps[i][0].t())
                 for j in range(1, k):
                     acc.addmm_(P2[j:j + M], self.wn_taps[i][j].t())

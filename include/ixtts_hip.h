@@ -160,7 +160,9 @@ int ixtts_adaln_rmsnorm_planes_varlen_f32(const float* x_dev, const float* wb_de
  *   ixtts_gemm_x6_f32    C[M][N] (row stride ldc) (+)= A[row0 .. row0 + M) . W^T + bias over planes holding rows_total rows (a
  *                        row-shifted window of one split buffer = one tap of a k-tap Conv1d); bias_dev [N] or NULL; accumulate != 0
  *                        adds to what C holds (torch's addmm_); tile: 0 = chosen by the fill of the 256 CUs, 2 / 3 = 256x128 /
- *                        128x128 (A/B timing). */
+ *                        128x128, 6 = 128x128 on the pipelined loop, one workgroup per CU (what 0 picks in place of 3 when
+ *                        there are no more 128x128 tiles than CUs; IXTTS_GEMM_X6_PIPE=0 keeps 3) -- the same bytes from
+ *                        every tile (A/B timing). */
 size_t ixtts_gemm_x6_packed_bytes(int N, int K);
 int ixtts_gemm_x6_pack(const float* w_dev, void* packed_dev, int N, int K, void* stream);
 long ixtts_gemm_x6_rows_padded(long rows);
@@ -179,7 +181,7 @@ int ixtts_gemm_x6_split_halo_varlen(const float* a_dev, long lda, void* planes_d
  * C[M][N/2] = f(a, b), a / b = the two halves' results + bias; epilogue 1 = silu(a) * b (SwiGLU), 2 = tanh(a + g_a) * sigmoid(b + g_b)
  * with (g_a | g_b) = gate_dev[min(r / rows_per_batch, nbatch - 1) * gate_ld + (0 .. N)) for output row r (the WaveNet gate).  taps > 1:
  * K = taps x K_a over planes of K_a columns, k block j of the weights reading the planes' rows shifted down by j (a k-tap Conv1d over a
- * row buffer in one GEMM; rows row0 .. row0 + M + taps - 1 of rows_total are read).  N a multiple of 64; tile 0 / 2 / 3 as above. */
+ * row buffer in one GEMM; rows row0 .. row0 + M + taps - 1 of rows_total are read).  N a multiple of 64; tile 0 / 2 / 3 / 6 as above. */
 int ixtts_gemm_x6_pair_f32(const void* a_planes_dev, long rows_total, long row0, int taps, const void* packed_dev, const float* bias_dev,
                            const float* gate_dev, long gate_ld, long rows_per_batch, int nbatch, float* c_dev, long ldc, int M, int N, int K,
                            int epilogue, int tile, void* stream);

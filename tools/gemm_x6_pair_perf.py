@@ -86,3 +86,7 @@ else:
         t = bench(lambda: G.pair_linear(Pp, plwn, G.GATE, taps=k, out=acts, gate=gate, rows_per_batch=Tp, tile=tile))
         line += f" | tile{tile} {t:6.1f} us ({fl / t / 1e6:5.1f} TF)"
     print(line, flush=True)
+    # tile 3 (two workgroups per CU by design, one in fact at 240 tiles) against tile 6 (the pipelined loop), alternating
+    for rnd in range(4):
+        t3, t6 = (bench(lambda: G.pair_linear(Pp, plwn, G.GATE, taps=k, out=acts, gate=gate, rows_per_batch=Tp, tile=tile), n=100) for tile in (3, 6))
+        print(f"  round {rnd}: tile3 {t3:6.1f} us | tile6 {t6:6.1f} us ({fl / t6 / 1e6:5.1f} TF) | tile6 / tile3 {t6 / t3:.3f}", flush=True)

@@ -138,7 +138,10 @@ struct GemmX6Params {
 // p.gate_seq_off instead of row / rows_per_batch); `run_gemm_x6` dispatches on p.epi / p.accumulate / p.gate_seq_off.
 // PIN: 1 = a step's MFMAs are fenced ahead of its closing wait and barrier (developer A/B, tiles 42 / 43); 0 = the scheduler places
 // them, which measured 1-2 % faster on both production kernels (profiles/r07_notes.md).
-template <int MT, int NT, int NST, int EPI = EPI_PLAIN, int ACC = 0, int SEQ = 0, int DBG = 0, int PIN = 0>
+// PIPE: 1 = the pipelined main loop (tile 6; 128 x 128, 4 stages, one workgroup per CU): a second fragment set in registers and the
+// copies spread through the MFMAs, for grids of no more tiles than CUs, where no second workgroup hides a wave's issue cycles
+// (profiles/r14_notes.md).  0 = the loop described above, instruction for instruction what it was before PIPE existed.
+template <int MT, int NT, int NST, int EPI = EPI_PLAIN, int ACC = 0, int SEQ = 0, int DBG = 0, int PIN = 0, int PIPE = 0>
 __global__ __launch_bounds__(256, (NST * (MT + NT) * 6 * 64 * 16 <= 80 * 1024) ? 2 : 1) void gemm_x6_kernel(GemmX6Params p) {
   constexpr int BM = 64 * MT, BN = 64 * NT;
   constexpr int A_UNITS = 6 * BM, W_UNITS = 6 * BN, STAGE = A_UNITS + W_UNITS;
@@ -198,22 +201,28 @@ __global__ __launch_bounds__(256, (NST * (MT + NT) * 6 * 64 * 16 <= 80 * 1024) ?
   long a_run = 0, w_run = 0;                      // the next step's offsets
   int a_group = 0;                                // and its k-group within the tap
   // STATEFUL: the k-th call issues the copies of step k.  The prologue calls it for steps 0 .. D - 1 and main-loop step s for step
-  // s + D, in that order and with none left out (DBG == 1 stops after the prologue).
-  auto issue_next = [&](uint4* st) {
-#pragma unroll
-    for (int q = 0; q < NA; ++q)
+  // s + D, in that order and with none left out (DBG == 1 stops after the prologue).  It is `issue_piece` for the wave's pieces
+  // q = 0 .. NDMA - 1 and then `issue_advance`; the pipelined loop (PIPE) makes those calls itself, one piece every few MFMAs.
+  auto issue_piece = [&](uint4* st, int q) {
+    if (q < NA)
       __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(asrc + (a_off[q] + a_run)),
                                        (__attribute__((address_space(3))) void*)(st + a_lds[q]), 16, 0, 0);
-#pragma unroll
-    for (int q = 0; q < NW; ++q)
-      __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(wsrc + (w_off[q] + w_run)),
-                                       (__attribute__((address_space(3))) void*)(st + w_lds[q]), 16, 0, 0);
+    else
+      __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(wsrc + (w_off[q - NA] + w_run)),
+                                       (__attribute__((address_space(3))) void*)(st + w_lds[q - NA]), 16, 0, 0);
+  };
+  auto issue_advance = [&]() {
     a_run += a_step;
     w_run += w_step;
     if (++a_group == p.tap_steps) {
       a_group = 0;
       a_run += a_wrap;
     }
+  };
+  auto issue_next = [&](uint4* st) {
+#pragma unroll
+    for (int q = 0; q < NDMA; ++q) issue_piece(st, q);
+    issue_advance();
   };
 
   const int steps = p.K >> 4;
@@ -230,20 +239,55 @@ __global__ __launch_bounds__(256, (NST * (MT + NT) * 6 * 64 * 16 <= 80 * 1024) ?
   };
   static_assert(D >= 1 && D <= 3, "1..3 steps of copies in flight behind the one waited for");
   wg_stamp(0);
-  for (int t = 0; t < D && t < steps; ++t) issue_next(smem + t * STAGE);  // steps 0 .. D - 1
-  wait_younger(min(D, steps) - 1);  // step 0's copies (the oldest) have landed
-  __builtin_amdgcn_s_barrier();
-  asm volatile("" ::: "memory");
-  wg_stamp(1);
-
-  // Step s computes on stage s % NST and, first, issues the copies of step s + D into stage (s + D) % NST (last read in step s - 1,
-  // which every wave has left).  Before its closing barrier a wave waits until its share of step s + 1's copies has landed; the
-  // copies of the steps behind that stay in flight.  Every memory operation here is issued by hand, so a run-time stage index and
-  // run-time issue condition are fine: the compiler has no wait of its own to miscount.
-  const unsigned base_addr = (unsigned)(uintptr_t)(const __attribute__((address_space(3))) void*)smem;
-  int st_cur = 0, st_nxt = D % NST;
-  for (int s = 0; s < steps; ++s) {
-    auto stamp = [&](int k) {
+  if constexpr (PIPE != 0) {
+    // PIPELINED LOOP (tile 6).  One workgroup per CU and one wave per SIMD: nothing else hides this wave's issue cycles, so the
+    // fragment reads of step s + 1 and the copies of step s + D are issued AMONG the 24 MFMAs of step s.  The fragments are double-
+    // buffered in registers: step s multiplies set s & 1 while the reads of step s + 1 fill the other set.  Stage of step t: t % NST.
+    // Step s, in order:  [MFMAs of step s on set s & 1, and among them: the read block of step s + 1 into set (s + 1) & 1, then the
+    // wave's NDMA copies of step s + D]  ->  lgkmcnt(0) (the reads have arrived; they take the set as "+v" operands, so the compiler
+    // can neither read nor move those registers across the wait)  ->  counted vmcnt (this wave's share of step s + 2's copies has
+    // landed; those of step s + 3 stay in flight)  ->  barrier.
+    // (a) Reads only see landed data: step s + 1's read block runs in step s, behind the barrier that closes step s - 1 (for s = 0:
+    //     the prologue's), in front of which every wave waited until its share of step s + 1's copies had landed.
+    // (b) A copy never overwrites a stage in use: step s's copies go to stage (s + D) % NST = (s - 1) % NST with D = NST - 1 = 3 --
+    //     neither the stage read in step s, (s + 1) % NST, nor the one read in step s + 1, (s + 2) % NST.  Its last reader was the
+    //     read block of step s - 1, issued in step s - 2 and waited for (lgkmcnt(0)) in front of the barrier that closes step s - 2.
+    // (c) Short runs: K is a multiple of 64 (checked at every entry), so steps is a multiple of 4 and >= 4 = D + 1.  The loop below
+    //     takes the steps that both read ahead and copy ahead in pairs (the register sets alternate); the last four steps are
+    //     written out: steps - 4 issues the last copies (of step steps - 1), steps - 3 waits for all of them, steps - 2 reads the
+    //     last step and needs no barrier (nothing is copied or read from LDS after it), steps - 1 only multiplies.  No read of a
+    //     step that does not exist, no wait for copies never issued.
+    // For every accumulator the MFMA order is the other loop's: steps in order, al.bh ah.bl am.bm am.bh ah.bm ah.bh within a step.
+    static_assert(MT == 2 && NT == 2 && NST == 4 && PIN == 0 && (DBG == 0 || DBG == 3), "the pipelined loop: 128 x 128 tile, 4 stages");
+    static_assert(D % NST != 0 && D % NST != 1 % NST && D % NST != 2 % NST, "(b): the copy target is none of the stages of steps s, s + 1, s + 2");
+    constexpr int RD_AT = 1, CP_AT = 2, CP_EVERY = 3;  // the read block follows MFMA RD_AT of the step's 24, copy q MFMA CP_AT + q CP_EVERY
+    static_assert(RD_AT < CP_AT && CP_AT + (NDMA - 1) * CP_EVERY < 6 * MT * NT, "reads, then the copies, all among the step's MFMAs");
+    const unsigned base_addr = (unsigned)(uintptr_t)(const __attribute__((address_space(3))) void*)smem;
+    const unsigned a_rel = (unsigned)((lh * BM + wm * (32 * MT) + l31) * 16), w_rel = (unsigned)((A_UNITS + lh * BN + wn * (32 * NT) + l31) * 16);
+    gx_u32x4 fa[2][3][MT], fb[2][3][NT];  // [set][plane][i or j]; the set index is a compile-time constant everywhere
+    // the 12 fragment reads of one step (stage `stage`) into one set (a, b): issued, NOT waited for
+    auto read_issue = [&](gx_u32x4 (&a)[3][MT], gx_u32x4 (&b)[3][NT], int stage) {
+      const unsigned aaddr = base_addr + (unsigned)(stage * STAGE * 16) + a_rel, waddr = base_addr + (unsigned)(stage * STAGE * 16) + w_rel;
+      asm volatile(
+          "ds_read_b128 %0, %12 offset:%14\n ds_read_b128 %1, %12 offset:%15\n ds_read_b128 %2, %12 offset:%16\n ds_read_b128 %3, %12 offset:%17\n"
+          "ds_read_b128 %4, %12 offset:%18\n ds_read_b128 %5, %12 offset:%19\n ds_read_b128 %6, %13 offset:%20\n ds_read_b128 %7, %13 offset:%21\n"
+          "ds_read_b128 %8, %13 offset:%22\n ds_read_b128 %9, %13 offset:%23\n ds_read_b128 %10, %13 offset:%24\n ds_read_b128 %11, %13 offset:%25"
+          : "=&v"(a[0][0]), "=&v"(a[0][1]), "=&v"(a[1][0]), "=&v"(a[1][1]), "=&v"(a[2][0]), "=&v"(a[2][1]), "=&v"(b[0][0]),
+            "=&v"(b[0][1]), "=&v"(b[1][0]), "=&v"(b[1][1]), "=&v"(b[2][0]), "=&v"(b[2][1])
+          : "v"(aaddr), "v"(waddr), "n"((0 * 2 * BM + 0) * 16), "n"((0 * 2 * BM + 32) * 16), "n"((1 * 2 * BM + 0) * 16), "n"((1 * 2 * BM + 32) * 16),
+            "n"((2 * 2 * BM + 0) * 16), "n"((2 * 2 * BM + 32) * 16), "n"((0 * 2 * BN + 0) * 16), "n"((0 * 2 * BN + 32) * 16), "n"((1 * 2 * BN + 0) * 16),
+            "n"((1 * 2 * BN + 32) * 16), "n"((2 * 2 * BN + 0) * 16), "n"((2 * 2 * BN + 32) * 16)
+          : "memory");
+    };
+    // ... and the wait that makes that set usable: the data dependency of everything that reads the set runs through this statement
+    auto read_wait = [&](gx_u32x4 (&a)[3][MT], gx_u32x4 (&b)[3][NT]) {
+      asm volatile("s_waitcnt lgkmcnt(0)"
+                   : "+v"(a[0][0]), "+v"(a[0][1]), "+v"(a[1][0]), "+v"(a[1][1]), "+v"(a[2][0]), "+v"(a[2][1]), "+v"(b[0][0]),
+                     "+v"(b[0][1]), "+v"(b[1][0]), "+v"(b[1][1]), "+v"(b[2][0]), "+v"(b[2][1])
+                   :
+                   : "memory");
+    };
+    auto stamp = [&](int s, int k) {
       if constexpr (DBG == 3) {
         if (blockIdx.x == 0 && tid == 0 && s < 16) {
           p.dbg[s * 8 + k] = __builtin_amdgcn_s_memtime();
@@ -251,72 +295,176 @@ __global__ __launch_bounds__(256, (NST * (MT + NT) * 6 * 64 * 16 <= 80 * 1024) ?
         }
       }
     };
-    stamp(0);
-    if (DBG != 1 && s + D < steps) issue_next(smem + st_nxt * STAGE);  // step s + D
-    stamp(1);
-    const unsigned cur_addr = base_addr + (unsigned)(st_cur * STAGE * 16);
-    if constexpr (DBG != 2) {
-      // fragments: A [plane][i] at unit (plane * 2 + lh) * BM + wm * 32 MT + i * 32 + l31; W likewise behind the A image
-      gx_u32x4 af[3][MT], bf[3][NT];
-      const unsigned aaddr = cur_addr + (unsigned)((lh * BM + wm * (32 * MT) + l31) * 16);
-      const unsigned waddr = cur_addr + (unsigned)((A_UNITS + lh * BN + wn * (32 * NT) + l31) * 16);
-      if constexpr (MT == 4 && NT == 2) {
-        asm volatile(
-            "ds_read_b128 %0, %18 offset:%20\n ds_read_b128 %1, %18 offset:%21\n ds_read_b128 %2, %18 offset:%22\n ds_read_b128 %3, %18 offset:%23\n"
-            "ds_read_b128 %4, %18 offset:%24\n ds_read_b128 %5, %18 offset:%25\n ds_read_b128 %6, %18 offset:%26\n ds_read_b128 %7, %18 offset:%27\n"
-            "ds_read_b128 %8, %18 offset:%28\n ds_read_b128 %9, %18 offset:%29\n ds_read_b128 %10, %18 offset:%30\n ds_read_b128 %11, %18 offset:%31\n"
-            "ds_read_b128 %12, %19 offset:%32\n ds_read_b128 %13, %19 offset:%33\n ds_read_b128 %14, %19 offset:%34\n ds_read_b128 %15, %19 offset:%35\n"
-            "ds_read_b128 %16, %19 offset:%36\n ds_read_b128 %17, %19 offset:%37\n s_waitcnt lgkmcnt(0)"
-            : "=&v"(af[0][0]), "=&v"(af[0][1]), "=&v"(af[0][2]), "=&v"(af[0][3]), "=&v"(af[1][0]), "=&v"(af[1][1]), "=&v"(af[1][2]), "=&v"(af[1][3]),
-              "=&v"(af[2][0]), "=&v"(af[2][1]), "=&v"(af[2][2]), "=&v"(af[2][3]), "=&v"(bf[0][0]), "=&v"(bf[0][1]), "=&v"(bf[1][0]), "=&v"(bf[1][1]),
-              "=&v"(bf[2][0]), "=&v"(bf[2][1])
-            : "v"(aaddr), "v"(waddr), "n"((0 * 2 * BM + 0) * 16), "n"((0 * 2 * BM + 32) * 16), "n"((0 * 2 * BM + 64) * 16), "n"((0 * 2 * BM + 96) * 16),
-              "n"((1 * 2 * BM + 0) * 16), "n"((1 * 2 * BM + 32) * 16), "n"((1 * 2 * BM + 64) * 16), "n"((1 * 2 * BM + 96) * 16), "n"((2 * 2 * BM + 0) * 16),
-              "n"((2 * 2 * BM + 32) * 16), "n"((2 * 2 * BM + 64) * 16), "n"((2 * 2 * BM + 96) * 16), "n"((0 * 2 * BN + 0) * 16), "n"((0 * 2 * BN + 32) * 16),
-              "n"((1 * 2 * BN + 0) * 16), "n"((1 * 2 * BN + 32) * 16), "n"((2 * 2 * BN + 0) * 16), "n"((2 * 2 * BN + 32) * 16)
-            : "memory");
-      } else {
-        static_assert(MT == 2 && NT == 2, "fragment block written for 256 x 128 and 128 x 128 tiles");
-        asm volatile(
-            "ds_read_b128 %0, %12 offset:%14\n ds_read_b128 %1, %12 offset:%15\n ds_read_b128 %2, %12 offset:%16\n ds_read_b128 %3, %12 offset:%17\n"
-            "ds_read_b128 %4, %12 offset:%18\n ds_read_b128 %5, %12 offset:%19\n ds_read_b128 %6, %13 offset:%20\n ds_read_b128 %7, %13 offset:%21\n"
-            "ds_read_b128 %8, %13 offset:%22\n ds_read_b128 %9, %13 offset:%23\n ds_read_b128 %10, %13 offset:%24\n ds_read_b128 %11, %13 offset:%25\n"
-            "s_waitcnt lgkmcnt(0)"
-            : "=&v"(af[0][0]), "=&v"(af[0][1]), "=&v"(af[1][0]), "=&v"(af[1][1]), "=&v"(af[2][0]), "=&v"(af[2][1]), "=&v"(bf[0][0]), "=&v"(bf[0][1]),
-              "=&v"(bf[1][0]), "=&v"(bf[1][1]), "=&v"(bf[2][0]), "=&v"(bf[2][1])
-            : "v"(aaddr), "v"(waddr), "n"((0 * 2 * BM + 0) * 16), "n"((0 * 2 * BM + 32) * 16), "n"((1 * 2 * BM + 0) * 16), "n"((1 * 2 * BM + 32) * 16),
-              "n"((2 * 2 * BM + 0) * 16), "n"((2 * 2 * BM + 32) * 16), "n"((0 * 2 * BN + 0) * 16), "n"((0 * 2 * BN + 32) * 16), "n"((1 * 2 * BN + 0) * 16),
-              "n"((1 * 2 * BN + 32) * 16), "n"((2 * 2 * BN + 0) * 16), "n"((2 * 2 * BN + 32) * 16)
-            : "memory");
-      }
-      stamp(2);
+    int st_rd = 1, st_cp = D % NST;  // stages of step s + 1 (read in step s) and of step s + D (copied in step s)
+    // one step on set c.  COPY: step s + D exists; READ: step s + 1 exists; SYNC: a later step still reads LDS
+    auto step = [&](auto set, auto copy, auto read, auto sync, int s) {
+      constexpr int c = decltype(set)::value;
+      constexpr bool COPY = decltype(copy)::value, READ = decltype(read)::value, SYNC = decltype(sync)::value;
+      static_assert(READ || !COPY, "copies are only issued for steps that will be read");
+      static_assert(READ || !SYNC, "the closing wait and barrier publish data to a later read block");
+      stamp(s, 0);
+      if constexpr (DBG == 3) __builtin_amdgcn_sched_barrier(0);
+      uint4* const cp_stage = smem + st_cp * STAGE;
+      auto among = [&](int k) {  // what follows MFMA k of the step (k is a constant once the loops below are unrolled)
+        if (READ && k == RD_AT) {
+          __builtin_amdgcn_sched_barrier(0);
+          read_issue(fa[1 - c], fb[1 - c], st_rd);
+          __builtin_amdgcn_sched_barrier(0);
+        }
+        if (COPY && k >= CP_AT && (k - CP_AT) % CP_EVERY == 0 && (k - CP_AT) / CP_EVERY < NDMA) {
+          __builtin_amdgcn_sched_barrier(0);
+          issue_piece(cp_stage, (k - CP_AT) / CP_EVERY);
+          __builtin_amdgcn_sched_barrier(0);
+        }
+      };
 #pragma unroll
       for (int i = 0; i < MT; ++i)
 #pragma unroll
         for (int j = 0; j < NT; ++j) {
-          const gx_bf16x8 ah = __builtin_bit_cast(gx_bf16x8, af[0][i]), am = __builtin_bit_cast(gx_bf16x8, af[1][i]), al = __builtin_bit_cast(gx_bf16x8, af[2][i]);
-          const gx_bf16x8 bh = __builtin_bit_cast(gx_bf16x8, bf[0][j]), bm = __builtin_bit_cast(gx_bf16x8, bf[1][j]), bl = __builtin_bit_cast(gx_bf16x8, bf[2][j]);
+          const gx_bf16x8 ah = __builtin_bit_cast(gx_bf16x8, fa[c][0][i]), am = __builtin_bit_cast(gx_bf16x8, fa[c][1][i]), al = __builtin_bit_cast(gx_bf16x8, fa[c][2][i]);
+          const gx_bf16x8 bh = __builtin_bit_cast(gx_bf16x8, fb[c][0][j]), bm = __builtin_bit_cast(gx_bf16x8, fb[c][1][j]), bl = __builtin_bit_cast(gx_bf16x8, fb[c][2][j]);
+          const int k0 = (i * NT + j) * 6;
           // smallest partial products first
           acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(al, bh, acc[i][j], 0, 0, 0);
+          among(k0 + 0);
           acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah, bl, acc[i][j], 0, 0, 0);
+          among(k0 + 1);
           acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(am, bm, acc[i][j], 0, 0, 0);
+          among(k0 + 2);
           acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(am, bh, acc[i][j], 0, 0, 0);
+          among(k0 + 3);
           acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah, bm, acc[i][j], 0, 0, 0);
+          among(k0 + 4);
           acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah, bh, acc[i][j], 0, 0, 0);
+          among(k0 + 5);
         }
+      if constexpr (COPY) issue_advance();
       if constexpr (DBG == 3) asm volatile("" ::"v"(acc[0][0][0]), "v"(acc[MT - 1][NT - 1][15]));  // (the stamp below sits behind the last MFMAs' results)
-      // The MFMAs touch registers only, so nothing orders them against the wait below and the scheduler may put the wait and the
-      // barrier in front of some of them.  Fencing them here was timed and lost (the CU's other workgroup keeps the matrix pipe fed).
-      if constexpr (PIN != 0) __builtin_amdgcn_sched_barrier(0);
-    }
-    stamp(3);
-    wait_younger(DBG == 1 ? 0 : max(0, min(D - 1, steps - s - 2)));
-    stamp(4);
+      stamp(s, 1);
+      if constexpr (READ) read_wait(fa[1 - c], fb[1 - c]);
+      stamp(s, 2);
+      if constexpr (SYNC) {
+        wait_younger(COPY ? 1 : 0);
+        stamp(s, 3);
+        __builtin_amdgcn_s_barrier();
+        asm volatile("" ::: "memory");
+      } else {
+        stamp(s, 3);
+      }
+      stamp(s, 4);
+      st_rd = (st_rd + 1) & (NST - 1);
+      st_cp = (st_cp + 1) & (NST - 1);
+    };
+    constexpr std::integral_constant<int, 0> S0;
+    constexpr std::integral_constant<int, 1> S1;
+    constexpr std::true_type Y;
+    constexpr std::false_type N_;
+
+    for (int t = 0; t < D; ++t) issue_next(smem + t * STAGE);  // steps 0 .. D - 1 (steps >= D + 1)
+    wait_younger(1);  // steps 0 and 1 have landed, step 2 stays in flight
     __builtin_amdgcn_s_barrier();
     asm volatile("" ::: "memory");
-    stamp(5);
-    st_cur = st_cur + 1 == NST ? 0 : st_cur + 1;
-    st_nxt = st_nxt + 1 == NST ? 0 : st_nxt + 1;
+    read_issue(fa[0], fb[0], 0);
+    read_wait(fa[0], fb[0]);
+    wg_stamp(1);
+    int s = 0;
+    for (; s + 4 < steps; s += 2) {
+      step(S0, Y, Y, Y, s);
+      step(S1, Y, Y, Y, s + 1);
+    }
+    step(S0, Y, Y, Y, s);         // steps - 4: the last copies
+    step(S1, N_, Y, Y, s + 1);    // steps - 3: waits for them
+    step(S0, N_, Y, N_, s + 2);   // steps - 2: the last reads
+    step(S1, N_, N_, N_, s + 3);  // steps - 1: multiplies only
+  } else {
+    for (int t = 0; t < D && t < steps; ++t) issue_next(smem + t * STAGE);  // steps 0 .. D - 1
+    wait_younger(min(D, steps) - 1);  // step 0's copies (the oldest) have landed
+    __builtin_amdgcn_s_barrier();
+    asm volatile("" ::: "memory");
+    wg_stamp(1);
+
+    // Step s computes on stage s % NST and, first, issues the copies of step s + D into stage (s + D) % NST (last read in step s - 1,
+    // which every wave has left).  Before its closing barrier a wave waits until its share of step s + 1's copies has landed; the
+    // copies of the steps behind that stay in flight.  Every memory operation here is issued by hand, so a run-time stage index and
+    // run-time issue condition are fine: the compiler has no wait of its own to miscount.
+    const unsigned base_addr = (unsigned)(uintptr_t)(const __attribute__((address_space(3))) void*)smem;
+    int st_cur = 0, st_nxt = D % NST;
+    for (int s = 0; s < steps; ++s) {
+      auto stamp = [&](int k) {
+        if constexpr (DBG == 3) {
+          if (blockIdx.x == 0 && tid == 0 && s < 16) {
+            p.dbg[s * 8 + k] = __builtin_amdgcn_s_memtime();
+            if (k == 0) p.dbg[s * 8 + 7] = __builtin_amdgcn_s_memrealtime();
+          }
+        }
+      };
+      stamp(0);
+      if (DBG != 1 && s + D < steps) issue_next(smem + st_nxt * STAGE);  // step s + D
+      stamp(1);
+      const unsigned cur_addr = base_addr + (unsigned)(st_cur * STAGE * 16);
+      if constexpr (DBG != 2) {
+        // fragments: A [plane][i] at unit (plane * 2 + lh) * BM + wm * 32 MT + i * 32 + l31; W likewise behind the A image
+        gx_u32x4 af[3][MT], bf[3][NT];
+        const unsigned aaddr = cur_addr + (unsigned)((lh * BM + wm * (32 * MT) + l31) * 16);
+        const unsigned waddr = cur_addr + (unsigned)((A_UNITS + lh * BN + wn * (32 * NT) + l31) * 16);
+        if constexpr (MT == 4 && NT == 2) {
+          asm volatile(
+              "ds_read_b128 %0, %18 offset:%20\n ds_read_b128 %1, %18 offset:%21\n ds_read_b128 %2, %18 offset:%22\n ds_read_b128 %3, %18 offset:%23\n"
+              "ds_read_b128 %4, %18 offset:%24\n ds_read_b128 %5, %18 offset:%25\n ds_read_b128 %6, %18 offset:%26\n ds_read_b128 %7, %18 offset:%27\n"
+              "ds_read_b128 %8, %18 offset:%28\n ds_read_b128 %9, %18 offset:%29\n ds_read_b128 %10, %18 offset:%30\n ds_read_b128 %11, %18 offset:%31\n"
+              "ds_read_b128 %12, %19 offset:%32\n ds_read_b128 %13, %19 offset:%33\n ds_read_b128 %14, %19 offset:%34\n ds_read_b128 %15, %19 offset:%35\n"
+              "ds_read_b128 %16, %19 offset:%36\n ds_read_b128 %17, %19 offset:%37\n s_waitcnt lgkmcnt(0)"
+              : "=&v"(af[0][0]), "=&v"(af[0][1]), "=&v"(af[0][2]), "=&v"(af[0][3]), "=&v"(af[1][0]), "=&v"(af[1][1]), "=&v"(af[1][2]), "=&v"(af[1][3]),
+                "=&v"(af[2][0]), "=&v"(af[2][1]), "=&v"(af[2][2]), "=&v"(af[2][3]), "=&v"(bf[0][0]), "=&v"(bf[0][1]), "=&v"(bf[1][0]), "=&v"(bf[1][1]),
+                "=&v"(bf[2][0]), "=&v"(bf[2][1])
+              : "v"(aaddr), "v"(waddr), "n"((0 * 2 * BM + 0) * 16), "n"((0 * 2 * BM + 32) * 16), "n"((0 * 2 * BM + 64) * 16), "n"((0 * 2 * BM + 96) * 16),
+                "n"((1 * 2 * BM + 0) * 16), "n"((1 * 2 * BM + 32) * 16), "n"((1 * 2 * BM + 64) * 16), "n"((1 * 2 * BM + 96) * 16), "n"((2 * 2 * BM + 0) * 16),
+                "n"((2 * 2 * BM + 32) * 16), "n"((2 * 2 * BM + 64) * 16), "n"((2 * 2 * BM + 96) * 16), "n"((0 * 2 * BN + 0) * 16), "n"((0 * 2 * BN + 32) * 16),
+                "n"((1 * 2 * BN + 0) * 16), "n"((1 * 2 * BN + 32) * 16), "n"((2 * 2 * BN + 0) * 16), "n"((2 * 2 * BN + 32) * 16)
+              : "memory");
+        } else {
+          static_assert(MT == 2 && NT == 2, "fragment block written for 256 x 128 and 128 x 128 tiles");
+          asm volatile(
+              "ds_read_b128 %0, %12 offset:%14\n ds_read_b128 %1, %12 offset:%15\n ds_read_b128 %2, %12 offset:%16\n ds_read_b128 %3, %12 offset:%17\n"
+              "ds_read_b128 %4, %12 offset:%18\n ds_read_b128 %5, %12 offset:%19\n ds_read_b128 %6, %13 offset:%20\n ds_read_b128 %7, %13 offset:%21\n"
+              "ds_read_b128 %8, %13 offset:%22\n ds_read_b128 %9, %13 offset:%23\n ds_read_b128 %10, %13 offset:%24\n ds_read_b128 %11, %13 offset:%25\n"
+              "s_waitcnt lgkmcnt(0)"
+              : "=&v"(af[0][0]), "=&v"(af[0][1]), "=&v"(af[1][0]), "=&v"(af[1][1]), "=&v"(af[2][0]), "=&v"(af[2][1]), "=&v"(bf[0][0]), "=&v"(bf[0][1]),
+                "=&v"(bf[1][0]), "=&v"(bf[1][1]), "=&v"(bf[2][0]), "=&v"(bf[2][1])
+              : "v"(aaddr), "v"(waddr), "n"((0 * 2 * BM + 0) * 16), "n"((0 * 2 * BM + 32) * 16), "n"((1 * 2 * BM + 0) * 16), "n"((1 * 2 * BM + 32) * 16),
+                "n"((2 * 2 * BM + 0) * 16), "n"((2 * 2 * BM + 32) * 16), "n"((0 * 2 * BN + 0) * 16), "n"((0 * 2 * BN + 32) * 16), "n"((1 * 2 * BN + 0) * 16),
+                "n"((1 * 2 * BN + 32) * 16), "n"((2 * 2 * BN + 0) * 16), "n"((2 * 2 * BN + 32) * 16)
+              : "memory");
+        }
+        stamp(2);
+#pragma unroll
+        for (int i = 0; i < MT; ++i)
+#pragma unroll
+          for (int j = 0; j < NT; ++j) {
+            const gx_bf16x8 ah = __builtin_bit_cast(gx_bf16x8, af[0][i]), am = __builtin_bit_cast(gx_bf16x8, af[1][i]), al = __builtin_bit_cast(gx_bf16x8, af[2][i]);
+            const gx_bf16x8 bh = __builtin_bit_cast(gx_bf16x8, bf[0][j]), bm = __builtin_bit_cast(gx_bf16x8, bf[1][j]), bl = __builtin_bit_cast(gx_bf16x8, bf[2][j]);
+            // smallest partial products first
+            acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(al, bh, acc[i][j], 0, 0, 0);
+            acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah, bl, acc[i][j], 0, 0, 0);
+            acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(am, bm, acc[i][j], 0, 0, 0);
+            acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(am, bh, acc[i][j], 0, 0, 0);
+            acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah, bm, acc[i][j], 0, 0, 0);
+            acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah, bh, acc[i][j], 0, 0, 0);
+          }
+        if constexpr (DBG == 3) asm volatile("" ::"v"(acc[0][0][0]), "v"(acc[MT - 1][NT - 1][15]));  // (the stamp below sits behind the last MFMAs' results)
+        // The MFMAs touch registers only, so nothing orders them against the wait below and the scheduler may put the wait and the
+        // barrier in front of some of them.  Fencing them here was timed and lost (the CU's other workgroup keeps the matrix pipe fed).
+        if constexpr (PIN != 0) __builtin_amdgcn_sched_barrier(0);
+      }
+      stamp(3);
+      wait_younger(DBG == 1 ? 0 : max(0, min(D - 1, steps - s - 2)));
+      stamp(4);
+      __builtin_amdgcn_s_barrier();
+      asm volatile("" ::: "memory");
+      stamp(5);
+      st_cur = st_cur + 1 == NST ? 0 : st_cur + 1;
+      st_nxt = st_nxt + 1 == NST ? 0 : st_nxt + 1;
+    }
   }
 
   wg_stamp(2);
@@ -380,7 +528,7 @@ __global__ __launch_bounds__(256, (NST * (MT + NT) * 6 * 64 * 16 <= 80 * 1024) ?
   }
 }
 
-template <int MT, int NT, int NST, int EPI = EPI_PLAIN, int ACC = 0, int SEQ = 0, int DBG = 0, int PIN = 0>
+template <int MT, int NT, int NST, int EPI = EPI_PLAIN, int ACC = 0, int SEQ = 0, int DBG = 0, int PIN = 0, int PIPE = 0>
 static int launch_gemm_x6(GemmX6Params p, hipStream_t st) {
   constexpr int BM = 64 * MT, BN = 64 * NT;
   constexpr size_t smem = (size_t)NST * (6 * BM + 6 * BN) * 16;
@@ -388,10 +536,11 @@ static int launch_gemm_x6(GemmX6Params p, hipStream_t st) {
   p.m_tiles = ceil_div(p.M, BM);
   p.n_tiles = ceil_div(p.N, BN);
   IX_ARG((long)p.n_tiles * BN <= p.Npad, "gemm_x6: packed weights padded to %d features, the %d-wide tile needs %d", p.Npad, BN, p.n_tiles * BN);
+  if constexpr (PIPE != 0) IX_ARG(p.K > 0 && p.K % 64 == 0, "gemm_x6: the pipelined loop takes its steps in fours, K %d", p.K);
   const int taps = (p.K >> 4) / p.tap_steps;  // the last tap reads taps - 1 rows below the tile
   IX_ARG(p.arow0 + (long)p.m_tiles * BM + taps - 1 <= p.Mpad, "gemm_x6: activation planes hold %ld rows, the %d-row tiles reach row %ld", p.Mpad, BM,
          p.arow0 + (long)p.m_tiles * BM + taps - 1);
-  auto kern = gemm_x6_kernel<MT, NT, NST, EPI, ACC, SEQ, DBG, PIN>;
+  auto kern = gemm_x6_kernel<MT, NT, NST, EPI, ACC, SEQ, DBG, PIN, PIPE>;
   static bool done = false;
   if (!done) {
     IX_HIP(hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem));
@@ -403,13 +552,14 @@ static int launch_gemm_x6(GemmX6Params p, hipStream_t st) {
 }
 
 // the kernel instantiation for what the tile writes (p.epi, p.accumulate, p.gate_seq_off); PAIR: this tile shape takes the pair epilogues
-template <int MT, int NT, int NST, bool PAIR>
+template <int MT, int NT, int NST, bool PAIR, int PIPE = 0>
 static int launch_gemm_x6_epilogue(const GemmX6Params& p, hipStream_t st) {
-  if (p.epi == EPI_PLAIN) return p.accumulate ? launch_gemm_x6<MT, NT, NST, EPI_PLAIN, 1>(p, st) : launch_gemm_x6<MT, NT, NST, EPI_PLAIN, 0>(p, st);
+  if (p.epi == EPI_PLAIN)
+    return p.accumulate ? launch_gemm_x6<MT, NT, NST, EPI_PLAIN, 1, 0, 0, 0, PIPE>(p, st) : launch_gemm_x6<MT, NT, NST, EPI_PLAIN, 0, 0, 0, 0, PIPE>(p, st);
   if constexpr (PAIR) {
-    if (p.epi == EPI_SWIGLU) return launch_gemm_x6<MT, NT, NST, EPI_SWIGLU>(p, st);
+    if (p.epi == EPI_SWIGLU) return launch_gemm_x6<MT, NT, NST, EPI_SWIGLU, 0, 0, 0, 0, PIPE>(p, st);
     if (p.epi == EPI_GATE)
-      return p.gate_seq_off ? launch_gemm_x6<MT, NT, NST, EPI_GATE, 0, 1>(p, st) : launch_gemm_x6<MT, NT, NST, EPI_GATE, 0, 0>(p, st);
+      return p.gate_seq_off ? launch_gemm_x6<MT, NT, NST, EPI_GATE, 0, 1, 0, 0, PIPE>(p, st) : launch_gemm_x6<MT, NT, NST, EPI_GATE, 0, 0, 0, 0, PIPE>(p, st);
   }
   set_error("gemm_x6: epilogue %d on a tile shape built without it", p.epi);
   return IXTTS_ERR_ARG;
@@ -471,10 +621,22 @@ extern "C" int ixtts_gemm_x6_split_halo_varlen(const float* a_dev, long lda, voi
   return IXTTS_OK;
 }
 
+static long device_cu_count() {  // of the current device, asked once
+  static const long n = [] {
+    int dev = 0, cus = 0;
+    return (hipGetDevice(&dev) == hipSuccess && hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess) ? (long)cus : 0L;
+  }();
+  return n;
+}
+
 static int run_gemm_x6(GemmX6Params p, int tile, hipStream_t st) {
   if (tile == 0) {  // by fill of the 256 CUs: the wider tile while it still gives most CUs work (operand bytes per MFMA fall with the tile)
     const long t42 = (long)ceil_div(p.M, 256) * ceil_div(p.N, 128);
     tile = t42 >= 140 ? 2 : 3;
+    // no more 128 x 128 tiles than CUs: tile 3's two workgroups per CU never meet, each SIMD holds one wave and nothing hides its
+    // issue cycles -- the pipelined loop hides them itself.  IXTTS_GEMM_X6_PIPE=0: tile 3 there as before (A/B runs, tests).
+    static const bool pipe = !(getenv("IXTTS_GEMM_X6_PIPE") && !strcmp(getenv("IXTTS_GEMM_X6_PIPE"), "0"));
+    if (tile == 3 && pipe && (long)ceil_div(p.M, 128) * ceil_div(p.N, 128) <= device_cu_count()) tile = 6;
   }
   switch (tile) {
     // two workgroups per CU (2 x 73.7 KB of LDS): one's copies, fragment reads and epilogue run under the other's MFMAs
@@ -483,6 +645,8 @@ static int run_gemm_x6(GemmX6Params p, int tile, hipStream_t st) {
     // one workgroup per CU, copies three steps ahead (A/B timing; plain epilogue only)
     case 4: return launch_gemm_x6_epilogue<4, 2, 4, false>(p, st);
     case 5: return launch_gemm_x6_epilogue<2, 2, 4, false>(p, st);
+    // one workgroup per CU, pipelined loop: next step's fragment reads and the copies issued among the MFMAs
+    case 6: return launch_gemm_x6_epilogue<2, 2, 4, true, 1>(p, st);
   }
   if (tile >= 12 && (p.epi != EPI_PLAIN || p.accumulate)) {
     set_error("gemm_x6: the developer variants (tile %d) are built with the plain, overwriting epilogue only", tile);
@@ -494,11 +658,12 @@ static int run_gemm_x6(GemmX6Params p, int tile, hipStream_t st) {
     case 22: return launch_gemm_x6<4, 2, 2, EPI_PLAIN, 0, 0, 2>(p, st);
     case 32: return launch_gemm_x6<4, 2, 2, EPI_PLAIN, 0, 0, 3>(p, st);
     case 33: return launch_gemm_x6<2, 2, 3, EPI_PLAIN, 0, 0, 3>(p, st);
+    case 36: return launch_gemm_x6<2, 2, 4, EPI_PLAIN, 0, 0, 3, 0, 1>(p, st);
     // the loop with a fence between a step's MFMAs and its closing wait (results as tiles 2 / 3; A/B timing of the fence)
     case 42: return launch_gemm_x6<4, 2, 2, EPI_PLAIN, 0, 0, 0, 1>(p, st);
     case 43: return launch_gemm_x6<2, 2, 3, EPI_PLAIN, 0, 0, 0, 1>(p, st);
   }
-  set_error("gemm_x6: tile %d (0 auto; 2 / 3: 256x128 / 128x128, two workgroups per CU; 4 / 5: the same, one per CU with a 4-stage ring)", tile);
+  set_error("gemm_x6: tile %d (0 auto; 2 / 3: 256x128 / 128x128, two workgroups per CU; 4 / 5: the same, one per CU with a 4-stage ring; 6: 128x128, one per CU, pipelined loop)", tile);
   return IXTTS_ERR_ARG;
 }
 
@@ -511,7 +676,7 @@ extern "C" int ixtts_gemm_x6_f32(const void* a_planes_dev, long rows_total, long
   p.Wp = reinterpret_cast<const uint4*>(packed_dev); p.bias = bias_dev; p.C = c_dev; p.ldc = ldc;
   p.M = M; p.N = N; p.Npad = (N + 255) / 256 * 256; p.K = K; p.accumulate = accumulate ? 1 : 0; p.m_tiles = p.n_tiles = 0;
   p.tap_steps = K >> 4; p.epi = EPI_PLAIN; p.gate = nullptr; p.gate_ld = 0; p.rows_per_batch = 1; p.nbatch = 1; p.gate_seq_off = nullptr;
-  p.dbg = (tile == 32 || tile == 33) ? reinterpret_cast<unsigned long long*>(const_cast<float*>(bias_dev)) : nullptr;  // developer stamps travel in the bias slot
+  p.dbg = (tile == 32 || tile == 33 || tile == 36) ? reinterpret_cast<unsigned long long*>(const_cast<float*>(bias_dev)) : nullptr;  // developer stamps travel in the bias slot
   if (p.dbg) p.bias = nullptr;
   return run_gemm_x6(p, tile, (hipStream_t)stream);
 }
@@ -525,7 +690,7 @@ extern "C" int ixtts_gemm_x6_pair_f32(const void* a_planes_dev, long rows_total,
          "gemm_x6_pair: epilogue %d (1 swiglu; 2 gate, with gate biases)", epilogue);
   IX_ARG(ldc >= N / 2 && row0 >= 0 && row0 + M + taps - 1 <= rows_total, "gemm_x6_pair: rows [%ld, %ld) + %d taps of %ld, ldc %ld", row0, row0 + M, taps,
          rows_total, ldc);
-  IX_ARG(tile == 0 || tile == 2 || tile == 3, "gemm_x6_pair: tile %d (0 auto, 2, 3)", tile);
+  IX_ARG(tile == 0 || tile == 2 || tile == 3 || tile == 6, "gemm_x6_pair: tile %d (0 auto, 2, 3, 6)", tile);
   GemmX6Params p;
   p.Ap = reinterpret_cast<const uint4*>(a_planes_dev); p.Mpad = ixtts_gemm_x6_rows_padded(rows_total); p.arow0 = row0;
   p.Wp = reinterpret_cast<const uint4*>(packed_dev); p.bias = bias_dev; p.C = c_dev; p.ldc = ldc;
@@ -544,7 +709,7 @@ extern "C" int ixtts_gemm_x6_pair_gate_varlen_f32(const void* a_planes_dev, long
   IX_ARG(K % taps == 0 && (K / taps) % 64 == 0 && N % 64 == 0, "gemm_x6_pair_gate_varlen: K %d = %d taps of a multiple of 64, N %d a multiple of 64", K, taps, N);
   IX_ARG(ldc >= N / 2 && row0 >= 0 && row0 + M + taps - 1 <= rows_total, "gemm_x6_pair_gate_varlen: rows [%ld, %ld) + %d taps of %ld, ldc %ld", row0, row0 + M,
          taps, rows_total, ldc);
-  IX_ARG(tile == 0 || tile == 2 || tile == 3, "gemm_x6_pair_gate_varlen: tile %d (0 auto, 2, 3)", tile);
+  IX_ARG(tile == 0 || tile == 2 || tile == 3 || tile == 6, "gemm_x6_pair_gate_varlen: tile %d (0 auto, 2, 3, 6)", tile);
   GemmX6Params p;
   p.Ap = reinterpret_cast<const uint4*>(a_planes_dev); p.Mpad = ixtts_gemm_x6_rows_padded(rows_total); p.arow0 = row0;
   p.Wp = reinterpret_cast<const uint4*>(packed_dev); p.bias = bias_dev; p.C = c_dev; p.ldc = ldc;

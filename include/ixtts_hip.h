@@ -237,6 +237,15 @@ int ixtts_bigvgan_forward(ixtts_bigvgan* h, const float* mel_dev, int B, int F, 
  * bit-identical to ixtts_bigvgan_forward on that row alone.  Same schedule and workspace (sized for B x Fmax). */
 int ixtts_bigvgan_forward_varlen(ixtts_bigvgan* h, const float* mel_dev, const int* frames_dev, const int* frames_host, int B, int Fmax,
                                  float* wav_dev, void* stream);
+/* Conv launches of this handle so far, by tile shape (rows x columns): plain host counters, incremented where the launcher
+ * decides; no device work.  `*f32_convs` tells which kernels the handle runs and so what the six slots are:
+ *   0 (default, conv1d_x3.hip):        128x128, 128x96, 64x128 chosen by score | 32x128, 64x128 fixed by Cout | unused
+ *   1 (IXTTS_BV_CONV=f32, conv1d.hip): 128x128, 64x128, 64x64  chosen by score | 32x256, 64x128, 96x128 fixed by Cout
+ * The developer switch IXTTS_BV_TILE=<one of the three scored names of the handle's kernels>, read by ixtts_bigvgan_create,
+ * puts that tile wherever the launcher would choose by score (convs on a fixed tile ignore it); any other value makes create
+ * fail with IXTTS_ERR_ARG. */
+#define IXTTS_BIGVGAN_TILE_SLOTS 6
+int ixtts_bigvgan_tile_launches(const ixtts_bigvgan* h, int64_t* counts /* [IXTTS_BIGVGAN_TILE_SLOTS] */, int* f32_convs);
 /* Algorithmic conv FLOPs of one forward at F frames. */
 double ixtts_bigvgan_flops(const ixtts_bigvgan* h, int B, int F);
 int ixtts_bigvgan_destroy(ixtts_bigvgan* h);

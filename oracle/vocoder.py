@@ -50,8 +50,9 @@ def kaiser_sinc_filter12(cutoff=0.25, half_width=0.3, kernel_size=12):
     return filt.to(torch.float32).numpy().copy()
 
 
-def aa_snake(x, log_alpha, log_beta, filt=None):
-    """y = Down2(SnakeBeta(Up2(x))) for x [B,C,T] fp32 (act.py:24-30).
+def aa_snake(x, log_alpha, log_beta, filt=None, dtype=torch.float32):
+    """y = Down2(SnakeBeta(Up2(x))) for x [B,C,T] fp32 (act.py:24-30).  `dtype=torch.float64`: the same arithmetic in fp64 on the
+    same numbers (the fp32 taps, alpha, beta and x, widened) -- the twin the error budgets are measured against.
 
     Written in polyphase/gather form rather than pad+conv_transpose+crop:
       Up2   (resample.py:29-38): replicate-pad 5/5, 2*conv_transpose(stride 2), crop 15/15
@@ -63,8 +64,8 @@ def aa_snake(x, log_alpha, log_beta, filt=None):
     """
     if filt is None:
         filt = kaiser_sinc_filter12()
-    f = torch.as_tensor(filt, dtype=torch.float32)
-    x = torch.as_tensor(x, dtype=torch.float32)
+    f = torch.as_tensor(filt, dtype=dtype)
+    x = torch.as_tensor(x, dtype=dtype)
     B, C, T = x.shape
     if T == 0:
         return x.clone()
@@ -75,8 +76,8 @@ def aa_snake(x, log_alpha, log_beta, filt=None):
         ue = ue + f[11 - 2 * a] * x[..., (m - 3 + a).clamp(0, T - 1)]
         uo = uo + f[10 - 2 * a] * x[..., (m - 2 + a).clamp(0, T - 1)]
     u = torch.stack((2.0 * ue, 2.0 * uo), dim=-1).reshape(B, C, 2 * T)
-    alpha = torch.exp(torch.as_tensor(log_alpha, dtype=torch.float32)).view(1, C, 1)
-    beta = torch.exp(torch.as_tensor(log_beta, dtype=torch.float32)).view(1, C, 1)
+    alpha = torch.exp(torch.as_tensor(log_alpha, dtype=dtype)).view(1, C, 1)
+    beta = torch.exp(torch.as_tensor(log_beta, dtype=dtype)).view(1, C, 1)
     s = u + (1.0 / (beta + 1e-9)) * torch.sin(u * alpha) ** 2
     t = torch.arange(T)
     y = torch.zeros_like(x)
@@ -117,26 +118,27 @@ def fold_weight_norm(sd):
     return out
 
 
-def amp_block1(x, W, prefix, k, dilations, filt):
-    """AMPBlock1.forward (bigvgan.py:132-141)."""
+def amp_block1(x, W, prefix, k, dilations, filt, dtype=torch.float32):
+    """AMPBlock1.forward (bigvgan.py:132-141).  x and W are tensors of `dtype` already."""
     for j, d in enumerate(dilations):
-        xt = aa_snake(x, W[f"{prefix}.activations.{2 * j}.act.alpha"], W[f"{prefix}.activations.{2 * j}.act.beta"], filt)
+        xt = aa_snake(x, W[f"{prefix}.activations.{2 * j}.act.alpha"], W[f"{prefix}.activations.{2 * j}.act.beta"], filt, dtype)
         xt = F.conv1d(xt, W[f"{prefix}.convs1.{j}.weight"], W[f"{prefix}.convs1.{j}.bias"], dilation=d, padding=get_padding(k, d))
-        xt = aa_snake(xt, W[f"{prefix}.activations.{2 * j + 1}.act.alpha"], W[f"{prefix}.activations.{2 * j + 1}.act.beta"], filt)
+        xt = aa_snake(xt, W[f"{prefix}.activations.{2 * j + 1}.act.alpha"], W[f"{prefix}.activations.{2 * j + 1}.act.beta"], filt, dtype)
         xt = F.conv1d(xt, W[f"{prefix}.convs2.{j}.weight"], W[f"{prefix}.convs2.{j}.bias"], dilation=1, padding=get_padding(k, 1))
         x = xt + x
     return x
 
 
-def bigvgan_forward(mel, W, cfg=BIGVGAN_CFG, filt=None, return_stages=False):
+def bigvgan_forward(mel, W, cfg=BIGVGAN_CFG, filt=None, return_stages=False, dtype=torch.float32):
     """BigVGAN.forward (bigvgan.py:360-386): mel [B,num_mels,F] fp32 -> wav [B,1,prod(rates)*F].
 
     use_tanh_at_final=false, use_bias_at_final=false (config.json:17-18) -> clamp(-1,1).
+    `dtype=torch.float64`: the fp64 twin -- the fp32 weights, mel and filter taps widened, every operation in fp64.
     """
     if filt is None:
         filt = kaiser_sinc_filter12()
-    W = {k: torch.as_tensor(v, dtype=torch.float32) for k, v in W.items()}
-    x = torch.as_tensor(mel, dtype=torch.float32)
+    W = {k: torch.as_tensor(v, dtype=dtype) for k, v in W.items()}
+    x = torch.as_tensor(mel, dtype=dtype)
     stages = []
     x = F.conv1d(x, W["conv_pre.weight"], W["conv_pre.bias"], padding=3)
     nk = len(cfg["resblock_kernel_sizes"])
@@ -144,12 +146,12 @@ def bigvgan_forward(mel, W, cfg=BIGVGAN_CFG, filt=None, return_stages=False):
         x = F.conv_transpose1d(x, W[f"ups.{i}.0.weight"], W[f"ups.{i}.0.bias"], stride=u, padding=(ku - u) // 2)
         xs = None
         for j, (k, dil) in enumerate(zip(cfg["resblock_kernel_sizes"], cfg["resblock_dilation_sizes"])):
-            r = amp_block1(x, W, f"resblocks.{i * nk + j}", k, dil, filt)
+            r = amp_block1(x, W, f"resblocks.{i * nk + j}", k, dil, filt, dtype)
             xs = r if xs is None else xs + r
         x = xs / nk
         if return_stages:
             stages.append(x)
-    x = aa_snake(x, W["activation_post.act.alpha"], W["activation_post.act.beta"], filt)
+    x = aa_snake(x, W["activation_post.act.alpha"], W["activation_post.act.beta"], filt, dtype)
     x = F.conv1d(x, W["conv_post.weight"], W.get("conv_post.bias"), padding=3)
     x = torch.clamp(x, min=-1.0, max=1.0)
     if return_stages:

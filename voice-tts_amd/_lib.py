@@ -11,6 +11,7 @@ LIB_PATH = os.environ.get("IXTTS_LIB") or os.path.join(HERE, "libixtts_hip.so") 
 
 MAX_STAGES = 8
 MAX_RESK = 4
+BIGVGAN_TILE_SLOTS = 6  # IXTTS_BIGVGAN_TILE_SLOTS
 
 
 class BigVGANCfg(C.Structure):
@@ -112,6 +113,7 @@ SYMBOLS = {
     "ixtts_bigvgan_adopt_arena": (C.c_int, [_P]),
     "ixtts_bigvgan_forward": (C.c_int, [_P, _P, C.c_int, C.c_int, _P, _P]),
     "ixtts_bigvgan_forward_varlen": (C.c_int, [_P, _P, _P, _P, C.c_int, C.c_int, _P, _P]),
+    "ixtts_bigvgan_tile_launches": (C.c_int, [_P, C.POINTER(C.c_int64), C.POINTER(C.c_int)]),
     "ixtts_bigvgan_flops": (C.c_double, [_P, C.c_int, C.c_int]),
     "ixtts_bigvgan_destroy": (C.c_int, [_P]),
     "ixtts_gpt_create": (C.c_int, [C.POINTER(_P), C.POINTER(GptCfg)]),

@@ -116,6 +116,19 @@ class BigVGAN(nn.Module):
     def remove_weight_norm(self):
         return self
 
+    # slots of ixtts_bigvgan_tile_launches: the tiles chosen by score (the names IXTTS_BV_TILE takes), then those a Cout fixes
+    TILE_NAMES = {0: ("128x128", "128x96", "64x128", "fixed 32x128", "fixed 64x128"),
+                  1: ("128x128", "64x128", "64x64", "fixed 32x256", "fixed 64x128", "fixed 96x128")}
+    SCORED_TILES = 3
+
+    def tile_launches(self):
+        """Conv launches of this handle so far by tile shape: {"128x128": n, ..., "fixed 64x128": n}.  The first SCORED_TILES keys are
+        the tiles the launcher chooses among by score (or IXTTS_BV_TILE names, read when the handle was created), the "fixed" ones those
+        a conv's Cout leaves no choice about.  Host counters; the names depend on the handle's kernels (IXTTS_BV_CONV)."""
+        counts, f32 = (C.c_int64 * _lib.BIGVGAN_TILE_SLOTS)(), C.c_int()
+        _lib.check(_lib.lib().ixtts_bigvgan_tile_launches(self._h, counts, C.byref(f32)), "ixtts_bigvgan_tile_launches")
+        return {name: int(counts[i]) for i, name in enumerate(self.TILE_NAMES[f32.value])}
+
     def flops(self, B, F):
         return _lib.lib().ixtts_bigvgan_flops(self._h, B, F)
 

@@ -53,6 +53,8 @@ struct ixtts_bigvgan {
   float* buf[NBUF] = {};
   size_t buf_floats = 0;
   bool x3 = true;      // convs on the bf16 matrix cores with three-way split operands (conv1d_x3.hip); IXTTS_BV_CONV=f32: conv1d.hip
+  int force_tile = 0;  // IXTTS_BV_TILE: 1 + slot of the tile that replaces the launchers' scored choice (ConvParams::force_tile); 0: by score
+  long long tile_counts[CONV_TILE_SLOTS] = {};  // conv launches of this handle by tile shape (host counters, ixtts_bigvgan_tile_launches)
   void* pbuf[4] = {};  // x planes: one per resblock branch + one for the mel / stage outputs
   size_t pbuf_bytes = 0;
   hipStream_t side[2] = {nullptr, nullptr};  // streams of the k = 3 / k = 7 branches (the caller's stream carries k = 11)
@@ -107,6 +109,19 @@ extern "C" int ixtts_bigvgan_create(ixtts_bigvgan** out, const ixtts_bigvgan_cfg
   h->cfg = *cfg;
   if (const char* e = getenv("IXTTS_BV_STREAMS")) h->concurrent = strcmp(e, "1") != 0;
   if (const char* e = getenv("IXTTS_BV_CONV")) h->x3 = strcmp(e, "f32") != 0;
+  if (const char* e = getenv("IXTTS_BV_TILE"); e && *e) {
+    // developer switch: the named tile wherever the launcher of this handle's arithmetic mode would choose by score
+    static const char* const scored[2][CONV_TILE_SCORED] = {{"128x128", "64x128", "64x64"}, {"128x128", "128x96", "64x128"}};
+    for (int t = 0; t < CONV_TILE_SCORED; ++t)
+      if (strcmp(e, scored[h->x3][t]) == 0) h->force_tile = 1 + t;
+    if (!h->force_tile) {
+      const bool x3 = h->x3;
+      delete h;
+      set_error("bigvgan_create: IXTTS_BV_TILE=%s is no scored tile of the %s convs (%s, %s, %s)", e, x3 ? "split-product" : "fp32-MFMA", scored[x3][0],
+                scored[x3][1], scored[x3][2]);
+      return IXTTS_ERR_ARG;
+    }
+  }
   size_t off = 0;
   h->filt_off = off;
   off += 16;
@@ -416,6 +431,8 @@ static int run_conv(ixtts_bigvgan* h, const std::string& name, const float* x, f
     p.lens_in = p.Tin / vl.fmax;
     p.lens_out = p.Tout / vl.fmax;
   }
+  p.force_tile = h->force_tile;
+  p.tile_counts = h->tile_counts;
   static const bool timing = getenv("IXTTS_BV_TIMING") != nullptr;  // developer table: per conv shape, time and TFLOP/s
   auto launch = [&]() { return h->x3 ? launch_conv1d_x3(p, st) : launch_conv1d(p, st); };
   if (!timing) return launch();
@@ -544,6 +561,14 @@ extern "C" int ixtts_bigvgan_forward_varlen(ixtts_bigvgan* h, const float* mel, 
   vl.host = frames_host;
   vl.fmax = Fmax;
   return forward_rows(h, mel, B, Fmax, wav, stream, vl);
+}
+
+static_assert(CONV_TILE_SLOTS == IXTTS_BIGVGAN_TILE_SLOTS, "the launchers' counter slots are the ABI's");
+extern "C" int ixtts_bigvgan_tile_launches(const ixtts_bigvgan* h, int64_t* counts, int* f32_convs) {
+  IX_ARG(h && counts && f32_convs, "bigvgan_tile_launches: null argument");
+  for (int t = 0; t < CONV_TILE_SLOTS; ++t) counts[t] = h->tile_counts[t];
+  *f32_convs = h->x3 ? 0 : 1;
+  return IXTTS_OK;
 }
 
 extern "C" double ixtts_bigvgan_flops(const ixtts_bigvgan* h, int B, int F) {

@@ -26,7 +26,18 @@ struct ConvParams {
   const int* lens;       // [B] frames per row, device
   const int* lens_host;  // the same on the host: tile scoring only, never dereferenced by a kernel
   int lens_max, lens_in, lens_out;
+  // ---- host only, read by the launchers and by no kernel
+  int force_tile;          // 0: the launcher scores its tiles; 1 + slot: that scored tile instead (IXTTS_BV_TILE).  Fixed tiles ignore it
+  long long* tile_counts;  // [CONV_TILE_SLOTS] launches per tile shape (host memory), or null
 };
+
+// Slots of ConvParams::tile_counts.  The first three are the tiles a launcher chooses among by score (and IXTTS_BV_TILE names), the
+// rest the tiles a Cout fixes:  conv1d_x3.hip  128x128 128x96 64x128 | 32x128 64x128
+//                               conv1d.hip     128x128 64x128 64x64  | 32x256 64x128 96x128
+constexpr int CONV_TILE_SCORED = 3, CONV_TILE_SLOTS = 6;
+inline void conv_count_tile(const ConvParams& p, int slot) {
+  if (p.tile_counts) ++p.tile_counts[slot];
+}
 
 // Bounds of row b of a varlen conv (workgroup-uniform: one scalar load).  An empty row has no columns at all.
 struct ConvRow {

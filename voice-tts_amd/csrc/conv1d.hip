@@ -252,14 +252,20 @@ int launch_conv1d(const ConvParams& p, hipStream_t st) {
   IX_ARG(p.Cin_pad % CG == 0, "conv: Cin_pad %d not a multiple of %d", p.Cin_pad, CG);
   const bool k24 = p.Cin_pad % 24 == 0 && p.Cin_pad % 32 != 0;  // 24 / 48 input channels: 24-channel chunks, no dead group
   switch (conv_tile_bm(p.Cout)) {
-    case 32: return k24 ? launch_cfg<1, 2, 1, 4, 3>(p, st) : launch_cfg<1, 2, 1, 4>(p, st);   // 32 x 256
-    case 64: return k24 ? launch_cfg<2, 1, 1, 4, 3>(p, st) : launch_cfg<2, 1, 1, 4>(p, st);   // 64 x 128
-    case 96: return launch_cfg<3, 1, 1, 4>(p, st);   // 96 x 128
+    case 32: return conv_count_tile(p, 3), k24 ? launch_cfg<1, 2, 1, 4, 3>(p, st) : launch_cfg<1, 2, 1, 4>(p, st);   // 32 x 256
+    case 64: return conv_count_tile(p, 4), k24 ? launch_cfg<2, 1, 1, 4, 3>(p, st) : launch_cfg<2, 1, 1, 4>(p, st);   // 64 x 128
+    case 96: return conv_count_tile(p, 5), launch_cfg<3, 1, 1, 4>(p, st);   // 96 x 128
     default: {
-      const double s128 = tile_score(p, 128, 128, 1.00), s64x128 = tile_score(p, 64, 128, 0.96), s64 = tile_score(p, 64, 64, 0.90);
-      if (s128 >= s64x128 && s128 >= s64) return launch_cfg<2, 2, 2, 2>(p, st);  // 128 x 128
-      if (s64x128 >= s64) return launch_cfg<1, 2, 2, 2>(p, st);                  // 64 x 128
-      return launch_cfg<1, 1, 2, 2>(p, st);                                      // 64 x 64
+      int tile = p.force_tile - 1;  // IXTTS_BV_TILE: the developer's choice in place of the score
+      if (tile < 0) {
+        const double s128 = tile_score(p, 128, 128, 1.00), s64x128 = tile_score(p, 64, 128, 0.96), s64 = tile_score(p, 64, 64, 0.90);
+        tile = (s128 >= s64x128 && s128 >= s64) ? 0 : s64x128 >= s64 ? 1 : 2;
+      }
+      IX_ARG(tile < CONV_TILE_SCORED, "conv: forced tile %d", tile);
+      conv_count_tile(p, tile);
+      if (tile == 0) return launch_cfg<2, 2, 2, 2>(p, st);  // 128 x 128
+      if (tile == 1) return launch_cfg<1, 2, 2, 2>(p, st);  // 64 x 128
+      return launch_cfg<1, 1, 2, 2>(p, st);                 // 64 x 64
     }
   }
 }

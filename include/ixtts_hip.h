@@ -364,6 +364,26 @@ int ixtts_gpt_share_arena(ixtts_gpt* h, ixtts_gpt* owner);
  * cache, resets the slot's history to the fake ids [1]*(P-1)+[start] (model_v2.py:652-661)
  * and leaves the first-step logits ready. */
 int ixtts_gpt_prefill(ixtts_gpt* h, int b, const float* embeds_dev, int n_rows, int n_left_pad, void* stream);
+/* ixtts_gpt_prefill of n sequences into the n slots `slots[i]` (any slots, any order, none twice) in one packed causal pass per
+ * layer: entry i is (slots[i], embeds_dev[i] [n_rows[i], D], n_rows[i], n_left_pad[i]).  Afterwards every named slot holds bit
+ * for bit what ixtts_gpt_prefill of its entry alone leaves -- first-step logits, K/V rows, history, prompt_len / valid_from,
+ * cleared bans, sequence-bias table and forced ids -- whatever shares the pass and however the call is cut into passes; slots
+ * not named are not touched.  A pass holds at most min(rows_max > 0 ? rows_max : max_seq, max_seq) packed rows (the rows
+ * workspaces hold max_seq; rows_max exists for tests, production passes 0) and the call makes the passes of
+ * ixtts_gpt_prefill_plan.  Every argument is checked before anything is enqueued: 0 <= n <= max_batch (n == 0: no-op), each
+ * slot in range and named once, each entry's rows as ixtts_gpt_prefill checks them; IXTTS_ERR_ARG names the entry and the slot
+ * and leaves every slot as it was.  Stream-ordered, no host synchronisation of its own.  The tables go down `stream` from one
+ * pageable host buffer of the handle, which the next call rewrites: like ixtts_gpt_set_bans and the scalars of
+ * ixtts_gpt_prefill, this relies on the HIP runtime having copied (or staged) a pageable source by the time hipMemcpyAsync
+ * returns.  The handle has one device copy of the tables and one set of rows workspaces: calls on one handle (this one,
+ * ixtts_gpt_prefill, ixtts_gpt_latent) must be ordered by one stream, or by events between streams.  The embeds must stay alive
+ * until the stream has consumed them. */
+int ixtts_gpt_prefill_many(ixtts_gpt* h, int n, const int* slots, const float* const* embeds_dev, const int* n_rows, const int* n_left_pad,
+                           int rows_max, void* stream);
+/* The pass rule of ixtts_gpt_prefill_many as a host function (no handle, no GPU): entries in the order given, entry i being
+ * n_rows[i] + 1 - n_left_pad[i] packed rows; a pass closes when the next entry would not fit in row_cap rows.  Writes the pass
+ * of each entry to pass_of[n] and returns the number of passes (0 for n == 0), IXTTS_ERR_ARG for a null array or row_cap < 1. */
+int ixtts_gpt_prefill_plan(const int* n_rows, const int* n_left_pad, int n, int row_cap, int* pass_of);
 /* Run up to `n_steps` decode steps for slots [0, n_active): logits -> processors -> token ->
  * embed -> 24 layers.  No host synchronisation inside; a slot that emits stop_mel_token
  * keeps emitting it (generation_utils.py:3255-3256).  Tokens accumulate on the device. */

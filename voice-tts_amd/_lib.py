@@ -123,6 +123,8 @@ SYMBOLS = {
     "ixtts_gpt_adopt_arena": (C.c_int, [_P]),
     "ixtts_gpt_share_arena": (C.c_int, [_P, _P]),
     "ixtts_gpt_prefill": (C.c_int, [_P, C.c_int, _P, C.c_int, C.c_int, _P]),
+    "ixtts_gpt_prefill_many": (C.c_int, [_P, C.c_int, C.POINTER(C.c_int), C.POINTER(_P), C.POINTER(C.c_int), C.POINTER(C.c_int), C.c_int, _P]),
+    "ixtts_gpt_prefill_plan": (C.c_int, [C.POINTER(C.c_int), C.POINTER(C.c_int), C.c_int, C.c_int, C.POINTER(C.c_int)]),
     "ixtts_gpt_decode": (C.c_int, [_P, C.c_int, C.c_int, C.POINTER(SamplerCfg), _P]),
     "ixtts_gpt_decode_slots": (C.c_int, [_P, C.c_int, C.c_int, C.POINTER(SamplerCfg), C.POINTER(C.c_uint32), _P]),
     "ixtts_gpt_read": (C.c_int, [_P, C.c_int, _P, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int), _P]),

@@ -131,6 +131,10 @@ struct ixtts_gpt {
   int beam_exec_nb = 0;
   // batched-rows workspace (prefill / latent): [max_seq][D] x4 + [max_seq][4D]
   float *rx = nullptr, *rxn = nullptr, *rq = nullptr, *ratt = nullptr, *rff = nullptr;
+  // ixtts_gpt_prefill_many: the tables of a call's passes, staged in pf_host and sent down the caller's stream in one copy
+  std::vector<uint8_t> pf_host;
+  uint8_t* pf_dev = nullptr;
+  size_t pf_bytes = 0;
 };
 
 #define A_F32(off) reinterpret_cast<float*>(h->arena + (off))
@@ -145,6 +149,24 @@ int forward_rows(ixtts_gpt* h, int slot, int T, int pos0, int valid_from, hipStr
 }  // namespace ixtts
 
 namespace ixtts {
+// ---- packed pass of ixtts_gpt_prefill_many: the valid rows of several sequences one after the other in h->rx, no padding between
+struct PackSeq {
+  const float* embeds;      // the caller's [n_rows][D]; the pass reads its rows pos0 ..
+  int slot, T, pos0, row0;  // T valid rows (start-mel row last) at packed rows row0 .., cache positions pos0 .. (pos0 = n_left_pad = valid_from)
+};
+struct PackedPass {       // device tables of one pass (regions of ixtts_gpt::pf_dev) and its sizes
+  const PackSeq* seqs;    // [n_seq]
+  const int* tiles;       // [n_tiles][2]: (sequence, first query row within it) of every 128-row attention tile
+  const int* row_at;      // [T]: cache row slot * H * smax + position of every packed row
+  const int* row_seq;     // [T]: its sequence
+  int n_seq, n_tiles, T;
+};
+// gather the sequences' embeds rows into h->rx and write each one's start-mel row
+int pack_rows(ixtts_gpt* h, const PackedPass& p, hipStream_t st);
+// the 24 layers over the packed rows: per-row kernels as forward_rows at T = p.T, K/V scattered by row_at, attention per sequence
+int forward_rows_packed(ixtts_gpt* h, const PackedPass& p, hipStream_t st);
+// each sequence's last row -> h->h + slot * D
+int unpack_last_rows(ixtts_gpt* h, const PackedPass& p, hipStream_t st);
 int final_norm_rows(ixtts_gpt* h, const float* x, float* y, int T, hipStream_t st);
 int embed_mel_rows(ixtts_gpt* h, float* x, const int32_t* codes, int rows, hipStream_t st);
 struct SamplerState;

@@ -414,6 +414,10 @@ static size_t take(size_t& off, size_t bytes) {
   return o;
 }
 
+static size_t pf_table_bytes(int n, int smax) {  // the most a call of n sequences can need: see the layout in ixtts_gpt_prefill_many
+  return (size_t)n * (sizeof(PackSeq) + 4) + (size_t)n * (smax / 128 + 1) * 8 + (size_t)n * smax * 8;
+}
+
 extern "C" int ixtts_gpt_create(ixtts_gpt** out, const ixtts_gpt_cfg* c) {
   IX_ARG(out && c, "gpt_create: null argument");
   IX_ARG(c->model_dim == 1280 || c->model_dim == 128, "gpt_create: model_dim %d has no kernel instantiation (1280 | 128)", c->model_dim);
@@ -537,7 +541,10 @@ extern "C" int ixtts_gpt_create(ixtts_gpt** out, const ixtts_gpt_cfg* c) {
   ok &= hipMalloc(&h->scratch, h->scratch_floats * 4) == hipSuccess;
   ok &= hipMalloc(&h->bans, (size_t)S * V) == hipSuccess;  // (after everything older: no other buffer's address moves)
   ok &= hipMalloc(&h->seq_bias, (size_t)S * IXTTS_SEQ_BIAS_MAX * sizeof(SeqBiasEntry)) == hipSuccess;
+  h->pf_bytes = pf_table_bytes(c->max_batch, h->smax);
+  ok &= hipMalloc(&h->pf_dev, h->pf_bytes) == hipSuccess;  // (the newest: as above)
   if (!ok) return fail("state");
+  h->pf_host.assign(h->pf_bytes, 0);
   hipMemset(h->cur_len, 0, S * 4);
   hipMemset(h->gen_count, 0, S * 4);
   hipMemset(h->prompt_len, 0, S * 4);
@@ -810,6 +817,135 @@ extern "C" int ixtts_gpt_prefill(ixtts_gpt* h, int b, const float* embeds, int n
   IX_HIP(hipMemcpyAsync(h->h + (size_t)b * D, h->rx + (size_t)(T - 1) * D, (size_t)D * 4, hipMemcpyDeviceToDevice, st));
   h->hc = h->h;
   IX_TRY(do_head(h, 1, b, nullptr, st));
+  IX_HIP(hipGetLastError());
+  return IXTTS_OK;
+}
+
+// ------------------------------------------------------------------------------------ prefill of many slots
+// The pass rule: sequences in the order given, T = n_rows + 1 - n_left_pad packed rows each; a pass closes when the next sequence
+// would not fit in row_cap rows (a sequence longer than row_cap still gets a pass of its own).  Pure host arithmetic.
+extern "C" int ixtts_gpt_prefill_plan(const int* n_rows, const int* n_left_pad, int n, int row_cap, int* pass_of) {
+  IX_ARG(n >= 0 && (n == 0 || (n_rows && n_left_pad && pass_of)) && row_cap >= 1, "gpt_prefill_plan: bad arguments (n %d, row_cap %d)", n, row_cap);
+  int pass = 0, used = 0;
+  for (int i = 0; i < n; ++i) {
+    const int T = n_rows[i] + 1 - n_left_pad[i];
+    if (used > 0 && used + T > row_cap) {
+      ++pass;
+      used = 0;
+    }
+    pass_of[i] = pass;
+    used += T;
+  }
+  return n > 0 ? pass + 1 : 0;
+}
+
+namespace ixtts {
+// the slot state ixtts_gpt_prefill resets with memsets and copies, for every sequence of a call in one launch (one workgroup each)
+__global__ __launch_bounds__(256) void prefill_reset_slots_kernel(const PackSeq* __restrict__ seqs, const int* __restrict__ prompt_lens, uint8_t* __restrict__ seen,
+                                                                   uint8_t* __restrict__ bans, int* __restrict__ gen_count, int* __restrict__ finished,
+                                                                   int* __restrict__ forced, int* __restrict__ prompt_len, int* __restrict__ valid_from, int V, int start_tok) {
+  const PackSeq s = seqs[blockIdx.x];
+  const int b = s.slot;
+  for (int v = threadIdx.x; v < V; v += blockDim.x) {
+    seen[(size_t)b * V + v] = (v == 1 || v == start_tok) ? 1 : 0;  // history = fake ids [1]*(P-1) + [start]
+    bans[(size_t)b * V + v] = 0;
+  }
+  if (threadIdx.x == 0) {
+    gen_count[b] = 0;
+    finished[b] = 0;
+    forced[b] = -1;
+    prompt_len[b] = prompt_lens[blockIdx.x];
+    valid_from[b] = s.pos0;
+  }
+}
+}  // namespace ixtts
+
+extern "C" int ixtts_gpt_prefill_many(ixtts_gpt* h, int n, const int* slots, const float* const* embeds_dev, const int* n_rows, const int* n_left_pad,
+                                      int rows_max, void* stream) {
+  NEED_READY(h, "gpt_prefill_many");
+  IX_ARG(n >= 0 && n <= h->cfg.max_batch, "gpt_prefill_many: %d entries (0..max_batch = %d)", n, h->cfg.max_batch);
+  if (n == 0) return IXTTS_OK;
+  IX_ARG(slots && embeds_dev && n_rows && n_left_pad, "gpt_prefill_many: null argument");
+  // everything is checked before anything is enqueued or any host state changes
+  for (int i = 0; i < n; ++i) {
+    const int b = slots[i];
+    IX_ARG(b >= 0 && b < h->cfg.max_batch, "gpt_prefill_many: entry %d: slot %d out of range", i, b);
+    for (int j = 0; j < i; ++j) IX_ARG(slots[j] != b, "gpt_prefill_many: entry %d: slot %d given twice (entry %d)", i, b, j);
+    IX_ARG(embeds_dev[i] && n_rows[i] >= 1 && n_left_pad[i] >= 0 && n_left_pad[i] < n_rows[i], "gpt_prefill_many: entry %d (slot %d): bad rows (%d, pad %d)", i, b,
+           n_rows[i], n_left_pad[i]);
+    IX_ARG(n_rows[i] + 2 < h->smax, "gpt_prefill_many: entry %d (slot %d): prompt of %d rows exceeds max_seq %d", i, b, n_rows[i] + 1, h->smax);
+  }
+  hipStream_t st = (hipStream_t)stream;
+  const int V = h->V, smax = h->smax;
+  const int row_cap = std::min(rows_max > 0 ? rows_max : smax, smax);
+  int pass_of[MAXB];
+  const int n_pass = ixtts_gpt_prefill_plan(n_rows, n_left_pad, n, row_cap, pass_of);
+  if (n_pass < 0) return n_pass;
+
+  // tables of the whole call: [n] PackSeq | [tiles][2] (both 8-byte aligned) | [n] prompt_len | [rows] row_at | [rows] row_seq, each pass a range of each
+  int rows_total = 0, tiles_total = 0;
+  for (int i = 0; i < n; ++i) {
+    const int T = n_rows[i] + 1 - n_left_pad[i];
+    rows_total += T;
+    tiles_total += ceil_div(T, 128);
+  }
+  static_assert(sizeof(PackSeq) % 8 == 0, "the tile pairs behind the PackSeq array are read as int2");
+  const size_t off_tiles = (size_t)n * sizeof(PackSeq), off_plen = off_tiles + (size_t)tiles_total * 8, off_at = off_plen + (size_t)n * 4,
+               off_seq = off_at + (size_t)rows_total * 4, bytes = off_seq + (size_t)rows_total * 4;
+  if (bytes > h->pf_bytes) {
+    set_error("gpt_prefill_many: tables of %zu bytes exceed the handle's %zu", bytes, h->pf_bytes);
+    return IXTTS_ERR_STATE;
+  }
+  uint8_t* hb = h->pf_host.data();
+  PackSeq* seqs = reinterpret_cast<PackSeq*>(hb);
+  int* plen = reinterpret_cast<int*>(hb + off_plen);
+  int* tiles = reinterpret_cast<int*>(hb + off_tiles);
+  int* row_at = reinterpret_cast<int*>(hb + off_at);
+  int* row_seq = reinterpret_cast<int*>(hb + off_seq);
+  struct Range { int seq0, n_seq, tile0, n_tiles, row0, T; } pr[MAXB] = {};
+  {
+    int tile = 0, row = 0;
+    for (int i = 0; i < n; ++i) {
+      Range& r = pr[pass_of[i]];
+      if (r.n_seq == 0) { r.seq0 = i; r.tile0 = tile; r.row0 = row; }
+      const int T = n_rows[i] + 1 - n_left_pad[i], local = i - r.seq0;
+      seqs[i] = PackSeq{embeds_dev[i], slots[i], T, n_left_pad[i], r.T};
+      plen[i] = n_rows[i] + 1;
+      for (int q0 = 0; q0 < T; q0 += 128) { tiles[2 * tile] = local; tiles[2 * tile + 1] = q0; ++tile; ++r.n_tiles; }
+      for (int t = 0; t < T; ++t) { row_at[row] = slots[i] * h->H * smax + n_left_pad[i] + t; row_seq[row] = local; ++row; }
+      ++r.n_seq;
+      r.T += T;
+    }
+  }
+  // host-side slot state, as ixtts_gpt_prefill leaves it
+  for (int i = 0; i < n; ++i) {
+    const int b = slots[i];
+    memset(h->bans_host.data() + (size_t)b * V, 0, V);
+    h->seq_bias_n[b] = 0;
+    h->host_prompt_len[b] = n_rows[i] + 1;
+    h->host_gen_est[b] = 0;
+  }
+  // (a pageable source: the runtime has taken its copy when this returns, which is what lets the next call rewrite pf_host -- the
+  //  reliance ixtts_gpt_set_bans and ixtts_gpt_prefill's `&P` make; pf_dev is ordered by the caller's stream, see the header)
+  IX_HIP(hipMemcpyAsync(h->pf_dev, hb, bytes, hipMemcpyHostToDevice, st));
+  const PackSeq* d_seqs = reinterpret_cast<const PackSeq*>(h->pf_dev);
+  hipLaunchKernelGGL(prefill_reset_slots_kernel, dim3(n), dim3(256), 0, st, d_seqs, reinterpret_cast<const int*>(h->pf_dev + off_plen), h->seen, h->bans,
+                     h->gen_count, h->finished, h->forced, h->prompt_len, h->valid_from, V, h->cfg.start_mel_token);
+  for (int p = 0; p < n_pass; ++p) {
+    const Range& r = pr[p];
+    PackedPass pk;
+    pk.seqs = d_seqs + r.seq0;
+    pk.tiles = reinterpret_cast<const int*>(h->pf_dev + off_tiles) + 2 * r.tile0;
+    pk.row_at = reinterpret_cast<const int*>(h->pf_dev + off_at) + r.row0;
+    pk.row_seq = reinterpret_cast<const int*>(h->pf_dev + off_seq) + r.row0;
+    pk.n_seq = r.n_seq; pk.n_tiles = r.n_tiles; pk.T = r.T;
+    IX_TRY(pack_rows(h, pk, st));
+    IX_TRY(forward_rows_packed(h, pk, st));
+    IX_TRY(unpack_last_rows(h, pk, st));
+    h->hc = h->h;
+    // the head per slot, the launch ixtts_gpt_prefill makes: a head over a run of slots is another launch shape on some engines
+    for (int i = r.seq0; i < r.seq0 + r.n_seq; ++i) IX_TRY(do_head(h, 1, slots[i], nullptr, st));
+  }
   IX_HIP(hipGetLastError());
   return IXTTS_OK;
 }
@@ -1377,7 +1513,7 @@ extern "C" int ixtts_gpt_destroy(ixtts_gpt* h) {
   void* ptrs[] = {h->arena, h->stage, h->kc, h->vc, h->h, h->q, h->ff, h->att, h->part, h->logits, h->rowbuf, h->cur_len, h->gen_count,
                   h->prompt_len, h->valid_from, h->finished, h->forced, h->tokens, h->seen, h->bans, h->seq_bias, h->d_samp, h->d_rng, h->probs, h->scratch, h->beam_scores, h->hyp_score, h->hyp_worst, h->beam_src, h->hyp_len,
                   h->n_hyp, h->beam_done, h->beam_forced_flag, h->beam_forced, h->hyp_tok, h->beam_cand_v, h->beam_cand_i, h->beam_cand_n, h->beam_lcp, h->beam_stream,
-                  h->rx, h->rxn, h->rq, h->ratt, h->rff, h->h2, h->wprx, h->mlp_part, h->mlp_ctr, h->fold_overflow};
+                  h->rx, h->rxn, h->rq, h->ratt, h->rff, h->h2, h->wprx, h->mlp_part, h->mlp_ctr, h->fold_overflow, h->pf_dev};
   for (void* p : ptrs)
     if (p) hipFree(p);
   delete h;

@@ -105,7 +105,7 @@ __global__ __launch_bounds__(256) void final_norm_rows_kernel(const float* __res
 }
 
 // ---- GEMM: C[T][N] = A[T][K] . Wt[N][K]^T + bias
-enum { RE_QKV = 0, RE_RESID = 1, RE_GELU = 2 };
+enum { RE_QKV = 0, RE_RESID = 1, RE_GELU = 2, RE_QKV_PACKED = 3 };
 
 struct GemmArgs {
   const float* A;    // [T][K] fp32
@@ -117,14 +117,21 @@ struct GemmArgs {
   int T, N, K, pos0, smax, D;
 };
 
+// RE_QKV_PACKED (ixtts_gpt_prefill_many): the T rows are the valid rows of several sequences one after the other; kcache / vcache
+// are the LAYER's bases and row m's K/V go to cache row row_at[m] = slot * H * smax + position (counted in rows of HD elements
+// from that base, head 0) -- the one line in which the epilogue differs from RE_QKV
+struct GemmArgsPacked : GemmArgs {
+  const int* row_at;  // [T]
+};
+
 constexpr int GBN = 128;
 
 // Tile BM x 128 x BK, 4 waves as 2 x 2, wave tile (BM/2) x 64.  bf16: BK = 64, both operands staged as bf16 in LDS (the
 // fp32 activations are converted in the staging pass), rows padded to 144 B so the 16-byte fragment reads of 8 consecutive
 // rows fall in 8 different bank groups; fp32: BK = 32, pitch 33.  The global loads of k-tile i+1 are issued before the
 // MFMAs of k-tile i and written to LDS after them (one register set, one LDS buffer, two barriers per k-tile).
-template <typename WT, int EPI, typename KVT, int BM>
-__global__ __launch_bounds__(256) void gemm_rows_kernel(GemmArgs g) {
+template <typename WT, int EPI, typename KVT, int BM, typename GA = GemmArgs>
+__global__ __launch_bounds__(256) void gemm_rows_kernel(GA g) {
   constexpr bool F32 = sizeof(WT) == 4;
   constexpr int BK = F32 ? 32 : 64;
   constexpr int MI = BM / 64;                              // 32-row blocks per wave
@@ -256,6 +263,16 @@ __global__ __launch_bounds__(256) void gemm_rows_kernel(GemmArgs g) {
           *o = *o + v;
         } else if constexpr (EPI == RE_GELU) {
           g.out[(size_t)m * g.N + n] = gelu_new_f(v);
+        } else if constexpr (EPI == RE_QKV_PACKED) {
+          if (n < g.D) {
+            g.out[(size_t)m * g.D + n] = v;
+          } else {
+            const int which = n / g.D;
+            const int c = n - which * g.D;
+            const int hh = c / HD, d = c % HD;
+            KVT* cache = reinterpret_cast<KVT*>(which == 1 ? g.kcache : g.vcache);
+            store_kv(cache + ((size_t)hh * g.smax + g.row_at[m]) * HD + d, v);
+          }
         } else {
           if (n < g.D) {
             g.out[(size_t)m * g.D + n] = v;
@@ -291,6 +308,10 @@ struct GemmArgs16 {
   int T, N, K, pos0, smax, D;
 };
 
+struct GemmArgs16Packed : GemmArgs16 {  // RE_QKV_PACKED, as GemmArgsPacked
+  const int* row_at;  // [T]
+};
+
 __device__ __forceinline__ void glds16(const void* gsrc, void* lds_wave_base) {
   __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)gsrc, (__attribute__((address_space(3))) void*)lds_wave_base, 16, 0, 0);
 }
@@ -299,8 +320,8 @@ constexpr int G16_NBUF = 2;                       // LDS buffers: NBUF - 1 k-til
 constexpr int G16_TILE = 128 * 64 * 2;            // 16 KiB per operand tile
 constexpr int G16_SMEM = G16_NBUF * 2 * G16_TILE; // 64 KiB: two workgroups per CU
 
-template <int EPI, typename KVT>
-__global__ __launch_bounds__(256) void gemm_rows_bf16_kernel(GemmArgs16 g) {  // KVT is also the operands' element type
+template <int EPI, typename KVT, typename GA = GemmArgs16>
+__global__ __launch_bounds__(256) void gemm_rows_bf16_kernel(GA g) {  // KVT is also the operands' element type
   using EL = RowsEl<KVT>;
   typedef typename EL::vec8 vec8;
   constexpr int BM = 128, BN = 128, BK = 64, TILE = G16_TILE, NBUF = G16_NBUF;
@@ -398,6 +419,37 @@ __global__ __launch_bounds__(256) void gemm_rows_bf16_kernel(GemmArgs16 g) {  //
           const int m = m0 + wm * 64 + mi * 32 + (r & 3) + 8 * (r >> 2) + 4 * lh;
           if (m < g.T && ncol[j] < g.N) xo[(size_t)m * g.N + ncol[j]] = old[mi][j][r] + (acc[mi][j][r] + bias[j]);
         }
+  } else if constexpr (EPI == RE_QKV_PACKED) {
+    // the rows' cache positions first, all of them, not under the row bound (clamped): the same rule as the residual loads above.
+    // Only a workgroup whose column tile holds K or V columns needs them (workgroup-uniform: a tile of Q columns skips the loads)
+    int at[2][16] = {};
+    if (n0 + BN > g.D) {
+#pragma unroll
+      for (int mi = 0; mi < 2; ++mi)
+#pragma unroll
+        for (int r = 0; r < 16; ++r) at[mi][r] = g.row_at[min(m0 + wm * 64 + mi * 32 + (r & 3) + 8 * (r >> 2) + 4 * lh, g.T - 1)];
+    }
+#pragma unroll
+    for (int mi = 0; mi < 2; ++mi)
+#pragma unroll
+      for (int j = 0; j < 2; ++j) {
+        const int n = ncol[j];
+#pragma unroll
+        for (int r = 0; r < 16; ++r) {
+          const int m = m0 + wm * 64 + mi * 32 + (r & 3) + 8 * (r >> 2) + 4 * lh;
+          if (m >= g.T || n >= g.N) continue;
+          const float v = acc[mi][j][r] + bias[j];
+          if (n < g.D) {
+            reinterpret_cast<float*>(g.out)[(size_t)m * g.D + n] = v;
+          } else {
+            const int which = n / g.D;
+            const int c = n - which * g.D;
+            const int hh = c / HD, d = c % HD;
+            KVT* cache = reinterpret_cast<KVT*>(which == 1 ? g.kcache : g.vcache);
+            store_kv(cache + ((size_t)hh * g.smax + at[mi][r]) * HD + d, v);
+          }
+        }
+      }
   } else {
 #pragma unroll
     for (int mi = 0; mi < 2; ++mi)
@@ -459,6 +511,63 @@ __global__ __launch_bounds__(256) void attn_rows_kernel(AttnRowsArgs a) {
   });
   const float o = attn_merge<KVT, NW>(st, sm, wave, lane);
   if (threadIdx.x < 64) store_kv(reinterpret_cast<OT*>(a.out) + (size_t)row * a.D + hh * HD + threadIdx.x, o);
+}
+
+// The packed pass of ixtts_gpt_prefill_many: several sequences' rows one after the other in q / out, each sequence with its own
+// slot cache, T, pos0 and valid_from.  A workgroup of the attention kernels below serves ONE sequence: it builds that sequence's
+// AttnRowsArgs from the table and runs on it the one-sequence kernel's statements, kept as a copy of their own (attn_rows_seq,
+// attn_rows_flash_seq: the one-sequence kernels stay the code they were, to the instruction): query partition, key-tile origin, wave
+// skips, masks and clamps are those of the solo launch.
+struct AttnPackedArgs {
+  const float* q;         // [sum T][D]
+  const void* kcache;     // LAYER base [slot][H][smax][64]
+  const void* vcache;
+  void* out;              // [sum T][D]
+  const PackSeq* seqs;
+  const int2* tiles;      // flash kernel: blockIdx.y -> (sequence, first query row of the 128-row tile within it)
+  const int* row_seq;     // row kernel: blockIdx.y (a packed row) -> sequence
+  int D, smax, H;
+};
+template <typename KVT, typename OT>
+__device__ __forceinline__ AttnRowsArgs packed_seq_args(const AttnPackedArgs& p, int seq) {
+  const PackSeq s = p.seqs[seq];
+  const size_t slot_off = (size_t)s.slot * p.H * p.smax * HD;
+  AttnRowsArgs a;
+  a.q = p.q + (size_t)s.row0 * p.D;
+  a.kcache = reinterpret_cast<const KVT*>(p.kcache) + slot_off;
+  a.vcache = reinterpret_cast<const KVT*>(p.vcache) + slot_off;
+  a.out = reinterpret_cast<OT*>(p.out) + (size_t)s.row0 * p.D;
+  a.T = s.T; a.D = p.D; a.smax = p.smax; a.pos0 = s.pos0; a.valid_from = s.pos0;
+  return a;
+}
+
+// attn_rows_kernel for one sequence of a packed pass: the same statements, `row` in place of blockIdx.y
+template <typename KVT, typename OT>
+__device__ __forceinline__ void attn_rows_seq(const AttnRowsArgs& a, const int row) {
+  constexpr int NW = 4;
+  using LY = KVLayout<KVT>;
+  __shared__ float sm[NW][LY::LPP][2 + LY::DPL];
+  const int hh = blockIdx.x;
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const int dp = lane % LY::LPP;
+  float qv[LY::DPL];
+  load_q_slice<KVT>(a.q + (size_t)row * a.D + hh * HD, dp, qv);
+  const KVT* kb = reinterpret_cast<const KVT*>(a.kcache) + (size_t)hh * a.smax * HD + dp * LY::DPL;
+  const KVT* vb = reinterpret_cast<const KVT*>(a.vcache) + (size_t)hh * a.smax * HD + dp * LY::DPL;
+  SoftAcc<LY::DPL> st;
+  st.init();
+  const int lo0 = a.valid_from, hi0 = a.pos0 + row + 1;
+  attn_sweep<KVT, NW, 8>(st, kb, vb, qv, a.smax, wave, lane, [&](int& lo, int& hi) {
+    lo = lo0;
+    hi = hi0;
+  });
+  const float o = attn_merge<KVT, NW>(st, sm, wave, lane);
+  if (threadIdx.x < 64) store_kv(reinterpret_cast<OT*>(a.out) + (size_t)row * a.D + hh * HD + threadIdx.x, o);
+}
+template <typename KVT, typename OT>
+__global__ __launch_bounds__(256) void attn_rows_packed_kernel(AttnPackedArgs p) {  // grid (H, sum T)
+  const int seq = p.row_seq[blockIdx.y];
+  attn_rows_seq<KVT, OT>(packed_seq_args<KVT, OT>(p, seq), (int)blockIdx.y - p.seqs[seq].row0);
 }
 
 // ---- the same attention as a causal flash kernel on the fp32 matrix cores (the latent pass: 1237 rows x 20 heads; the
@@ -646,6 +755,160 @@ __global__ __launch_bounds__(256) void attn_rows_flash_kernel(AttnRowsArgs a) {
   }
 }
 
+// attn_rows_flash_kernel for one sequence of a packed pass: the same statements, with q0 (the first row of the workgroup's 128-row
+// tile within the sequence) in place of blockIdx.y * 128.  A change to one of the two belongs in the other.
+template <typename KVT, typename OT>
+__device__ __forceinline__ void attn_rows_flash_seq(const AttnRowsArgs& a, const int q0) {
+  __shared__ __attribute__((aligned(16))) float Ks[FR_KT * FR_KP];
+  __shared__ __attribute__((aligned(16))) float Vs[FR_KT * HD];
+  const int hh = blockIdx.x;
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const int l31 = lane & 31, lh = lane >> 5;
+  const int qw0 = q0 + wave * 32;  // first row of this wave
+  const KVT* kb = reinterpret_cast<const KVT*>(a.kcache) + (size_t)hh * a.smax * HD;
+  const KVT* vb = reinterpret_cast<const KVT*>(a.vcache) + (size_t)hh * a.smax * HD;
+  const int last_key = a.pos0 + a.T - 1;  // last cache row this pass has written
+
+  float qr[HD / 2];  // Q[row l31][d = 8m + 4 lh + i] for k-step 4m + i, scaled by log2(e) / sqrt(64)
+  {
+    const int qi = min(qw0 + l31, a.T - 1);
+    const float* qp = a.q + (size_t)qi * a.D + hh * HD + 4 * lh;
+    const float qs = 0.125f * 1.4426950408889634f;
+#pragma unroll
+    for (int m = 0; m < HD / 8; ++m) {
+      const float4 t = *reinterpret_cast<const float4*>(qp + 8 * m);
+      qr[4 * m] = t.x * qs; qr[4 * m + 1] = t.y * qs; qr[4 * m + 2] = t.z * qs; qr[4 * m + 3] = t.w * qs;
+    }
+  }
+  f32x16 ot[2];
+#pragma unroll
+  for (int j = 0; j < 2; ++j)
+#pragma unroll
+    for (int r = 0; r < 16; ++r) ot[j][r] = 0.f;
+  float m_run = -INFINITY, l_run = 0.f;
+  const int lim = a.pos0 + qw0 + l31;             // last key this lane's row may see
+  const int wave_lim = a.pos0 + min(qw0 + 31, a.T - 1);  // ... and any row of this wave
+  const int wg_lim = a.pos0 + min(q0 + 127, a.T - 1);
+  const int t_first = (a.valid_from / FR_KT) * FR_KT;
+
+  for (int t0 = t_first; t0 <= wg_lim; t0 += FR_KT) {
+    __syncthreads();
+    {  // stage 64 keys x 64 dims of K and V, widened to fp32: each thread one quarter row of each
+      const int key = threadIdx.x >> 2, c16 = (threadIdx.x & 3) * 16;
+      // rows past the pass repeat its last one, rows before valid_from (left padding: never written, the cache holds whatever the
+      // allocation held -- 0 x NaN in the P V product would poison the row) repeat the first valid one; both are masked below
+      const int t = min(max(t0 + key, a.valid_from), last_key);
+      float kv[16], vv[16];
+      load_row16<KVT>(kb + (size_t)t * HD + c16, kv);
+      load_row16<KVT>(vb + (size_t)t * HD + c16, vv);
+#pragma unroll
+      for (int i = 0; i < 4; ++i) {
+        *reinterpret_cast<float4*>(Ks + key * FR_KP + c16 + 4 * i) = make_float4(kv[4 * i], kv[4 * i + 1], kv[4 * i + 2], kv[4 * i + 3]);
+        *reinterpret_cast<float4*>(Vs + key * HD + c16 + 4 * i) = make_float4(vv[4 * i], vv[4 * i + 1], vv[4 * i + 2], vv[4 * i + 3]);
+      }
+    }
+    __syncthreads();
+    if (t0 > wave_lim) continue;  // wave-uniform: nothing in this tile is visible to this wave's rows
+
+    f32x16 st[2];
+#pragma unroll
+    for (int j = 0; j < 2; ++j)
+#pragma unroll
+      for (int r = 0; r < 16; ++r) st[j][r] = 0.f;
+    const float* kp0 = Ks + l31 * FR_KP + 4 * lh;
+    const float* kp1 = kp0 + 32 * FR_KP;
+    float4 ka[2][2];
+    ka[0][0] = *reinterpret_cast<const float4*>(kp0);
+    ka[0][1] = *reinterpret_cast<const float4*>(kp1);
+#pragma unroll
+    for (int m = 0; m < HD / 8; ++m) {
+      if (m + 1 < HD / 8) {
+        ka[(m + 1) & 1][0] = *reinterpret_cast<const float4*>(kp0 + 8 * (m + 1));
+        ka[(m + 1) & 1][1] = *reinterpret_cast<const float4*>(kp1 + 8 * (m + 1));
+      }
+#pragma unroll
+      for (int j = 0; j < 2; ++j) {
+        const float4 kk4 = ka[m & 1][j];
+        st[j] = __builtin_amdgcn_mfma_f32_32x32x2f32(kk4.x, qr[4 * m], st[j], 0, 0, 0);
+        st[j] = __builtin_amdgcn_mfma_f32_32x32x2f32(kk4.y, qr[4 * m + 1], st[j], 0, 0, 0);
+        st[j] = __builtin_amdgcn_mfma_f32_32x32x2f32(kk4.z, qr[4 * m + 2], st[j], 0, 0, 0);
+        st[j] = __builtin_amdgcn_mfma_f32_32x32x2f32(kk4.w, qr[4 * m + 3], st[j], 0, 0, 0);
+      }
+    }
+    // causal / left-padding mask (only the first and the diagonal tiles have masked keys)
+    if (t0 < a.valid_from || t0 + FR_KT - 1 > a.pos0 + qw0) {
+#pragma unroll
+      for (int j = 0; j < 2; ++j)
+#pragma unroll
+        for (int r = 0; r < 16; ++r) {
+          const int key = t0 + j * 32 + (r & 3) + 8 * (r >> 2) + 4 * lh;
+          if (key < a.valid_from || key > lim) st[j][r] = -INFINITY;
+        }
+    }
+    float tmax = -INFINITY;
+#pragma unroll
+    for (int j = 0; j < 2; ++j)
+#pragma unroll
+      for (int r = 0; r < 16; ++r) tmax = fmaxf(tmax, st[j][r]);
+    tmax = fmaxf(tmax, __shfl_xor(tmax, 32, 64));
+    // (a tile may be all -inf for a lane -- behind its limit: alpha = 1, weights 0.  A left-padding row, t < valid_from,
+    // sees no key at all: its maximum stays -inf and is replaced by 0 in the exponents, so it ends as a row of zeros,
+    // finite like everything else that reaches the cache)
+    const float mn = fmaxf(m_run, tmax);
+    const float mref = (mn == -INFINITY) ? 0.f : mn;
+    const float alpha = __builtin_amdgcn_exp2f(m_run - mref);
+    float psum = 0.f;
+#pragma unroll
+    for (int j = 0; j < 2; ++j)
+#pragma unroll
+      for (int r = 0; r < 16; ++r) {
+        const float pw = __builtin_amdgcn_exp2f(st[j][r] - mref);
+        st[j][r] = pw;
+        psum += pw;
+      }
+    psum += __shfl_xor(psum, 32, 64);
+    l_run = l_run * alpha + psum;
+    m_run = mn;
+    if (alpha != 1.0f) {
+#pragma unroll
+      for (int j = 0; j < 2; ++j)
+#pragma unroll
+        for (int r = 0; r < 16; ++r) ot[j][r] *= alpha;
+    }
+    const float* vp = Vs + (4 * lh) * HD + l31;
+    float va[2][2];
+    va[0][0] = vp[0];
+    va[0][1] = vp[32];
+#pragma unroll
+    for (int s2 = 0; s2 < 32; ++s2) {
+      const int j = s2 >> 4, r = s2 & 15;
+      if (s2 + 1 < 32) {
+        const int j1 = (s2 + 1) >> 4, r1 = (s2 + 1) & 15;
+        const float* vrow = vp + (j1 * 32 + (r1 & 3) + 8 * (r1 >> 2)) * HD;
+        va[(s2 + 1) & 1][0] = vrow[0];
+        va[(s2 + 1) & 1][1] = vrow[32];
+      }
+      const float pv = st[j][r];
+      ot[0] = __builtin_amdgcn_mfma_f32_32x32x2f32(va[s2 & 1][0], pv, ot[0], 0, 0, 0);
+      ot[1] = __builtin_amdgcn_mfma_f32_32x32x2f32(va[s2 & 1][1], pv, ot[1], 0, 0, 0);
+    }
+  }
+  const int qi = qw0 + l31;
+  if (qi < a.T) {
+    const float inv = l_run > 0.f ? 1.0f / l_run : 0.f;
+    OT* op = reinterpret_cast<OT*>(a.out) + (size_t)qi * a.D + hh * HD;
+#pragma unroll
+    for (int j = 0; j < 2; ++j)
+#pragma unroll
+      for (int r = 0; r < 16; ++r) store_kv(op + j * 32 + (r & 3) + 8 * (r >> 2) + 4 * lh, ot[j][r] * inv);
+  }
+}
+template <typename KVT, typename OT>
+__global__ __launch_bounds__(256) void attn_rows_flash_packed_kernel(AttnPackedArgs p) {  // grid (H, tiles of the pass)
+  const int2 t = p.tiles[blockIdx.y];
+  attn_rows_flash_seq<KVT, OT>(packed_seq_args<KVT, OT>(p, t.x), t.y);
+}
+
 template <typename KVT, typename OT>
 static void launch_attn_rows(ixtts_gpt* h, const AttnRowsArgs& a, hipStream_t st) {
   static const bool legacy = getenv("IXTTS_ROWS_ATTN") && !strcmp(getenv("IXTTS_ROWS_ATTN"), "legacy");  // A/B switch
@@ -653,18 +916,31 @@ static void launch_attn_rows(ixtts_gpt* h, const AttnRowsArgs& a, hipStream_t st
   else hipLaunchKernelGGL((attn_rows_flash_kernel<KVT, OT>), dim3(h->H, ceil_div(a.T, 128)), dim3(256), 0, st, a);
 }
 
-template <typename WT, typename KVT, int EPI>
-static void launch_gemm(const GemmArgs& g, hipStream_t st) {
+// the packed pass's attention: one workgroup per (head, 128-row tile of ONE sequence) / per (head, packed row)
+template <typename KVT, typename OT>
+static void launch_attn_packed(ixtts_gpt* h, const PackedPass& pk, const void* kc_layer, const void* vc_layer, void* out, hipStream_t st) {
+  static const bool legacy = getenv("IXTTS_ROWS_ATTN") && !strcmp(getenv("IXTTS_ROWS_ATTN"), "legacy");
+  AttnPackedArgs p;
+  p.q = h->rq; p.kcache = kc_layer; p.vcache = vc_layer; p.out = out; p.seqs = pk.seqs; p.tiles = reinterpret_cast<const int2*>(pk.tiles);
+  p.row_seq = pk.row_seq; p.D = h->D; p.smax = h->smax; p.H = h->H;
+  if (legacy) hipLaunchKernelGGL((attn_rows_packed_kernel<KVT, OT>), dim3(h->H, pk.T), dim3(256), 0, st, p);
+  else hipLaunchKernelGGL((attn_rows_flash_packed_kernel<KVT, OT>), dim3(h->H, pk.n_tiles), dim3(256), 0, st, p);
+}
+
+template <typename WT, typename KVT, int EPI, typename GA = GemmArgs>
+static void launch_gemm(const GA& g, hipStream_t st) {
   // 128-row tiles once there are enough rows to fill the GPU with them (latent pass), 64-row tiles for prompts
   if (g.T >= 512) {
-    hipLaunchKernelGGL((gemm_rows_kernel<WT, EPI, KVT, 128>), dim3(ceil_div(g.N, GBN), ceil_div(g.T, 128)), dim3(256), 0, st, g);
+    hipLaunchKernelGGL((gemm_rows_kernel<WT, EPI, KVT, 128, GA>), dim3(ceil_div(g.N, GBN), ceil_div(g.T, 128)), dim3(256), 0, st, g);
   } else {
-    hipLaunchKernelGGL((gemm_rows_kernel<WT, EPI, KVT, 64>), dim3(ceil_div(g.N, GBN), ceil_div(g.T, 64)), dim3(256), 0, st, g);
+    hipLaunchKernelGGL((gemm_rows_kernel<WT, EPI, KVT, 64, GA>), dim3(ceil_div(g.N, GBN), ceil_div(g.T, 64)), dim3(256), 0, st, g);
   }
 }
 
+// pk == nullptr: T rows of the sequence in `slot`.  pk: the packed rows of *pk (T = pk->T; slot, pos0, valid_from unused): the QKV
+// GEMM and the attention take their packed forms, every other launch is the one-sequence launch at more rows.
 template <typename WT, typename KVT, int D>
-static int forward_rows_t(ixtts_gpt* h, int slot, int T, int pos0, int valid_from, hipStream_t st) {
+static int forward_rows_t(ixtts_gpt* h, int slot, int T, int pos0, int valid_from, hipStream_t st, const PackedPass* pk = nullptr) {
   const size_t lstride = (size_t)h->slots * D * h->smax * sizeof(KVT);
   const size_t sstride = (size_t)D * h->smax * sizeof(KVT);
   for (int l = 0; l < h->L; ++l) {
@@ -675,10 +951,18 @@ static int forward_rows_t(ixtts_gpt* h, int slot, int T, int pos0, int valid_fro
     GemmArgs g;
     g.A = h->rxn; g.wt = A_PTR(o.wqkv); g.bias = A_F32(o.bqkv); g.out = h->rq; g.kcache = kc; g.vcache = vc;
     g.T = T; g.N = 3 * D; g.K = D; g.pos0 = pos0; g.smax = h->smax; g.D = D;
-    launch_gemm<WT, KVT, RE_QKV>(g, st);
-    AttnRowsArgs a;
-    a.q = h->rq; a.kcache = kc; a.vcache = vc; a.out = h->ratt; a.T = T; a.D = D; a.smax = h->smax; a.pos0 = pos0; a.valid_from = valid_from;
-    launch_attn_rows<KVT, float>(h, a, st);
+    if (pk) {
+      GemmArgsPacked gp;
+      static_cast<GemmArgs&>(gp) = g;
+      gp.row_at = pk->row_at;
+      launch_gemm<WT, KVT, RE_QKV_PACKED>(gp, st);
+      launch_attn_packed<KVT, float>(h, *pk, kc, vc, h->ratt, st);
+    } else {
+      launch_gemm<WT, KVT, RE_QKV>(g, st);
+      AttnRowsArgs a;
+      a.q = h->rq; a.kcache = kc; a.vcache = vc; a.out = h->ratt; a.T = T; a.D = D; a.smax = h->smax; a.pos0 = pos0; a.valid_from = valid_from;
+      launch_attn_rows<KVT, float>(h, a, st);
+    }
     g.A = h->ratt; g.wt = A_PTR(o.wo); g.bias = A_F32(o.bo); g.out = h->rx; g.N = D; g.K = D;
     launch_gemm<WT, KVT, RE_RESID>(g, st);
     hipLaunchKernelGGL(ln_rows_kernel<D>, dim3(ceil_div(T, 4)), dim3(256), 0, st, h->rx, h->rxn, T);
@@ -694,7 +978,7 @@ static int forward_rows_t(ixtts_gpt* h, int slot, int T, int pos0, int valid_fro
 // bf16 / fp16 weights: the producers write rows of the weights' type (into the same workspaces; fp16 rows saturate at
 // +-65504, store_kv) and the GEMMs are the LDS-DMA kernel
 template <typename KVT, int D>
-static int forward_rows_16(ixtts_gpt* h, int slot, int T, int pos0, int valid_from, hipStream_t st) {
+static int forward_rows_16(ixtts_gpt* h, int slot, int T, int pos0, int valid_from, hipStream_t st, const PackedPass* pk = nullptr) {
   const size_t lstride = (size_t)h->slots * D * h->smax * sizeof(KVT);
   const size_t sstride = (size_t)D * h->smax * sizeof(KVT);
   KVT* xn16 = reinterpret_cast<KVT*>(h->rxn);
@@ -707,6 +991,7 @@ static int forward_rows_16(ixtts_gpt* h, int slot, int T, int pos0, int valid_fr
     IX_HIP(hipFuncSetAttribute((const void*)gemm_rows_bf16_kernel<RE_QKV, KVT>, hipFuncAttributeMaxDynamicSharedMemorySize, G16_SMEM));
     IX_HIP(hipFuncSetAttribute((const void*)gemm_rows_bf16_kernel<RE_RESID, KVT>, hipFuncAttributeMaxDynamicSharedMemorySize, G16_SMEM));
     IX_HIP(hipFuncSetAttribute((const void*)gemm_rows_bf16_kernel<RE_GELU, KVT>, hipFuncAttributeMaxDynamicSharedMemorySize, G16_SMEM));
+    IX_HIP(hipFuncSetAttribute((const void*)gemm_rows_bf16_kernel<RE_QKV_PACKED, KVT, GemmArgs16Packed>, hipFuncAttributeMaxDynamicSharedMemorySize, G16_SMEM));
     attr_done = true;
   }
   for (int l = 0; l < h->L; ++l) {
@@ -717,10 +1002,18 @@ static int forward_rows_16(ixtts_gpt* h, int slot, int T, int pos0, int valid_fr
     GemmArgs16 g;
     g.A = reinterpret_cast<const unsigned short*>(xn16); g.wt = reinterpret_cast<const unsigned short*>(A_PTR(o.wqkv)); g.bias = A_F32(o.bqkv);
     g.out = h->rq; g.kcache = kc; g.vcache = vc; g.T = T; g.N = 3 * D; g.K = D; g.pos0 = pos0; g.smax = h->smax; g.D = D;
-    hipLaunchKernelGGL((gemm_rows_bf16_kernel<RE_QKV, KVT>), grid(g.N), blk, G16_SMEM, st, g);
-    AttnRowsArgs a;
-    a.q = h->rq; a.kcache = kc; a.vcache = vc; a.out = att16; a.T = T; a.D = D; a.smax = h->smax; a.pos0 = pos0; a.valid_from = valid_from;
-    launch_attn_rows<KVT, KVT>(h, a, st);
+    if (pk) {
+      GemmArgs16Packed gp;
+      static_cast<GemmArgs16&>(gp) = g;
+      gp.row_at = pk->row_at;
+      hipLaunchKernelGGL((gemm_rows_bf16_kernel<RE_QKV_PACKED, KVT, GemmArgs16Packed>), grid(g.N), blk, G16_SMEM, st, gp);
+      launch_attn_packed<KVT, KVT>(h, *pk, kc, vc, att16, st);
+    } else {
+      hipLaunchKernelGGL((gemm_rows_bf16_kernel<RE_QKV, KVT>), grid(g.N), blk, G16_SMEM, st, g);
+      AttnRowsArgs a;
+      a.q = h->rq; a.kcache = kc; a.vcache = vc; a.out = att16; a.T = T; a.D = D; a.smax = h->smax; a.pos0 = pos0; a.valid_from = valid_from;
+      launch_attn_rows<KVT, KVT>(h, a, st);
+    }
     g.A = reinterpret_cast<const unsigned short*>(att16); g.wt = reinterpret_cast<const unsigned short*>(A_PTR(o.wo)); g.bias = A_F32(o.bo);
     g.out = h->rx; g.N = D; g.K = D;
     hipLaunchKernelGGL((gemm_rows_bf16_kernel<RE_RESID, KVT>), grid(g.N), blk, G16_SMEM, st, g);
@@ -745,6 +1038,50 @@ int forward_rows(ixtts_gpt* h, int slot, int T, int pos0, int valid_from, hipStr
   if (h->cfg.weight_dtype == IXTTS_DTYPE_F16)
     return h->D == 1280 ? forward_rows_16<f16, 1280>(h, slot, T, pos0, valid_from, st) : forward_rows_16<f16, 128>(h, slot, T, pos0, valid_from, st);
   return h->D == 1280 ? forward_rows_16<bf16, 1280>(h, slot, T, pos0, valid_from, st) : forward_rows_16<bf16, 128>(h, slot, T, pos0, valid_from, st);
+}
+
+int forward_rows_packed(ixtts_gpt* h, const PackedPass& p, hipStream_t st) {
+  if (p.T <= 0) return IXTTS_OK;
+  // (slot 0: kc / vc in the layer loops are then the layer's bases, which is what the packed launches take)
+  if (h->cfg.weight_dtype == IXTTS_DTYPE_F32) {
+    return h->D == 1280 ? forward_rows_t<float, float, 1280>(h, 0, p.T, 0, 0, st, &p) : forward_rows_t<float, float, 128>(h, 0, p.T, 0, 0, st, &p);
+  }
+  if (h->cfg.weight_dtype == IXTTS_DTYPE_F16)
+    return h->D == 1280 ? forward_rows_16<f16, 1280>(h, 0, p.T, 0, 0, st, &p) : forward_rows_16<f16, 128>(h, 0, p.T, 0, 0, st, &p);
+  return h->D == 1280 ? forward_rows_16<bf16, 1280>(h, 0, p.T, 0, 0, st, &p) : forward_rows_16<bf16, 128>(h, 0, p.T, 0, 0, st, &p);
+}
+
+// ---- packed pass, in and out.  One workgroup per packed row: row r of sequence s is the caller's embeds row pos0 + r, its last row
+// the start-mel row mel_emb[start] + mel_pos[0] (the sum add_vec_kernel makes in ixtts_gpt_prefill: one fp32 add per element).
+__global__ __launch_bounds__(256) void pack_rows_kernel(float* __restrict__ x, const PackSeq* __restrict__ seqs, const int* __restrict__ row_seq,
+                                                         const float* __restrict__ start_emb, const float* __restrict__ mel_pos0, int D) {
+  const int row = blockIdx.x;
+  const PackSeq s = seqs[row_seq[row]];
+  const int r = row - s.row0;
+  float* dst = x + (size_t)row * D;
+  if (r == s.T - 1) {
+    for (int i = threadIdx.x; i < D; i += blockDim.x) dst[i] = start_emb[i] + mel_pos0[i];
+  } else {
+    const float* src = s.embeds + (size_t)(s.pos0 + r) * D;
+    for (int i = threadIdx.x; i < D; i += blockDim.x) dst[i] = src[i];
+  }
+}
+__global__ __launch_bounds__(256) void unpack_last_rows_kernel(float* __restrict__ hrow, const float* __restrict__ x, const PackSeq* __restrict__ seqs, int D) {
+  const PackSeq s = seqs[blockIdx.x];
+  const float* src = x + (size_t)(s.row0 + s.T - 1) * D;
+  for (int i = threadIdx.x; i < D; i += blockDim.x) hrow[(size_t)s.slot * D + i] = src[i];
+}
+
+int pack_rows(ixtts_gpt* h, const PackedPass& p, hipStream_t st) {
+  hipLaunchKernelGGL(pack_rows_kernel, dim3(p.T), dim3(256), 0, st, h->rx, p.seqs, p.row_seq,
+                     (const float*)(A_F32(h->mel_emb) + (size_t)h->cfg.start_mel_token * h->D), (const float*)A_F32(h->mel_pos), h->D);
+  IX_HIP(hipGetLastError());
+  return IXTTS_OK;
+}
+int unpack_last_rows(ixtts_gpt* h, const PackedPass& p, hipStream_t st) {
+  hipLaunchKernelGGL(unpack_last_rows_kernel, dim3(p.n_seq), dim3(256), 0, st, h->h, (const float*)h->rx, p.seqs, h->D);
+  IX_HIP(hipGetLastError());
+  return IXTTS_OK;
 }
 
 int final_norm_rows(ixtts_gpt* h, const float* x, float* y, int T, hipStream_t st) {

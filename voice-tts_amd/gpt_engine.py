@@ -259,6 +259,39 @@ class GptEngine:
         _lib.check(rc, "ixtts_gpt_prefill")
         self._keep = e  # keep alive until the stream has consumed it
 
+    def prefill_many(self, entries, rows_max=0):
+        """`prefill` of several sequences into several slots in one packed pass per layer: entries = [(slot, embeds, n_left_pad),
+        ...], any slots in any order, none twice.  Every slot ends bit for bit as `prefill(slot, embeds, n_left_pad)` alone
+        leaves it; slots not named are untouched.  `rows_max` caps the packed rows of a pass (0: what the workspaces hold,
+        max_seq): more passes, the same bits."""
+        entries = list(entries)
+        n = len(entries)
+        keep = []
+        for slot, embeds, n_left_pad in entries:
+            e = embeds.to(self.device, torch.float32).contiguous()
+            assert e.dim() == 2 and e.shape[1] == self.D
+            keep.append(e)
+        slots = (C.c_int * max(n, 1))(*[int(s) for s, _, _ in entries])
+        ptrs = (C.c_void_p * max(n, 1))(*[e.data_ptr() for e in keep])
+        rows = (C.c_int * max(n, 1))(*[int(e.shape[0]) for e in keep])
+        pads = (C.c_int * max(n, 1))(*[int(p) for _, _, p in entries])
+        with torch.cuda.device(self.device):
+            rc = _lib.lib().ixtts_gpt_prefill_many(self._h, n, slots, ptrs, rows, pads, int(rows_max), self._stream())
+        _lib.check(rc, "ixtts_gpt_prefill_many")
+        if keep:
+            self._keep_many = keep  # keep alive until the stream has consumed them
+
+    @staticmethod
+    def prefill_plan(n_rows, n_left_pad, row_cap):
+        """The passes `prefill_many` cuts a list of prompts into (host arithmetic, no GPU): -> (pass index of each, pass count)."""
+        n = len(n_rows)
+        assert len(n_left_pad) == n
+        out = (C.c_int * max(n, 1))()
+        rc = _lib.lib().ixtts_gpt_prefill_plan((C.c_int * max(n, 1))(*map(int, n_rows)), (C.c_int * max(n, 1))(*map(int, n_left_pad)), n, int(row_cap), out)
+        if rc < 0:
+            _lib.check(rc, "ixtts_gpt_prefill_plan")
+        return list(out[:n]), rc
+
     @staticmethod
     def _sampler_cfg(v):
         """One SamplerCfg from a dict with every keyword of `decode()` / `beam_decode()` (`length_penalty` may be missing)."""

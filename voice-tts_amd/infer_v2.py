@@ -164,6 +164,9 @@ class IndexTTS2:
         # reference precision: fp16 GPT under use_fp16 (infer_v2.py:79,88-89); here bf16 is the throughput mode and the default,
         # gpt_dtype="f16" / IXTTS_GPT_DTYPE=f16 gives the reference's IEEE half (resolve_gpt_dtype)
         self.gpt_dtype = resolve_gpt_dtype(self.use_fp16, gpt_dtype)
+        from .scheduler import resolve_batch_prefill
+
+        self.prefill_batch = resolve_batch_prefill()  # IXTTS_PREFILL_BATCH: refill rounds of the decode schedulers as one packed prefill
         self.gpt = GptEngine(gcfg, dtype=self.gpt_dtype, max_seq=max_seq, max_batch=3, device=self.device)
         # ---- weights: rank 0 (or a lone worker) reads model_dir; with `weight_broadcast=(rank, world)` (torch.distributed initialised,
         # backend nccl = RCCL over xGMI) the other workers of the node read nothing but config.yaml / bpe.model / the w2v-bert
@@ -749,10 +752,10 @@ class IndexTTS2:
         sampler = dict(repetition_penalty=g.repetition_penalty, temperature=g.temperature, top_k=g.top_k, top_p=g.top_p, seed=g.seed,
                        typical_mass=g.typical_mass)
         if todo and g.num_beams > 1:
-            BeamGroupScheduler(engine, g.num_beams).run(todo, lambda seg, ids, score: out.__setitem__((seg.request, seg.index), ids),
+            BeamGroupScheduler(engine, g.num_beams, batch_prefill=getattr(self, "prefill_batch", None)).run(todo, lambda seg, ids, score: out.__setitem__((seg.request, seg.index), ids),
                                                         length_penalty=g.length_penalty, **sampler)
         elif todo:
-            DecodeScheduler(engine, engine.max_batch, self.stop_mel_token).run(
+            DecodeScheduler(engine, engine.max_batch, self.stop_mel_token, batch_prefill=getattr(self, "prefill_batch", None)).run(
                 todo, lambda seg, ids: out.__setitem__((seg.request, seg.index), ids), do_sample=g.top_k != 1, **sampler)
         torch.cuda.synchronize(self.device)
         return out

@@ -14,8 +14,47 @@ engine shape (wide and register engines differ in logit bits).  A run in which n
 uniform calls (`decode`, `beam_decode`), where a sampling slot's stream is its slot index.
 """
 import collections
+import os
 
 import numpy as np
+
+# Refill rounds as one `engine.prefill_many` (one packed pass over the weights for all the slots a round fills) instead of one
+# `engine.prefill` per slot.  The tokens are the same bit for bit either way (tests/test_gpu_scheduler_prefill_many.py).  On by
+# default: every row of profiles/prefill_many.json and profiles/prefill_many_sched.json has the batched refill faster, beyond the
+# run-to-run spread (DESIGN.md 4.1b).  IXTTS_PREFILL_BATCH=0|1 overrides this, the schedulers' `batch_prefill=` overrides both.
+BATCH_PREFILL_DEFAULT = True
+
+
+def resolve_batch_prefill(batch_prefill=None):
+    """The constructor keyword if given, else IXTTS_PREFILL_BATCH (0 | 1), else the default."""
+    if batch_prefill is not None:
+        return bool(batch_prefill)
+    v = os.environ.get("IXTTS_PREFILL_BATCH")
+    if v is None or v == "":
+        return BATCH_PREFILL_DEFAULT
+    if v not in ("0", "1"):
+        raise ValueError(f"IXTTS_PREFILL_BATCH has to be 0 or 1, but is {v!r}")
+    return v == "1"
+
+
+def _prefill_round(engine, batch, entries, after, stats):
+    """A refill round: entries = [(slot, segment, ...), ...] in slot order, `after(*entry)` = the calls that set a slot's state once
+    its prefill has cleared it (set_bans, set_processors, beam_begin).  Batching on and an engine that has `prefill_many`: one
+    packed prefill of the round, then the `after` calls in slot order.  Else -- batching off, the fakes of the scheduler tests,
+    any third-party engine -- `prefill` and `after` slot by slot, the calls in the order they always had."""
+    if not entries:
+        return
+    if batch and hasattr(engine, "prefill_many"):
+        engine.prefill_many([(e[0], e[1].embeds, e[1].n_left_pad) for e in entries])
+        stats["prefill_calls"] += 1
+        for e in entries:
+            after(*e)
+    else:
+        for e in entries:
+            engine.prefill(e[0], e[1].embeds, e[1].n_left_pad)
+            after(*e)
+        stats["prefill_calls"] += len(entries)
+    stats["prefill_seqs"] += len(entries)
 
 
 class Segment:
@@ -57,14 +96,16 @@ class DecodeScheduler:
     engine: `GptEngine`-like object with prefill(slot, embeds, n_left_pad), decode(n_active, n_steps, **sampler) and
     read(slot) -> (ids, finished); decode_slots(n_steps, cfgs, streams) too when a segment carries `sampler` or `stream`, and
     set_bans(slot, suppress_tokens, begin_suppress_tokens) when one carries `bans`, set_processors(slot, state) when one carries
-    `processors`.
+    `processors`.  With `prefill_many(entries)` the slots a refill round fills are prefilled in one call (`batch_prefill`, default
+    IXTTS_PREFILL_BATCH, on); the stub re-prefill of an idle slot stays a single `prefill`.
     `stop_token` ends a sequence (inclusive) unless `fixed_length`.
     """
 
-    def __init__(self, engine, max_batch, stop_token, sync_every=64):
+    def __init__(self, engine, max_batch, stop_token, sync_every=64, batch_prefill=None):
         assert 1 <= max_batch
         self.engine, self.max_batch, self.stop_token, self.sync_every = engine, max_batch, stop_token, sync_every
-        self.stats = dict(decode_calls=0, slot_steps=0, busy_slot_steps=0, refills=0)
+        self.batch_prefill = resolve_batch_prefill(batch_prefill)
+        self.stats = dict(decode_calls=0, slot_steps=0, busy_slot_steps=0, refills=0, prefill_calls=0, prefill_seqs=0)
 
     def run(self, segments, on_done, fixed_length=False, **sampler):
         """Decode every segment; `on_done(segment, ids)` is called as each finishes (ids: int32 array, stop token included
@@ -79,19 +120,24 @@ class DecodeScheduler:
         max_seq = getattr(self.engine, "max_seq", None)
         primed = 0                       # slots that have held a sequence at least once (the engine needs a prompt in every active slot)
         while queue or any(s is not None for s in slots):
+            filled = []  # this round's (slot, segment), in slot order
             for b in range(self.max_batch):
                 if slots[b] is None and queue and b <= primed:
                     seg = queue.popleft()
-                    self.engine.prefill(b, seg.embeds, seg.n_left_pad)
-                    if getattr(seg, "bans", None) is not None:
-                        self.engine.set_bans(b, *seg.bans)
-                    if getattr(seg, "processors", None) is not None:
-                        self.engine.set_processors(b, seg.processors)
+                    filled.append((b, seg))
                     if b < primed:
                         self.stats["refills"] += 1
                     primed = max(primed, b + 1)
                     slots[b] = [seg, 0]
                     length[b] = int(seg.embeds.shape[0]) + 1
+
+            def after(b, seg):
+                if getattr(seg, "bans", None) is not None:
+                    self.engine.set_bans(b, *seg.bans)
+                if getattr(seg, "processors", None) is not None:
+                    self.engine.set_processors(b, seg.processors)
+
+            _prefill_round(self.engine, self.batch_prefill, filled, after, self.stats)
             live = [b for b in range(self.max_batch) if slots[b] is not None]
             n_active = max(live) + 1
             steps = min([self.sync_every] + [slots[b][0].max_new - slots[b][1] for b in live])
@@ -147,14 +193,15 @@ class BeamGroupScheduler:
     carries `processors`.
     """
 
-    def __init__(self, engine, num_beams, max_groups=None, sync_every=64):
+    def __init__(self, engine, num_beams, max_groups=None, sync_every=64, batch_prefill=None):
         self.engine, self.num_beams, self.sync_every = engine, int(num_beams), sync_every
+        self.batch_prefill = resolve_batch_prefill(batch_prefill)
         cap = engine.max_batch // self.num_beams
         if engine.max_batch <= 4:  # register GEMVs: one group
             cap = min(cap, 1)
         self.max_groups = max(1, min(cap, max_groups or cap))
         assert self.max_groups * self.num_beams <= engine.max_batch, (self.max_groups, self.num_beams, engine.max_batch)
-        self.stats = dict(decode_calls=0, group_steps=0, busy_group_steps=0, refills=0)
+        self.stats = dict(decode_calls=0, group_steps=0, busy_group_steps=0, refills=0, prefill_calls=0, prefill_seqs=0)
 
     def run(self, segments, on_done, fixed_length=False, **sampler):
         """Decode every segment; `on_done(segment, ids, score)` as each finishes: ids = the best hypothesis as
@@ -169,19 +216,24 @@ class BeamGroupScheduler:
         begun = 0                           # groups that have held a segment (fill from 0 upwards)
         eng, nb = self.engine, self.num_beams
         while queue or any(g is not None for g in groups):
+            filled = []  # this round's (first slot, segment, group, stream), in group order
             for g in range(self.max_groups):
                 if groups[g] is None and queue and g <= begun:
                     seg, stream = queue.popleft()
-                    eng.prefill(g * nb, seg.embeds, seg.n_left_pad)
-                    if getattr(seg, "bans", None) is not None:
-                        eng.set_bans(g * nb, *seg.bans)  # the group's: the flags of its first slot hold for all its beams
-                    if getattr(seg, "processors", None) is not None:
-                        eng.set_processors(g * nb, seg.processors)  # the group's too
-                    eng.beam_begin(nb, group=g, rng_stream=stream)
+                    filled.append((g * nb, seg, g, stream))
                     if g < begun:
                         self.stats["refills"] += 1
                     begun = max(begun, g + 1)
                     groups[g] = [seg, 0]
+
+            def after(slot, seg, g, stream):
+                if getattr(seg, "bans", None) is not None:
+                    eng.set_bans(slot, *seg.bans)  # the group's: the flags of its first slot hold for all its beams
+                if getattr(seg, "processors", None) is not None:
+                    eng.set_processors(slot, seg.processors)  # the group's too
+                eng.beam_begin(nb, group=g, rng_stream=stream)
+
+            _prefill_round(eng, self.batch_prefill, filled, after, self.stats)
             live = [g for g in range(self.max_groups) if groups[g] is not None]
             n_groups = max(live) + 1
             for g in range(n_groups):

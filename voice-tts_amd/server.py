@@ -287,6 +287,8 @@ def create_app(model_factory=default_model_factory):
                       "use_deepspeed": False}
         if getattr(m, "gpt_dtype", None) is not None:  # the GPT weight type the worker resolved (IXTTS_GPT_DTYPE / gpt_dtype)
             model_info["gpt_dtype"] = m.gpt_dtype
+        if getattr(m, "prefill_batch", None) is not None:  # IXTTS_PREFILL_BATCH as resolved: refill rounds as one packed prefill
+            model_info["prefill_batch"] = bool(m.prefill_batch)
         return {"worker_id": os.environ.get("WORKER_ID", "unknown"), "pid": os.getpid(),
                 "cuda_visible_devices": os.environ.get("CUDA_VISIBLE_DEVICES", "not set"), "gpu_info": gpu, "model_info": model_info}
 

@@ -472,6 +472,29 @@ int ixtts_gpt_beam_force_group(ixtts_gpt* h, int group, const int32_t* picks_hos
  * ln_f + final_norm, writes the first n mel rows to latent_dev [n, D] fp32. */
 int ixtts_gpt_latent(ixtts_gpt* h, const float* prefix_dev, int n_prefix, const int32_t* codes_dev, int n,
                      float* latent_dev, void* stream);
+/* ixtts_gpt_latent of n sequences in packed causal passes over the weights: entry i is (prefix_dev[i] [n_prefix[i], D],
+ * codes_dev[i] [n_codes[i]]) -> latent_dev[i] [n_codes[i], D], bit for bit what ixtts_gpt_latent of that entry alone writes, for
+ * every weight type, whatever else is in the call, in whatever order, under any rows_max.  Any n >= 0 (n == 0: no-op; not bounded
+ * by max_batch: like ixtts_gpt_latent the pass runs in the handle's scratch sequence and touches no decode slot, so it may run
+ * while slots are in mid-decode); an entry with n_codes == 0 writes nothing.  Every entry is checked as ixtts_gpt_latent checks its
+ * arguments before anything is enqueued: IXTTS_ERR_ARG names the entry and leaves every output untouched.  The sequences of a
+ * pass share the scratch sequence's cache at disjoint positions, each starting on a multiple of 64 (the key-tile width of the
+ * rows attention: only there does a sequence get the tiles, and the rounding, of a pass of its own), and the call makes the
+ * passes of ixtts_gpt_latent_plan with row_cap = min(rows_max > 0 ? rows_max : max_seq, max_seq); rows_max exists for tests,
+ * production passes 0.  Stream-ordered, no host synchronisation of its own.  The tables of each pass go down `stream` from one
+ * pageable host buffer of the handle (its own, not ixtts_gpt_prefill_many's), which the next pass and the next call rewrite: as
+ * there, this relies on the HIP runtime having copied (or staged) a pageable source by the time hipMemcpyAsync returns.  One
+ * device copy of the tables and one set of rows workspaces per handle: calls on one handle (this one, ixtts_gpt_latent,
+ * ixtts_gpt_prefill, ixtts_gpt_prefill_many) must be ordered by one stream, or by events between streams.  Inputs and outputs must
+ * stay alive until the stream has consumed them. */
+int ixtts_gpt_latent_many(ixtts_gpt* h, int n, const float* const* prefix_dev, const int* n_prefix, const int32_t* const* codes_dev,
+                          const int* n_codes, float* const* latent_dev, int rows_max, void* stream);
+/* The pass rule of ixtts_gpt_latent_many as a host function (no handle, no GPU): entries in the order given, entry i being
+ * T = n_prefix[i] + n_codes[i] rows that occupy ceil(T / 64) * 64 cache positions; a pass closes when the next entry would not fit
+ * in row_cap positions (an entry larger than row_cap gets a pass of its own); an entry with n_codes == 0 occupies nothing and
+ * takes the pass of its neighbour.  Writes the pass of each entry to pass_of[n] and returns the number of passes (0 for n == 0),
+ * IXTTS_ERR_ARG for a null array or row_cap < 1. */
+int ixtts_gpt_latent_plan(const int* n_prefix, const int* n_codes, int n, int row_cap, int* pass_of);
 
 /* Microbench hook for bench.py's roofline leg: launches the decode-step GEMV kernel of
  * `which` (0 qkv, 1 attn-out, 2 fc, 3 mlp-out, 4 head) for layer `layer` once on `stream`. */

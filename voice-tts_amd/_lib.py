@@ -145,6 +145,8 @@ SYMBOLS = {
     "ixtts_gpt_set_sequence_bias": (C.c_int, [_P, C.c_int, _P, _P, _P, C.c_int, _P]),
     "ixtts_gpt_set_forced_eos": (C.c_int, [_P, C.c_int, _P, C.c_int, _P]),
     "ixtts_gpt_latent": (C.c_int, [_P, _P, C.c_int, _P, C.c_int, _P, _P]),
+    "ixtts_gpt_latent_many": (C.c_int, [_P, C.c_int, C.POINTER(_P), C.POINTER(C.c_int), C.POINTER(_P), C.POINTER(C.c_int), C.POINTER(_P), C.c_int, _P]),
+    "ixtts_gpt_latent_plan": (C.c_int, [C.POINTER(C.c_int), C.POINTER(C.c_int), C.c_int, C.c_int, C.POINTER(C.c_int)]),
     "ixtts_gpt_bench_gemv": (C.c_int, [_P, C.c_int, C.c_int, C.c_int, _P]),
     "ixtts_gpt_step_bytes": (C.c_double, [_P, C.c_int, C.c_int]),
     "ixtts_gpt_max_batch": (C.c_int, []),

@@ -135,6 +135,11 @@ struct ixtts_gpt {
   std::vector<uint8_t> pf_host;
   uint8_t* pf_dev = nullptr;
   size_t pf_bytes = 0;
+  // ixtts_gpt_latent_many: the tables of ONE pass (at most max_seq rows), staged in lm_host and sent down the caller's stream once per
+  // pass; a buffer of its own, sized by max_seq and not by max_batch (the latent pass uses no decode slot)
+  std::vector<uint8_t> lm_host;
+  uint8_t* lm_dev = nullptr;
+  size_t lm_bytes = 0;
 };
 
 #define A_F32(off) reinterpret_cast<float*>(h->arena + (off))
@@ -160,7 +165,26 @@ struct PackedPass {       // device tables of one pass (regions of ixtts_gpt::pf
   const int* row_at;      // [T]: cache row slot * H * smax + position of every packed row
   const int* row_seq;     // [T]: its sequence
   int n_seq, n_tiles, T;
+  // a pass of ixtts_gpt_latent_many: all sequences share the scratch slot at disjoint positions pos0; the row-at-a-time attention
+  // (IXTTS_ROWS_ATTN=legacy) then sweeps each sequence's keys from ITS position 0 (attn_rows_packed_rebased_kernel)
+  bool keys_rebased = false;
 };
+// what the in / out kernels of a latent pass need of one sequence beside its PackSeq (same index)
+struct LatentSeq {
+  const float* prefix;    // [n_prefix][D]
+  const int32_t* codes;   // [n_codes]
+  float* latent;          // [n_codes][D]
+  int n_prefix, n_codes;
+};
+struct LatentPass {       // device tables of one latent pass beside its PackedPass
+  const LatentSeq* lseqs; // [n_seq]
+  const int* mel_row;     // [n_mel]: the packed row of every mel row of the pass
+  int n_mel;
+};
+// rows of a latent pass into h->rx: prefix rows copied, mel rows mel_emb[tok] + mel_pos[r] (tok: start, then codes[r - 1])
+int pack_latent_rows(ixtts_gpt* h, const PackedPass& p, const LatentPass& lp, hipStream_t st);
+// ln_f then final_norm of every mel row of the pass -> its sequence's latent rows
+int scatter_latent_rows(ixtts_gpt* h, const PackedPass& p, const LatentPass& lp, hipStream_t st);
 // gather the sequences' embeds rows into h->rx and write each one's start-mel row
 int pack_rows(ixtts_gpt* h, const PackedPass& p, hipStream_t st);
 // the 24 layers over the packed rows: per-row kernels as forward_rows at T = p.T, K/V scattered by row_at, attention per sequence

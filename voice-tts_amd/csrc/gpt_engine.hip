@@ -418,6 +418,13 @@ static size_t pf_table_bytes(int n, int smax) {  // the most a call of n sequenc
   return (size_t)n * (sizeof(PackSeq) + 4) + (size_t)n * (smax / 128 + 1) * 8 + (size_t)n * smax * 8;
 }
 
+// one pass of ixtts_gpt_latent_many: at most smax rows, smax / 64 + 1 sequences (each takes 64 positions or more of the pass, or the
+// pass alone), a 128-row tile per 128 rows and one more per sequence; the layout is in ixtts_gpt_latent_many
+static size_t lm_table_bytes(int smax) {
+  const size_t n_seq = (size_t)smax / 64 + 1;
+  return n_seq * (sizeof(PackSeq) + sizeof(LatentSeq)) + (n_seq + (size_t)smax / 128 + 1) * 8 + (size_t)smax * 12;
+}
+
 extern "C" int ixtts_gpt_create(ixtts_gpt** out, const ixtts_gpt_cfg* c) {
   IX_ARG(out && c, "gpt_create: null argument");
   IX_ARG(c->model_dim == 1280 || c->model_dim == 128, "gpt_create: model_dim %d has no kernel instantiation (1280 | 128)", c->model_dim);
@@ -543,8 +550,11 @@ extern "C" int ixtts_gpt_create(ixtts_gpt** out, const ixtts_gpt_cfg* c) {
   ok &= hipMalloc(&h->seq_bias, (size_t)S * IXTTS_SEQ_BIAS_MAX * sizeof(SeqBiasEntry)) == hipSuccess;
   h->pf_bytes = pf_table_bytes(c->max_batch, h->smax);
   ok &= hipMalloc(&h->pf_dev, h->pf_bytes) == hipSuccess;  // (the newest: as above)
+  h->lm_bytes = lm_table_bytes(h->smax);
+  ok &= hipMalloc(&h->lm_dev, h->lm_bytes) == hipSuccess;  // (the newest)
   if (!ok) return fail("state");
   h->pf_host.assign(h->pf_bytes, 0);
+  h->lm_host.assign(h->lm_bytes, 0);
   hipMemset(h->cur_len, 0, S * 4);
   hipMemset(h->gen_count, 0, S * 4);
   hipMemset(h->prompt_len, 0, S * 4);
@@ -1471,6 +1481,122 @@ extern "C" int ixtts_gpt_latent(ixtts_gpt* h, const float* prefix, int n_prefix,
   return IXTTS_OK;
 }
 
+// ------------------------------------------------------------------------------------ latent pass of many sequences
+// The pass rule: entries in the order given, T = n_prefix + n_codes rows each at cache positions that start on a multiple of 64, so an
+// entry occupies ceil64(T) positions; a pass closes when the next entry would not fit in row_cap positions (an entry larger than
+// row_cap still gets a pass of its own).  An entry without codes occupies nothing.  Pure host arithmetic.
+extern "C" int ixtts_gpt_latent_plan(const int* n_prefix, const int* n_codes, int n, int row_cap, int* pass_of) {
+  IX_ARG(n >= 0 && (n == 0 || (n_prefix && n_codes && pass_of)) && row_cap >= 1, "gpt_latent_plan: bad arguments (n %d, row_cap %d)", n, row_cap);
+  int pass = 0;
+  long used = 0;
+  for (int i = 0; i < n; ++i) {
+    if (n_codes[i] > 0) {
+      const long need = ((long)n_prefix[i] + n_codes[i] + 63) / 64 * 64;
+      if (used > 0 && used + need > row_cap) {
+        ++pass;
+        used = 0;
+      }
+      used += need;
+    }
+    pass_of[i] = pass;
+  }
+  return n > 0 ? pass + 1 : 0;
+}
+
+extern "C" int ixtts_gpt_latent_many(ixtts_gpt* h, int n, const float* const* prefix_dev, const int* n_prefix, const int32_t* const* codes_dev,
+                                     const int* n_codes, float* const* latent_dev, int rows_max, void* stream) {
+  NEED_READY(h, "gpt_latent_many");
+  IX_ARG(n >= 0, "gpt_latent_many: %d entries", n);
+  if (n == 0) return IXTTS_OK;
+  IX_ARG(prefix_dev && n_prefix && codes_dev && n_codes && latent_dev, "gpt_latent_many: null argument");
+  // everything is checked, as ixtts_gpt_latent checks it, before anything is enqueued
+  for (int i = 0; i < n; ++i) {
+    const int P = n_prefix[i], c = n_codes[i];
+    IX_ARG(prefix_dev[i] && P >= 1 && c >= 0 && (codes_dev[i] || c == 0) && (latent_dev[i] || c == 0), "gpt_latent_many: entry %d: bad argument", i);
+    IX_ARG(c + 2 <= h->cfg.n_mel_pos, "gpt_latent_many: entry %d: %d codes exceed the mel position table", i, c);
+    IX_ARG((long)P + c + 2 < h->smax, "gpt_latent_many: entry %d: sequence of %ld rows exceeds max_seq %d", i, (long)P + c + 2, h->smax);
+  }
+  hipStream_t st = (hipStream_t)stream;
+  const int smax = h->smax, slot = h->slots - 1;  // the scratch sequence of ixtts_gpt_latent: no decode slot is touched
+  const int row_cap = std::min(rows_max > 0 ? rows_max : smax, smax);
+  std::vector<int> pass_of(n);
+  const int n_pass = ixtts_gpt_latent_plan(n_prefix, n_codes, n, row_cap, pass_of.data());
+  if (n_pass < 0) return n_pass;
+
+  // tables of ONE pass: [n_seq] PackSeq | [n_seq] LatentSeq | [tiles][2] (all 8-byte aligned) | [T] row_at | [T] row_seq | [n_mel] mel_row
+  static_assert(sizeof(PackSeq) % 8 == 0 && sizeof(LatentSeq) % 8 == 0, "pointers and int2 pairs behind the records");
+  uint8_t* hb = h->lm_host.data();
+  for (int i0 = 0; i0 < n;) {
+    int i1 = i0, n_seq = 0, T = 0, n_tiles = 0, n_mel = 0;
+    for (; i1 < n && pass_of[i1] == pass_of[i0]; ++i1) {
+      if (n_codes[i1] == 0) continue;
+      const int Ti = n_prefix[i1] + n_codes[i1];
+      ++n_seq; T += Ti; n_tiles += ceil_div(Ti, 128); n_mel += n_codes[i1];
+    }
+    if (n_seq == 1) {
+      // a pass of one sequence is ixtts_gpt_latent itself: the same launches, no tables to send (two sequences of more than max_seq / 2
+      // positions each cannot share a pass, and a call of such sequences must cost what the loop of solo calls costs)
+      for (int i = i0; i < i1; ++i)
+        if (n_codes[i] > 0) IX_TRY(ixtts_gpt_latent(h, prefix_dev[i], n_prefix[i], codes_dev[i], n_codes[i], latent_dev[i], stream));
+    } else if (n_seq > 0) {
+      const size_t off_ls = (size_t)n_seq * sizeof(PackSeq), off_tiles = off_ls + (size_t)n_seq * sizeof(LatentSeq), off_at = off_tiles + (size_t)n_tiles * 8,
+                   off_seq = off_at + (size_t)T * 4, off_mel = off_seq + (size_t)T * 4, bytes = off_mel + (size_t)n_mel * 4;
+      if (bytes > h->lm_bytes || T > smax) {  // (the plan keeps a pass within max_seq positions, so neither can happen)
+        set_error("gpt_latent_many: a pass of %d rows, tables of %zu bytes, exceeds the handle's %d rows, %zu bytes", T, bytes, smax, h->lm_bytes);
+        return IXTTS_ERR_STATE;
+      }
+      PackSeq* seqs = reinterpret_cast<PackSeq*>(hb);
+      LatentSeq* ls = reinterpret_cast<LatentSeq*>(hb + off_ls);
+      int* tiles = reinterpret_cast<int*>(hb + off_tiles);
+      int* row_at = reinterpret_cast<int*>(hb + off_at);
+      int* row_seq = reinterpret_cast<int*>(hb + off_seq);
+      int* mel_row = reinterpret_cast<int*>(hb + off_mel);
+      int q = 0, row = 0, pos = 0, tile = 0, mel = 0;
+      for (int i = i0; i < i1; ++i) {
+        if (n_codes[i] == 0) continue;
+        const int P = n_prefix[i], Ti = P + n_codes[i];
+        if (pos + Ti > smax) {  // (nor this: K/V rows are written through row_at)
+          set_error("gpt_latent_many: entry %d would end at cache position %d of %d", i, pos + Ti, smax);
+          return IXTTS_ERR_STATE;
+        }
+        // cache positions [pos, pos + Ti), pos a multiple of 64: the key tiles of the flash attention lie on absolute multiples of 64, so
+        // only there does the sequence get the tiles -- and the online-softmax order, and the bits -- of the solo pass at position 0
+        seqs[q] = PackSeq{nullptr, slot, Ti, pos, row};
+        ls[q] = LatentSeq{prefix_dev[i], codes_dev[i], latent_dev[i], P, n_codes[i]};
+        for (int q0 = 0; q0 < Ti; q0 += 128) { tiles[2 * tile] = q; tiles[2 * tile + 1] = q0; ++tile; }
+        for (int t = 0; t < Ti; ++t) {
+          row_at[row] = slot * h->H * smax + pos + t;
+          row_seq[row] = q;
+          if (t >= P) mel_row[mel++] = row;
+          ++row;
+        }
+        pos += ceil_div(Ti, 64) * 64;
+        ++q;
+      }
+      // (a pageable source, rewritten for the next pass and the next call: the runtime has taken its copy when this returns -- the
+      //  reliance of ixtts_gpt_prefill_many; lm_dev is ordered by the caller's stream, see the header)
+      IX_HIP(hipMemcpyAsync(h->lm_dev, hb, bytes, hipMemcpyHostToDevice, st));
+      PackedPass pk;
+      pk.seqs = reinterpret_cast<const PackSeq*>(h->lm_dev);
+      pk.tiles = reinterpret_cast<const int*>(h->lm_dev + off_tiles);
+      pk.row_at = reinterpret_cast<const int*>(h->lm_dev + off_at);
+      pk.row_seq = reinterpret_cast<const int*>(h->lm_dev + off_seq);
+      pk.n_seq = n_seq; pk.n_tiles = n_tiles; pk.T = T;
+      pk.keys_rebased = true;
+      LatentPass lp;
+      lp.lseqs = reinterpret_cast<const LatentSeq*>(h->lm_dev + off_ls);
+      lp.mel_row = reinterpret_cast<const int*>(h->lm_dev + off_mel);
+      lp.n_mel = n_mel;
+      IX_TRY(pack_latent_rows(h, pk, lp, st));
+      IX_TRY(forward_rows_packed(h, pk, st));
+      IX_TRY(scatter_latent_rows(h, pk, lp, st));
+    }
+    i0 = i1;
+  }
+  IX_HIP(hipGetLastError());
+  return IXTTS_OK;
+}
+
 // ------------------------------------------------------------------------------------ bench hooks
 extern "C" int ixtts_gpt_bench_gemv(ixtts_gpt* h, int which, int layer, int batch, void* stream) {
   NEED_READY(h, "gpt_bench_gemv");
@@ -1513,7 +1639,7 @@ extern "C" int ixtts_gpt_destroy(ixtts_gpt* h) {
   void* ptrs[] = {h->arena, h->stage, h->kc, h->vc, h->h, h->q, h->ff, h->att, h->part, h->logits, h->rowbuf, h->cur_len, h->gen_count,
                   h->prompt_len, h->valid_from, h->finished, h->forced, h->tokens, h->seen, h->bans, h->seq_bias, h->d_samp, h->d_rng, h->probs, h->scratch, h->beam_scores, h->hyp_score, h->hyp_worst, h->beam_src, h->hyp_len,
                   h->n_hyp, h->beam_done, h->beam_forced_flag, h->beam_forced, h->hyp_tok, h->beam_cand_v, h->beam_cand_i, h->beam_cand_n, h->beam_lcp, h->beam_stream,
-                  h->rx, h->rxn, h->rq, h->ratt, h->rff, h->h2, h->wprx, h->mlp_part, h->mlp_ctr, h->fold_overflow, h->pf_dev};
+                  h->rx, h->rxn, h->rq, h->ratt, h->rff, h->h2, h->wprx, h->mlp_part, h->mlp_ctr, h->fold_overflow, h->pf_dev, h->lm_dev};
   for (void* p : ptrs)
     if (p) hipFree(p);
   delete h;

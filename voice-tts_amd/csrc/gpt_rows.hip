@@ -68,16 +68,14 @@ __global__ __launch_bounds__(256) void ln_rows_kernel(const float* __restrict__ 
   for (int i = 0; i < PL; ++i) store_kv(yr + lane + 64 * i, (v[i] - mean) * rstd);
 }
 
-// ---- ln_f (explicit affine) then final_norm (explicit affine) per row -> latent rows
+// ---- ln_f (explicit affine) then final_norm (explicit affine) per row -> latent rows.  One wave per row; the row's arithmetic is
+// final_norm_row, shared by the one-sequence kernel and the scatter of a packed latent pass (latent_norm_scatter_kernel)
 template <int K>
-__global__ __launch_bounds__(256) void final_norm_rows_kernel(const float* __restrict__ x, float* __restrict__ y, int T,
-                                                               const float* __restrict__ w1, const float* __restrict__ b1,
-                                                               const float* __restrict__ w2, const float* __restrict__ b2) {
-  const int row = blockIdx.x * 4 + (threadIdx.x >> 6);
-  const int lane = threadIdx.x & 63;
-  if (row >= T) return;
+__device__ __forceinline__ void final_norm_row(const float* __restrict__ x, float* __restrict__ y, const size_t row_in, const size_t row_out, const int lane,
+                                               const float* __restrict__ w1, const float* __restrict__ b1, const float* __restrict__ w2,
+                                               const float* __restrict__ b2) {
   constexpr int PL = K / 64;
-  const float* xr = x + (size_t)row * K;
+  const float* xr = x + row_in * K;
   float v[PL];
 #pragma unroll
   for (int i = 0; i < PL; ++i) v[i] = xr[lane + 64 * i];
@@ -99,9 +97,18 @@ __global__ __launch_bounds__(256) void final_norm_rows_kernel(const float* __res
 #pragma unroll
     for (int i = 0; i < PL; ++i) v[i] = (v[i] - mean) * rstd * w[lane + 64 * i] + b[lane + 64 * i];
   }
-  float* yr = y + (size_t)row * K;
+  float* yr = y + row_out * K;
 #pragma unroll
   for (int i = 0; i < PL; ++i) yr[lane + 64 * i] = v[i];
+}
+template <int K>
+__global__ __launch_bounds__(256) void final_norm_rows_kernel(const float* __restrict__ x, float* __restrict__ y, int T,
+                                                               const float* __restrict__ w1, const float* __restrict__ b1,
+                                                               const float* __restrict__ w2, const float* __restrict__ b2) {
+  const int row = blockIdx.x * 4 + (threadIdx.x >> 6);
+  const int lane = threadIdx.x & 63;
+  if (row >= T) return;
+  final_norm_row<K>(x, y, (size_t)row, (size_t)row, lane, w1, b1, w2, b2);
 }
 
 // ---- GEMM: C[T][N] = A[T][K] . Wt[N][K]^T + bias
@@ -570,6 +577,37 @@ __global__ __launch_bounds__(256) void attn_rows_packed_kernel(AttnPackedArgs p)
   attn_rows_seq<KVT, OT>(packed_seq_args<KVT, OT>(p, seq), (int)blockIdx.y - p.seqs[seq].row0);
 }
 
+// A sequence of a latent pass (ixtts_gpt_latent_many) sits in the scratch slot at cache positions pos0 .., pos0 a multiple of 64 and
+// not of attn_sweep's stride (NW * PPW * IT keys: 128 for fp32, 256 for 16-bit caches).  attn_sweep groups the keys of one softmax
+// update by ABSOLUTE position, so attn_rows_seq at such a pos0 would update in other groups than the solo pass at position 0 does and
+// round differently.  This kernel hands the sweep the sequence's own keys as positions 0 .. (cache pointers advanced by pos0 rows, the
+// clamp shortened by as much): the groups, masks and speculative first pass of the solo launch, whatever pos0 is.
+template <typename KVT, typename OT>
+__global__ __launch_bounds__(256) void attn_rows_packed_rebased_kernel(AttnPackedArgs p) {  // grid (H, sum T)
+  constexpr int NW = 4;
+  using LY = KVLayout<KVT>;
+  __shared__ float sm[NW][LY::LPP][2 + LY::DPL];
+  const int seq = p.row_seq[blockIdx.y];
+  const AttnRowsArgs a = packed_seq_args<KVT, OT>(p, seq);
+  const int row = (int)blockIdx.y - p.seqs[seq].row0;
+  const int hh = blockIdx.x;
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const int dp = lane % LY::LPP;
+  float qv[LY::DPL];
+  load_q_slice<KVT>(a.q + (size_t)row * a.D + hh * HD, dp, qv);
+  const KVT* kb = reinterpret_cast<const KVT*>(a.kcache) + ((size_t)hh * a.smax + a.pos0) * HD + dp * LY::DPL;
+  const KVT* vb = reinterpret_cast<const KVT*>(a.vcache) + ((size_t)hh * a.smax + a.pos0) * HD + dp * LY::DPL;
+  SoftAcc<LY::DPL> st;
+  st.init();
+  const int hi0 = row + 1;
+  attn_sweep<KVT, NW, 8>(st, kb, vb, qv, a.smax - a.pos0, wave, lane, [&](int& lo, int& hi) {
+    lo = 0;
+    hi = hi0;
+  });
+  const float o = attn_merge<KVT, NW>(st, sm, wave, lane);
+  if (threadIdx.x < 64) store_kv(reinterpret_cast<OT*>(a.out) + (size_t)row * a.D + hh * HD + threadIdx.x, o);
+}
+
 // ---- the same attention as a causal flash kernel on the fp32 matrix cores (the latent pass: 1237 rows x 20 heads; the
 // row-at-a-time kernel above re-streams every row's whole key prefix from L2: 94 GB per pass, 6.5 of its 10.4 ms).
 // Structure of csrc/attn_full.hip (S^T = K Q^T leaves, in accumulator register r of lane l, the score of query l&31 against
@@ -923,7 +961,8 @@ static void launch_attn_packed(ixtts_gpt* h, const PackedPass& pk, const void* k
   AttnPackedArgs p;
   p.q = h->rq; p.kcache = kc_layer; p.vcache = vc_layer; p.out = out; p.seqs = pk.seqs; p.tiles = reinterpret_cast<const int2*>(pk.tiles);
   p.row_seq = pk.row_seq; p.D = h->D; p.smax = h->smax; p.H = h->H;
-  if (legacy) hipLaunchKernelGGL((attn_rows_packed_kernel<KVT, OT>), dim3(h->H, pk.T), dim3(256), 0, st, p);
+  if (legacy && pk.keys_rebased) hipLaunchKernelGGL((attn_rows_packed_rebased_kernel<KVT, OT>), dim3(h->H, pk.T), dim3(256), 0, st, p);
+  else if (legacy) hipLaunchKernelGGL((attn_rows_packed_kernel<KVT, OT>), dim3(h->H, pk.T), dim3(256), 0, st, p);
   else hipLaunchKernelGGL((attn_rows_flash_packed_kernel<KVT, OT>), dim3(h->H, pk.n_tiles), dim3(256), 0, st, p);
 }
 
@@ -1109,6 +1148,60 @@ int embed_mel_rows(ixtts_gpt* h, float* x, const int32_t* codes, int rows, hipSt
   if (rows <= 0) return IXTTS_OK;
   hipLaunchKernelGGL(embed_mel_rows_kernel, dim3(rows), dim3(256), 0, st, x, (const float*)A_F32(h->mel_emb), (const float*)A_F32(h->mel_pos), codes,
                      h->cfg.start_mel_token, rows, h->D);
+  IX_HIP(hipGetLastError());
+  return IXTTS_OK;
+}
+
+// ---- latent pass of several sequences (ixtts_gpt_latent_many), in and out.  In: one workgroup per packed row, the launch shape of
+// embed_mel_rows_kernel; row r of a sequence is its prefix row r, or from r = n_prefix on the mel row m = r - n_prefix:
+// mel_emb[m == 0 ? start : codes[m - 1]] + mel_pos[m], the one fp32 add embed_mel_rows_kernel makes.
+__global__ __launch_bounds__(256) void latent_pack_rows_kernel(float* __restrict__ x, const PackSeq* __restrict__ seqs, const LatentSeq* __restrict__ lseqs,
+                                                                const int* __restrict__ row_seq, const float* __restrict__ mel_emb,
+                                                                const float* __restrict__ mel_pos, int start_tok, int D) {
+  const int row = blockIdx.x;
+  const int q = row_seq[row];
+  const LatentSeq e = lseqs[q];
+  const int r = row - seqs[q].row0;
+  float* dst = x + (size_t)row * D;
+  if (r < e.n_prefix) {
+    const float* src = e.prefix + (size_t)r * D;
+    for (int i = threadIdx.x; i < D; i += blockDim.x) dst[i] = src[i];
+  } else {
+    const int m = r - e.n_prefix;
+    const int tok = (m == 0) ? start_tok : e.codes[m - 1];
+    for (int i = threadIdx.x; i < D; i += blockDim.x) dst[i] = mel_emb[(size_t)tok * D + i] + mel_pos[(size_t)m * D + i];
+  }
+}
+// Out: one wave per mel row of the pass, the launch shape of final_norm_rows_kernel and its row arithmetic (final_norm_row)
+template <int K>
+__global__ __launch_bounds__(256) void latent_norm_scatter_kernel(const float* __restrict__ x, const PackSeq* __restrict__ seqs,
+                                                                   const LatentSeq* __restrict__ lseqs, const int* __restrict__ row_seq,
+                                                                   const int* __restrict__ mel_row, int n_mel, const float* __restrict__ w1,
+                                                                   const float* __restrict__ b1, const float* __restrict__ w2, const float* __restrict__ b2) {
+  const int m = blockIdx.x * 4 + (threadIdx.x >> 6);
+  const int lane = threadIdx.x & 63;
+  if (m >= n_mel) return;
+  const int row = mel_row[m];
+  const int q = row_seq[row];
+  const LatentSeq e = lseqs[q];
+  final_norm_row<K>(x, e.latent, (size_t)row, (size_t)(row - seqs[q].row0 - e.n_prefix), lane, w1, b1, w2, b2);
+}
+
+int pack_latent_rows(ixtts_gpt* h, const PackedPass& p, const LatentPass& lp, hipStream_t st) {
+  if (p.T <= 0) return IXTTS_OK;
+  hipLaunchKernelGGL(latent_pack_rows_kernel, dim3(p.T), dim3(256), 0, st, h->rx, p.seqs, lp.lseqs, p.row_seq, (const float*)A_F32(h->mel_emb),
+                     (const float*)A_F32(h->mel_pos), h->cfg.start_mel_token, h->D);
+  IX_HIP(hipGetLastError());
+  return IXTTS_OK;
+}
+int scatter_latent_rows(ixtts_gpt* h, const PackedPass& p, const LatentPass& lp, hipStream_t st) {
+  if (lp.n_mel <= 0) return IXTTS_OK;
+  if (h->D == 1280)
+    hipLaunchKernelGGL(latent_norm_scatter_kernel<1280>, dim3(ceil_div(lp.n_mel, 4)), dim3(256), 0, st, (const float*)h->rx, p.seqs, lp.lseqs, p.row_seq, lp.mel_row,
+                       lp.n_mel, (const float*)A_F32(h->lnf_w), (const float*)A_F32(h->lnf_b), (const float*)A_F32(h->fn_w), (const float*)A_F32(h->fn_b));
+  else
+    hipLaunchKernelGGL(latent_norm_scatter_kernel<128>, dim3(ceil_div(lp.n_mel, 4)), dim3(256), 0, st, (const float*)h->rx, p.seqs, lp.lseqs, p.row_seq, lp.mel_row,
+                       lp.n_mel, (const float*)A_F32(h->lnf_w), (const float*)A_F32(h->lnf_b), (const float*)A_F32(h->fn_w), (const float*)A_F32(h->fn_b));
   IX_HIP(hipGetLastError());
   return IXTTS_OK;
 }

@@ -498,6 +498,49 @@ class GptEngine:
         self._keep2 = (p, c)
         return out
 
+    def latent_many(self, entries, rows_max=0):
+        """`latent` of several sequences in packed passes over the weights: entries = [(prefix [P_i, D], codes [n_i]), ...] -> a
+        list of [n_i, D] fp32 tensors (views of one ragged buffer), each bit for bit what `latent(prefix, codes)` alone returns.
+        No decode slot is touched and the count is not bounded by max_batch.  `rows_max` caps the cache positions of a pass (0:
+        what the workspaces hold, max_seq): more passes, the same bits."""
+        entries = list(entries)
+        n = len(entries)
+        keep = []
+        for prefix, codes in entries:
+            p = prefix.to(self.device, torch.float32).contiguous()
+            c = torch.as_tensor(codes).to(self.device, torch.int32).contiguous().reshape(-1)
+            assert p.dim() == 2 and p.shape[1] == self.D
+            keep.append((p, c))
+        counts = [int(c.numel()) for _, c in keep]
+        buf = torch.empty(max(sum(counts), 1), self.D, device=self.device, dtype=torch.float32)
+        outs, at = [], 0
+        for k in counts:
+            outs.append(buf[at:at + k])
+            at += k
+        m = max(n, 1)
+        pp = (C.c_void_p * m)(*[p.data_ptr() for p, _ in keep])
+        cp = (C.c_void_p * m)(*[c.data_ptr() if c.numel() else None for _, c in keep])
+        op = (C.c_void_p * m)(*[o.data_ptr() if o.shape[0] else None for o in outs])
+        np_ = (C.c_int * m)(*[int(p.shape[0]) for p, _ in keep])
+        nc = (C.c_int * m)(*counts)
+        with torch.cuda.device(self.device):
+            rc = _lib.lib().ixtts_gpt_latent_many(self._h, n, pp, np_, cp, nc, op, int(rows_max), self._stream())
+        _lib.check(rc, "ixtts_gpt_latent_many")
+        if keep:
+            self._keep_latents = keep  # keep alive until the stream has consumed them
+        return outs
+
+    @staticmethod
+    def latent_plan(n_prefix, n_codes, row_cap):
+        """The passes `latent_many` cuts a list of sequences into (host arithmetic, no GPU): -> (pass index of each, pass count)."""
+        n = len(n_prefix)
+        assert len(n_codes) == n
+        out = (C.c_int * max(n, 1))()
+        rc = _lib.lib().ixtts_gpt_latent_plan((C.c_int * max(n, 1))(*map(int, n_prefix)), (C.c_int * max(n, 1))(*map(int, n_codes)), n, int(row_cap), out)
+        if rc < 0:
+            _lib.check(rc, "ixtts_gpt_latent_plan")
+        return list(out[:n]), rc
+
     def step_bytes(self, B, S):
         return _lib.lib().ixtts_gpt_step_bytes(self._h, B, S)
 

@@ -164,9 +164,10 @@ class IndexTTS2:
         # reference precision: fp16 GPT under use_fp16 (infer_v2.py:79,88-89); here bf16 is the throughput mode and the default,
         # gpt_dtype="f16" / IXTTS_GPT_DTYPE=f16 gives the reference's IEEE half (resolve_gpt_dtype)
         self.gpt_dtype = resolve_gpt_dtype(self.use_fp16, gpt_dtype)
-        from .scheduler import resolve_batch_prefill
+        from .scheduler import resolve_batch_prefill, resolve_latent_batch
 
         self.prefill_batch = resolve_batch_prefill()  # IXTTS_PREFILL_BATCH: refill rounds of the decode schedulers as one packed prefill
+        self.latent_batch = resolve_latent_batch()  # IXTTS_LATENT_BATCH: the latents of a call's segments in packed passes (latent_many)
         self.gpt = GptEngine(gcfg, dtype=self.gpt_dtype, max_seq=max_seq, max_batch=3, device=self.device)
         # ---- weights: rank 0 (or a lone worker) reads model_dir; with `weight_broadcast=(rank, world)` (torch.distributed initialised,
         # backend nccl = RCCL over xGMI) the other workers of the node read nothing but config.yaml / bpe.model / the w2v-bert
@@ -767,13 +768,26 @@ class IndexTTS2:
         n = int(stops[0]) if stops.numel() else row.numel()
         return row[:n].reshape(1, -1)
 
-    def _s2mel_item(self, conds_latent, text_ids, codes, spk):
-        """-> (latent [1, n, D], codes, prompt_condition, ref_mel, style): the latent pass (UnifiedVoice.forward, model_v2.py:554-596)
-        over [conds; text] and the codes, refused on the host when a code lies outside the codebook."""
+    def _latent_batching(self):
+        """Whether a call's latents go through one `gpt.latent_many`: IXTTS_LATENT_BATCH as resolved, an engine that has the method
+        (as the schedulers ask for `prefill_many`), and a `gpt.latent` that is the engine's own.  A `latent` replaced on the engine
+        object -- a recorder or a third-party wrapper around the per-segment call -- keeps getting one call per segment: the packed
+        call would go round it."""
+        return bool(getattr(self, "latent_batch", False)) and hasattr(self.gpt, "latent_many") and "latent" not in vars(self.gpt)
+
+    def _latent_entry(self, conds_latent, text_ids, codes):
+        """-> (prefix [34 + L + 2, D], codes [n]), what `gpt.latent` / one entry of `gpt.latent_many` takes; refused on the host when a
+        code lies outside the codebook."""
         self._check_codes(codes)
-        prefix = latent_prefix(self.gpt_cfg, self.text_embedding, self.text_pos_embedding, conds_latent, text_ids)
-        latent = self.gpt.latent(prefix, codes[0]).unsqueeze(0)
-        return latent, codes, spk["prompt_condition"], spk["ref_mel"], spk["style"]
+        return latent_prefix(self.gpt_cfg, self.text_embedding, self.text_pos_embedding, conds_latent, text_ids), codes[0]
+
+    def _s2mel_item(self, conds_latent, text_ids, codes, spk, latent=None):
+        """-> (latent [1, n, D], codes, prompt_condition, ref_mel, style): the latent pass (UnifiedVoice.forward, model_v2.py:554-596)
+        over [conds; text] and the codes, refused on the host when a code lies outside the codebook.  `latent` [n, D]: the pass has
+        run already (one `latent_many` for several segments)."""
+        if latent is None:
+            latent = self.gpt.latent(*self._latent_entry(conds_latent, text_ids, codes))
+        return latent.unsqueeze(0), codes, spk["prompt_condition"], spk["ref_mel"], spk["style"]
 
     def _mels(self, items, spk, packed=False, noises=None):
         """s2mel items -> one mel [1, 80, F] each (infer_v2.py:713-731): segment after segment through the built-in or the injected
@@ -885,13 +899,40 @@ class IndexTTS2:
         t_decode = time.perf_counter() - start
         # per request: codes -> latents (a code outside the codebook fails its request only, before anything is packed); a segment
         # without codes is left out
+        # IXTTS_LATENT_BATCH=1 (the default): the checks per request, then ONE `latent_many` over every surviving segment of every
+        # request (packed passes over the weights, every latent the bits of its own `latent` call), the latents handed back to their
+        # plans; should the packed call raise, the latents are redone segment by segment so that an exception lands on the request
+        # that caused it (the rule of `vocode_many`)
+        batch = self._latent_batching()
         for ri, plan in enumerate(plans):
             if ri in failed:
                 continue
             try:
                 codes = [self._trim_codes(decoded[ri, si]) for si in range(len(plan["segments"]))]
-                kept = [si for si, c in enumerate(codes) if c.shape[1]]
-                plan["items"] = [self._s2mel_item(plan["cl"], plan["segments"][si], codes[si], plan["spk"]) for si in kept]
+                plan["kept"] = kept = [si for si, c in enumerate(codes) if c.shape[1]]
+                plan["codes"] = codes
+                if batch:
+                    plan["entries"] = [self._latent_entry(plan["cl"], plan["segments"][si], codes[si]) for si in kept]
+                else:
+                    plan["latents"] = [None] * len(kept)  # `_s2mel_item` runs the pass
+            except Exception as e:  # this request only
+                failed[ri] = e
+        if batch:
+            live = [ri for ri in range(len(plans)) if ri not in failed]
+            try:
+                lat = iter(self.gpt.latent_many([en for ri in live for en in plans[ri]["entries"]]))
+                for ri in live:
+                    plans[ri]["latents"] = [next(lat) for _ in plans[ri]["entries"]]
+            except Exception:
+                for ri in live:
+                    plans[ri]["latents"] = [None] * len(plans[ri]["entries"])
+        for ri, plan in enumerate(plans):
+            if ri in failed:
+                continue
+            try:
+                kept, codes = plan["kept"], plan["codes"]
+                plan["items"] = [self._s2mel_item(plan["cl"], plan["segments"][si], codes[si], plan["spk"], latent=lt)
+                                 for si, lt in zip(kept, plan["latents"])]
                 # a pinned request's audio is a function of the request: the built-in s2mel's noise comes from its seed, per segment
                 pin = plan["seed"] is not None and self.s2mel is not None
                 plan["noises"] = [self._pinned_noise(it, plan["seed"], si) if pin else None for si, it in zip(kept, plan["items"])]
@@ -996,6 +1037,21 @@ class IndexTTS2:
         wavs = []
         has_warned = False
         silence = None
+        # the segments were decoded up front, so every segment's codes are known: IXTTS_LATENT_BATCH=1 runs ONE `latent_many` for all of
+        # them here and the loop takes its latents from the result (the same bits as its own `latent` call).  Anything this cannot
+        # do -- a segment without codes, a code outside the codebook -- is left to the loop, which raises it where it always did.
+        latents = trimmed = None
+        if pre is not None and self._latent_batching():
+            m0 = time.perf_counter()
+            trimmed = [self._trim_codes(torch.from_numpy(np.asarray(pre[0, i]).astype(np.int64)).reshape(1, -1).to(self.device))
+                       for i in range(len(segments))]  # (once per segment: the loop takes them from here)
+            try:
+                if all(c.shape[1] for c in trimmed):
+                    latents = self.gpt.latent_many([self._latent_entry(cl, ids, c) for ids, c in zip(segments, trimmed)])
+                    torch.cuda.synchronize(self.device)
+            except Exception:
+                latents = None
+            gpt_forward_time += time.perf_counter() - m0
         for seg_index, sent_ids in enumerate(segments):
             m0 = time.perf_counter()
             if pre is not None:
@@ -1020,7 +1076,8 @@ class IndexTTS2:
                               f"({max_text_tokens_per_segment}) or increasing `max_mel_tokens`.", category=RuntimeWarning)
                 has_warned = True
             m0 = time.perf_counter()
-            item = self._s2mel_item(cl, sent_ids, self._trim_codes(codes), spk)
+            item = self._s2mel_item(cl, sent_ids, self._trim_codes(codes) if trimmed is None else trimmed[seg_index], spk,
+                                    latent=None if latents is None else latents[seg_index])
             torch.cuda.synchronize(self.device)
             gpt_forward_time += time.perf_counter() - m0
             if packed is not None:  # every segment's CFM in one solve after the loop

@@ -219,6 +219,13 @@ class HotPath:
         codes = torch.as_tensor(np.asarray(codes), dtype=torch.int32, device=self.device)
         return self.gpt.latent(prefix, codes)
 
+    def latent_many(self, items):
+        """`latent` of several segments in packed passes (GptEngine.latent_many): items = [(conds_latent, text_ids, codes), ...]
+        -> [latent [n_i, D], ...], each bit for bit what `latent` of the item returns."""
+        entries = [(self.latent_prefix(cl, text_ids), torch.as_tensor(np.asarray(codes), dtype=torch.int32, device=self.device))
+                   for cl, text_ids, codes in items]
+        return self.gpt.latent_many(entries)
+
     # ------------------------------------------------------------------ N2 (PyTorch glue, optional)
     def attach_conditioning(self, W, cfg=None):
         """Conformer/perceiver conditioning encoders (voice-tts_amd/conditioning.py); W keyed like UnifiedVoice.state_dict()."""

@@ -37,6 +37,22 @@ def resolve_batch_prefill(batch_prefill=None):
     return v == "1"
 
 
+LATENT_BATCH_DEFAULT = True
+
+
+def resolve_latent_batch(latent_batch=None):
+    """The argument if given, else IXTTS_LATENT_BATCH (0 | 1), else the default: the latents of several segments in packed passes
+    (GptEngine.latent_many) or segment by segment -- the same bits either way."""
+    if latent_batch is not None:
+        return bool(latent_batch)
+    v = os.environ.get("IXTTS_LATENT_BATCH")
+    if v is None or v == "":
+        return LATENT_BATCH_DEFAULT
+    if v not in ("0", "1"):
+        raise ValueError(f"IXTTS_LATENT_BATCH has to be 0 or 1, but is {v!r}")
+    return v == "1"
+
+
 def _prefill_round(engine, batch, entries, after, stats):
     """A refill round: entries = [(slot, segment, ...), ...] in slot order, `after(*entry)` = the calls that set a slot's state once
     its prefill has cleared it (set_bans, set_processors, beam_begin).  Batching on and an engine that has `prefill_many`: one

@@ -289,6 +289,8 @@ def create_app(model_factory=default_model_factory):
             model_info["gpt_dtype"] = m.gpt_dtype
         if getattr(m, "prefill_batch", None) is not None:  # IXTTS_PREFILL_BATCH as resolved: refill rounds as one packed prefill
             model_info["prefill_batch"] = bool(m.prefill_batch)
+        if getattr(m, "latent_batch", None) is not None:  # IXTTS_LATENT_BATCH as resolved: a call's latents in packed passes
+            model_info["latent_batch"] = bool(m.latent_batch)
         return {"worker_id": os.environ.get("WORKER_ID", "unknown"), "pid": os.getpid(),
                 "cuda_visible_devices": os.environ.get("CUDA_VISIBLE_DEVICES", "not set"), "gpu_info": gpu, "model_info": model_info}
 

@@ -599,6 +599,39 @@ int ixtts_qwen_read_logits_slot(ixtts_qwen* h, int slot, float* logits_host, voi
 int ixtts_qwen_read_kept_slot(ixtts_qwen* h, int slot, int32_t* ids_host, float* probs_host, int cap, int* n_kept, void* stream);
 int ixtts_qwen_destroy(ixtts_qwen* h);
 
+/* ---- output stage: requested sample rate and sample encoding, after the vocoder -----------------------------------------------
+ * What the reference leaves to its caller: `infer` ends at 22 050 Hz int16 (infer_v2.py:735-783); a deployment that wants 8 kHz
+ * G.711 or 16 / 24 / 48 kHz resamples and re-encodes the WAV on its own side.  Here both happen on the device, for every segment
+ * of a call in one launch each.
+ *
+ * Rows: `rows_dev` (int64, device) [n_rows][3] = (src offset, n, dst offset), in elements of the input / output buffer.
+ *
+ * ixtts_resample_varlen_f32: torchaudio.transforms.Resample(22050, sr) (sinc_interp_hann, lowpass_filter_width 6, rolloff 0.99) of
+ *     n_rows packed fp32 rows of unequal length.  orig / new_ = the two rates over their gcd; output sample j = q * new_ + p of a row
+ *     of n samples is sum_k h[p][k] xpad[q * orig + k], xpad = the row behind `width` zeros and zeros after it; a row yields
+ *     ceil(n * new_ / orig) samples at y_dev + dst, clamped to +-32767.0.  The tap table arrives as compacted bands (the non-zero
+ *     taps of a phase are contiguous in the fp32 table): bands_dev [new_][band | 1] fp32 (row stride band | 1, the whole table
+ *     padded to a multiple of 4 floats, 16-byte aligned; bands_elems = floats it holds) with bands[p][k] = h[p][starts[p] + k],
+ *     starts_dev (int32) [new_], starts[p] + band <= 2 * width + orig.  max_n = the longest row (it sizes the grid).  A row with
+ *     n = 0 writes nothing; a row the buffers cannot hold (src + n > x_elems, dst + ceil(..) > y_elems) is left alone.  A sample
+ *     is one fma chain over its own row: the same bits alone, in any batch, at any position.  n_rows <= 65535.
+ * ixtts_resample_tile: output samples one workgroup of the resampler produces (IXTTS_RESAMPLE_TILE), for tests that aim at its edges.
+ * ixtts_pcm_assemble: out_dev[0 .. total) samples of `encoding`: sample i inside a row's [dst, dst + n) is the conversion of
+ *     x_dev[src + i - dst] (fp32 at the +-32767 scale, clamped to the int16 range, truncated toward zero -- `.type(torch.int16)`;
+ *     IXTTS_PCM_MULAW / _ALAW: ITU-T G.711 of that int16, one byte, as audioop.lin2ulaw / lin2alaw), every other sample the
+ *     encoding's code for silence (0, 0xFF, 0xD5).  Rows ascend in dst and do not overlap.  out_dev is 8-byte aligned and holds
+ *     `total` int16 (IXTTS_PCM_S16LE) or bytes.
+ * Both run on `stream`, allocate nothing, and return IXTTS_ERR_ARG (text in ixtts_last_error) for a bad shape or an unknown encoding.
+ */
+#define IXTTS_RESAMPLE_TILE 1024
+#define IXTTS_PCM_S16LE 0
+#define IXTTS_PCM_MULAW 1
+#define IXTTS_PCM_ALAW 2
+int ixtts_resample_tile(void);
+int ixtts_resample_varlen_f32(const float* x_dev, long x_elems, float* y_dev, long y_elems, const int64_t* rows_dev, int n_rows, long max_n,
+                              const float* bands_dev, long bands_elems, const int* starts_dev, int orig, int new_, int width, int band, void* stream);
+int ixtts_pcm_assemble(const float* x_dev, long x_elems, void* out_dev, long total, const int64_t* rows_dev, int n_rows, int encoding, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

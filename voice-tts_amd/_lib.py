@@ -51,6 +51,9 @@ QWEN_TOPK_MAX = 64  # IXTTS_QWEN_TOPK_MAX
 QWEN_MAX_EOS = 8
 QWEN_MAX_SLOTS = 4  # IXTTS_QWEN_MAX_SLOTS
 
+RESAMPLE_TILE = 1024  # IXTTS_RESAMPLE_TILE: output samples per workgroup of the resampler (`resample_tile()` asks the library)
+PCM_ENCODINGS = {"pcm_s16le": 0, "mulaw": 1, "alaw": 2}  # IXTTS_PCM_*
+
 
 class QwenCfg(C.Structure):
     _fields_ = [
@@ -171,6 +174,9 @@ SYMBOLS = {
     "ixtts_qwen_read_logits_slot": (C.c_int, [_P, C.c_int, _P, _P]),
     "ixtts_qwen_read_kept_slot": (C.c_int, [_P, C.c_int, _P, _P, C.c_int, C.POINTER(C.c_int), _P]),
     "ixtts_qwen_destroy": (C.c_int, [_P]),
+    "ixtts_resample_tile": (C.c_int, []),
+    "ixtts_resample_varlen_f32": (C.c_int, [_P, C.c_long, _P, C.c_long, _P, C.c_int, C.c_long, _P, C.c_long, _P, C.c_int, C.c_int, C.c_int, C.c_int, _P]),
+    "ixtts_pcm_assemble": (C.c_int, [_P, C.c_long, _P, C.c_long, _P, C.c_int, C.c_int, _P]),
 }
 
 _lib = None
@@ -225,6 +231,11 @@ def max_batch_for(dtype):
             raise ValueError(f"max_batch_for: unknown weight type {dtype!r}")
         dtype = _DTYPE_CODES[dtype]
     return int(lib().ixtts_gpt_max_batch_for(int(dtype)))
+
+
+def resample_tile():
+    """Output samples one workgroup of the resampler produces (a build constant of libixtts_hip.so)."""
+    return int(lib().ixtts_resample_tile())
 
 
 def current_stream_ptr():

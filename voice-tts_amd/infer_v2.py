@@ -27,6 +27,7 @@ import torch
 
 from .bigvgan import BigVGAN
 from .gpt_engine import GptEngine, generation_constraints, generation_processors, resolve_gpt_dtype, resolve_min_length
+from . import output as _output  # (through the module: a test may wrap `finish_pcm_many`)
 from .pipeline import conds_latent, decode_segment, latent_prefix, prepare_gpt_inputs, vocode, vocode_many
 from .weights import BIGVGAN_CFG, GPT_CFG, load_bigvgan_checkpoint, load_gpt_checkpoint
 
@@ -805,13 +806,31 @@ class IndexTTS2:
                 mels.append(self._stage("s2mel", None)(latent, codes, lens, spk))
         return mels
 
+    @staticmethod
+    def _output_format(output_sample_rate, output_encoding, stream_return=False):
+        """-> (rate, encoding) of a call that asks for an output format; ValueError for a value outside `output.SAMPLE_RATES` /
+        `output.ENCODINGS`, and for an encoding on a stream (its segments are fp32 tensors)."""
+        if stream_return and output_encoding is not None:
+            raise ValueError("output_encoding cannot be combined with stream_return=True: the stream yields fp32 segments "
+                             "(output_sample_rate alone resamples them)")
+        return _output.check_format(output_sample_rate, output_encoding)
+
     # ------------------------------------------------------------------ API
     def infer(self, spk_audio_prompt, text, output_path, emo_audio_prompt=None, emo_alpha=1.0, emo_vector=None,
               use_emo_text=False, emo_text=None, use_random=False, interval_silence=200, verbose=False,
-              max_text_tokens_per_segment=120, stream_return=False, more_segment_before=0, **generation_kwargs):
+              max_text_tokens_per_segment=120, stream_return=False, more_segment_before=0, output_sample_rate=None,
+              output_encoding=None, **generation_kwargs):
+        """`output_sample_rate` (one of `output.SAMPLE_RATES`) / `output_encoding` (`pcm_s16le`, `mulaw`, `alaw`): the output stage on
+        the device (output.py) takes the place of the host-side cat and int16 cast -- the `(sr, pcm)` return, the file at
+        `output_path` and `last_timing["audio_length"]` follow the requested rate; pcm is uint8 for the G.711 encodings.  With
+        `stream_return=True` the yielded segments are the resampled fp32 rows and an encoding is refused (the stream yields floats,
+        as the reference's does).  Both None: 22 050 Hz int16, as ever."""
+        if output_sample_rate is not None or output_encoding is not None:  # refused here, not at the generator's first step
+            self._output_format(output_sample_rate, output_encoding, stream_return)
         gen = self.infer_generator(spk_audio_prompt, text, output_path, emo_audio_prompt, emo_alpha, emo_vector, use_emo_text,
                                    emo_text, use_random, interval_silence, verbose, max_text_tokens_per_segment, stream_return,
-                                   more_segment_before, **generation_kwargs)
+                                   more_segment_before, output_sample_rate=output_sample_rate, output_encoding=output_encoding,
+                                   **generation_kwargs)
         if stream_return:
             return gen
         try:
@@ -820,7 +839,8 @@ class IndexTTS2:
             return None
 
     @torch.no_grad()
-    def infer_many(self, requests, interval_silence=200, max_text_tokens_per_segment=120, decode_slots=8, **generation_kwargs):
+    def infer_many(self, requests, interval_silence=200, max_text_tokens_per_segment=120, decode_slots=8, output_sample_rate=None,
+                   output_encoding=None, **generation_kwargs):
         """Several `/tts` requests served TOGETHER (the worker's global lock, server.py:25,384, replaced by the
         decode scheduler): every request's segments share the decode slots -- the weights are read once per step for all of them
         -- and the post-decode stages run per segment as in `infer`, through the same helpers.  Each request is a dict with
@@ -846,7 +866,13 @@ class IndexTTS2:
         `num_beams` the engine chosen for `decode_slots` cannot hold, fails that request only.  Requests without the key behave
         as ever: the call's settings, streams by slot / submission order, noise from the default generator.
 
-        Returns one entry per request: `(22050, int16 [N, 1])`, None (empty text), or the EXCEPTION that
+        `output_sample_rate` / `output_encoding` (see `infer`) hold for the call; a request may carry its own `sample_rate` and
+        `encoding` beside `generation` (they do not pin it).  The requests that ask for a format leave through the output stage on
+        the device together (`output.finish_pcm_many`: one resample launch per distinct rate, one conversion launch per distinct
+        encoding, one copy to the host), and a pinned request's bytes stay a function of the request alone; a value outside the
+        accepted sets fails that request only.  The requests that ask for nothing take the host path they always took.
+
+        Returns one entry per request: `(22050, int16 [N, 1])` (`(rate, int16 | uint8 [N, 1])` with a format), None (empty text), or the EXCEPTION that
         request raised (bad prompt audio, a code outside the codebook ...) -- one request's failure leaves the others of the
         batch alone."""
         g, _ = self._generation_args(generation_kwargs)
@@ -872,6 +898,13 @@ class IndexTTS2:
                 spk, emo_cond = self._encode_prompts(spk_prompt, emo_prompt)
                 cl = self._conds_latent(spk, emo_cond, emo_is_spk, emo_alpha, emo_vector, rq.get("use_random", False))
                 segments = self._segments_of(rq["text"], max_text_tokens_per_segment)
+                # the output format: the request's own keys, else the call's; None = the host path of old
+                fmt = (rq["sample_rate"] if rq.get("sample_rate") is not None else output_sample_rate,
+                       rq["encoding"] if rq.get("encoding") is not None else output_encoding)
+                if fmt == (None, None):
+                    fmt = None
+                else:
+                    self._output_format(*fmt)  # a value outside the accepted sets fails this request
                 gr, pinned, cons = self._request_generation(rq, generation_kwargs, g)
                 procs = self._generation_processors({**generation_kwargs, **(rq.get("generation") or {})})
                 nb = gr.num_beams
@@ -885,7 +918,7 @@ class IndexTTS2:
                 mine = [self._segment(cl, ids, eng, gr.max_mel_tokens, request=ri, index=si, stream=si if pinned else None, sampler=sampler,
                                       constraints=cons, processors=procs)
                         for si, ids in enumerate(segments)]
-                plans[ri] = dict(spk=spk, cl=cl, segments=segments, seed=gr.seed if pinned else None)
+                plans[ri] = dict(spk=spk, cl=cl, segments=segments, seed=gr.seed if pinned else None, fmt=fmt)
                 classes.setdefault(nb, []).extend(mine)  # only once the whole request is known to be well-formed
             except Exception as e:  # this request only
                 failed[ri] = e
@@ -962,10 +995,23 @@ class IndexTTS2:
         pcm = iter(vocode_many(self.bigvgan, [mel for ri in live for mel in plans[ri]["mels"]]))
         for ri in live:
             plans[ri]["pcm"] = [next(pcm) for _ in plans[ri]["mels"]]
+        # the requests that asked for a sample rate or an encoding: through the output stage on the device, all of them together
+        formatted = {}
+        mine = [ri for ri in live if plans[ri]["fmt"] is not None and not any(isinstance(w, Exception) for w in plans[ri]["pcm"])]
+        if mine:
+            try:
+                res = _output.finish_pcm_many([plans[ri]["pcm"] for ri in mine], [plans[ri]["fmt"][0] for ri in mine],
+                                              [plans[ri]["fmt"][1] for ri in mine], interval_silence)
+                formatted = dict(zip(mine, res))
+            except Exception as e:
+                formatted = {ri: e for ri in mine}
         out = []
         for ri, plan in enumerate(plans):
             if ri in failed:
                 out.append(failed[ri])
+                continue
+            if ri in formatted:
+                out.append(formatted[ri])
                 continue
             try:
                 for w in plan["pcm"]:
@@ -981,6 +1027,8 @@ class IndexTTS2:
                 out.append(e)
         total = time.perf_counter() - start
         audio = sum(o[1].shape[0] for o in out if isinstance(o, tuple)) / 22050.0
+        if formatted:  # every result at its own rate
+            audio = sum(o[1].shape[0] / float(o[0]) for o in out if isinstance(o, tuple))
         logger.info(f"infer_many: {len(requests)} requests ({sum(isinstance(o, Exception) for o in out)} failed), {len(todo)} segments, "
                     f"decode {t_decode:.2f} s, total {total:.2f} s, audio {audio:.2f} s, RTF {total / max(audio, 1e-9):.4f}")
         self.last_timing = dict(gpt_gen_time=t_decode, total=total, audio_length=audio)
@@ -988,9 +1036,14 @@ class IndexTTS2:
 
     def infer_generator(self, spk_audio_prompt, text, output_path, emo_audio_prompt=None, emo_alpha=1.0, emo_vector=None,
                         use_emo_text=False, emo_text=None, use_random=False, interval_silence=200, verbose=False,
-                        max_text_tokens_per_segment=120, stream_return=False, quick_streaming_tokens=0, **generation_kwargs):
+                        max_text_tokens_per_segment=120, stream_return=False, quick_streaming_tokens=0, output_sample_rate=None,
+                        output_encoding=None, **generation_kwargs):
         logger.info("Starting inference...")
         start_time = time.perf_counter()
+        # an output format (see `infer`): the segments stay on the device and leave through `output.finish_pcm`
+        fmt = output_sample_rate is not None or output_encoding is not None
+        if fmt:
+            out_rate, out_enc = self._output_format(output_sample_rate, output_encoding, stream_return)
         self._prompt_stages()
         gpt_gen_time = gpt_forward_time = s2mel_time = bigvgan_time = 0.0
         if use_emo_text:
@@ -1091,6 +1144,14 @@ class IndexTTS2:
             wav = vocode(self.bigvgan, mel)
             torch.cuda.synchronize(self.device)
             bigvgan_time += time.perf_counter() - m0
+            if fmt:
+                wavs.append(wav)
+                if stream_return:  # the resampled, clamped fp32 row, and silence of the new length
+                    yield (wav if out_rate == sampling_rate else _output.Resampler(out_rate, wav.device).forward_many([wav])[0]).cpu()
+                    if silence is None:
+                        silence = torch.zeros(wav.size(0), _output.gap_len(out_rate, interval_silence))
+                    yield silence
+                continue
             wavs.append(wav.cpu())
             if stream_return:
                 yield wav.cpu()
@@ -1107,14 +1168,21 @@ class IndexTTS2:
             for w in vocode_many(self.bigvgan, mels):  # one batched pass (IXTTS_BV_BATCH=0: mel after mel)
                 if isinstance(w, Exception):
                     raise w
-                wavs.append(w.cpu())  # (.cpu() waits for the vocoder)
+                wavs.append(w if fmt else w.cpu())  # (.cpu() waits for the vocoder)
+            if fmt:
+                torch.cuda.synchronize(self.device)
             bigvgan_time += time.perf_counter() - m0
         end_time = time.perf_counter()
         if not wavs:
             return
-        wavs = self.insert_interval_silence(wavs, sampling_rate=sampling_rate, interval_silence=interval_silence)
-        wav = torch.cat(wavs, dim=1)
-        wav_length = wav.shape[-1] / sampling_rate
+        if fmt:
+            sampling_rate, pcm = _output.finish_pcm(wavs, output_sample_rate, output_encoding, interval_silence)
+            wav_length = pcm.shape[0] / sampling_rate
+            end_time = time.perf_counter()  # (the output stage is part of the request)
+        else:
+            wavs = self.insert_interval_silence(wavs, sampling_rate=sampling_rate, interval_silence=interval_silence)
+            wav = torch.cat(wavs, dim=1)
+            wav_length = wav.shape[-1] / sampling_rate
         logger.info(f"gpt_gen_time: {gpt_gen_time:.2f} seconds")
         logger.info(f"gpt_forward_time: {gpt_forward_time:.2f} seconds")
         logger.info(f"s2mel_time: {s2mel_time:.2f} seconds")
@@ -1124,6 +1192,17 @@ class IndexTTS2:
         logger.info(f"RTF: {(end_time - start_time) / wav_length:.4f}")
         self.last_timing = dict(gpt_gen_time=gpt_gen_time, gpt_forward_time=gpt_forward_time, s2mel_time=s2mel_time,
                                 bigvgan_time=bigvgan_time, total=end_time - start_time, audio_length=wav_length)
+        if fmt:
+            if output_path:
+                if os.path.isfile(output_path):
+                    os.remove(output_path)
+                if os.path.dirname(output_path) != "":
+                    os.makedirs(os.path.dirname(output_path), exist_ok=True)
+                with open(output_path, "wb") as f:
+                    f.write(_output.wav_bytes(sampling_rate, pcm, out_enc))
+            if not stream_return:
+                yield output_path if output_path else (sampling_rate, pcm)
+            return
         wav = wav.cpu()
         if output_path:
             if os.path.isfile(output_path):

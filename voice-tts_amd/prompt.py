@@ -31,6 +31,7 @@ import torch
 import torch.nn.functional as F
 
 from .convs import conv1d, conv2d  # GEMM forms: no MIOpen in the request path (convs.py)
+from .output import resample_ratio, resample_taps
 
 from .weights import fold_weight_norm
 
@@ -155,29 +156,15 @@ def load_and_cut_audio(audio_input, max_audio_length_seconds, sr=None):
 
 
 # ===================================================================================================== resampling
-_RESAMPLE_KERNELS = {}
-
-
 def sinc_resample(wave, orig_freq, new_freq, lowpass_filter_width=6, rolloff=0.99):
     """`torchaudio.transforms.Resample(orig, new)` with its defaults (sinc_interp_hann): one Hann-windowed sinc kernel per
-    output phase, applied as a strided conv1d.  wave [..., time] -> [..., ceil(time * new / orig)]."""
+    output phase, applied as a strided conv1d.  wave [..., time] -> [..., ceil(time * new / orig)].  The kernel bank is
+    `output.resample_taps`, the table the device resampler of the output stage reads too."""
     orig_freq, new_freq = int(orig_freq), int(new_freq)
     if orig_freq == new_freq:
         return wave
-    g = math.gcd(orig_freq, new_freq)
-    orig, new = orig_freq // g, new_freq // g
-    key = (orig, new, lowpass_filter_width, rolloff, wave.device)
-    if key not in _RESAMPLE_KERNELS:
-        base = min(orig, new) * rolloff
-        width = math.ceil(lowpass_filter_width * orig / base)
-        idx = torch.arange(-width, width + orig, dtype=torch.float64)[None, None] / orig
-        t = torch.arange(0, -new, -1, dtype=torch.float64)[:, None, None] / new + idx
-        t = (t * base).clamp_(-lowpass_filter_width, lowpass_filter_width)
-        window = torch.cos(t * math.pi / lowpass_filter_width / 2) ** 2
-        t = t * math.pi
-        kern = torch.where(t == 0, torch.ones_like(t), t.sin() / t) * window * (base / orig)
-        _RESAMPLE_KERNELS[key] = (kern.to(torch.float32).to(wave.device), width)
-    kern, width = _RESAMPLE_KERNELS[key]
+    orig, new = resample_ratio(orig_freq, new_freq)
+    kern, width = resample_taps(orig_freq, new_freq, wave.device, lowpass_filter_width, rolloff)
     shape = wave.shape
     x = wave.reshape(-1, shape[-1]).float()
     x = F.pad(x, (width, width + orig))

@@ -1,7 +1,8 @@
 """The reference's HTTP surface (`server.py`) over this repository's `IndexTTS2` -- SURVEY.md 8(b) "HTTP API".
 
 Same endpoints, models, priorities, error codes and CLI as the reference:
-  POST /tts   TTSRequest{text, spk_audio (URL | hex > 100 chars), emo_audio?, emotion? (str | {str: float in [0,1]}), emo_alpha in [0,1] = 1.0}
+  POST /tts   TTSRequest{text, spk_audio (URL | hex > 100 chars), emo_audio?, emotion? (str | {str: float in [0,1]}), emo_alpha in [0,1] = 1.0,
+                         sample_rate?, encoding?}   (the last two are this build's: the output stage of output.py; 422 outside its sets)
               -> TTSResponse{audio_hex, audio_length, inference_time, rtf, text}                       (server.py:183-235,320-440)
               emo_audio beats emotion (:352-370); emo_alpha is forced to 1.0 unless emo_audio is given (:391)
   GET /       {"status","model_loaded","service","version"}                                            (:238-246)
@@ -79,6 +80,16 @@ class TTSRequest(BaseModel):
     emo_audio: Optional[str] = Field(None, description="emotion reference audio (URL or hex); takes priority over `emotion`")
     emotion: Optional[Union[str, Dict[str, float]]] = Field(None, description="one emotion label, or {label: strength in [0,1]}")
     emo_alpha: float = Field(default=1.0, description="emotion strength in [0,1]")
+    sample_rate: Optional[int] = Field(None, description="output sample rate in Hz (8000, 11025, 16000, 22050, 24000, 32000, 44100, 48000); default 22050")
+    encoding: Optional[str] = Field(None, description="output sample encoding: pcm_s16le (default), mulaw or alaw (ITU-T G.711, 8 bits)")
+
+    @field_validator("sample_rate", "encoding")
+    @classmethod
+    def _output_format(cls, v, info):
+        from .output import check_format  # (imported in the worker, with the model: nothing touches torch at import time)
+
+        check_format(**{info.field_name: v})  # ValueError naming the accepted set -> 422
+        return v
 
     @field_validator("emo_alpha")
     @classmethod
@@ -311,26 +322,35 @@ def create_app(model_factory=default_model_factory):
                     emo_vector = create_emotion_vector(request.emotion, request.emo_alpha)
                 else:
                     emo_vector = create_emotion_vector(request.emotion)
+            # the output format goes on only when the request sets it: a model without the keywords keeps working
+            fmt_kw = {k: v for k, v in (("output_sample_rate", request.sample_rate), ("output_encoding", request.encoding)) if v is not None}
             start = time.time()
             if state["batcher"] is not None:  # opt-in: queued requests decode together (IXTTS_BATCH_SLOTS)
                 import io
 
                 res = state["batcher"].submit(dict(spk_audio_prompt=spk_audio_data, text=request.text, emo_audio_prompt=emo_audio_data if emo_audio_data else None,
-                                                   emo_alpha=request.emo_alpha if emo_audio_data else 1.0, emo_vector=emo_vector)).result()
+                                                   emo_alpha=request.emo_alpha if emo_audio_data else 1.0, emo_vector=emo_vector,
+                                                   **{k: v for k, v in (("sample_rate", request.sample_rate), ("encoding", request.encoding)) if v is not None})).result()
                 if res is None:
                     raise RuntimeError("the text produced no speech segment")
                 sr, pcm = res
-                buf = io.BytesIO()
-                with wave.open(buf, "wb") as w:
-                    w.setnchannels(pcm.shape[1])
-                    w.setsampwidth(2)
-                    w.setframerate(sr)
-                    w.writeframes(pcm.astype("<i2").tobytes())
+                if fmt_kw:
+                    from .output import wav_bytes
+
+                    riff = wav_bytes(sr, pcm, request.encoding)
+                else:
+                    buf = io.BytesIO()
+                    with wave.open(buf, "wb") as w:
+                        w.setnchannels(pcm.shape[1])
+                        w.setsampwidth(2)
+                        w.setframerate(sr)
+                        w.writeframes(pcm.astype("<i2").tobytes())
+                    riff = buf.getvalue()
                 inference_time = time.time() - start
                 audio_length = pcm.shape[0] / float(sr)
                 rtf = inference_time / audio_length if audio_length > 0 else 0.0
                 logger.info(f"TTS completed (batched): audio_length={audio_length:.2f}s, inference_time={inference_time:.2f}s, rtf={rtf:.4f}")
-                return TTSResponse(audio_hex=buf.getvalue().hex(), audio_length=audio_length, inference_time=inference_time, rtf=rtf, text=request.text)
+                return TTSResponse(audio_hex=riff.hex(), audio_length=audio_length, inference_time=inference_time, rtf=rtf, text=request.text)
             if getattr(model, "returns_pcm_without_path", False):
                 # The reference writes the waveform to a temporary file, reopens it for its length and reads it back for the hex
                 # string (server.py:375-408).  `infer(output_path=None)` hands back (22050, int16 [N, 1]) -- the same samples the
@@ -340,20 +360,26 @@ def create_app(model_factory=default_model_factory):
                 with inference_lock:  # one inference at a time per worker (server.py:25,384)
                     res = model.infer(spk_audio_prompt=spk_audio_data, text=request.text, output_path=None,
                                       emo_audio_prompt=emo_audio_data if emo_audio_data else None,
-                                      emo_alpha=request.emo_alpha if emo_audio_data else 1.0, emo_vector=emo_vector, verbose=False)
+                                      emo_alpha=request.emo_alpha if emo_audio_data else 1.0, emo_vector=emo_vector, verbose=False, **fmt_kw)
                 if res is None:
                     raise RuntimeError("the text produced no speech segment")
                 sr, pcm = res
-                buf = io.BytesIO()
-                with wave.open(buf, "wb") as w:
-                    w.setnchannels(pcm.shape[1])
-                    w.setsampwidth(2)
-                    w.setframerate(sr)
-                    w.writeframes(pcm.astype("<i2").tobytes())
+                if fmt_kw:
+                    from .output import wav_bytes
+
+                    riff = wav_bytes(sr, pcm, request.encoding)
+                else:
+                    buf = io.BytesIO()
+                    with wave.open(buf, "wb") as w:
+                        w.setnchannels(pcm.shape[1])
+                        w.setsampwidth(2)
+                        w.setframerate(sr)
+                        w.writeframes(pcm.astype("<i2").tobytes())
+                    riff = buf.getvalue()
                 inference_time = time.time() - start
                 audio_length = pcm.shape[0] / float(sr)
                 rtf = inference_time / audio_length if audio_length > 0 else 0.0
-                audio_hex = buf.getvalue().hex()
+                audio_hex = riff.hex()
                 logger.info(f"TTS completed: audio_length={audio_length:.2f}s, inference_time={inference_time:.2f}s, rtf={rtf:.4f}, size={len(audio_hex)//2} bytes")
                 return TTSResponse(audio_hex=audio_hex, audio_length=audio_length, inference_time=inference_time, rtf=rtf, text=request.text)
             with tempfile.NamedTemporaryFile(suffix=".wav", delete=False) as tmp:
@@ -361,12 +387,18 @@ def create_app(model_factory=default_model_factory):
             with inference_lock:  # one inference at a time per worker (server.py:25,384)
                 result_path = model.infer(spk_audio_prompt=spk_audio_data, text=request.text, output_path=output_path,
                                           emo_audio_prompt=emo_audio_data if emo_audio_data else None,
-                                          emo_alpha=request.emo_alpha if emo_audio_data else 1.0, emo_vector=emo_vector, verbose=False)
+                                          emo_alpha=request.emo_alpha if emo_audio_data else 1.0, emo_vector=emo_vector, verbose=False, **fmt_kw)
             inference_time = time.time() - start
             with open(result_path, "rb") as f:
                 audio_hex = f.read().hex()
-            with wave.open(result_path, "rb") as w:
-                audio_length = w.getnframes() / float(w.getframerate())
+            if request.encoding in ("mulaw", "alaw"):  # (`wave` reads PCM only)
+                from .output import riff_info
+
+                info = riff_info(bytes.fromhex(audio_hex))
+                audio_length = info["frames"] / float(info["rate"])
+            else:
+                with wave.open(result_path, "rb") as w:
+                    audio_length = w.getnframes() / float(w.getframerate())
             rtf = inference_time / audio_length if audio_length > 0 else 0.0
             os.remove(output_path)
             logger.info(f"TTS completed: audio_length={audio_length:.2f}s, inference_time={inference_time:.2f}s, rtf={rtf:.4f}, size={len(audio_hex)//2} bytes")

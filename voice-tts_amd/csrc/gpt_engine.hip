@@ -414,15 +414,53 @@ static size_t take(size_t& off, size_t bytes) {
   return o;
 }
 
-static size_t pf_table_bytes(int n, int smax) {  // the most a call of n sequences can need: see the layout in ixtts_gpt_prefill_many
-  return (size_t)n * (sizeof(PackSeq) + 4) + (size_t)n * (smax / 128 + 1) * 8 + (size_t)n * smax * 8;
-}
+// The tables of packed passes that go to the device in one copy (ixtts_gpt_prefill_many: all passes of a call; ixtts_gpt_latent_many:
+// one pass), in one buffer:
+//   [n_seq] PackSeq | the caller's records (rec_bytes, a multiple of 8) | [n_tiles] int2 | [rows] row_at | [rows] row_seq | the caller's ints
+// The constructor lays the regions out for given counts -- the calls with what they hold, the capacities at create with the most a
+// call can hold -- and add() appends one sequence to a host image.
+struct PassTables {
+  size_t off_rec, off_tiles, off_at, off_seq, off_ints, bytes;
+  int n_seq = 0, n_tiles = 0, rows = 0;  // appended so far
+  PassTables(size_t seqs, size_t tiles, size_t rows_, size_t rec_bytes, size_t n_ints) {
+    static_assert(sizeof(PackSeq) % 8 == 0, "the records and the tile pairs behind the PackSeq array hold pointers and are read as int2");
+    off_rec = seqs * sizeof(PackSeq);
+    off_tiles = off_rec + rec_bytes;
+    off_at = off_tiles + tiles * 8;
+    off_seq = off_at + rows_ * 4;
+    off_ints = off_seq + rows_ * 4;
+    bytes = off_ints + n_ints * 4;
+  }
+  // sequence `local` of its pass: T rows at the pass's packed rows row0 .., K/V at positions pos0 .. of `slot` (slot_rows = H * max_seq
+  // cache rows per slot): its PackSeq, its 128-row attention tiles and its rows' row_at / row_seq
+  void add(uint8_t* host, const float* embeds, int slot, int T, int pos0, int local, int row0, int slot_rows) {
+    reinterpret_cast<PackSeq*>(host)[n_seq++] = PackSeq{embeds, slot, T, pos0, row0};
+    int* tiles = reinterpret_cast<int*>(host + off_tiles);
+    for (int q0 = 0; q0 < T; q0 += 128, ++n_tiles) { tiles[2 * n_tiles] = local; tiles[2 * n_tiles + 1] = q0; }
+    int* row_at = reinterpret_cast<int*>(host + off_at);
+    int* row_seq = reinterpret_cast<int*>(host + off_seq);
+    for (int t = 0; t < T; ++t, ++rows) { row_at[rows] = slot * slot_rows + pos0 + t; row_seq[rows] = local; }
+  }
+  // the pass that holds sequences seq0 .., tiles tile0 .. and rows row0 .. of the device image
+  PackedPass pass(const uint8_t* dev, int seq0, int n_seq_, int tile0, int n_tiles_, int row0, int T) const {
+    PackedPass pk;
+    pk.seqs = reinterpret_cast<const PackSeq*>(dev) + seq0;
+    pk.tiles = reinterpret_cast<const int*>(dev + off_tiles) + 2 * tile0;
+    pk.row_at = reinterpret_cast<const int*>(dev + off_at) + row0;
+    pk.row_seq = reinterpret_cast<const int*>(dev + off_seq) + row0;
+    pk.n_seq = n_seq_; pk.n_tiles = n_tiles_; pk.T = T;
+    return pk;
+  }
+};
+
+// the most a call of n sequences can need: max_seq rows and max_seq / 128 + 1 tiles each, and the call's prompt_len per sequence
+static size_t pf_table_bytes(int n, int smax) { return PassTables(n, (size_t)n * (smax / 128 + 1), (size_t)n * smax, 0, n).bytes; }
 
 // one pass of ixtts_gpt_latent_many: at most smax rows, smax / 64 + 1 sequences (each takes 64 positions or more of the pass, or the
-// pass alone), a 128-row tile per 128 rows and one more per sequence; the layout is in ixtts_gpt_latent_many
+// pass alone), a 128-row tile per 128 rows and one more per sequence; a LatentSeq per sequence and at most a mel_row per row
 static size_t lm_table_bytes(int smax) {
   const size_t n_seq = (size_t)smax / 64 + 1;
-  return n_seq * (sizeof(PackSeq) + sizeof(LatentSeq)) + (n_seq + (size_t)smax / 128 + 1) * 8 + (size_t)smax * 12;
+  return PassTables(n_seq, n_seq + (size_t)smax / 128 + 1, smax, n_seq * sizeof(LatentSeq), smax).bytes;
 }
 
 extern "C" int ixtts_gpt_create(ixtts_gpt** out, const ixtts_gpt_cfg* c) {
@@ -892,40 +930,30 @@ extern "C" int ixtts_gpt_prefill_many(ixtts_gpt* h, int n, const int* slots, con
   const int n_pass = ixtts_gpt_prefill_plan(n_rows, n_left_pad, n, row_cap, pass_of);
   if (n_pass < 0) return n_pass;
 
-  // tables of the whole call: [n] PackSeq | [tiles][2] (both 8-byte aligned) | [n] prompt_len | [rows] row_at | [rows] row_seq, each pass a range of each
+  // tables of the whole call (PassTables; the ints behind them: [n] prompt_len), each pass a range of each region
   int rows_total = 0, tiles_total = 0;
   for (int i = 0; i < n; ++i) {
     const int T = n_rows[i] + 1 - n_left_pad[i];
     rows_total += T;
     tiles_total += ceil_div(T, 128);
   }
-  static_assert(sizeof(PackSeq) % 8 == 0, "the tile pairs behind the PackSeq array are read as int2");
-  const size_t off_tiles = (size_t)n * sizeof(PackSeq), off_plen = off_tiles + (size_t)tiles_total * 8, off_at = off_plen + (size_t)n * 4,
-               off_seq = off_at + (size_t)rows_total * 4, bytes = off_seq + (size_t)rows_total * 4;
-  if (bytes > h->pf_bytes) {
-    set_error("gpt_prefill_many: tables of %zu bytes exceed the handle's %zu", bytes, h->pf_bytes);
+  PassTables tb(n, tiles_total, rows_total, 0, n);
+  if (tb.bytes > h->pf_bytes) {
+    set_error("gpt_prefill_many: tables of %zu bytes exceed the handle's %zu", tb.bytes, h->pf_bytes);
     return IXTTS_ERR_STATE;
   }
   uint8_t* hb = h->pf_host.data();
-  PackSeq* seqs = reinterpret_cast<PackSeq*>(hb);
-  int* plen = reinterpret_cast<int*>(hb + off_plen);
-  int* tiles = reinterpret_cast<int*>(hb + off_tiles);
-  int* row_at = reinterpret_cast<int*>(hb + off_at);
-  int* row_seq = reinterpret_cast<int*>(hb + off_seq);
+  int* plen = reinterpret_cast<int*>(hb + tb.off_ints);
   struct Range { int seq0, n_seq, tile0, n_tiles, row0, T; } pr[MAXB] = {};
-  {
-    int tile = 0, row = 0;
-    for (int i = 0; i < n; ++i) {
-      Range& r = pr[pass_of[i]];
-      if (r.n_seq == 0) { r.seq0 = i; r.tile0 = tile; r.row0 = row; }
-      const int T = n_rows[i] + 1 - n_left_pad[i], local = i - r.seq0;
-      seqs[i] = PackSeq{embeds_dev[i], slots[i], T, n_left_pad[i], r.T};
-      plen[i] = n_rows[i] + 1;
-      for (int q0 = 0; q0 < T; q0 += 128) { tiles[2 * tile] = local; tiles[2 * tile + 1] = q0; ++tile; ++r.n_tiles; }
-      for (int t = 0; t < T; ++t) { row_at[row] = slots[i] * h->H * smax + n_left_pad[i] + t; row_seq[row] = local; ++row; }
-      ++r.n_seq;
-      r.T += T;
-    }
+  for (int i = 0; i < n; ++i) {
+    Range& r = pr[pass_of[i]];
+    if (r.n_seq == 0) { r.seq0 = i; r.tile0 = tb.n_tiles; r.row0 = tb.rows; }
+    const int T = n_rows[i] + 1 - n_left_pad[i];
+    tb.add(hb, embeds_dev[i], slots[i], T, n_left_pad[i], i - r.seq0, r.T, h->H * smax);
+    plen[i] = n_rows[i] + 1;
+    ++r.n_seq;
+    r.n_tiles = tb.n_tiles - r.tile0;
+    r.T += T;
   }
   // host-side slot state, as ixtts_gpt_prefill leaves it
   for (int i = 0; i < n; ++i) {
@@ -937,18 +965,13 @@ extern "C" int ixtts_gpt_prefill_many(ixtts_gpt* h, int n, const int* slots, con
   }
   // (a pageable source: the runtime has taken its copy when this returns, which is what lets the next call rewrite pf_host -- the
   //  reliance ixtts_gpt_set_bans and ixtts_gpt_prefill's `&P` make; pf_dev is ordered by the caller's stream, see the header)
-  IX_HIP(hipMemcpyAsync(h->pf_dev, hb, bytes, hipMemcpyHostToDevice, st));
-  const PackSeq* d_seqs = reinterpret_cast<const PackSeq*>(h->pf_dev);
-  hipLaunchKernelGGL(prefill_reset_slots_kernel, dim3(n), dim3(256), 0, st, d_seqs, reinterpret_cast<const int*>(h->pf_dev + off_plen), h->seen, h->bans,
-                     h->gen_count, h->finished, h->forced, h->prompt_len, h->valid_from, V, h->cfg.start_mel_token);
+  IX_HIP(hipMemcpyAsync(h->pf_dev, hb, tb.bytes, hipMemcpyHostToDevice, st));
+  hipLaunchKernelGGL(prefill_reset_slots_kernel, dim3(n), dim3(256), 0, st, reinterpret_cast<const PackSeq*>(h->pf_dev),
+                     reinterpret_cast<const int*>(h->pf_dev + tb.off_ints), h->seen, h->bans, h->gen_count, h->finished, h->forced, h->prompt_len,
+                     h->valid_from, V, h->cfg.start_mel_token);
   for (int p = 0; p < n_pass; ++p) {
     const Range& r = pr[p];
-    PackedPass pk;
-    pk.seqs = d_seqs + r.seq0;
-    pk.tiles = reinterpret_cast<const int*>(h->pf_dev + off_tiles) + 2 * r.tile0;
-    pk.row_at = reinterpret_cast<const int*>(h->pf_dev + off_at) + r.row0;
-    pk.row_seq = reinterpret_cast<const int*>(h->pf_dev + off_seq) + r.row0;
-    pk.n_seq = r.n_seq; pk.n_tiles = r.n_tiles; pk.T = r.T;
+    const PackedPass pk = tb.pass(h->pf_dev, r.seq0, r.n_seq, r.tile0, r.n_tiles, r.row0, r.T);
     IX_TRY(pack_rows(h, pk, st));
     IX_TRY(forward_rows_packed(h, pk, st));
     IX_TRY(unpack_last_rows(h, pk, st));
@@ -1523,8 +1546,8 @@ extern "C" int ixtts_gpt_latent_many(ixtts_gpt* h, int n, const float* const* pr
   const int n_pass = ixtts_gpt_latent_plan(n_prefix, n_codes, n, row_cap, pass_of.data());
   if (n_pass < 0) return n_pass;
 
-  // tables of ONE pass: [n_seq] PackSeq | [n_seq] LatentSeq | [tiles][2] (all 8-byte aligned) | [T] row_at | [T] row_seq | [n_mel] mel_row
-  static_assert(sizeof(PackSeq) % 8 == 0 && sizeof(LatentSeq) % 8 == 0, "pointers and int2 pairs behind the records");
+  // tables of ONE pass (PassTables; the records: [n_seq] LatentSeq, the ints: [n_mel] mel_row)
+  static_assert(sizeof(LatentSeq) % 8 == 0, "pointers and int2 pairs behind the records");
   uint8_t* hb = h->lm_host.data();
   for (int i0 = 0; i0 < n;) {
     int i1 = i0, n_seq = 0, T = 0, n_tiles = 0, n_mel = 0;
@@ -1539,19 +1562,14 @@ extern "C" int ixtts_gpt_latent_many(ixtts_gpt* h, int n, const float* const* pr
       for (int i = i0; i < i1; ++i)
         if (n_codes[i] > 0) IX_TRY(ixtts_gpt_latent(h, prefix_dev[i], n_prefix[i], codes_dev[i], n_codes[i], latent_dev[i], stream));
     } else if (n_seq > 0) {
-      const size_t off_ls = (size_t)n_seq * sizeof(PackSeq), off_tiles = off_ls + (size_t)n_seq * sizeof(LatentSeq), off_at = off_tiles + (size_t)n_tiles * 8,
-                   off_seq = off_at + (size_t)T * 4, off_mel = off_seq + (size_t)T * 4, bytes = off_mel + (size_t)n_mel * 4;
-      if (bytes > h->lm_bytes || T > smax) {  // (the plan keeps a pass within max_seq positions, so neither can happen)
-        set_error("gpt_latent_many: a pass of %d rows, tables of %zu bytes, exceeds the handle's %d rows, %zu bytes", T, bytes, smax, h->lm_bytes);
+      PassTables tb(n_seq, n_tiles, T, (size_t)n_seq * sizeof(LatentSeq), n_mel);
+      if (tb.bytes > h->lm_bytes || T > smax) {  // (the plan keeps a pass within max_seq positions, so neither can happen)
+        set_error("gpt_latent_many: a pass of %d rows, tables of %zu bytes, exceeds the handle's %d rows, %zu bytes", T, tb.bytes, smax, h->lm_bytes);
         return IXTTS_ERR_STATE;
       }
-      PackSeq* seqs = reinterpret_cast<PackSeq*>(hb);
-      LatentSeq* ls = reinterpret_cast<LatentSeq*>(hb + off_ls);
-      int* tiles = reinterpret_cast<int*>(hb + off_tiles);
-      int* row_at = reinterpret_cast<int*>(hb + off_at);
-      int* row_seq = reinterpret_cast<int*>(hb + off_seq);
-      int* mel_row = reinterpret_cast<int*>(hb + off_mel);
-      int q = 0, row = 0, pos = 0, tile = 0, mel = 0;
+      LatentSeq* ls = reinterpret_cast<LatentSeq*>(hb + tb.off_rec);
+      int* mel_row = reinterpret_cast<int*>(hb + tb.off_ints);
+      int pos = 0, mel = 0;
       for (int i = i0; i < i1; ++i) {
         if (n_codes[i] == 0) continue;
         const int P = n_prefix[i], Ti = P + n_codes[i];
@@ -1561,31 +1579,20 @@ extern "C" int ixtts_gpt_latent_many(ixtts_gpt* h, int n, const float* const* pr
         }
         // cache positions [pos, pos + Ti), pos a multiple of 64: the key tiles of the flash attention lie on absolute multiples of 64, so
         // only there does the sequence get the tiles -- and the online-softmax order, and the bits -- of the solo pass at position 0
-        seqs[q] = PackSeq{nullptr, slot, Ti, pos, row};
+        const int q = tb.n_seq, row0 = tb.rows;
+        tb.add(hb, nullptr, slot, Ti, pos, q, row0, h->H * smax);
         ls[q] = LatentSeq{prefix_dev[i], codes_dev[i], latent_dev[i], P, n_codes[i]};
-        for (int q0 = 0; q0 < Ti; q0 += 128) { tiles[2 * tile] = q; tiles[2 * tile + 1] = q0; ++tile; }
-        for (int t = 0; t < Ti; ++t) {
-          row_at[row] = slot * h->H * smax + pos + t;
-          row_seq[row] = q;
-          if (t >= P) mel_row[mel++] = row;
-          ++row;
-        }
+        for (int t = P; t < Ti; ++t) mel_row[mel++] = row0 + t;
         pos += ceil_div(Ti, 64) * 64;
-        ++q;
       }
       // (a pageable source, rewritten for the next pass and the next call: the runtime has taken its copy when this returns -- the
       //  reliance of ixtts_gpt_prefill_many; lm_dev is ordered by the caller's stream, see the header)
-      IX_HIP(hipMemcpyAsync(h->lm_dev, hb, bytes, hipMemcpyHostToDevice, st));
-      PackedPass pk;
-      pk.seqs = reinterpret_cast<const PackSeq*>(h->lm_dev);
-      pk.tiles = reinterpret_cast<const int*>(h->lm_dev + off_tiles);
-      pk.row_at = reinterpret_cast<const int*>(h->lm_dev + off_at);
-      pk.row_seq = reinterpret_cast<const int*>(h->lm_dev + off_seq);
-      pk.n_seq = n_seq; pk.n_tiles = n_tiles; pk.T = T;
+      IX_HIP(hipMemcpyAsync(h->lm_dev, hb, tb.bytes, hipMemcpyHostToDevice, st));
+      PackedPass pk = tb.pass(h->lm_dev, 0, n_seq, 0, n_tiles, 0, T);
       pk.keys_rebased = true;
       LatentPass lp;
-      lp.lseqs = reinterpret_cast<const LatentSeq*>(h->lm_dev + off_ls);
-      lp.mel_row = reinterpret_cast<const int*>(h->lm_dev + off_mel);
+      lp.lseqs = reinterpret_cast<const LatentSeq*>(h->lm_dev + tb.off_rec);
+      lp.mel_row = reinterpret_cast<const int*>(h->lm_dev + tb.off_ints);
       lp.n_mel = n_mel;
       IX_TRY(pack_latent_rows(h, pk, lp, st));
       IX_TRY(forward_rows_packed(h, pk, st));

@@ -497,34 +497,20 @@ struct AttnRowsArgs {
   int T, D, smax, pos0, valid_from;
 };
 
+// (the statements are attn_rows_body.h, shared as text with the two packed row kernels below)
 template <typename KVT, typename OT = float>
 __global__ __launch_bounds__(256) void attn_rows_kernel(AttnRowsArgs a) {
-  constexpr int NW = 4;
-  using LY = KVLayout<KVT>;
-  __shared__ float sm[NW][LY::LPP][2 + LY::DPL];
-  const int hh = blockIdx.x, row = blockIdx.y;
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  const int dp = lane % LY::LPP;
-  float qv[LY::DPL];
-  load_q_slice<KVT>(a.q + (size_t)row * a.D + hh * HD, dp, qv);
-  const KVT* kb = reinterpret_cast<const KVT*>(a.kcache) + (size_t)hh * a.smax * HD + dp * LY::DPL;
-  const KVT* vb = reinterpret_cast<const KVT*>(a.vcache) + (size_t)hh * a.smax * HD + dp * LY::DPL;
-  SoftAcc<LY::DPL> st;
-  st.init();
-  const int lo0 = a.valid_from, hi0 = a.pos0 + row + 1;
-  attn_sweep<KVT, NW, 8>(st, kb, vb, qv, a.smax, wave, lane, [&](int& lo, int& hi) {
-    lo = lo0;
-    hi = hi0;
-  });
-  const float o = attn_merge<KVT, NW>(st, sm, wave, lane);
-  if (threadIdx.x < 64) store_kv(reinterpret_cast<OT*>(a.out) + (size_t)row * a.D + hh * HD + threadIdx.x, o);
+#define ROWS_ROW ((int)blockIdx.y)
+#define ROWS_K0 0
+#include "attn_rows_body.h"
+#undef ROWS_ROW
+#undef ROWS_K0
 }
 
 // The packed pass of ixtts_gpt_prefill_many: several sequences' rows one after the other in q / out, each sequence with its own
 // slot cache, T, pos0 and valid_from.  A workgroup of the attention kernels below serves ONE sequence: it builds that sequence's
-// AttnRowsArgs from the table and runs on it the one-sequence kernel's statements, kept as a copy of their own (attn_rows_seq,
-// attn_rows_flash_seq: the one-sequence kernels stay the code they were, to the instruction): query partition, key-tile origin, wave
-// skips, masks and clamps are those of the solo launch.
+// AttnRowsArgs from the table and runs on it the one-sequence kernel's statements (attn_rows_body.h, attn_rows_flash_body.h): query
+// partition, key-tile origin, wave skips, masks and clamps are those of the solo launch.
 struct AttnPackedArgs {
   const float* q;         // [sum T][D]
   const void* kcache;     // LAYER base [slot][H][smax][64]
@@ -548,64 +534,31 @@ __device__ __forceinline__ AttnRowsArgs packed_seq_args(const AttnPackedArgs& p,
   return a;
 }
 
-// attn_rows_kernel for one sequence of a packed pass: the same statements, `row` in place of blockIdx.y
-template <typename KVT, typename OT>
-__device__ __forceinline__ void attn_rows_seq(const AttnRowsArgs& a, const int row) {
-  constexpr int NW = 4;
-  using LY = KVLayout<KVT>;
-  __shared__ float sm[NW][LY::LPP][2 + LY::DPL];
-  const int hh = blockIdx.x;
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  const int dp = lane % LY::LPP;
-  float qv[LY::DPL];
-  load_q_slice<KVT>(a.q + (size_t)row * a.D + hh * HD, dp, qv);
-  const KVT* kb = reinterpret_cast<const KVT*>(a.kcache) + (size_t)hh * a.smax * HD + dp * LY::DPL;
-  const KVT* vb = reinterpret_cast<const KVT*>(a.vcache) + (size_t)hh * a.smax * HD + dp * LY::DPL;
-  SoftAcc<LY::DPL> st;
-  st.init();
-  const int lo0 = a.valid_from, hi0 = a.pos0 + row + 1;
-  attn_sweep<KVT, NW, 8>(st, kb, vb, qv, a.smax, wave, lane, [&](int& lo, int& hi) {
-    lo = lo0;
-    hi = hi0;
-  });
-  const float o = attn_merge<KVT, NW>(st, sm, wave, lane);
-  if (threadIdx.x < 64) store_kv(reinterpret_cast<OT*>(a.out) + (size_t)row * a.D + hh * HD + threadIdx.x, o);
-}
 template <typename KVT, typename OT>
 __global__ __launch_bounds__(256) void attn_rows_packed_kernel(AttnPackedArgs p) {  // grid (H, sum T)
   const int seq = p.row_seq[blockIdx.y];
-  attn_rows_seq<KVT, OT>(packed_seq_args<KVT, OT>(p, seq), (int)blockIdx.y - p.seqs[seq].row0);
+  const AttnRowsArgs a = packed_seq_args<KVT, OT>(p, seq);
+#define ROWS_ROW ((int)blockIdx.y - p.seqs[seq].row0)
+#define ROWS_K0 0
+#include "attn_rows_body.h"
+#undef ROWS_ROW
+#undef ROWS_K0
 }
 
 // A sequence of a latent pass (ixtts_gpt_latent_many) sits in the scratch slot at cache positions pos0 .., pos0 a multiple of 64 and
 // not of attn_sweep's stride (NW * PPW * IT keys: 128 for fp32, 256 for 16-bit caches).  attn_sweep groups the keys of one softmax
-// update by ABSOLUTE position, so attn_rows_seq at such a pos0 would update in other groups than the solo pass at position 0 does and
-// round differently.  This kernel hands the sweep the sequence's own keys as positions 0 .. (cache pointers advanced by pos0 rows, the
-// clamp shortened by as much): the groups, masks and speculative first pass of the solo launch, whatever pos0 is.
+// update by ABSOLUTE position, so at such a pos0 the kernel above would update in other groups than the solo pass at position 0 does
+// and round differently.  This kernel hands the sweep the sequence's own keys as positions 0 .. (key offset pos0 = valid_from): the
+// groups, masks and speculative first pass of the solo launch, whatever pos0 is.
 template <typename KVT, typename OT>
 __global__ __launch_bounds__(256) void attn_rows_packed_rebased_kernel(AttnPackedArgs p) {  // grid (H, sum T)
-  constexpr int NW = 4;
-  using LY = KVLayout<KVT>;
-  __shared__ float sm[NW][LY::LPP][2 + LY::DPL];
   const int seq = p.row_seq[blockIdx.y];
   const AttnRowsArgs a = packed_seq_args<KVT, OT>(p, seq);
-  const int row = (int)blockIdx.y - p.seqs[seq].row0;
-  const int hh = blockIdx.x;
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  const int dp = lane % LY::LPP;
-  float qv[LY::DPL];
-  load_q_slice<KVT>(a.q + (size_t)row * a.D + hh * HD, dp, qv);
-  const KVT* kb = reinterpret_cast<const KVT*>(a.kcache) + ((size_t)hh * a.smax + a.pos0) * HD + dp * LY::DPL;
-  const KVT* vb = reinterpret_cast<const KVT*>(a.vcache) + ((size_t)hh * a.smax + a.pos0) * HD + dp * LY::DPL;
-  SoftAcc<LY::DPL> st;
-  st.init();
-  const int hi0 = row + 1;
-  attn_sweep<KVT, NW, 8>(st, kb, vb, qv, a.smax - a.pos0, wave, lane, [&](int& lo, int& hi) {
-    lo = 0;
-    hi = hi0;
-  });
-  const float o = attn_merge<KVT, NW>(st, sm, wave, lane);
-  if (threadIdx.x < 64) store_kv(reinterpret_cast<OT*>(a.out) + (size_t)row * a.D + hh * HD + threadIdx.x, o);
+#define ROWS_ROW ((int)blockIdx.y - p.seqs[seq].row0)
+#define ROWS_K0 a.pos0
+#include "attn_rows_body.h"
+#undef ROWS_ROW
+#undef ROWS_K0
 }
 
 // ---- the same attention as a causal flash kernel on the fp32 matrix cores (the latent pass: 1237 rows x 20 heads; the
@@ -646,300 +599,20 @@ __device__ __forceinline__ void load_row16<bf16>(const bf16* p, float (&v)[16]) 
   }
 }
 
+// (the statements are attn_rows_flash_body.h, shared as text with attn_rows_flash_seq below)
 template <typename KVT, typename OT>
 __global__ __launch_bounds__(256) void attn_rows_flash_kernel(AttnRowsArgs a) {
-  __shared__ __attribute__((aligned(16))) float Ks[FR_KT * FR_KP];
-  __shared__ __attribute__((aligned(16))) float Vs[FR_KT * HD];
-  const int hh = blockIdx.x;
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  const int l31 = lane & 31, lh = lane >> 5;
-  const int qw0 = blockIdx.y * 128 + wave * 32;  // first row of this wave
-  const KVT* kb = reinterpret_cast<const KVT*>(a.kcache) + (size_t)hh * a.smax * HD;
-  const KVT* vb = reinterpret_cast<const KVT*>(a.vcache) + (size_t)hh * a.smax * HD;
-  const int last_key = a.pos0 + a.T - 1;  // last cache row this pass has written
-
-  float qr[HD / 2];  // Q[row l31][d = 8m + 4 lh + i] for k-step 4m + i, scaled by log2(e) / sqrt(64)
-  {
-    const int qi = min(qw0 + l31, a.T - 1);
-    const float* qp = a.q + (size_t)qi * a.D + hh * HD + 4 * lh;
-    const float qs = 0.125f * 1.4426950408889634f;
-#pragma unroll
-    for (int m = 0; m < HD / 8; ++m) {
-      const float4 t = *reinterpret_cast<const float4*>(qp + 8 * m);
-      qr[4 * m] = t.x * qs; qr[4 * m + 1] = t.y * qs; qr[4 * m + 2] = t.z * qs; qr[4 * m + 3] = t.w * qs;
-    }
-  }
-  f32x16 ot[2];
-#pragma unroll
-  for (int j = 0; j < 2; ++j)
-#pragma unroll
-    for (int r = 0; r < 16; ++r) ot[j][r] = 0.f;
-  float m_run = -INFINITY, l_run = 0.f;
-  const int lim = a.pos0 + qw0 + l31;             // last key this lane's row may see
-  const int wave_lim = a.pos0 + min(qw0 + 31, a.T - 1);  // ... and any row of this wave
-  const int wg_lim = a.pos0 + min((int)blockIdx.y * 128 + 127, a.T - 1);
-  const int t_first = (a.valid_from / FR_KT) * FR_KT;
-
-  for (int t0 = t_first; t0 <= wg_lim; t0 += FR_KT) {
-    __syncthreads();
-    {  // stage 64 keys x 64 dims of K and V, widened to fp32: each thread one quarter row of each
-      const int key = threadIdx.x >> 2, c16 = (threadIdx.x & 3) * 16;
-      // rows past the pass repeat its last one, rows before valid_from (left padding: never written, the cache holds whatever the
-      // allocation held -- 0 x NaN in the P V product would poison the row) repeat the first valid one; both are masked below
-      const int t = min(max(t0 + key, a.valid_from), last_key);
-      float kv[16], vv[16];
-      load_row16<KVT>(kb + (size_t)t * HD + c16, kv);
-      load_row16<KVT>(vb + (size_t)t * HD + c16, vv);
-#pragma unroll
-      for (int i = 0; i < 4; ++i) {
-        *reinterpret_cast<float4*>(Ks + key * FR_KP + c16 + 4 * i) = make_float4(kv[4 * i], kv[4 * i + 1], kv[4 * i + 2], kv[4 * i + 3]);
-        *reinterpret_cast<float4*>(Vs + key * HD + c16 + 4 * i) = make_float4(vv[4 * i], vv[4 * i + 1], vv[4 * i + 2], vv[4 * i + 3]);
-      }
-    }
-    __syncthreads();
-    if (t0 > wave_lim) continue;  // wave-uniform: nothing in this tile is visible to this wave's rows
-
-    f32x16 st[2];
-#pragma unroll
-    for (int j = 0; j < 2; ++j)
-#pragma unroll
-      for (int r = 0; r < 16; ++r) st[j][r] = 0.f;
-    const float* kp0 = Ks + l31 * FR_KP + 4 * lh;
-    const float* kp1 = kp0 + 32 * FR_KP;
-    float4 ka[2][2];
-    ka[0][0] = *reinterpret_cast<const float4*>(kp0);
-    ka[0][1] = *reinterpret_cast<const float4*>(kp1);
-#pragma unroll
-    for (int m = 0; m < HD / 8; ++m) {
-      if (m + 1 < HD / 8) {
-        ka[(m + 1) & 1][0] = *reinterpret_cast<const float4*>(kp0 + 8 * (m + 1));
-        ka[(m + 1) & 1][1] = *reinterpret_cast<const float4*>(kp1 + 8 * (m + 1));
-      }
-#pragma unroll
-      for (int j = 0; j < 2; ++j) {
-        const float4 kk4 = ka[m & 1][j];
-        st[j] = __builtin_amdgcn_mfma_f32_32x32x2f32(kk4.x, qr[4 * m], st[j], 0, 0, 0);
-        st[j] = __builtin_amdgcn_mfma_f32_32x32x2f32(kk4.y, qr[4 * m + 1], st[j], 0, 0, 0);
-        st[j] = __builtin_amdgcn_mfma_f32_32x32x2f32(kk4.z, qr[4 * m + 2], st[j], 0, 0, 0);
-        st[j] = __builtin_amdgcn_mfma_f32_32x32x2f32(kk4.w, qr[4 * m + 3], st[j], 0, 0, 0);
-      }
-    }
-    // causal / left-padding mask (only the first and the diagonal tiles have masked keys)
-    if (t0 < a.valid_from || t0 + FR_KT - 1 > a.pos0 + qw0) {
-#pragma unroll
-      for (int j = 0; j < 2; ++j)
-#pragma unroll
-        for (int r = 0; r < 16; ++r) {
-          const int key = t0 + j * 32 + (r & 3) + 8 * (r >> 2) + 4 * lh;
-          if (key < a.valid_from || key > lim) st[j][r] = -INFINITY;
-        }
-    }
-    float tmax = -INFINITY;
-#pragma unroll
-    for (int j = 0; j < 2; ++j)
-#pragma unroll
-      for (int r = 0; r < 16; ++r) tmax = fmaxf(tmax, st[j][r]);
-    tmax = fmaxf(tmax, __shfl_xor(tmax, 32, 64));
-    // (a tile may be all -inf for a lane -- behind its limit: alpha = 1, weights 0.  A left-padding row, t < valid_from,
-    // sees no key at all: its maximum stays -inf and is replaced by 0 in the exponents, so it ends as a row of zeros,
-    // finite like everything else that reaches the cache)
-    const float mn = fmaxf(m_run, tmax);
-    const float mref = (mn == -INFINITY) ? 0.f : mn;
-    const float alpha = __builtin_amdgcn_exp2f(m_run - mref);
-    float psum = 0.f;
-#pragma unroll
-    for (int j = 0; j < 2; ++j)
-#pragma unroll
-      for (int r = 0; r < 16; ++r) {
-        const float pw = __builtin_amdgcn_exp2f(st[j][r] - mref);
-        st[j][r] = pw;
-        psum += pw;
-      }
-    psum += __shfl_xor(psum, 32, 64);
-    l_run = l_run * alpha + psum;
-    m_run = mn;
-    if (alpha != 1.0f) {
-#pragma unroll
-      for (int j = 0; j < 2; ++j)
-#pragma unroll
-        for (int r = 0; r < 16; ++r) ot[j][r] *= alpha;
-    }
-    const float* vp = Vs + (4 * lh) * HD + l31;
-    float va[2][2];
-    va[0][0] = vp[0];
-    va[0][1] = vp[32];
-#pragma unroll
-    for (int s2 = 0; s2 < 32; ++s2) {
-      const int j = s2 >> 4, r = s2 & 15;
-      if (s2 + 1 < 32) {
-        const int j1 = (s2 + 1) >> 4, r1 = (s2 + 1) & 15;
-        const float* vrow = vp + (j1 * 32 + (r1 & 3) + 8 * (r1 >> 2)) * HD;
-        va[(s2 + 1) & 1][0] = vrow[0];
-        va[(s2 + 1) & 1][1] = vrow[32];
-      }
-      const float pv = st[j][r];
-      ot[0] = __builtin_amdgcn_mfma_f32_32x32x2f32(va[s2 & 1][0], pv, ot[0], 0, 0, 0);
-      ot[1] = __builtin_amdgcn_mfma_f32_32x32x2f32(va[s2 & 1][1], pv, ot[1], 0, 0, 0);
-    }
-  }
-  const int qi = qw0 + l31;
-  if (qi < a.T) {
-    const float inv = l_run > 0.f ? 1.0f / l_run : 0.f;
-    OT* op = reinterpret_cast<OT*>(a.out) + (size_t)qi * a.D + hh * HD;
-#pragma unroll
-    for (int j = 0; j < 2; ++j)
-#pragma unroll
-      for (int r = 0; r < 16; ++r) store_kv(op + j * 32 + (r & 3) + 8 * (r >> 2) + 4 * lh, ot[j][r] * inv);
-  }
+#define FLASH_Q0 ((int)blockIdx.y * 128)
+#include "attn_rows_flash_body.h"
+#undef FLASH_Q0
 }
 
-// attn_rows_flash_kernel for one sequence of a packed pass: the same statements, with q0 (the first row of the workgroup's 128-row
-// tile within the sequence) in place of blockIdx.y * 128.  A change to one of the two belongs in the other.
+// the same for one sequence of a packed pass: q0 is the first row of the workgroup's 128-row tile within the sequence
 template <typename KVT, typename OT>
 __device__ __forceinline__ void attn_rows_flash_seq(const AttnRowsArgs& a, const int q0) {
-  __shared__ __attribute__((aligned(16))) float Ks[FR_KT * FR_KP];
-  __shared__ __attribute__((aligned(16))) float Vs[FR_KT * HD];
-  const int hh = blockIdx.x;
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  const int l31 = lane & 31, lh = lane >> 5;
-  const int qw0 = q0 + wave * 32;  // first row of this wave
-  const KVT* kb = reinterpret_cast<const KVT*>(a.kcache) + (size_t)hh * a.smax * HD;
-  const KVT* vb = reinterpret_cast<const KVT*>(a.vcache) + (size_t)hh * a.smax * HD;
-  const int last_key = a.pos0 + a.T - 1;  // last cache row this pass has written
-
-  float qr[HD / 2];  // Q[row l31][d = 8m + 4 lh + i] for k-step 4m + i, scaled by log2(e) / sqrt(64)
-  {
-    const int qi = min(qw0 + l31, a.T - 1);
-    const float* qp = a.q + (size_t)qi * a.D + hh * HD + 4 * lh;
-    const float qs = 0.125f * 1.4426950408889634f;
-#pragma unroll
-    for (int m = 0; m < HD / 8; ++m) {
-      const float4 t = *reinterpret_cast<const float4*>(qp + 8 * m);
-      qr[4 * m] = t.x * qs; qr[4 * m + 1] = t.y * qs; qr[4 * m + 2] = t.z * qs; qr[4 * m + 3] = t.w * qs;
-    }
-  }
-  f32x16 ot[2];
-#pragma unroll
-  for (int j = 0; j < 2; ++j)
-#pragma unroll
-    for (int r = 0; r < 16; ++r) ot[j][r] = 0.f;
-  float m_run = -INFINITY, l_run = 0.f;
-  const int lim = a.pos0 + qw0 + l31;             // last key this lane's row may see
-  const int wave_lim = a.pos0 + min(qw0 + 31, a.T - 1);  // ... and any row of this wave
-  const int wg_lim = a.pos0 + min(q0 + 127, a.T - 1);
-  const int t_first = (a.valid_from / FR_KT) * FR_KT;
-
-  for (int t0 = t_first; t0 <= wg_lim; t0 += FR_KT) {
-    __syncthreads();
-    {  // stage 64 keys x 64 dims of K and V, widened to fp32: each thread one quarter row of each
-      const int key = threadIdx.x >> 2, c16 = (threadIdx.x & 3) * 16;
-      // rows past the pass repeat its last one, rows before valid_from (left padding: never written, the cache holds whatever the
-      // allocation held -- 0 x NaN in the P V product would poison the row) repeat the first valid one; both are masked below
-      const int t = min(max(t0 + key, a.valid_from), last_key);
-      float kv[16], vv[16];
-      load_row16<KVT>(kb + (size_t)t * HD + c16, kv);
-      load_row16<KVT>(vb + (size_t)t * HD + c16, vv);
-#pragma unroll
-      for (int i = 0; i < 4; ++i) {
-        *reinterpret_cast<float4*>(Ks + key * FR_KP + c16 + 4 * i) = make_float4(kv[4 * i], kv[4 * i + 1], kv[4 * i + 2], kv[4 * i + 3]);
-        *reinterpret_cast<float4*>(Vs + key * HD + c16 + 4 * i) = make_float4(vv[4 * i], vv[4 * i + 1], vv[4 * i + 2], vv[4 * i + 3]);
-      }
-    }
-    __syncthreads();
-    if (t0 > wave_lim) continue;  // wave-uniform: nothing in this tile is visible to this wave's rows
-
-    f32x16 st[2];
-#pragma unroll
-    for (int j = 0; j < 2; ++j)
-#pragma unroll
-      for (int r = 0; r < 16; ++r) st[j][r] = 0.f;
-    const float* kp0 = Ks + l31 * FR_KP + 4 * lh;
-    const float* kp1 = kp0 + 32 * FR_KP;
-    float4 ka[2][2];
-    ka[0][0] = *reinterpret_cast<const float4*>(kp0);
-    ka[0][1] = *reinterpret_cast<const float4*>(kp1);
-#pragma unroll
-    for (int m = 0; m < HD / 8; ++m) {
-      if (m + 1 < HD / 8) {
-        ka[(m + 1) & 1][0] = *reinterpret_cast<const float4*>(kp0 + 8 * (m + 1));
-        ka[(m + 1) & 1][1] = *reinterpret_cast<const float4*>(kp1 + 8 * (m + 1));
-      }
-#pragma unroll
-      for (int j = 0; j < 2; ++j) {
-        const float4 kk4 = ka[m & 1][j];
-        st[j] = __builtin_amdgcn_mfma_f32_32x32x2f32(kk4.x, qr[4 * m], st[j], 0, 0, 0);
-        st[j] = __builtin_amdgcn_mfma_f32_32x32x2f32(kk4.y, qr[4 * m + 1], st[j], 0, 0, 0);
-        st[j] = __builtin_amdgcn_mfma_f32_32x32x2f32(kk4.z, qr[4 * m + 2], st[j], 0, 0, 0);
-        st[j] = __builtin_amdgcn_mfma_f32_32x32x2f32(kk4.w, qr[4 * m + 3], st[j], 0, 0, 0);
-      }
-    }
-    // causal / left-padding mask (only the first and the diagonal tiles have masked keys)
-    if (t0 < a.valid_from || t0 + FR_KT - 1 > a.pos0 + qw0) {
-#pragma unroll
-      for (int j = 0; j < 2; ++j)
-#pragma unroll
-        for (int r = 0; r < 16; ++r) {
-          const int key = t0 + j * 32 + (r & 3) + 8 * (r >> 2) + 4 * lh;
-          if (key < a.valid_from || key > lim) st[j][r] = -INFINITY;
-        }
-    }
-    float tmax = -INFINITY;
-#pragma unroll
-    for (int j = 0; j < 2; ++j)
-#pragma unroll
-      for (int r = 0; r < 16; ++r) tmax = fmaxf(tmax, st[j][r]);
-    tmax = fmaxf(tmax, __shfl_xor(tmax, 32, 64));
-    // (a tile may be all -inf for a lane -- behind its limit: alpha = 1, weights 0.  A left-padding row, t < valid_from,
-    // sees no key at all: its maximum stays -inf and is replaced by 0 in the exponents, so it ends as a row of zeros,
-    // finite like everything else that reaches the cache)
-    const float mn = fmaxf(m_run, tmax);
-    const float mref = (mn == -INFINITY) ? 0.f : mn;
-    const float alpha = __builtin_amdgcn_exp2f(m_run - mref);
-    float psum = 0.f;
-#pragma unroll
-    for (int j = 0; j < 2; ++j)
-#pragma unroll
-      for (int r = 0; r < 16; ++r) {
-        const float pw = __builtin_amdgcn_exp2f(st[j][r] - mref);
-        st[j][r] = pw;
-        psum += pw;
-      }
-    psum += __shfl_xor(psum, 32, 64);
-    l_run = l_run * alpha + psum;
-    m_run = mn;
-    if (alpha != 1.0f) {
-#pragma unroll
-      for (int j = 0; j < 2; ++j)
-#pragma unroll
-        for (int r = 0; r < 16; ++r) ot[j][r] *= alpha;
-    }
-    const float* vp = Vs + (4 * lh) * HD + l31;
-    float va[2][2];
-    va[0][0] = vp[0];
-    va[0][1] = vp[32];
-#pragma unroll
-    for (int s2 = 0; s2 < 32; ++s2) {
-      const int j = s2 >> 4, r = s2 & 15;
-      if (s2 + 1 < 32) {
-        const int j1 = (s2 + 1) >> 4, r1 = (s2 + 1) & 15;
-        const float* vrow = vp + (j1 * 32 + (r1 & 3) + 8 * (r1 >> 2)) * HD;
-        va[(s2 + 1) & 1][0] = vrow[0];
-        va[(s2 + 1) & 1][1] = vrow[32];
-      }
-      const float pv = st[j][r];
-      ot[0] = __builtin_amdgcn_mfma_f32_32x32x2f32(va[s2 & 1][0], pv, ot[0], 0, 0, 0);
-      ot[1] = __builtin_amdgcn_mfma_f32_32x32x2f32(va[s2 & 1][1], pv, ot[1], 0, 0, 0);
-    }
-  }
-  const int qi = qw0 + l31;
-  if (qi < a.T) {
-    const float inv = l_run > 0.f ? 1.0f / l_run : 0.f;
-    OT* op = reinterpret_cast<OT*>(a.out) + (size_t)qi * a.D + hh * HD;
-#pragma unroll
-    for (int j = 0; j < 2; ++j)
-#pragma unroll
-      for (int r = 0; r < 16; ++r) store_kv(op + j * 32 + (r & 3) + 8 * (r >> 2) + 4 * lh, ot[j][r] * inv);
-  }
+#define FLASH_Q0 q0
+#include "attn_rows_flash_body.h"
+#undef FLASH_Q0
 }
 template <typename KVT, typename OT>
 __global__ __launch_bounds__(256) void attn_rows_flash_packed_kernel(AttnPackedArgs p) {  // grid (H, tiles of the pass)
@@ -947,17 +620,21 @@ __global__ __launch_bounds__(256) void attn_rows_flash_packed_kernel(AttnPackedA
   attn_rows_flash_seq<KVT, OT>(packed_seq_args<KVT, OT>(p, t.x), t.y);
 }
 
+static bool rows_attn_legacy() {  // IXTTS_ROWS_ATTN=legacy: the row-at-a-time kernels in place of the flash ones (A/B switch)
+  static const bool legacy = getenv("IXTTS_ROWS_ATTN") && !strcmp(getenv("IXTTS_ROWS_ATTN"), "legacy");
+  return legacy;
+}
+
 template <typename KVT, typename OT>
 static void launch_attn_rows(ixtts_gpt* h, const AttnRowsArgs& a, hipStream_t st) {
-  static const bool legacy = getenv("IXTTS_ROWS_ATTN") && !strcmp(getenv("IXTTS_ROWS_ATTN"), "legacy");  // A/B switch
-  if (legacy) hipLaunchKernelGGL((attn_rows_kernel<KVT, OT>), dim3(h->H, a.T), dim3(256), 0, st, a);
+  if (rows_attn_legacy()) hipLaunchKernelGGL((attn_rows_kernel<KVT, OT>), dim3(h->H, a.T), dim3(256), 0, st, a);
   else hipLaunchKernelGGL((attn_rows_flash_kernel<KVT, OT>), dim3(h->H, ceil_div(a.T, 128)), dim3(256), 0, st, a);
 }
 
 // the packed pass's attention: one workgroup per (head, 128-row tile of ONE sequence) / per (head, packed row)
 template <typename KVT, typename OT>
 static void launch_attn_packed(ixtts_gpt* h, const PackedPass& pk, const void* kc_layer, const void* vc_layer, void* out, hipStream_t st) {
-  static const bool legacy = getenv("IXTTS_ROWS_ATTN") && !strcmp(getenv("IXTTS_ROWS_ATTN"), "legacy");
+  const bool legacy = rows_attn_legacy();
   AttnPackedArgs p;
   p.q = h->rq; p.kcache = kc_layer; p.vcache = vc_layer; p.out = out; p.seqs = pk.seqs; p.tiles = reinterpret_cast<const int2*>(pk.tiles);
   p.row_seq = pk.row_seq; p.D = h->D; p.smax = h->smax; p.H = h->H;
@@ -966,129 +643,104 @@ static void launch_attn_packed(ixtts_gpt* h, const PackedPass& pk, const void* k
   else hipLaunchKernelGGL((attn_rows_flash_packed_kernel<KVT, OT>), dim3(h->H, pk.n_tiles), dim3(256), 0, st, p);
 }
 
-template <typename WT, typename KVT, int EPI, typename GA = GemmArgs>
-static void launch_gemm(const GA& g, hipStream_t st) {
-  // 128-row tiles once there are enough rows to fill the GPU with them (latent pass), 64-row tiles for prompts
-  if (g.T >= 512) {
-    hipLaunchKernelGGL((gemm_rows_kernel<WT, EPI, KVT, 128, GA>), dim3(ceil_div(g.N, GBN), ceil_div(g.T, 128)), dim3(256), 0, st, g);
-  } else {
-    hipLaunchKernelGGL((gemm_rows_kernel<WT, EPI, KVT, 64, GA>), dim3(ceil_div(g.N, GBN), ceil_div(g.T, 64)), dim3(256), 0, st, g);
+// What the layer loop needs to know of a weight type: the GEMM's argument structs, the element type of the rows its producers
+// (LayerNorm, attention, gelu) write into the workspaces, and the GEMM launch.
+// bf16 / fp16 weights: rows of the weights' type (fp16 rows saturate at +-65504, store_kv), the LDS-DMA kernel on 128 x 128 tiles
+template <typename WT, typename KVT>
+struct RowsPath {
+  typedef GemmArgs16 Args;
+  typedef GemmArgs16Packed ArgsPacked;
+  typedef KVT Act;
+  template <int EPI, typename GA>
+  static int gemm(const GA& g, hipStream_t st) {
+    static const hipError_t attr = hipFuncSetAttribute((const void*)gemm_rows_bf16_kernel<EPI, KVT, GA>, hipFuncAttributeMaxDynamicSharedMemorySize, G16_SMEM);
+    IX_HIP(attr);  // (once per kernel: the function is a template)
+    hipLaunchKernelGGL((gemm_rows_bf16_kernel<EPI, KVT, GA>), dim3(ceil_div(g.N, 128), ceil_div(g.T, 128)), dim3(256), G16_SMEM, st, g);
+    return IXTTS_OK;
   }
-}
+};
+// fp32 weights: fp32 rows; 128-row tiles once there are enough rows to fill the GPU with them (latent pass), 64-row tiles for prompts
+template <typename KVT>
+struct RowsPath<float, KVT> {
+  typedef GemmArgs Args;
+  typedef GemmArgsPacked ArgsPacked;
+  typedef float Act;
+  template <int EPI, typename GA>
+  static int gemm(const GA& g, hipStream_t st) {
+    if (g.T >= 512) {
+      hipLaunchKernelGGL((gemm_rows_kernel<float, EPI, KVT, 128, GA>), dim3(ceil_div(g.N, GBN), ceil_div(g.T, 128)), dim3(256), 0, st, g);
+    } else {
+      hipLaunchKernelGGL((gemm_rows_kernel<float, EPI, KVT, 64, GA>), dim3(ceil_div(g.N, GBN), ceil_div(g.T, 64)), dim3(256), 0, st, g);
+    }
+    return IXTTS_OK;
+  }
+};
 
-// pk == nullptr: T rows of the sequence in `slot`.  pk: the packed rows of *pk (T = pk->T; slot, pos0, valid_from unused): the QKV
-// GEMM and the attention take their packed forms, every other launch is the one-sequence launch at more rows.
+// pk == nullptr: T rows of the sequence in `slot`.  pk: the packed rows of *pk (T = pk->T, slot 0 -- kc / vc are then the layer's
+// bases, which is what the packed launches take -- pos0 and valid_from unused): the QKV GEMM and the attention take their packed
+// forms, every other launch is the one-sequence launch at more rows.
 template <typename WT, typename KVT, int D>
-static int forward_rows_t(ixtts_gpt* h, int slot, int T, int pos0, int valid_from, hipStream_t st, const PackedPass* pk = nullptr) {
+static int forward_rows_impl(ixtts_gpt* h, int slot, int T, int pos0, int valid_from, hipStream_t st, const PackedPass* pk) {
+  using P = RowsPath<WT, KVT>;
+  using Act = typename P::Act;
   const size_t lstride = (size_t)h->slots * D * h->smax * sizeof(KVT);
   const size_t sstride = (size_t)D * h->smax * sizeof(KVT);
+  Act* xn = reinterpret_cast<Act*>(h->rxn);
+  Act* att = reinterpret_cast<Act*>(h->ratt);
+  Act* ff = reinterpret_cast<Act*>(h->rff);
+  typename P::Args g;
+  g.T = T; g.pos0 = pos0; g.smax = h->smax; g.D = D;
+  auto operands = [&](const void* A, size_t w, size_t bias, void* out, int N, int K) {
+    g.A = static_cast<decltype(g.A)>(A); g.wt = static_cast<decltype(g.wt)>(A_PTR(w)); g.bias = A_F32(bias);
+    g.out = static_cast<decltype(g.out)>(out); g.N = N; g.K = K;
+  };
   for (int l = 0; l < h->L; ++l) {
     const LayerOff& o = h->lo[l];
     uint8_t* kc = (uint8_t*)h->kc + l * lstride + slot * sstride;
     uint8_t* vc = (uint8_t*)h->vc + l * lstride + slot * sstride;
-    hipLaunchKernelGGL(ln_rows_kernel<D>, dim3(ceil_div(T, 4)), dim3(256), 0, st, h->rx, h->rxn, T);
-    GemmArgs g;
-    g.A = h->rxn; g.wt = A_PTR(o.wqkv); g.bias = A_F32(o.bqkv); g.out = h->rq; g.kcache = kc; g.vcache = vc;
-    g.T = T; g.N = 3 * D; g.K = D; g.pos0 = pos0; g.smax = h->smax; g.D = D;
+    hipLaunchKernelGGL((ln_rows_kernel<D, Act>), dim3(ceil_div(T, 4)), dim3(256), 0, st, h->rx, xn, T);
+    operands(xn, o.wqkv, o.bqkv, h->rq, 3 * D, D);
+    g.kcache = kc; g.vcache = vc;
     if (pk) {
-      GemmArgsPacked gp;
-      static_cast<GemmArgs&>(gp) = g;
+      typename P::ArgsPacked gp;
+      static_cast<typename P::Args&>(gp) = g;
       gp.row_at = pk->row_at;
-      launch_gemm<WT, KVT, RE_QKV_PACKED>(gp, st);
-      launch_attn_packed<KVT, float>(h, *pk, kc, vc, h->ratt, st);
+      IX_TRY((P::template gemm<RE_QKV_PACKED>(gp, st)));
+      launch_attn_packed<KVT, Act>(h, *pk, kc, vc, att, st);
     } else {
-      launch_gemm<WT, KVT, RE_QKV>(g, st);
+      IX_TRY((P::template gemm<RE_QKV>(g, st)));
       AttnRowsArgs a;
-      a.q = h->rq; a.kcache = kc; a.vcache = vc; a.out = h->ratt; a.T = T; a.D = D; a.smax = h->smax; a.pos0 = pos0; a.valid_from = valid_from;
-      launch_attn_rows<KVT, float>(h, a, st);
+      a.q = h->rq; a.kcache = kc; a.vcache = vc; a.out = att; a.T = T; a.D = D; a.smax = h->smax; a.pos0 = pos0; a.valid_from = valid_from;
+      launch_attn_rows<KVT, Act>(h, a, st);
     }
-    g.A = h->ratt; g.wt = A_PTR(o.wo); g.bias = A_F32(o.bo); g.out = h->rx; g.N = D; g.K = D;
-    launch_gemm<WT, KVT, RE_RESID>(g, st);
-    hipLaunchKernelGGL(ln_rows_kernel<D>, dim3(ceil_div(T, 4)), dim3(256), 0, st, h->rx, h->rxn, T);
-    g.A = h->rxn; g.wt = A_PTR(o.wfc); g.bias = A_F32(o.bfc); g.out = h->rff; g.N = 4 * D; g.K = D;
-    launch_gemm<WT, KVT, RE_GELU>(g, st);
-    g.A = h->rff; g.wt = A_PTR(o.wpr); g.bias = A_F32(o.bpr); g.out = h->rx; g.N = D; g.K = 4 * D;
-    launch_gemm<WT, KVT, RE_RESID>(g, st);
+    operands(att, o.wo, o.bo, h->rx, D, D);
+    IX_TRY((P::template gemm<RE_RESID>(g, st)));
+    hipLaunchKernelGGL((ln_rows_kernel<D, Act>), dim3(ceil_div(T, 4)), dim3(256), 0, st, h->rx, xn, T);
+    operands(xn, o.wfc, o.bfc, ff, 4 * D, D);
+    IX_TRY((P::template gemm<RE_GELU>(g, st)));
+    operands(ff, o.wpr, o.bpr, h->rx, D, 4 * D);
+    IX_TRY((P::template gemm<RE_RESID>(g, st)));
   }
   IX_HIP(hipGetLastError());
   return IXTTS_OK;
 }
 
-// bf16 / fp16 weights: the producers write rows of the weights' type (into the same workspaces; fp16 rows saturate at
-// +-65504, store_kv) and the GEMMs are the LDS-DMA kernel
-template <typename KVT, int D>
-static int forward_rows_16(ixtts_gpt* h, int slot, int T, int pos0, int valid_from, hipStream_t st, const PackedPass* pk = nullptr) {
-  const size_t lstride = (size_t)h->slots * D * h->smax * sizeof(KVT);
-  const size_t sstride = (size_t)D * h->smax * sizeof(KVT);
-  KVT* xn16 = reinterpret_cast<KVT*>(h->rxn);
-  KVT* att16 = reinterpret_cast<KVT*>(h->ratt);
-  KVT* ff16 = reinterpret_cast<KVT*>(h->rff);
-  const dim3 blk(256);
-  auto grid = [&](int N) { return dim3(ceil_div(N, 128), ceil_div(T, 128)); };
-  static bool attr_done = false;  // (one flag per element type: the function is a template)
-  if (!attr_done) {
-    IX_HIP(hipFuncSetAttribute((const void*)gemm_rows_bf16_kernel<RE_QKV, KVT>, hipFuncAttributeMaxDynamicSharedMemorySize, G16_SMEM));
-    IX_HIP(hipFuncSetAttribute((const void*)gemm_rows_bf16_kernel<RE_RESID, KVT>, hipFuncAttributeMaxDynamicSharedMemorySize, G16_SMEM));
-    IX_HIP(hipFuncSetAttribute((const void*)gemm_rows_bf16_kernel<RE_GELU, KVT>, hipFuncAttributeMaxDynamicSharedMemorySize, G16_SMEM));
-    IX_HIP(hipFuncSetAttribute((const void*)gemm_rows_bf16_kernel<RE_QKV_PACKED, KVT, GemmArgs16Packed>, hipFuncAttributeMaxDynamicSharedMemorySize, G16_SMEM));
-    attr_done = true;
-  }
-  for (int l = 0; l < h->L; ++l) {
-    const LayerOff& o = h->lo[l];
-    uint8_t* kc = (uint8_t*)h->kc + l * lstride + slot * sstride;
-    uint8_t* vc = (uint8_t*)h->vc + l * lstride + slot * sstride;
-    hipLaunchKernelGGL((ln_rows_kernel<D, KVT>), dim3(ceil_div(T, 4)), blk, 0, st, h->rx, xn16, T);
-    GemmArgs16 g;
-    g.A = reinterpret_cast<const unsigned short*>(xn16); g.wt = reinterpret_cast<const unsigned short*>(A_PTR(o.wqkv)); g.bias = A_F32(o.bqkv);
-    g.out = h->rq; g.kcache = kc; g.vcache = vc; g.T = T; g.N = 3 * D; g.K = D; g.pos0 = pos0; g.smax = h->smax; g.D = D;
-    if (pk) {
-      GemmArgs16Packed gp;
-      static_cast<GemmArgs16&>(gp) = g;
-      gp.row_at = pk->row_at;
-      hipLaunchKernelGGL((gemm_rows_bf16_kernel<RE_QKV_PACKED, KVT, GemmArgs16Packed>), grid(g.N), blk, G16_SMEM, st, gp);
-      launch_attn_packed<KVT, KVT>(h, *pk, kc, vc, att16, st);
-    } else {
-      hipLaunchKernelGGL((gemm_rows_bf16_kernel<RE_QKV, KVT>), grid(g.N), blk, G16_SMEM, st, g);
-      AttnRowsArgs a;
-      a.q = h->rq; a.kcache = kc; a.vcache = vc; a.out = att16; a.T = T; a.D = D; a.smax = h->smax; a.pos0 = pos0; a.valid_from = valid_from;
-      launch_attn_rows<KVT, KVT>(h, a, st);
-    }
-    g.A = reinterpret_cast<const unsigned short*>(att16); g.wt = reinterpret_cast<const unsigned short*>(A_PTR(o.wo)); g.bias = A_F32(o.bo);
-    g.out = h->rx; g.N = D; g.K = D;
-    hipLaunchKernelGGL((gemm_rows_bf16_kernel<RE_RESID, KVT>), grid(g.N), blk, G16_SMEM, st, g);
-    hipLaunchKernelGGL((ln_rows_kernel<D, KVT>), dim3(ceil_div(T, 4)), blk, 0, st, h->rx, xn16, T);
-    g.A = reinterpret_cast<const unsigned short*>(xn16); g.wt = reinterpret_cast<const unsigned short*>(A_PTR(o.wfc)); g.bias = A_F32(o.bfc);
-    g.out = ff16; g.N = 4 * D; g.K = D;
-    hipLaunchKernelGGL((gemm_rows_bf16_kernel<RE_GELU, KVT>), grid(g.N), blk, G16_SMEM, st, g);
-    g.A = reinterpret_cast<const unsigned short*>(ff16); g.wt = reinterpret_cast<const unsigned short*>(A_PTR(o.wpr)); g.bias = A_F32(o.bpr);
-    g.out = h->rx; g.N = D; g.K = 4 * D;
-    hipLaunchKernelGGL((gemm_rows_bf16_kernel<RE_RESID, KVT>), grid(g.N), blk, G16_SMEM, st, g);
-  }
-  IX_HIP(hipGetLastError());
-  return IXTTS_OK;
-}
-
-int forward_rows(ixtts_gpt* h, int slot, int T, int pos0, int valid_from, hipStream_t st) {
+static int forward_rows_any(ixtts_gpt* h, int slot, int T, int pos0, int valid_from, hipStream_t st, const PackedPass* pk) {
   if (T <= 0) return IXTTS_OK;
-  if (h->cfg.weight_dtype == IXTTS_DTYPE_F32) {
-    return h->D == 1280 ? forward_rows_t<float, float, 1280>(h, slot, T, pos0, valid_from, st)
-                        : forward_rows_t<float, float, 128>(h, slot, T, pos0, valid_from, st);
+  const bool wide = h->D == 1280;  // (create admits 1280 | 128)
+  switch (h->cfg.weight_dtype) {
+    case IXTTS_DTYPE_F32:
+      return wide ? forward_rows_impl<float, float, 1280>(h, slot, T, pos0, valid_from, st, pk) : forward_rows_impl<float, float, 128>(h, slot, T, pos0, valid_from, st, pk);
+    case IXTTS_DTYPE_F16:
+      return wide ? forward_rows_impl<f16, f16, 1280>(h, slot, T, pos0, valid_from, st, pk) : forward_rows_impl<f16, f16, 128>(h, slot, T, pos0, valid_from, st, pk);
+    default:
+      return wide ? forward_rows_impl<bf16, bf16, 1280>(h, slot, T, pos0, valid_from, st, pk) : forward_rows_impl<bf16, bf16, 128>(h, slot, T, pos0, valid_from, st, pk);
   }
-  if (h->cfg.weight_dtype == IXTTS_DTYPE_F16)
-    return h->D == 1280 ? forward_rows_16<f16, 1280>(h, slot, T, pos0, valid_from, st) : forward_rows_16<f16, 128>(h, slot, T, pos0, valid_from, st);
-  return h->D == 1280 ? forward_rows_16<bf16, 1280>(h, slot, T, pos0, valid_from, st) : forward_rows_16<bf16, 128>(h, slot, T, pos0, valid_from, st);
 }
 
-int forward_rows_packed(ixtts_gpt* h, const PackedPass& p, hipStream_t st) {
-  if (p.T <= 0) return IXTTS_OK;
-  // (slot 0: kc / vc in the layer loops are then the layer's bases, which is what the packed launches take)
-  if (h->cfg.weight_dtype == IXTTS_DTYPE_F32) {
-    return h->D == 1280 ? forward_rows_t<float, float, 1280>(h, 0, p.T, 0, 0, st, &p) : forward_rows_t<float, float, 128>(h, 0, p.T, 0, 0, st, &p);
-  }
-  if (h->cfg.weight_dtype == IXTTS_DTYPE_F16)
-    return h->D == 1280 ? forward_rows_16<f16, 1280>(h, 0, p.T, 0, 0, st, &p) : forward_rows_16<f16, 128>(h, 0, p.T, 0, 0, st, &p);
-  return h->D == 1280 ? forward_rows_16<bf16, 1280>(h, 0, p.T, 0, 0, st, &p) : forward_rows_16<bf16, 128>(h, 0, p.T, 0, 0, st, &p);
-}
+int forward_rows(ixtts_gpt* h, int slot, int T, int pos0, int valid_from, hipStream_t st) { return forward_rows_any(h, slot, T, pos0, valid_from, st, nullptr); }
+
+int forward_rows_packed(ixtts_gpt* h, const PackedPass& p, hipStream_t st) { return forward_rows_any(h, 0, p.T, 0, 0, st, &p); }
 
 // ---- packed pass, in and out.  One workgroup per packed row: row r of sequence s is the caller's embeds row pos0 + r, its last row
 // the start-mel row mel_emb[start] + mel_pos[0] (the sum add_vec_kernel makes in ixtts_gpt_prefill: one fp32 add per element).

@@ -632,6 +632,54 @@ int ixtts_resample_varlen_f32(const float* x_dev, long x_elems, float* y_dev, lo
                               const float* bands_dev, long bands_elems, const int* starts_dev, int orig, int new_, int width, int band, void* stream);
 int ixtts_pcm_assemble(const float* x_dev, long x_elems, void* out_dev, long total, const int64_t* rows_dev, int n_rows, int encoding, void* stream);
 
+/* ---- output stage: programme loudness (ITU-R BS.1770-4) and a sample-peak ceiling -----------------------------------------------
+ * The programme of a request is what it delivers: its rows (fp32 at the +-32767 scale) at their offsets, zeros between them, taken
+ * as x / 32768.  Tables (device): `rows_dev` int64 [n_rows][3] = (src, n, dst) as above, the rows of a request consecutive and
+ * ascending in dst; `reqs_dev` int64 [n_reqs][IXTTS_LOUDNESS_REQ_COLS] = (first row, rows, start, extent, hop, first hop slot): the
+ * programme is [start, start + extent) in the coordinate of dst, hop = (fs + 5) / 10 samples, and hop k of the request has slot
+ * `first hop slot + k` of the two hop arrays, k < ceil(extent / hop).
+ *
+ * ixtts_loudness_measure: K-weighting (`coefs_dev` fp64 [n_reqs][IXTTS_LOUDNESS_COEF_COLS] = shelf b0 b1 b2 a1 a2, high-pass a1 a2
+ *     with b = 1 -2 1, one unused, then M row-major 4 x 4) over the whole programme from zero state, through the gaps, in fp64;
+ *     energy_dev[slot] = the sum of squares of the weighted signal over the hop, hop_peak_dev[slot] = max |x| over it in sample
+ *     units (a trailing partial hop gets both over the samples it has).  One wave per hop filters the window from R = hop + hop / 2
+ *     samples before the hop (what the filter's slowest pole leaves of a state by then is 1e-14 of it, at every rate) to its end:
+ *     a lane filters its chunk of Cw = ceil((R + hop) / 64) | 1 samples from zero state, the chunks' end states are chained with
+ *     M = A^Cw -- A the zero-input update of the state (s1, s2, u1, u2) of the two transposed-direct-form-II sections:
+ *     s1' = -a1 s1 + s2, s2' = -a2 s1, u1' = -(h1 + 2) s1 - h1 u1 + u2, u2' = (1 - h2) s1 - h2 u1 -- and the lane filters its
+ *     chunk again from the state it starts in; the 64 partial sums are added in lane order -- no atomics, a request's numbers are
+ *     the same alone and in any launch.  max_hops = the largest
+ *     ceil(extent / hop) (it sizes the grid), hop <= IXTTS_LOUDNESS_MAX_HOP, n_reqs <= 65535; a source range outside
+ *     [0, x_elems) reads as silence and a slot outside [0, hops_elems) is not written.
+ * ixtts_loudness_gain: one workgroup per request, fixed reduction order.  Blocks of 4 hops, z_j = (e_j + .. + e_j+3) / (4 hop),
+ *     l_j = -0.691 + 10 log10 z_j, the absolute gate at -70 and the relative gate 10 below the mean of what passed it ->
+ *     L (none with fewer than 4 hops or no block above -70).  `targets_dev` fp64 [n_reqs][2] = (target LUFS | NaN: none, ceiling
+ *     dBFS | NaN: none).  g = 10^((target - L) / 20) with a target and an L, else 1; with a ceiling c = 32768 * 10^(dBFS / 20) and
+ *     g * peak > c, g = c / peak.  records_dev [n_reqs] of ixtts_loudness_record (8-byte aligned): L (NaN: none), g rounded to
+ *     fp32 once, the input peak in sample units, flags IXTTS_LOUDNESS_CEILING_BOUND | IXTTS_LOUDNESS_NO_BLOCK, the number of
+ *     blocks; gains_dev fp32 [n_reqs] = the same g.
+ * ixtts_pcm_assemble_gain: ixtts_pcm_assemble with rows_dev int64 [n_rows][4] = (src, n, dst, gain index): a sample of a row with
+ *     0 <= index < n_gains is the conversion of the fp32 product gains_dev[index] * x (one rounding), any other index converts x.
+ */
+#define IXTTS_LOUDNESS_REQ_COLS 6
+#define IXTTS_LOUDNESS_COEF_COLS 24
+#define IXTTS_LOUDNESS_MAX_HOP 4800
+#define IXTTS_LOUDNESS_CEILING_BOUND 1u
+#define IXTTS_LOUDNESS_NO_BLOCK 2u
+typedef struct ixtts_loudness_record {
+  double lufs;
+  float gain;
+  float peak;
+  uint32_t flags;
+  uint32_t blocks;
+} ixtts_loudness_record;
+int ixtts_loudness_measure(const float* x_dev, long x_elems, const int64_t* rows_dev, int n_rows, const int64_t* reqs_dev, const double* coefs_dev,
+                           int n_reqs, long max_hops, double* energy_dev, float* hop_peak_dev, long hops_elems, void* stream);
+int ixtts_loudness_gain(const double* energy_dev, const float* hop_peak_dev, long hops_elems, const int64_t* reqs_dev, const double* targets_dev,
+                        int n_reqs, ixtts_loudness_record* records_dev, float* gains_dev, void* stream);
+int ixtts_pcm_assemble_gain(const float* x_dev, long x_elems, void* out_dev, long total, const int64_t* rows_dev, int n_rows, const float* gains_dev,
+                            int n_gains, int encoding, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1,7 +1,8 @@
 """The output stage (`output.finish_pcm`: resample, convert, lay out, ONE copy to the host) against the vocoder pass that feeds it, at
 production width (BIGVGAN_CFG, synthetic weights), on two shapes:
   (a) the headline request's 2 x 1892 frames;  (b) one 150-code segment, 258 frames
-and two formats: 48 000 Hz pcm_s16le and 8 000 Hz mu-law.  The forms alternate inside one process, every window repeats its form
+and two formats: 48 000 Hz pcm_s16le and 8 000 Hz mu-law, each without and with a loudness target (`loudness=-23.0`: the measurement
+and gating launches of DESIGN.md 4.3c before the conversion).  The forms alternate inside one process, every window repeats its form
 until it is `--window` seconds long and ends in a device synchronise (the output stage ends in its copy to the host, which waits),
 and a form is reported as the median of `--rounds` windows with their min .. max.  The vocoder is `pipeline.vocode_many` on the
 same mels, which this stage leaves as it was.
@@ -26,6 +27,8 @@ from voice_tts_amd.pipeline import vocode_many  # noqa: E402
 
 SHAPES = {"a: 2 x 1892 frames": [1892, 1892], "b: 1 x 258 frames": [258]}
 FORMATS = {"48000 pcm_s16le": (48000, "pcm_s16le"), "8000 mulaw": (8000, "mulaw")}
+TARGET = -23.0  # LUFS, the loudness column
+LEVELLED = ", %g LUFS" % TARGET
 
 
 def main():
@@ -61,6 +64,8 @@ def main():
         forms = {"vocoder": lambda: vocode_many(m, mels)}
         for k, (sr, enc) in FORMATS.items():
             forms["output stage " + k] = lambda sr=sr, enc=enc: O.finish_pcm(wavs, sr, enc, 200)
+        for k, (sr, enc) in FORMATS.items():
+            forms["output stage " + k + LEVELLED] = lambda sr=sr, enc=enc: O.finish_pcm(wavs, sr, enc, 200, loudness=TARGET)
         if args.stage_only:
             for k, fn in forms.items():
                 if k != "vocoder":
@@ -83,10 +88,12 @@ def main():
             med = statistics.median(ts)
             row["forms"][k] = dict(median_ms=round(med, 4), min_ms=round(min(ts), 4), max_ms=round(max(ts), 4))
             if k != "vocoder":
-                sr, enc = FORMATS[k[len("output stage "):]]
+                sr, enc = FORMATS[k[len("output stage "):].replace(LEVELLED, "")]
                 out_samples = sum(O.resampled_len(w.shape[1], 22050, sr) for w in wavs) + O.gap_len(sr) * (len(wavs) - 1)
                 row["forms"][k].update(samples_out=out_samples, share_of_vocoder=round(med / voc, 4))
-            print(f"({name}) {k:30s}: median {med:8.3f} ms  [{min(ts):8.3f} .. {max(ts):8.3f}]"
+                if k.endswith(LEVELLED):
+                    row["forms"][k].update(over_plain_ms=round(med - statistics.median(times[k[:-len(LEVELLED)]]), 4))
+            print(f"({name}) {k:41s}: median {med:8.3f} ms  [{min(ts):8.3f} .. {max(ts):8.3f}]"
                   + (f"  {100 * med / voc:5.2f} % of the vocoder pass" if k != "vocoder" else ""), flush=True)
         results.append(row)
     if args.stage_only:

@@ -53,6 +53,11 @@ QWEN_MAX_SLOTS = 4  # IXTTS_QWEN_MAX_SLOTS
 
 RESAMPLE_TILE = 1024  # IXTTS_RESAMPLE_TILE: output samples per workgroup of the resampler (`resample_tile()` asks the library)
 PCM_ENCODINGS = {"pcm_s16le": 0, "mulaw": 1, "alaw": 2}  # IXTTS_PCM_*
+LOUDNESS_REQ_COLS = 6  # IXTTS_LOUDNESS_REQ_COLS: (first row, rows, start, extent, hop, first hop slot)
+LOUDNESS_COEF_COLS = 24  # IXTTS_LOUDNESS_COEF_COLS: shelf b0 b1 b2 a1 a2, high-pass a1 a2, one unused, the chunk transition 4 x 4
+LOUDNESS_MAX_HOP = 4800  # IXTTS_LOUDNESS_MAX_HOP
+LOUDNESS_CEILING_BOUND, LOUDNESS_NO_BLOCK = 1, 2  # flags of a record
+LOUDNESS_RECORD_BYTES = 24  # ixtts_loudness_record: f64 lufs, f32 gain, f32 peak, u32 flags, u32 blocks
 
 
 class QwenCfg(C.Structure):
@@ -177,6 +182,9 @@ SYMBOLS = {
     "ixtts_resample_tile": (C.c_int, []),
     "ixtts_resample_varlen_f32": (C.c_int, [_P, C.c_long, _P, C.c_long, _P, C.c_int, C.c_long, _P, C.c_long, _P, C.c_int, C.c_int, C.c_int, C.c_int, _P]),
     "ixtts_pcm_assemble": (C.c_int, [_P, C.c_long, _P, C.c_long, _P, C.c_int, C.c_int, _P]),
+    "ixtts_loudness_measure": (C.c_int, [_P, C.c_long, _P, C.c_int, _P, _P, C.c_int, C.c_long, _P, _P, C.c_long, _P]),
+    "ixtts_loudness_gain": (C.c_int, [_P, _P, C.c_long, _P, _P, C.c_int, _P, _P, _P]),
+    "ixtts_pcm_assemble_gain": (C.c_int, [_P, C.c_long, _P, C.c_long, _P, C.c_int, _P, C.c_int, C.c_int, _P]),
 }
 
 _lib = None

@@ -815,22 +815,42 @@ class IndexTTS2:
                              "(output_sample_rate alone resamples them)")
         return _output.check_format(output_sample_rate, output_encoding)
 
+    last_loudness = None  # the level report of the last call: see `infer` / `infer_many`
+
+    @staticmethod
+    def _output_level(output_loudness, output_peak, stream_return=False):
+        """-> None, or (loudness | None, peak) of a call that asks for a level (`output.check_level`); ValueError for a value outside the
+        ranges, and for either control on a stream: it has no whole programme to measure."""
+        if stream_return and (output_loudness is not None or output_peak is not None):
+            raise ValueError("output_loudness / output_peak cannot be combined with stream_return=True: the level is measured over "
+                             "the whole programme, which a stream does not have")
+        return _output.check_level(output_loudness, output_peak)
+
     # ------------------------------------------------------------------ API
     def infer(self, spk_audio_prompt, text, output_path, emo_audio_prompt=None, emo_alpha=1.0, emo_vector=None,
               use_emo_text=False, emo_text=None, use_random=False, interval_silence=200, verbose=False,
               max_text_tokens_per_segment=120, stream_return=False, more_segment_before=0, output_sample_rate=None,
-              output_encoding=None, **generation_kwargs):
+              output_encoding=None, output_loudness=None, output_peak=None, **generation_kwargs):
         """`output_sample_rate` (one of `output.SAMPLE_RATES`) / `output_encoding` (`pcm_s16le`, `mulaw`, `alaw`): the output stage on
         the device (output.py) takes the place of the host-side cat and int16 cast -- the `(sr, pcm)` return, the file at
         `output_path` and `last_timing["audio_length"]` follow the requested rate; pcm is uint8 for the G.711 encodings.  With
         `stream_return=True` the yielded segments are the resampled fp32 rows and an encoding is refused (the stream yields floats,
-        as the reference's does).  Both None: 22 050 Hz int16, as ever."""
+        as the reference's does).  Both None: 22 050 Hz int16, as ever.
+
+        `output_loudness` (target integrated loudness, LUFS in [-50, -5]) / `output_peak` (sample-peak ceiling, dBFS in [-20, 0];
+        -1 beside a loudness target): the output stage measures the delivered programme (ITU-R BS.1770-4, gaps included) on the device
+        and applies ONE gain before the conversion -- lowered, never limited, when the ceiling would be passed.  Either one routes
+        the request through the output stage (22 050 Hz `pcm_s16le` when no format is asked) and is refused with
+        `stream_return=True`.  Afterwards `last_loudness` is dict(measured_lufs | None, gain_db, peak_dbfs_in, target_met), or None
+        when neither was given -- and then nothing changes anywhere."""
         if output_sample_rate is not None or output_encoding is not None:  # refused here, not at the generator's first step
             self._output_format(output_sample_rate, output_encoding, stream_return)
+        if output_loudness is not None or output_peak is not None:
+            self._output_level(output_loudness, output_peak, stream_return)
         gen = self.infer_generator(spk_audio_prompt, text, output_path, emo_audio_prompt, emo_alpha, emo_vector, use_emo_text,
                                    emo_text, use_random, interval_silence, verbose, max_text_tokens_per_segment, stream_return,
                                    more_segment_before, output_sample_rate=output_sample_rate, output_encoding=output_encoding,
-                                   **generation_kwargs)
+                                   output_loudness=output_loudness, output_peak=output_peak, **generation_kwargs)
         if stream_return:
             return gen
         try:
@@ -840,7 +860,7 @@ class IndexTTS2:
 
     @torch.no_grad()
     def infer_many(self, requests, interval_silence=200, max_text_tokens_per_segment=120, decode_slots=8, output_sample_rate=None,
-                   output_encoding=None, **generation_kwargs):
+                   output_encoding=None, output_loudness=None, output_peak=None, **generation_kwargs):
         """Several `/tts` requests served TOGETHER (the worker's global lock, server.py:25,384, replaced by the
         decode scheduler): every request's segments share the decode slots -- the weights are read once per step for all of them
         -- and the post-decode stages run per segment as in `infer`, through the same helpers.  Each request is a dict with
@@ -872,6 +892,10 @@ class IndexTTS2:
         encoding, one copy to the host), and a pinned request's bytes stay a function of the request alone; a value outside the
         accepted sets fails that request only.  The requests that ask for nothing take the host path they always took.
 
+        `output_loudness` / `output_peak` (see `infer`) hold for the call as well, a request may carry `loudness` / `peak` (they do
+        not pin it either, and a bad value fails that request only); a request with either leaves through the output stage.
+        `last_loudness` is then a list with one entry per request: the level report, or None where no control was asked.
+
         Returns one entry per request: `(22050, int16 [N, 1])` (`(rate, int16 | uint8 [N, 1])` with a format), None (empty text), or the EXCEPTION that
         request raised (bad prompt audio, a code outside the codebook ...) -- one request's failure leaves the others of the
         batch alone."""
@@ -901,7 +925,9 @@ class IndexTTS2:
                 # the output format: the request's own keys, else the call's; None = the host path of old
                 fmt = (rq["sample_rate"] if rq.get("sample_rate") is not None else output_sample_rate,
                        rq["encoding"] if rq.get("encoding") is not None else output_encoding)
-                if fmt == (None, None):
+                level = self._output_level(rq["loudness"] if rq.get("loudness") is not None else output_loudness,
+                                           rq["peak"] if rq.get("peak") is not None else output_peak)  # a bad value fails this request
+                if fmt == (None, None) and level is None:
                     fmt = None
                 else:
                     self._output_format(*fmt)  # a value outside the accepted sets fails this request
@@ -918,7 +944,7 @@ class IndexTTS2:
                 mine = [self._segment(cl, ids, eng, gr.max_mel_tokens, request=ri, index=si, stream=si if pinned else None, sampler=sampler,
                                       constraints=cons, processors=procs)
                         for si, ids in enumerate(segments)]
-                plans[ri] = dict(spk=spk, cl=cl, segments=segments, seed=gr.seed if pinned else None, fmt=fmt)
+                plans[ri] = dict(spk=spk, cl=cl, segments=segments, seed=gr.seed if pinned else None, fmt=fmt, level=level)
                 classes.setdefault(nb, []).extend(mine)  # only once the whole request is known to be well-formed
             except Exception as e:  # this request only
                 failed[ri] = e
@@ -997,11 +1023,20 @@ class IndexTTS2:
             plans[ri]["pcm"] = [next(pcm) for _ in plans[ri]["mels"]]
         # the requests that asked for a sample rate or an encoding: through the output stage on the device, all of them together
         formatted = {}
+        self.last_loudness = [None] * len(requests)
         mine = [ri for ri in live if plans[ri]["fmt"] is not None and not any(isinstance(w, Exception) for w in plans[ri]["pcm"])]
         if mine:
             try:
-                res = _output.finish_pcm_many([plans[ri]["pcm"] for ri in mine], [plans[ri]["fmt"][0] for ri in mine],
-                                              [plans[ri]["fmt"][1] for ri in mine], interval_silence)
+                args = ([plans[ri]["pcm"] for ri in mine], [plans[ri]["fmt"][0] for ri in mine], [plans[ri]["fmt"][1] for ri in mine], interval_silence)
+                if any(plans[ri]["level"] is not None for ri in mine):  # (a call without a level control makes the call it always made)
+                    levels, reports = [plans[ri]["level"] or (None, None) for ri in mine], []
+                    res = _output.finish_pcm_many(*args, loudness=[lv[0] for lv in levels], peak=[lv[1] for lv in levels], reports=reports)
+                    for ri, rep in zip(mine, reports):
+                        self.last_loudness[ri] = rep
+                        if rep is not None:
+                            logger.info(f"infer_many: request {ri} level: {rep}")
+                else:
+                    res = _output.finish_pcm_many(*args)
                 formatted = dict(zip(mine, res))
             except Exception as e:
                 formatted = {ri: e for ri in mine}
@@ -1037,11 +1072,13 @@ class IndexTTS2:
     def infer_generator(self, spk_audio_prompt, text, output_path, emo_audio_prompt=None, emo_alpha=1.0, emo_vector=None,
                         use_emo_text=False, emo_text=None, use_random=False, interval_silence=200, verbose=False,
                         max_text_tokens_per_segment=120, stream_return=False, quick_streaming_tokens=0, output_sample_rate=None,
-                        output_encoding=None, **generation_kwargs):
+                        output_encoding=None, output_loudness=None, output_peak=None, **generation_kwargs):
         logger.info("Starting inference...")
         start_time = time.perf_counter()
-        # an output format (see `infer`): the segments stay on the device and leave through `output.finish_pcm`
-        fmt = output_sample_rate is not None or output_encoding is not None
+        # an output format or a level (see `infer`): the segments stay on the device and leave through `output.finish_pcm`
+        level = self._output_level(output_loudness, output_peak, stream_return)
+        self.last_loudness = None
+        fmt = output_sample_rate is not None or output_encoding is not None or level is not None
         if fmt:
             out_rate, out_enc = self._output_format(output_sample_rate, output_encoding, stream_return)
         self._prompt_stages()
@@ -1176,7 +1213,14 @@ class IndexTTS2:
         if not wavs:
             return
         if fmt:
-            sampling_rate, pcm = _output.finish_pcm(wavs, output_sample_rate, output_encoding, interval_silence)
+            if level is None:
+                sampling_rate, pcm = _output.finish_pcm(wavs, output_sample_rate, output_encoding, interval_silence)
+            else:
+                reports = []
+                sampling_rate, pcm = _output.finish_pcm(wavs, output_sample_rate, output_encoding, interval_silence, loudness=level[0],
+                                                        peak=level[1], reports=reports)
+                self.last_loudness = reports[0]
+                logger.info(f"output level: {self.last_loudness}")
             wav_length = pcm.shape[0] / sampling_rate
             end_time = time.perf_counter()  # (the output stage is part of the request)
         else:

@@ -6,6 +6,9 @@ the caller asked for, ON THE DEVICE (csrc/output.hip), and reaches the host in o
   Resampler         packed rows of unequal length -> the requested rate, one launch for all of them
   pcm_assemble      rows -> one buffer of int16 / G.711 bytes, the gaps (interval silence) holding the encoding's code for zero
   finish_pcm(_many) the tail of `infer` / `infer_many`: resample, convert, lay out, copy to the host once
+  k_weighting       the two biquads of ITU-R BS.1770 at a sample rate -- the ONE builder, for the measurement kernel and the tests
+  measure_levels    K-weighted hop energies and sample peak of every programme of a call, then gating and gain: two launches
+  pcm_assemble_gain `pcm_assemble` with a gain per row, read from the device
   wav_bytes         the RIFF container of a result
 
 With nothing requested none of this runs: `infer` keeps its host-side cat and `.type(torch.int16)`.
@@ -88,9 +91,9 @@ def tap_bands(sr_in, sr_out):
     return bands, starts.to(torch.int32), L
 
 
-def _row_table(rows, device):
+def _row_table(rows, device, cols=3):
     """[(src, n, dst)] -> int64 [R, 3] on the device, copied from pinned memory so that the host does not wait for the stream."""
-    t = torch.tensor(rows, dtype=torch.int64).reshape(-1, 3)
+    t = torch.tensor(rows, dtype=torch.int64).reshape(-1, cols)
     if device.type == "cuda":
         t = t.pin_memory()
     return t.to(device, non_blocking=True)
@@ -178,13 +181,179 @@ def gap_len(sample_rate, interval_silence=200):
     return int(sample_rate * interval_silence / 1000.0)
 
 
-def finish_pcm_many(wav_lists, sample_rates, encodings, interval_silence=200):
+# --------------------------------------------------------------------------- loudness target and peak ceiling (ITU-R BS.1770-4)
+LOUDNESS_RANGE = (-50.0, -5.0)  # LUFS
+PEAK_RANGE = (-20.0, 0.0)  # dBFS, sample peak
+DEFAULT_PEAK = -1.0  # the ceiling of a request that gives a loudness target alone
+_RECORD = np.dtype([("lufs", "<f8"), ("gain", "<f4"), ("peak", "<f4"), ("flags", "<u4"), ("blocks", "<u4")])
+assert _RECORD.itemsize == _lib.LOUDNESS_RECORD_BYTES
+
+
+def check_level(loudness=None, peak=None):
+    """-> None when neither is given, else (loudness | None, peak | None) as floats, the ceiling defaulting to -1 dBFS beside a
+    loudness target; ValueError for a bool, a NaN, anything that is not a number and a value outside [-50, -5] LUFS / [-20, 0] dBFS."""
+    if loudness is None and peak is None:
+        return None
+    for name, v, (lo, hi), unit in (("loudness", loudness, LOUDNESS_RANGE, "LUFS"), ("peak", peak, PEAK_RANGE, "dBFS")):
+        if v is None:
+            continue
+        if isinstance(v, bool) or not isinstance(v, (int, float, np.integer, np.floating)) or not lo <= float(v) <= hi:  # (NaN fails the comparison)
+            raise ValueError(f"output {name} {v!r} is not a number in [{lo:g}, {hi:g}] {unit}")
+    return (None if loudness is None else float(loudness)), (DEFAULT_PEAK if peak is None else float(peak))
+
+
+def hop_len(fs):
+    """Samples of one hop (100 ms) of the gating blocks at `fs`: 1103 at 11 025 Hz."""
+    return (int(fs) + 5) // 10
+
+
+def k_weighting(fs):
+    """-> (b_shelf, a_shelf, b_highpass, a_highpass), fp64 [3] each: the K-weighting of ITU-R BS.1770 at `fs`, the analogue prototypes
+    behind the standard's 48 kHz table carried to `fs` by the bilinear transform (at 48 000 Hz: the table, within 1e-12)."""
+    fs = float(fs)
+    f0, G, Q = 1681.974450955533, 3.999843853973347, 0.7071752369554196
+    K = math.tan(math.pi * f0 / fs)
+    Vh = 10.0 ** (G / 20.0)
+    Vb = Vh ** 0.4996667741545416
+    a0 = 1.0 + K / Q + K * K
+    b_s = np.array([Vh + Vb * K / Q + K * K, 2.0 * (K * K - Vh), Vh - Vb * K / Q + K * K], np.float64) / a0
+    a_s = np.array([1.0, 2.0 * (K * K - 1.0) / a0, (1.0 - K / Q + K * K) / a0], np.float64)
+    f0, Q = 38.13547087602444, 0.5003270373238773
+    K = math.tan(math.pi * f0 / fs)
+    a0 = 1.0 + K / Q + K * K
+    b_h = np.array([1.0, -2.0, 1.0], np.float64)
+    a_h = np.array([1.0, 2.0 * (K * K - 1.0) / a0, (1.0 - K / Q + K * K) / a0], np.float64)
+    return b_s, a_s, b_h, a_h
+
+
+def chunk_transition(fs):
+    """-> (Cw, M fp64 [4, 4]): the samples of one lane's chunk in the measurement kernel -- ceil((R + H) / 64) | 1 with H the hop and
+    R = H + H // 2 the run-in -- and the zero-input transition of the K-weighting's state over such a chunk, A^Cw, where A updates
+    (s1, s2, u1, u2) of the two transposed-direct-form-II sections by one sample."""
+    H = hop_len(fs)
+    Cw = -(-(H + H // 2 + H) // 64) | 1
+    _, a_s, _, a_h = k_weighting(fs)
+    A = np.array([[-a_s[1], 1.0, 0.0, 0.0], [-a_s[2], 0.0, 0.0, 0.0], [-a_h[1] - 2.0, 0.0, -a_h[1], 1.0], [1.0 - a_h[2], 0.0, -a_h[2], 0.0]], np.float64)
+    return Cw, np.linalg.matrix_power(A, Cw)
+
+
+def level_report(record, loudness):
+    """One record of the gating kernel -> dict(measured_lufs | None, gain_db, peak_dbfs_in, target_met): target_met is False when a
+    loudness target was asked for and missed -- the ceiling bound the gain, or the programme has no block to measure."""
+    none = bool(record["flags"] & _lib.LOUDNESS_NO_BLOCK)
+    bound = bool(record["flags"] & _lib.LOUDNESS_CEILING_BOUND)
+    p = float(record["peak"])
+    return dict(measured_lufs=None if none else float(record["lufs"]), gain_db=20.0 * math.log10(float(record["gain"])),
+                peak_dbfs_in=20.0 * math.log10(p / 32768.0) if p > 0 else float("-inf"),
+                target_met=loudness is None or not (none or bound))
+
+
+class LevelPlan:
+    """The tables of `measure_levels` for the programmes of a call: programme q = (rows [(src, n, dst)] with dst counted from the
+    programme's start, ascending and disjoint; extent; sample rate; loudness target | None; ceiling | None).  Everything goes up in
+    ONE pinned copy; `rows`, `reqs`, `coefs`, `targets` are views of it."""
+
+    def __init__(self, programmes, device):
+        rows, reqs, coefs, targets, at, slot = [], [], [], [], 0, 0
+        self.hops = []
+        for prog_rows, extent, rate, loudness, peak in programmes:
+            H, extent = hop_len(rate), int(extent)
+            if H > _lib.LOUDNESS_MAX_HOP:
+                raise ValueError(f"loudness: a hop of {H} samples ({rate} Hz) is more than the kernel's {_lib.LOUDNESS_MAX_HOP}")
+            end = 0
+            for s, n, d in prog_rows:
+                if s < 0 or n < 0 or d < end or d + n > extent:
+                    raise ValueError(f"loudness row (src={s}, n={n}, dst={d}) overlaps its neighbour or leaves its programme of {extent} samples")
+                end = d + n
+            hops = -(-extent // H)
+            reqs.append((len(rows), len(prog_rows), at, extent, H, slot))
+            rows += [(int(s), int(n), at + int(d)) for s, n, d in prog_rows]
+            b_s, a_s, _, a_h = k_weighting(rate)
+            coefs.append([b_s[0], b_s[1], b_s[2], a_s[1], a_s[2], a_h[1], a_h[2], 0.0] + [float(v) for v in chunk_transition(rate)[1].reshape(-1)])
+            targets.append([math.nan if loudness is None else loudness, math.nan if peak is None else peak])
+            self.hops.append((slot, hops, extent // H))
+            at, slot = at + extent, slot + hops
+        self.n, self.slots, self.max_hops, self.n_rows = len(reqs), slot, max([h for _, h, _ in self.hops], default=0), len(rows)
+        ints = np.array([v for r in rows for v in r] + [v for r in reqs for v in r], np.int64)
+        blob = torch.from_numpy(np.concatenate([ints, np.array([v for r in coefs + targets for v in r], np.float64).view(np.int64)]))
+        if torch.device(device).type == "cuda":
+            blob = blob.pin_memory()
+        blob = blob.to(device, non_blocking=True)
+        a, b = 3 * len(rows), 3 * len(rows) + _lib.LOUDNESS_REQ_COLS * self.n
+        c = b + _lib.LOUDNESS_COEF_COLS * self.n
+        self.rows, self.reqs = blob[:a], blob[a:b]
+        self.coefs, self.targets = blob[b:c].view(torch.float64), blob[c:].view(torch.float64)
+
+
+def measure_levels(x, plan, records=None):
+    """TWO launches for every programme of `plan`: the K-weighted energy and the sample peak of every hop (fp64 recursion over the fp32
+    samples of `x`, through the gaps), then gating, integrated loudness and gain per programme.  -> (energy fp64 [plan.slots],
+    hop_peak fp32 [plan.slots], records uint8 [24 n] (`_RECORD`; `records`: write there), gains fp32 [n]), all on the device: the
+    gain reaches `pcm_assemble_gain` without visiting the host."""
+    assert x.dtype == torch.float32 and x.is_contiguous()
+    dev = x.device
+    n = max(plan.slots, 1)
+    work = torch.zeros(n + (n + 1) // 2, dtype=torch.float64, device=dev)  # (one fill: a hop the kernel skips reads as silence)
+    energy, hop_peak = work[:n], work[n:].view(torch.float32)
+    gains = torch.empty(max(plan.n, 1), dtype=torch.float32, device=dev)
+    if records is None:
+        records = torch.empty(plan.n * _RECORD.itemsize, dtype=torch.uint8, device=dev)
+    assert records.dtype == torch.uint8 and records.is_contiguous() and records.numel() >= plan.n * _RECORD.itemsize and records.device == dev
+    if plan.n == 0:
+        return energy[:0], hop_peak[:0], records, gains[:0]
+    L, P, s = _lib.lib(), C.c_void_p, _lib.current_stream_ptr()
+    _lib.check(L.ixtts_loudness_measure(P(x.data_ptr()), x.numel(), P(plan.rows.data_ptr()), plan.n_rows, P(plan.reqs.data_ptr()), P(plan.coefs.data_ptr()),
+                                        plan.n, plan.max_hops, P(energy.data_ptr()), P(hop_peak.data_ptr()), plan.slots, s), "ixtts_loudness_measure")
+    _lib.check(L.ixtts_loudness_gain(P(energy.data_ptr()), P(hop_peak.data_ptr()), plan.slots, P(plan.reqs.data_ptr()), P(plan.targets.data_ptr()), plan.n,
+                                     P(records.data_ptr()), P(gains.data_ptr()), s), "ixtts_loudness_gain")
+    return energy[:plan.slots], hop_peak[:plan.slots], records, gains
+
+
+def read_records(records, n):
+    """The records of `measure_levels` (a uint8 tensor or array) -> numpy structured array [n] of `_RECORD`."""
+    raw = records.cpu().numpy() if isinstance(records, torch.Tensor) else np.asarray(records)
+    return np.frombuffer(raw[:n * _RECORD.itemsize].tobytes(), dtype=_RECORD)
+
+
+def pcm_assemble_gain(x, rows, total, encoding, gains, out=None):
+    """`pcm_assemble` over rows (src, n, dst, index): a sample of a row with 0 <= index < len(gains) is the conversion of the fp32
+    product gains[index] * x (one rounding; `gains`: fp32 on the device), any other index converts x as `pcm_assemble` does."""
+    if encoding not in ENCODINGS:
+        raise ValueError(f"output encoding {encoding!r} is not one of {ENCODINGS}")
+    assert x.dtype == torch.float32 and x.is_contiguous() and gains.dtype == torch.float32 and gains.is_contiguous() and gains.device == x.device
+    rows = sorted(((int(s), int(n), int(d), int(g)) for s, n, d, g in rows), key=lambda r: (r[2], r[1]))
+    end = 0
+    for s, n, d, _ in rows:
+        if s < 0 or n < 0 or d < end or s + n > x.numel() or d + n > total:
+            raise ValueError(f"assemble row (src={s}, n={n}, dst={d}) overlaps its neighbour or leaves its buffers ({x.numel()} in, {total} out)")
+        end = d + n
+    dtype = torch.int16 if encoding == "pcm_s16le" else torch.uint8
+    if out is None:
+        out = torch.empty(int(total), dtype=dtype, device=x.device)
+    assert out.dtype == dtype and out.is_contiguous() and out.numel() >= total and out.device == x.device
+    table = _row_table(rows if rows else [(0, 0, 0, -1)], x.device, 4)
+    _lib.check(_lib.lib().ixtts_pcm_assemble_gain(C.c_void_p(x.data_ptr()), x.numel(), C.c_void_p(out.data_ptr()), int(total), C.c_void_p(table.data_ptr()),
+                                                  len(rows), C.c_void_p(gains.data_ptr()), gains.numel(), _lib.PCM_ENCODINGS[encoding],
+                                                  _lib.current_stream_ptr()), "ixtts_pcm_assemble_gain")
+    return out
+
+
+def finish_pcm_many(wav_lists, sample_rates, encodings, interval_silence=200, loudness=None, peak=None, reports=None):
     """The segments of several requests (each a list of fp32 [1, n_i] device tensors at 22 050 Hz, +-32767) -> one
     `(sr, ndarray [N, 1])` per request, int16 or uint8 (None for a request without segments): segment, `int(sr * interval_silence /
     1000)` samples of silence, segment ...  One resample launch per distinct target rate, one assemble launch per distinct
     encoding, then ONE copy to the host; the host waits for nothing before that copy.  A request's bytes depend on its own
-    segments, rate and encoding alone."""
+    segments, rate and encoding alone.
+
+    `loudness` / `peak` (one entry per request, None: not asked; see `check_level`): the request's programme -- what it delivers, at
+    its rate, gaps included -- is measured after the resample launches (`measure_levels`), and its samples are converted from the
+    fp32 product gain * x; the records ride behind the PCM in the same buffer, so there is still one copy and no wait before it.
+    `reports`: a list that receives one `level_report` per request (None where no control was asked).  A request without a control
+    produces the bytes it produces without these arguments."""
     fmts = [check_format(sr, enc) for sr, enc in zip(sample_rates, encodings)]
+    levels = [check_level(lo, pk) for lo, pk in zip(loudness or [None] * len(fmts), peak or [None] * len(fmts))]
+    if reports is not None:
+        reports[:] = [None] * len(wav_lists)
     live = [i for i, w in enumerate(wav_lists) if w]
     if not live:
         return [None] * len(wav_lists)
@@ -227,12 +396,36 @@ def finish_pcm_many(wav_lists, sample_rates, encodings, interval_silence=200):
         width = 2 if enc == "pcm_s16le" else 1
         by_enc[enc] = (rows, total, nbytes)
         nbytes = (nbytes + total * width + 15) // 16 * 16
+    # the requests with a level control: programme q of the plan; their records go behind the PCM
+    asked = [i for i in live if levels[i] is not None]
+    plan = gains = None
+    if asked:
+        progs = []
+        for i in asked:
+            at, gap, mine = 0, gap_len(fmts[i][0], interval_silence), []
+            for k in range(len(wav_lists[i])):
+                at += gap if k else 0
+                mine.append((src[i, k][0], src[i, k][1], at))
+                at += src[i, k][1]
+            progs.append((mine, at, fmts[i][0], levels[i][0], levels[i][1]))
+        plan = LevelPlan(progs, device)
+        rec_off, nbytes = nbytes, nbytes + plan.n * _RECORD.itemsize
     buf = torch.empty(nbytes, dtype=torch.uint8, device=device)
+    if asked:
+        gains = measure_levels(arena, plan, records=buf[rec_off:])[3]
     for enc, (rows, total, off) in by_enc.items():
         width = 2 if enc == "pcm_s16le" else 1
         region = buf[off:off + total * width]
-        pcm_assemble(arena, rows, total, enc, out=region.view(torch.int16) if width == 2 else region)
+        region = region.view(torch.int16) if width == 2 else region
+        if any(fmts[i][1] == enc for i in asked):
+            index = [asked.index(i) if i in asked else -1 for i in live if fmts[i][1] == enc for _ in wav_lists[i]]
+            pcm_assemble_gain(arena, [r + (g,) for r, g in zip(rows, index)], total, enc, gains, out=region)
+        else:
+            pcm_assemble(arena, rows, total, enc, out=region)
     host = buf.cpu().numpy()  # the one copy (it waits for the stream)
+    if asked and reports is not None:
+        for i, rec in zip(asked, read_records(host[rec_off:], plan.n)):
+            reports[i] = level_report(rec, levels[i][0])
     out = [None] * len(wav_lists)
     for i in live:
         enc, start, n = where[i]
@@ -245,10 +438,12 @@ def finish_pcm_many(wav_lists, sample_rates, encodings, interval_silence=200):
     return out
 
 
-def finish_pcm(wavs, sample_rate=None, encoding=None, interval_silence=200):
+def finish_pcm(wavs, sample_rate=None, encoding=None, interval_silence=200, loudness=None, peak=None, reports=None):
     """One request's segments -> `(sr, ndarray [N, 1])`, int16 (`pcm_s16le`) or uint8 (`mulaw`, `alaw`); sr = the requested rate, or
     22050.  See `finish_pcm_many`."""
-    return finish_pcm_many([list(wavs)], [sample_rate], [encoding], interval_silence)[0]
+    if loudness is None and peak is None:
+        return finish_pcm_many([list(wavs)], [sample_rate], [encoding], interval_silence)[0]
+    return finish_pcm_many([list(wavs)], [sample_rate], [encoding], interval_silence, [loudness], [peak], reports)[0]
 
 
 def wav_bytes(sr, pcm, encoding=None):

@@ -2,7 +2,7 @@
 
 Same endpoints, models, priorities, error codes and CLI as the reference:
   POST /tts   TTSRequest{text, spk_audio (URL | hex > 100 chars), emo_audio?, emotion? (str | {str: float in [0,1]}), emo_alpha in [0,1] = 1.0,
-                         sample_rate?, encoding?}   (the last two are this build's: the output stage of output.py; 422 outside its sets)
+                         sample_rate?, encoding?, loudness?, peak?}   (the last four are this build's: the output stage of output.py; 422 outside its sets / ranges)
               -> TTSResponse{audio_hex, audio_length, inference_time, rtf, text}                       (server.py:183-235,320-440)
               emo_audio beats emotion (:352-370); emo_alpha is forced to 1.0 unless emo_audio is given (:391)
   GET /       {"status","model_loaded","service","version"}                                            (:238-246)
@@ -82,6 +82,17 @@ class TTSRequest(BaseModel):
     emo_alpha: float = Field(default=1.0, description="emotion strength in [0,1]")
     sample_rate: Optional[int] = Field(None, description="output sample rate in Hz (8000, 11025, 16000, 22050, 24000, 32000, 44100, 48000); default 22050")
     encoding: Optional[str] = Field(None, description="output sample encoding: pcm_s16le (default), mulaw or alaw (ITU-T G.711, 8 bits)")
+
+    loudness: Optional[float] = Field(None, description="target integrated loudness in LUFS (ITU-R BS.1770-4), -50 .. -5; default: the level of the synthesis")
+    peak: Optional[float] = Field(None, description="sample-peak ceiling in dBFS, -20 .. 0; default -1 beside `loudness`")
+
+    @field_validator("loudness", "peak")
+    @classmethod
+    def _output_level(cls, v, info):
+        from .output import check_level
+
+        check_level(**{info.field_name: v})  # ValueError naming the range -> 422
+        return v
 
     @field_validator("sample_rate", "encoding")
     @classmethod
@@ -323,14 +334,17 @@ def create_app(model_factory=default_model_factory):
                 else:
                     emo_vector = create_emotion_vector(request.emotion)
             # the output format goes on only when the request sets it: a model without the keywords keeps working
-            fmt_kw = {k: v for k, v in (("output_sample_rate", request.sample_rate), ("output_encoding", request.encoding)) if v is not None}
+            fmt_kw = {k: v for k, v in (("output_sample_rate", request.sample_rate), ("output_encoding", request.encoding),
+                                        ("output_loudness", request.loudness), ("output_peak", request.peak)) if v is not None}
+            leveled = request.loudness is not None or request.peak is not None
             start = time.time()
             if state["batcher"] is not None:  # opt-in: queued requests decode together (IXTTS_BATCH_SLOTS)
                 import io
 
                 res = state["batcher"].submit(dict(spk_audio_prompt=spk_audio_data, text=request.text, emo_audio_prompt=emo_audio_data if emo_audio_data else None,
                                                    emo_alpha=request.emo_alpha if emo_audio_data else 1.0, emo_vector=emo_vector,
-                                                   **{k: v for k, v in (("sample_rate", request.sample_rate), ("encoding", request.encoding)) if v is not None})).result()
+                                                   **{k: v for k, v in (("sample_rate", request.sample_rate), ("encoding", request.encoding),
+                                                                        ("loudness", request.loudness), ("peak", request.peak)) if v is not None})).result()
                 if res is None:
                     raise RuntimeError("the text produced no speech segment")
                 sr, pcm = res
@@ -380,7 +394,8 @@ def create_app(model_factory=default_model_factory):
                 audio_length = pcm.shape[0] / float(sr)
                 rtf = inference_time / audio_length if audio_length > 0 else 0.0
                 audio_hex = riff.hex()
-                logger.info(f"TTS completed: audio_length={audio_length:.2f}s, inference_time={inference_time:.2f}s, rtf={rtf:.4f}, size={len(audio_hex)//2} bytes")
+                logger.info(f"TTS completed: audio_length={audio_length:.2f}s, inference_time={inference_time:.2f}s, rtf={rtf:.4f}, size={len(audio_hex)//2} bytes"
+                            + (f", level={getattr(model, 'last_loudness', None)}" if leveled else ""))
                 return TTSResponse(audio_hex=audio_hex, audio_length=audio_length, inference_time=inference_time, rtf=rtf, text=request.text)
             with tempfile.NamedTemporaryFile(suffix=".wav", delete=False) as tmp:
                 output_path = tmp.name
@@ -401,7 +416,8 @@ def create_app(model_factory=default_model_factory):
                     audio_length = w.getnframes() / float(w.getframerate())
             rtf = inference_time / audio_length if audio_length > 0 else 0.0
             os.remove(output_path)
-            logger.info(f"TTS completed: audio_length={audio_length:.2f}s, inference_time={inference_time:.2f}s, rtf={rtf:.4f}, size={len(audio_hex)//2} bytes")
+            logger.info(f"TTS completed: audio_length={audio_length:.2f}s, inference_time={inference_time:.2f}s, rtf={rtf:.4f}, size={len(audio_hex)//2} bytes"
+                        + (f", level={getattr(model, 'last_loudness', None)}" if leveled else ""))
             return TTSResponse(audio_hex=audio_hex, audio_length=audio_length, inference_time=inference_time, rtf=rtf, text=request.text)
         except HTTPException:
             raise

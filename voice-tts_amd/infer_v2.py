@@ -29,6 +29,7 @@ from .bigvgan import BigVGAN
 from .gpt_engine import GptEngine, generation_constraints, generation_processors, resolve_gpt_dtype, resolve_min_length
 from . import output as _output  # (through the module: a test may wrap `finish_pcm_many`)
 from .pipeline import conds_latent, decode_segment, latent_prefix, prepare_gpt_inputs, vocode, vocode_many
+from .s2mel import check_speed, target_frames
 from .weights import BIGVGAN_CFG, GPT_CFG, load_bigvgan_checkpoint, load_gpt_checkpoint
 
 logger = logging.getLogger("indextts.infer_v2")
@@ -736,11 +737,12 @@ class IndexTTS2:
             return self._many_engine(groups * num_beams) if groups * num_beams > 4 else self.gpt
         return self._many_engine(decode_slots)
 
-    def _pinned_noise(self, item, seed, index):
+    def _pinned_noise(self, item, seed, index, frames=None):
         """The CFM noise [1, in_channels, T] of segment `index` of a pinned request: drawn from (seed, index) alone, not from the
-        process-wide generator whose state depends on what was served before."""
+        process-wide generator whose state depends on what was served before.  `frames`: the segment's frame count under a speed
+        or a fitted duration (None: `target_frames` of its codes)."""
         codes, pc = item[1], item[2]
-        T = pc.shape[1] + int((torch.tensor([codes.shape[-1]]) * 1.72).long())
+        T = pc.shape[1] + (target_frames(codes.shape[-1]) if frames is None else int(frames))
         gen = torch.Generator(device=self.device).manual_seed((int(seed) * 1000003 + int(index)) & 0x7FFFFFFFFFFFFFFF)
         return torch.randn(1, self.s2mel.cfg["in_channels"], T, device=self.device, generator=gen)
 
@@ -790,18 +792,21 @@ class IndexTTS2:
             latent = self.gpt.latent(*self._latent_entry(conds_latent, text_ids, codes))
         return latent.unsqueeze(0), codes, spk["prompt_condition"], spk["ref_mel"], spk["style"]
 
-    def _mels(self, items, spk, packed=False, noises=None):
+    def _mels(self, items, spk, packed=False, noises=None, frames=None):
         """s2mel items -> one mel [1, 80, F] each (infer_v2.py:713-731): segment after segment through the built-in or the injected
         stage (which gets the speaker dict `spk`), or -- `packed`, IXTTS_S2MEL_BATCH=1 -- as ONE packed solve (S2Mel.solve_many).
-        `noises`: per item the CFM noise of the built-in stage, or None for a draw from the default generator."""
+        `noises`: per item the CFM noise of the built-in stage, or None for a draw from the default generator.  `frames`: per item
+        the frame count of the built-in stage under a speed or a fitted duration (None, also for the whole list: the natural one)."""
         if packed:
-            return self.s2mel.solve_many(items, n_timesteps=25, inference_cfg_rate=0.7, noises=noises)
+            kw = {} if frames is None or all(f is None for f in frames) else dict(frames=frames)
+            return self.s2mel.solve_many(items, n_timesteps=25, inference_cfg_rate=0.7, noises=noises, **kw)
         mels = []
         for i, (latent, codes, pc, rm, st) in enumerate(items):
             lens = torch.tensor([codes.shape[1]], dtype=torch.long, device=self.device)
             if self.s2mel is not None:
+                kw = {} if frames is None or frames[i] is None else dict(frames=frames[i])
                 mels.append(self.s2mel(latent, codes, lens, pc, rm, st, n_timesteps=25, inference_cfg_rate=0.7,
-                                       noise=None if noises is None else noises[i]))
+                                       noise=None if noises is None else noises[i], **kw))
             else:
                 mels.append(self._stage("s2mel", None)(latent, codes, lens, spk))
         return mels
@@ -826,11 +831,50 @@ class IndexTTS2:
                              "the whole programme, which a stream does not have")
         return _output.check_level(output_loudness, output_peak)
 
+    last_duration = None  # the pace report of the last call: see `infer` / `infer_many`
+
+    def _rate_control(self, speed, duration, stream_return=False):
+        """-> (speed | None, duration | None) of a call that asks for a pace; ValueError for a value outside `s2mel.SPEED_RANGE`, a
+        duration that is not a positive number, both together (a duration implies its speed) and a duration on a stream (the fit
+        needs every segment's code count before the first mel); NotImplementedError when the s2mel stage is an injected one."""
+        if speed is None and duration is None:
+            return None, None
+        if speed is not None and duration is not None:
+            raise ValueError("speed and duration cannot be combined: a duration fixes the speaking rate itself")
+        if duration is not None and stream_return:
+            raise ValueError("duration cannot be combined with stream_return=True: the fit needs every segment's codes before the first mel")
+        speed, duration = check_speed(speed), _output.check_duration(duration)
+        if self.s2mel is None:
+            raise NotImplementedError("speed / duration set the frame count of the built-in s2mel stage (`S2Mel`: s2mel_state_dict=... or "
+                                      "model_dir/<s2mel_checkpoint>); an injected `Glue.s2mel` has no such argument")
+        return speed, duration
+
+    @staticmethod
+    def _paced_frames(items, speed=None, duration=None, rate=22050, interval_silence=200):
+        """s2mel items -> (natural frame counts, the frame counts to ask for | None, delivered samples | None): `target_frames` at
+        `speed`, or the fit of `duration` seconds at `rate` (`output.fit_frames`; DurationError when the range cannot reach it)."""
+        natural = [target_frames(it[1].shape[1]) for it in items]
+        if not items:
+            return natural, None, None
+        if duration is not None:
+            frames, total, _ = _output.fit_frames(natural, duration, rate, interval_silence)
+            return natural, frames, total
+        if speed is not None:
+            return natural, [target_frames(it[1].shape[1], speed) for it in items], None
+        return natural, None, None
+
+    @staticmethod
+    def _duration_report(natural, frames, rate, interval_silence, delivered):
+        """-> dict(natural_s, delivered_s, speed, pad_samples): the programme at its natural pace and as delivered (seconds at the
+        delivered rate, gaps included), the effective speed sum(natural) / sum(frames), the trailing samples of silence."""
+        return dict(natural_s=_output.delivered_len(natural, rate, interval_silence) / float(rate), delivered_s=delivered / float(rate),
+                    speed=sum(natural) / float(sum(frames)), pad_samples=int(delivered - _output.delivered_len(frames, rate, interval_silence)))
+
     # ------------------------------------------------------------------ API
     def infer(self, spk_audio_prompt, text, output_path, emo_audio_prompt=None, emo_alpha=1.0, emo_vector=None,
               use_emo_text=False, emo_text=None, use_random=False, interval_silence=200, verbose=False,
               max_text_tokens_per_segment=120, stream_return=False, more_segment_before=0, output_sample_rate=None,
-              output_encoding=None, output_loudness=None, output_peak=None, **generation_kwargs):
+              output_encoding=None, output_loudness=None, output_peak=None, speed=None, duration=None, **generation_kwargs):
         """`output_sample_rate` (one of `output.SAMPLE_RATES`) / `output_encoding` (`pcm_s16le`, `mulaw`, `alaw`): the output stage on
         the device (output.py) takes the place of the host-side cat and int16 cast -- the `(sr, pcm)` return, the file at
         `output_path` and `last_timing["audio_length"]` follow the requested rate; pcm is uint8 for the G.711 encodings.  With
@@ -842,7 +886,19 @@ class IndexTTS2:
         and applies ONE gain before the conversion -- lowered, never limited, when the ceiling would be passed.  Either one routes
         the request through the output stage (22 050 Hz `pcm_s16le` when no format is asked) and is refused with
         `stream_return=True`.  Afterwards `last_loudness` is dict(measured_lufs | None, gain_db, peak_dbfs_in, target_met), or None
-        when neither was given -- and then nothing changes anywhere."""
+        when neither was given -- and then nothing changes anywhere.
+
+        `speed` (speaking rate, a float in `s2mel.SPEED_RANGE` = [0.5, 2.0]): the length regulator stretches every segment's codes to
+        `target_frames(n, speed)` mel frames -- tempo changes, pitch does not; the codes are those of any other speed.  `duration`
+        (seconds of the whole delivered programme, gaps included, at the delivered rate): the frame counts are fitted once every
+        segment's codes are known (`output.fit_frames`: proportional to the natural ones, the largest total that fits), and trailing
+        silence fills the rest: exactly int(duration * rate + 0.5) samples leave, through the output stage (22 050 Hz `pcm_s16le`
+        when no format is asked).  A duration whose implied speed leaves the range raises `output.DurationError` (a ValueError with
+        `natural_s`, `min_s`, `max_s`).  The two are refused together, `duration` also with `stream_return=True`, and either with an
+        injected `Glue.s2mel` (NotImplementedError).  Afterwards `last_duration` is dict(natural_s, delivered_s, speed, pad_samples),
+        or None when neither was given -- and then nothing changes anywhere."""
+        if speed is not None or duration is not None:
+            self._rate_control(speed, duration, stream_return)
         if output_sample_rate is not None or output_encoding is not None:  # refused here, not at the generator's first step
             self._output_format(output_sample_rate, output_encoding, stream_return)
         if output_loudness is not None or output_peak is not None:
@@ -850,7 +906,8 @@ class IndexTTS2:
         gen = self.infer_generator(spk_audio_prompt, text, output_path, emo_audio_prompt, emo_alpha, emo_vector, use_emo_text,
                                    emo_text, use_random, interval_silence, verbose, max_text_tokens_per_segment, stream_return,
                                    more_segment_before, output_sample_rate=output_sample_rate, output_encoding=output_encoding,
-                                   output_loudness=output_loudness, output_peak=output_peak, **generation_kwargs)
+                                   output_loudness=output_loudness, output_peak=output_peak,
+                                   **({} if speed is None and duration is None else dict(speed=speed, duration=duration)), **generation_kwargs)
         if stream_return:
             return gen
         try:
@@ -860,7 +917,7 @@ class IndexTTS2:
 
     @torch.no_grad()
     def infer_many(self, requests, interval_silence=200, max_text_tokens_per_segment=120, decode_slots=8, output_sample_rate=None,
-                   output_encoding=None, output_loudness=None, output_peak=None, **generation_kwargs):
+                   output_encoding=None, output_loudness=None, output_peak=None, speed=None, duration=None, **generation_kwargs):
         """Several `/tts` requests served TOGETHER (the worker's global lock, server.py:25,384, replaced by the
         decode scheduler): every request's segments share the decode slots -- the weights are read once per step for all of them
         -- and the post-decode stages run per segment as in `infer`, through the same helpers.  Each request is a dict with
@@ -896,6 +953,12 @@ class IndexTTS2:
         not pin it either, and a bad value fails that request only); a request with either leaves through the output stage.
         `last_loudness` is then a list with one entry per request: the level report, or None where no control was asked.
 
+        `speed` / `duration` (see `infer`) hold for the call; a request may carry its own `speed` or `duration` (then the call's pair
+        does not apply to it; they do not pin it, and a bad value or a duration that cannot be met fails that request only).  The
+        decode and the latent pass do not see them.  A request with a duration leaves through the output stage.  A pinned request
+        with either keeps its guarantee also under IXTTS_S2MEL_BATCH=1: its segments are then packed among themselves, not with
+        the rest of the batch.  `last_duration` is a list with one entry per request: the pace report, or None where neither was asked.
+
         Returns one entry per request: `(22050, int16 [N, 1])` (`(rate, int16 | uint8 [N, 1])` with a format), None (empty text), or the EXCEPTION that
         request raised (bad prompt audio, a code outside the codebook ...) -- one request's failure leaves the others of the
         batch alone."""
@@ -927,7 +990,9 @@ class IndexTTS2:
                        rq["encoding"] if rq.get("encoding") is not None else output_encoding)
                 level = self._output_level(rq["loudness"] if rq.get("loudness") is not None else output_loudness,
                                            rq["peak"] if rq.get("peak") is not None else output_peak)  # a bad value fails this request
-                if fmt == (None, None) and level is None:
+                own = rq.get("speed") is not None or rq.get("duration") is not None  # the request's own pace, else the call's
+                pace = self._rate_control(rq.get("speed") if own else speed, rq.get("duration") if own else duration)  # a bad value fails this request
+                if fmt == (None, None) and level is None and pace[1] is None:
                     fmt = None
                 else:
                     self._output_format(*fmt)  # a value outside the accepted sets fails this request
@@ -944,7 +1009,7 @@ class IndexTTS2:
                 mine = [self._segment(cl, ids, eng, gr.max_mel_tokens, request=ri, index=si, stream=si if pinned else None, sampler=sampler,
                                       constraints=cons, processors=procs)
                         for si, ids in enumerate(segments)]
-                plans[ri] = dict(spk=spk, cl=cl, segments=segments, seed=gr.seed if pinned else None, fmt=fmt, level=level)
+                plans[ri] = dict(spk=spk, cl=cl, segments=segments, seed=gr.seed if pinned else None, fmt=fmt, level=level, pace=pace)
                 classes.setdefault(nb, []).extend(mine)  # only once the whole request is known to be well-formed
             except Exception as e:  # this request only
                 failed[ri] = e
@@ -994,6 +1059,13 @@ class IndexTTS2:
                                  for si, lt in zip(kept, plan["latents"])]
                 # a pinned request's audio is a function of the request: the built-in s2mel's noise comes from its seed, per segment
                 pin = plan["seed"] is not None and self.s2mel is not None
+                plan["frames"] = None
+                if plan["pace"] != (None, None):  # the frame counts under the request's speed, or fitted to its duration (which may refuse)
+                    plan["rate"] = _output.check_format(*plan["fmt"])[0] if plan["fmt"] is not None else 22050
+                    plan["natural"], plan["frames"], plan["total"] = self._paced_frames(plan["items"], *plan["pace"], plan["rate"], interval_silence)
+                    plan["noises"] = [self._pinned_noise(it, plan["seed"], si, fr) if pin else None
+                                      for si, it, fr in zip(kept, plan["items"], plan["frames"])]
+                    continue
                 plan["noises"] = [self._pinned_noise(it, plan["seed"], si) if pin else None for si, it in zip(kept, plan["items"])]
             except Exception as e:  # this request only
                 failed[ri] = e
@@ -1001,18 +1073,28 @@ class IndexTTS2:
         # is returned for every request of the batch; default, or an injected s2mel stage: segment after segment
         live = [ri for ri in range(len(plans)) if ri not in failed]
         if self.s2mel is not None and s2mel_batching():
+            # a pinned request with a pace: a pack of its own, so that its bits stay a function of the request alone
+            alone = [ri for ri in live if plans[ri]["frames"] is not None and plans[ri]["seed"] is not None]
+            for ri in alone:
+                try:
+                    plans[ri]["mels"] = self._mels(plans[ri]["items"], None, packed=True, noises=plans[ri]["noises"], frames=plans[ri]["frames"])
+                except Exception as e:  # this request only
+                    failed[ri] = e
+            live = [ri for ri in live if ri not in alone]
             try:
-                mels = iter(self._mels([it for ri in live for it in plans[ri]["items"]], None, packed=True,
-                                       noises=[z for ri in live for z in plans[ri]["noises"]]))
-                for ri in live:
-                    plans[ri]["mels"] = [next(mels) for _ in plans[ri]["items"]]
+                if live or not alone:
+                    frames = [f for ri in live for f in (plans[ri]["frames"] or [None] * len(plans[ri]["items"]))]
+                    mels = iter(self._mels([it for ri in live for it in plans[ri]["items"]], None, packed=True,
+                                           noises=[z for ri in live for z in plans[ri]["noises"]], frames=frames))
+                    for ri in live:
+                        plans[ri]["mels"] = [next(mels) for _ in plans[ri]["items"]]
             except Exception as e:
                 for ri in live:
                     failed[ri] = e
         else:
             for ri in live:
                 try:
-                    plans[ri]["mels"] = self._mels(plans[ri]["items"], plans[ri]["spk"], noises=plans[ri]["noises"])
+                    plans[ri]["mels"] = self._mels(plans[ri]["items"], plans[ri]["spk"], noises=plans[ri]["noises"], frames=plans[ri]["frames"])
                 except Exception as e:  # this request only
                     failed[ri] = e
         # vocoder: the mels of every surviving request in batched passes (`vocode_many`; IXTTS_BV_BATCH=0, or an injected vocoder:
@@ -1028,15 +1110,17 @@ class IndexTTS2:
         if mine:
             try:
                 args = ([plans[ri]["pcm"] for ri in mine], [plans[ri]["fmt"][0] for ri in mine], [plans[ri]["fmt"][1] for ri in mine], interval_silence)
+                totals = [plans[ri].get("total") for ri in mine]  # the sample counts of the requests with a duration
+                kw = {} if all(t is None for t in totals) else dict(totals=totals)
                 if any(plans[ri]["level"] is not None for ri in mine):  # (a call without a level control makes the call it always made)
                     levels, reports = [plans[ri]["level"] or (None, None) for ri in mine], []
-                    res = _output.finish_pcm_many(*args, loudness=[lv[0] for lv in levels], peak=[lv[1] for lv in levels], reports=reports)
+                    res = _output.finish_pcm_many(*args, loudness=[lv[0] for lv in levels], peak=[lv[1] for lv in levels], reports=reports, **kw)
                     for ri, rep in zip(mine, reports):
                         self.last_loudness[ri] = rep
                         if rep is not None:
                             logger.info(f"infer_many: request {ri} level: {rep}")
                 else:
-                    res = _output.finish_pcm_many(*args)
+                    res = _output.finish_pcm_many(*args, **kw)
                 formatted = dict(zip(mine, res))
             except Exception as e:
                 formatted = {ri: e for ri in mine}
@@ -1060,6 +1144,10 @@ class IndexTTS2:
                 out.append((22050, wav.type(torch.int16).numpy().T))
             except Exception as e:  # this request only
                 out.append(e)
+        self.last_duration = [None] * len(requests)
+        for ri, plan in enumerate(plans):
+            if isinstance(out[ri], tuple) and plan.get("frames"):
+                self.last_duration[ri] = self._duration_report(plan["natural"], plan["frames"], plan["rate"], interval_silence, out[ri][1].shape[0])
         total = time.perf_counter() - start
         audio = sum(o[1].shape[0] for o in out if isinstance(o, tuple)) / 22050.0
         if formatted:  # every result at its own rate
@@ -1072,13 +1160,16 @@ class IndexTTS2:
     def infer_generator(self, spk_audio_prompt, text, output_path, emo_audio_prompt=None, emo_alpha=1.0, emo_vector=None,
                         use_emo_text=False, emo_text=None, use_random=False, interval_silence=200, verbose=False,
                         max_text_tokens_per_segment=120, stream_return=False, quick_streaming_tokens=0, output_sample_rate=None,
-                        output_encoding=None, output_loudness=None, output_peak=None, **generation_kwargs):
+                        output_encoding=None, output_loudness=None, output_peak=None, speed=None, duration=None, **generation_kwargs):
         logger.info("Starting inference...")
         start_time = time.perf_counter()
         # an output format or a level (see `infer`): the segments stay on the device and leave through `output.finish_pcm`
         level = self._output_level(output_loudness, output_peak, stream_return)
         self.last_loudness = None
-        fmt = output_sample_rate is not None or output_encoding is not None or level is not None
+        speed, duration = self._rate_control(speed, duration, stream_return)  # a pace (see `infer`); a duration leaves through the output stage too
+        self.last_duration = None
+        paced = []  # (natural, asked) frame counts per segment, for `last_duration`
+        fmt = output_sample_rate is not None or output_encoding is not None or level is not None or duration is not None
         if fmt:
             out_rate, out_enc = self._output_format(output_sample_rate, output_encoding, stream_return)
         self._prompt_stages()
@@ -1123,7 +1214,8 @@ class IndexTTS2:
         gpt_gen_time += time.perf_counter() - m0
         # several segments, whole audio at the end, IXTTS_S2MEL_BATCH=1: their CFM solves run as ONE packed solve (default: segment
         # after segment, as the reference); streaming keeps the per-segment order for its first-chunk latency
-        packed = [] if (not stream_return and len(segments) > 1 and self.s2mel is not None and s2mel_batching()) else None
+        pack_solve = not stream_return and len(segments) > 1 and self.s2mel is not None and s2mel_batching()
+        packed = [] if pack_solve or duration is not None else None  # (a duration is fitted once every segment's codes are known)
         wavs = []
         has_warned = False
         silence = None
@@ -1174,7 +1266,12 @@ class IndexTTS2:
                 packed.append(item)
                 continue
             m0 = time.perf_counter()
-            mel = self._mels([item], spk)[0]
+            if speed is None:
+                mel = self._mels([item], spk)[0]
+            else:
+                natural, frames, _ = self._paced_frames([item], speed)
+                paced.append((natural[0], frames[0]))
+                mel = self._mels([item], spk, frames=frames)[0]
             torch.cuda.synchronize(self.device)
             s2mel_time += time.perf_counter() - m0
             m0 = time.perf_counter()
@@ -1197,7 +1294,13 @@ class IndexTTS2:
                 yield silence
         if packed:
             m0 = time.perf_counter()
-            mels = self._mels(packed, spk, packed=True)
+            total = None
+            if speed is None and duration is None:
+                mels = self._mels(packed, spk, packed=True)
+            else:
+                natural, frames, total = self._paced_frames(packed, speed, duration, out_rate if fmt else sampling_rate, interval_silence)
+                paced = list(zip(natural, frames))
+                mels = self._mels(packed, spk, packed=pack_solve, frames=frames)
             torch.cuda.synchronize(self.device)
             s2mel_time += time.perf_counter() - m0
             m0 = time.perf_counter()
@@ -1213,12 +1316,13 @@ class IndexTTS2:
         if not wavs:
             return
         if fmt:
+            kw = {} if duration is None else dict(total=total)  # (without a duration: the call it always made)
             if level is None:
-                sampling_rate, pcm = _output.finish_pcm(wavs, output_sample_rate, output_encoding, interval_silence)
+                sampling_rate, pcm = _output.finish_pcm(wavs, output_sample_rate, output_encoding, interval_silence, **kw)
             else:
                 reports = []
                 sampling_rate, pcm = _output.finish_pcm(wavs, output_sample_rate, output_encoding, interval_silence, loudness=level[0],
-                                                        peak=level[1], reports=reports)
+                                                        peak=level[1], reports=reports, **kw)
                 self.last_loudness = reports[0]
                 logger.info(f"output level: {self.last_loudness}")
             wav_length = pcm.shape[0] / sampling_rate
@@ -1227,6 +1331,10 @@ class IndexTTS2:
             wavs = self.insert_interval_silence(wavs, sampling_rate=sampling_rate, interval_silence=interval_silence)
             wav = torch.cat(wavs, dim=1)
             wav_length = wav.shape[-1] / sampling_rate
+        if paced:
+            self.last_duration = self._duration_report([a for a, _ in paced], [b for _, b in paced], sampling_rate, interval_silence,
+                                                       int(round(wav_length * sampling_rate)))
+            logger.info(f"pace: {self.last_duration}")
         logger.info(f"gpt_gen_time: {gpt_gen_time:.2f} seconds")
         logger.info(f"gpt_forward_time: {gpt_forward_time:.2f} seconds")
         logger.info(f"s2mel_time: {s2mel_time:.2f} seconds")

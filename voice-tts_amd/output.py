@@ -181,6 +181,79 @@ def gap_len(sample_rate, interval_silence=200):
     return int(sample_rate * interval_silence / 1000.0)
 
 
+# --------------------------------------------------------------------------- a target duration: the frame counts that fit it
+HOP = 256  # samples of one mel frame at MODEL_RATE
+
+
+class DurationError(ValueError):
+    """A `duration` the speaking-rate range cannot reach.  `natural_s`: what the request delivers at its natural pace; `min_s`,
+    `max_s`: the durations its fastest and slowest allowed pace deliver (both can be asked for), all at the delivered rate."""
+
+    def __init__(self, duration, natural_s, min_s, max_s):
+        self.duration, self.natural_s, self.min_s, self.max_s = float(duration), float(natural_s), float(min_s), float(max_s)
+        super().__init__(f"duration {duration!r} s cannot be met: the natural duration is {natural_s:.3f} s, a duration in "
+                         f"[{min_s:.3f}, {max_s:.3f}] s can be")
+
+
+def check_duration(duration):
+    """-> None, or `duration` as a float; ValueError for a bool, a NaN, an infinity, anything that is not a number or not positive."""
+    if duration is None:
+        return None
+    if isinstance(duration, bool) or not isinstance(duration, (int, float, np.integer, np.floating)) or not 0.0 < float(duration) < math.inf:
+        raise ValueError(f"duration {duration!r} is not a positive number of seconds")
+    return float(duration)
+
+
+def delivered_len(frames, sample_rate=MODEL_RATE, interval_silence=200):
+    """Samples a programme of segments of `frames` mel frames delivers at `sample_rate`: every segment under the resampler's
+    ceil(n * new / orig) rule, `gap_len` samples between two segments."""
+    return sum(resampled_len(f * HOP, MODEL_RATE, sample_rate) for f in frames) + max(0, len(frames) - 1) * gap_len(sample_rate, interval_silence)
+
+
+def share_frames(natural, total):
+    """`total` frames among the segments in proportion to their `natural` frame counts, by the largest remainder: every count within
+    1 of its exact share, and at least 1 (total >= len(natural))."""
+    assert total >= len(natural) and all(f >= 1 for f in natural)
+    S = sum(natural)
+    out = [f * total // S for f in natural]  # exact integer floors of the shares
+    order = sorted(range(len(natural)), key=lambda i: (-(natural[i] * total % S), i))
+    for i in order[:total - sum(out)]:
+        out[i] += 1
+    for i in range(len(out)):  # a share below 1 that rounded down: one frame from the segment furthest above its share
+        if out[i] == 0:
+            j = max((k for k in range(len(out)) if out[k] >= 2), key=lambda k: out[k] * S - natural[k] * total)
+            out[j] -= 1
+            out[i] = 1
+    return out
+
+
+def fit_frames(natural, duration, sample_rate=MODEL_RATE, interval_silence=200, speed_range=None):
+    """The frame counts with which segments of `natural` frames (>= 1 each) fill `duration` seconds at `sample_rate` -> (frames,
+    N, pad): N = int(duration * sample_rate + 0.5) samples are delivered, `frames` (`share_frames`) has the largest total whose
+    `delivered_len` does not exceed N, and pad = N - delivered_len(frames) trailing samples of silence fill the rest -- less than
+    one frame's worth of delivered samples plus one sample per segment (each segment's ceil adds less than one).  Speech is never
+    cut.  `DurationError` when the implied speed sum(natural) / sum(frames) leaves `speed_range` (`s2mel.SPEED_RANGE`)."""
+    if speed_range is None:
+        from .s2mel import SPEED_RANGE as speed_range
+    natural = [int(f) for f in natural]
+    duration = check_duration(duration)
+    S, n = sum(natural), len(natural)
+    N = int(duration * sample_rate + 0.5)
+    orig, new = resample_ratio(MODEL_RATE, sample_rate)
+    gaps = max(0, n - 1) * gap_len(sample_rate, interval_silence)
+    length = lambda total: delivered_len(share_frames(natural, total), sample_rate, interval_silence)  # noqa: E731
+    lo_speed, hi_speed = speed_range
+    least = max(n, math.ceil(S / hi_speed))  # the totals whose implied speed lies in the range
+    most = max(least, math.floor(S / lo_speed))
+    total = (N - gaps) * orig // (HOP * new) if N > gaps else 0  # no larger total fits: a segment delivers at least its exact length
+    while total >= max(n, 1) and length(total) > N:
+        total -= 1
+    if not least <= total <= most:
+        raise DurationError(duration, length(S) / sample_rate, length(least) / sample_rate, length(most) / sample_rate)
+    frames = share_frames(natural, total)
+    return frames, N, N - delivered_len(frames, sample_rate, interval_silence)
+
+
 # --------------------------------------------------------------------------- loudness target and peak ceiling (ITU-R BS.1770-4)
 LOUDNESS_RANGE = (-50.0, -5.0)  # LUFS
 PEAK_RANGE = (-20.0, 0.0)  # dBFS, sample peak
@@ -338,7 +411,7 @@ def pcm_assemble_gain(x, rows, total, encoding, gains, out=None):
     return out
 
 
-def finish_pcm_many(wav_lists, sample_rates, encodings, interval_silence=200, loudness=None, peak=None, reports=None):
+def finish_pcm_many(wav_lists, sample_rates, encodings, interval_silence=200, loudness=None, peak=None, reports=None, totals=None):
     """The segments of several requests (each a list of fp32 [1, n_i] device tensors at 22 050 Hz, +-32767) -> one
     `(sr, ndarray [N, 1])` per request, int16 or uint8 (None for a request without segments): segment, `int(sr * interval_silence /
     1000)` samples of silence, segment ...  One resample launch per distinct target rate, one assemble launch per distinct
@@ -349,7 +422,10 @@ def finish_pcm_many(wav_lists, sample_rates, encodings, interval_silence=200, lo
     its rate, gaps included -- is measured after the resample launches (`measure_levels`), and its samples are converted from the
     fp32 product gain * x; the records ride behind the PCM in the same buffer, so there is still one copy and no wait before it.
     `reports`: a list that receives one `level_report` per request (None where no control was asked).  A request without a control
-    produces the bytes it produces without these arguments."""
+    produces the bytes it produces without these arguments.
+
+    `totals` (one entry per request, None: not asked): the request delivers exactly this many samples -- what follows its last
+    segment holds the encoding's code for zero, and a measured programme extends over it.  ValueError when the segments are longer."""
     fmts = [check_format(sr, enc) for sr, enc in zip(sample_rates, encodings)]
     levels = [check_level(lo, pk) for lo, pk in zip(loudness or [None] * len(fmts), peak or [None] * len(fmts))]
     if reports is not None:
@@ -392,6 +468,10 @@ def finish_pcm_many(wav_lists, sample_rates, encodings, interval_silence=200, lo
                 total += gap if k else 0
                 rows.append((src[i, k][0], src[i, k][1], total))
                 total += src[i, k][1]
+            if totals is not None and totals[i] is not None:
+                if int(totals[i]) < total - start:
+                    raise ValueError(f"request {i}: {total - start} samples of segments and gaps do not fit a total of {int(totals[i])}")
+                total = start + int(totals[i])
             where[i] = (enc, start, total - start)
         width = 2 if enc == "pcm_s16le" else 1
         by_enc[enc] = (rows, total, nbytes)
@@ -407,6 +487,8 @@ def finish_pcm_many(wav_lists, sample_rates, encodings, interval_silence=200, lo
                 at += gap if k else 0
                 mine.append((src[i, k][0], src[i, k][1], at))
                 at += src[i, k][1]
+            if totals is not None and totals[i] is not None:
+                at = max(at, int(totals[i]))  # the trailing silence is part of what is delivered
             progs.append((mine, at, fmts[i][0], levels[i][0], levels[i][1]))
         plan = LevelPlan(progs, device)
         rec_off, nbytes = nbytes, nbytes + plan.n * _RECORD.itemsize
@@ -438,9 +520,11 @@ def finish_pcm_many(wav_lists, sample_rates, encodings, interval_silence=200, lo
     return out
 
 
-def finish_pcm(wavs, sample_rate=None, encoding=None, interval_silence=200, loudness=None, peak=None, reports=None):
+def finish_pcm(wavs, sample_rate=None, encoding=None, interval_silence=200, loudness=None, peak=None, reports=None, total=None):
     """One request's segments -> `(sr, ndarray [N, 1])`, int16 (`pcm_s16le`) or uint8 (`mulaw`, `alaw`); sr = the requested rate, or
     22050.  See `finish_pcm_many`."""
+    if total is not None:
+        return finish_pcm_many([list(wavs)], [sample_rate], [encoding], interval_silence, [loudness], [peak], reports, totals=[total])[0]
     if loudness is None and peak is None:
         return finish_pcm_many([list(wavs)], [sample_rate], [encoding], interval_silence)[0]
     return finish_pcm_many([list(wavs)], [sample_rate], [encoding], interval_silence, [loudness], [peak], reports)[0]

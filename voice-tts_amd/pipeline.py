@@ -249,21 +249,25 @@ class HotPath:
         self.s2mel_model = S2Mel(W, S2MEL_CFG if cfg is None else cfg, device=self.device)
         return self
 
-    def s2mel(self, latent, codes, prompt_condition, ref_mel, style, n_timesteps=25, inference_cfg_rate=0.7, noise=None):
-        """infer_v2.py:713-731: latent [n,D] + codes [n] -> mel [1,80,floor(1.72 n)] (fp32, as the reference runs this stage)."""
+    def s2mel(self, latent, codes, prompt_condition, ref_mel, style, n_timesteps=25, inference_cfg_rate=0.7, noise=None, frames=None):
+        """infer_v2.py:713-731: latent [n,D] + codes [n] -> mel [1,80,F] (fp32, as the reference runs this stage); F =
+        `s2mel.target_frames(n)`, or `frames` (e.g. `target_frames(n, speed)`: the speaking rate)."""
         codes = torch.as_tensor(np.asarray(codes), dtype=torch.long, device=self.device).reshape(1, -1)
         lens = torch.tensor([codes.shape[1]], device=self.device)
+        kw = {} if frames is None else dict(frames=frames)
         return self.s2mel_model(latent.reshape(1, codes.shape[1], -1), codes, lens, prompt_condition, ref_mel, style,
-                                n_timesteps=n_timesteps, inference_cfg_rate=inference_cfg_rate, noise=noise)
+                                n_timesteps=n_timesteps, inference_cfg_rate=inference_cfg_rate, noise=noise, **kw)
 
-    def s2mel_many(self, segments, n_timesteps=25, inference_cfg_rate=0.7, noises=None):
+    def s2mel_many(self, segments, n_timesteps=25, inference_cfg_rate=0.7, noises=None, frames=None):
         """`s2mel` for several segments in ONE packed CFM solve (S2Mel.solve_many): segments are (latent [n,D], codes [n],
-        prompt_condition, ref_mel, style) tuples; returns one mel [1,80,floor(1.72 n)] per segment."""
+        prompt_condition, ref_mel, style) tuples; returns one mel [1,80,F_i] per segment, F_i = `s2mel.target_frames(n_i)` or
+        `frames[i]` where that is not None."""
         items = []
         for latent, codes, prompt_condition, ref_mel, style in segments:
             codes = torch.as_tensor(np.asarray(codes), dtype=torch.long, device=self.device).reshape(1, -1)
             items.append((latent.reshape(1, codes.shape[1], -1), codes, prompt_condition, ref_mel, style))
-        return self.s2mel_model.solve_many(items, n_timesteps=n_timesteps, inference_cfg_rate=inference_cfg_rate, noises=noises)
+        kw = {} if frames is None else dict(frames=frames)
+        return self.s2mel_model.solve_many(items, n_timesteps=n_timesteps, inference_cfg_rate=inference_cfg_rate, noises=noises, **kw)
 
     # ------------------------------------------------------------------ V0-V5
     def vocode(self, mel):
@@ -275,11 +279,13 @@ class HotPath:
         return vocode_many(self.bigvgan, mels)
 
 
-def audio_seconds(n_codes_per_segment, interval_silence_ms=200):
-    """Audio length the reference produces for these code counts (infer_v2.py:719,752-754)."""
+def audio_seconds(n_codes_per_segment, interval_silence_ms=200, speed=1.0):
+    """Audio length the reference produces for these code counts (infer_v2.py:719,752-754); `speed`: at that speaking rate."""
+    from .s2mel import target_frames
+
     total = 0.0
     for n in n_codes_per_segment:
-        frames = int(n * 1.72)
+        frames = target_frames(n, None if speed == 1.0 else speed)
         total += frames * 256 / SAMPLE_RATE
     total += (len(n_codes_per_segment) - 1) * interval_silence_ms / 1000.0
     return total

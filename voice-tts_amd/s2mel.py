@@ -32,6 +32,34 @@ S2MEL_CFG = dict(
 )
 
 
+FRAMES_PER_CODE = 1.72  # mel frames (22 050 Hz, hop 256) per semantic code at the natural pace (infer_v2.py:719)
+SPEED_RANGE = (0.5, 2.0)  # an interface condition, not a measurement: at 0.5 the nearest-neighbour regulator repeats every code frame 3-4 times
+
+
+def check_speed(speed):
+    """-> None, or `speed` as a float; ValueError for a bool, a NaN, anything that is not a number and a value outside `SPEED_RANGE`."""
+    if speed is None:
+        return None
+    lo, hi = SPEED_RANGE
+    if isinstance(speed, bool) or not isinstance(speed, (int, float)) or not lo <= float(speed) <= hi:  # (NaN fails the comparison)
+        raise ValueError(f"speed {speed!r} is not a number in [{lo:g}, {hi:g}]")
+    return float(speed)
+
+
+def target_frames(n_codes, speed=None):
+    """Mel frames the length regulator stretches `n_codes` codes to: THE definition (`S2Mel`, the pinned noise, `audio_seconds`).
+    `speed` None: `(code_lens * 1.72).long()` as the reference evaluates it (infer_v2.py:719) -- an integer tensor times a Python
+    float in torch's default dtype.  Otherwise `(code_lens * 1.72 / speed).long()`, at least 1 frame (1 code at speed 2.0 truncates
+    to 0).  More frames per code is a slower tempo at the same pitch: the vocoder still sees 22 050 Hz mels.  A tensor of lengths
+    gives a tensor (same device), an int an int."""
+    code_lens = n_codes if torch.is_tensor(n_codes) else torch.tensor([int(n_codes)])
+    if speed is None:
+        frames = (code_lens * FRAMES_PER_CODE).long()
+    else:
+        frames = (code_lens * FRAMES_PER_CODE / speed).long().clamp_(min=1)
+    return frames if torch.is_tensor(n_codes) else int(frames)
+
+
 def tiny_s2mel_cfg(**kw):
     c = dict(S2MEL_CFG)
     c.update(hidden_dim=64, num_heads=2, depth=5, content_dim=32, style_dim=12, wavenet_hidden=64, wavenet_layers=3,
@@ -901,10 +929,12 @@ class S2Mel:
 
     # ------------------------------------------------------------------ the stage as infer_v2.py:713-731 calls it
     @torch.no_grad()
-    def __call__(self, latent, codes, code_lens, prompt_condition, ref_mel, style, n_timesteps=25, inference_cfg_rate=0.7, noise=None):
+    def __call__(self, latent, codes, code_lens, prompt_condition, ref_mel, style, n_timesteps=25, inference_cfg_rate=0.7, noise=None, frames=None):
+        """`frames` (an int >= 1): the regulator stretches the codes to this many mel frames instead of `target_frames(code_lens)` --
+        the speaking rate (`target_frames(n, speed)`) or a fitted duration; the CFM noise is then [1, 80, Tp + frames]."""
         lat = self.gpt_layer(latent)
         S = self.vq2emb(codes) + lat
-        target = (code_lens * 1.72).long()
+        target = target_frames(code_lens) if frames is None else torch.tensor([int(frames)], device=code_lens.device)
         cond = self.length_regulator(S, target)
         cat = torch.cat([prompt_condition, cond], dim=1)
         lens = torch.tensor([cat.shape[1]], device=cat.device, dtype=torch.long)
@@ -1091,17 +1121,19 @@ class S2Mel:
         return [x[xo[i]:xo[i + 1]].t()[None] for i in range(n)]
 
     @torch.no_grad()
-    def solve_many(self, items, n_timesteps=25, inference_cfg_rate=0.7, noises=None):
+    def solve_many(self, items, n_timesteps=25, inference_cfg_rate=0.7, noises=None, frames=None):
         """`__call__` for several segments: items are (latent, codes, prompt_condition, ref_mel, style) as `__call__` takes them (code
         lengths = codes.shape[1]); returns one mel [1, 80, frames_i] per item, each equal to its own `__call__` up to fp32
         reassociation.  The length regulator runs per item; the CFM solves of all items run as ONE Euler loop over packed rows
         (`_cfm_packed`), at most IXTTS_S2MEL_BATCH_FRAMES frames per pack (larger requests: several packs, grouped by length).  With
-        noises None each item's noise is drawn as n successive `__call__`s would draw it (item order, default generator)."""
+        noises None each item's noise is drawn as n successive `__call__`s would draw it (item order, default generator).  `frames`: per
+        item None or the frame count its `__call__` would be given."""
         segs = []
         for i, (latent, codes, prompt_condition, ref_mel, style) in enumerate(items):
             code_lens = torch.tensor([codes.shape[-1]], device=codes.device)
             S = self.vq2emb(codes) + self.gpt_layer(latent)
-            cond = self.length_regulator(S, (code_lens * 1.72).long())
+            target = target_frames(code_lens) if frames is None or frames[i] is None else torch.tensor([int(frames[i])], device=codes.device)
+            cond = self.length_regulator(S, target)
             mu = torch.cat([prompt_condition, cond], dim=1)
             T = mu.shape[1]
             z = torch.randn(1, self.cfg["in_channels"], T, device=mu.device) if noises is None or noises[i] is None else \

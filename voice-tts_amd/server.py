@@ -2,7 +2,9 @@
 
 Same endpoints, models, priorities, error codes and CLI as the reference:
   POST /tts   TTSRequest{text, spk_audio (URL | hex > 100 chars), emo_audio?, emotion? (str | {str: float in [0,1]}), emo_alpha in [0,1] = 1.0,
-                         sample_rate?, encoding?, loudness?, peak?}   (the last four are this build's: the output stage of output.py; 422 outside its sets / ranges)
+                         sample_rate?, encoding?, loudness?, peak?, speed?, duration?}   (the last six are this build's: the output stage of output.py,
+                         the speaking rate in [0.5, 2.0] and the target duration in seconds; 422 outside their sets / ranges, for speed together with
+                         duration, and for a duration the rate range cannot reach -- its detail carries natural_s, min_s, max_s)
               -> TTSResponse{audio_hex, audio_length, inference_time, rtf, text}                       (server.py:183-235,320-440)
               emo_audio beats emotion (:352-370); emo_alpha is forced to 1.0 unless emo_audio is given (:391)
   GET /       {"status","model_loaded","service","version"}                                            (:238-246)
@@ -28,7 +30,7 @@ from typing import Dict, Optional, Union
 
 from fastapi import FastAPI, HTTPException
 from fastapi.middleware.cors import CORSMiddleware
-from pydantic import BaseModel, Field, field_validator
+from pydantic import BaseModel, Field, field_validator, model_validator
 
 from .emotion import create_emotion_vector
 
@@ -85,6 +87,31 @@ class TTSRequest(BaseModel):
 
     loudness: Optional[float] = Field(None, description="target integrated loudness in LUFS (ITU-R BS.1770-4), -50 .. -5; default: the level of the synthesis")
     peak: Optional[float] = Field(None, description="sample-peak ceiling in dBFS, -20 .. 0; default -1 beside `loudness`")
+
+    speed: Optional[float] = Field(None, description="speaking rate, 0.5 .. 2.0 (tempo changes, pitch does not); default: the natural pace")
+    duration: Optional[float] = Field(None, description="seconds the whole delivered audio lasts (trailing silence fills the rest); not together with `speed`")
+
+    @field_validator("speed")
+    @classmethod
+    def _speed(cls, v):
+        from .s2mel import check_speed
+
+        check_speed(v)  # ValueError naming the range -> 422
+        return v
+
+    @field_validator("duration")
+    @classmethod
+    def _duration(cls, v):
+        from .output import check_duration
+
+        check_duration(v)
+        return v
+
+    @model_validator(mode="after")
+    def _one_pace(self):
+        if self.speed is not None and self.duration is not None:
+            raise ValueError("speed and duration cannot be combined: a duration fixes the speaking rate itself")
+        return self
 
     @field_validator("loudness", "peak")
     @classmethod
@@ -335,7 +362,8 @@ def create_app(model_factory=default_model_factory):
                     emo_vector = create_emotion_vector(request.emotion)
             # the output format goes on only when the request sets it: a model without the keywords keeps working
             fmt_kw = {k: v for k, v in (("output_sample_rate", request.sample_rate), ("output_encoding", request.encoding),
-                                        ("output_loudness", request.loudness), ("output_peak", request.peak)) if v is not None}
+                                        ("output_loudness", request.loudness), ("output_peak", request.peak), ("speed", request.speed),
+                                        ("duration", request.duration)) if v is not None}
             leveled = request.loudness is not None or request.peak is not None
             start = time.time()
             if state["batcher"] is not None:  # opt-in: queued requests decode together (IXTTS_BATCH_SLOTS)
@@ -344,7 +372,8 @@ def create_app(model_factory=default_model_factory):
                 res = state["batcher"].submit(dict(spk_audio_prompt=spk_audio_data, text=request.text, emo_audio_prompt=emo_audio_data if emo_audio_data else None,
                                                    emo_alpha=request.emo_alpha if emo_audio_data else 1.0, emo_vector=emo_vector,
                                                    **{k: v for k, v in (("sample_rate", request.sample_rate), ("encoding", request.encoding),
-                                                                        ("loudness", request.loudness), ("peak", request.peak)) if v is not None})).result()
+                                                                        ("loudness", request.loudness), ("peak", request.peak), ("speed", request.speed),
+                                                                        ("duration", request.duration)) if v is not None})).result()
                 if res is None:
                     raise RuntimeError("the text produced no speech segment")
                 sr, pcm = res
@@ -422,6 +451,8 @@ def create_app(model_factory=default_model_factory):
         except HTTPException:
             raise
         except Exception as e:
+            if type(e).__name__ == "DurationError":  # output.py: the request's own duration, outside what the speaking-rate range reaches
+                raise HTTPException(status_code=422, detail=dict(error=str(e), natural_s=e.natural_s, min_s=e.min_s, max_s=e.max_s))
             if type(e).__name__ == "UnsupportedAudioError":  # prompt.py: the built-in decoder reads RIFF/WAVE only -- the caller's input, not a server fault
                 raise HTTPException(status_code=415, detail=f"Unsupported prompt audio: {str(e)}")
             logger.error(f"TTS inference failed: {str(e)}")

@@ -680,6 +680,39 @@ int ixtts_loudness_gain(const double* energy_dev, const float* hop_peak_dev, lon
 int ixtts_pcm_assemble_gain(const float* x_dev, long x_elems, void* out_dev, long total, const int64_t* rows_dev, int n_rows, const float* gains_dev,
                             int n_gains, int encoding, void* stream);
 
+/* ---- output stage: true peak (ITU-R BS.1770 Annex 2) and a look-ahead limiter ---------------------------------------------------
+ * Programmes are described as above (`rows_dev`, and for the true peak `reqs_dev`).  Interpolator: `taps` fp64
+ * [IXTTS_TRUE_PEAK_TAPS], h[m] = sinc(m / 4) 0.5 (1 + cos(pi m / 24)) at index m + 24; the point n + k / 4 of a programme y is
+ * z[4 n + k] = sum_j h[k - 4 j] y[n + j] over the taps that exist (k = 0: the sample; k = 1 .. 3: j = -5 .. 6), fp64 in
+ * ascending j over the fp32 samples, zeros outside the programme; points exist for n in [0, extent) only.
+ *
+ * ixtts_true_peak: hop_peak_dev[slot] = the largest |z| over the points whose n lies in the hop, rounded to fp32 once, for every
+ *     programme q with modes_dev[q] == 1 (int64 [n_reqs]; null: every programme) -- the slots `ixtts_loudness_measure` filled with
+ *     the sample peak, to be launched between it and `ixtts_loudness_gain`.  One workgroup per hop; max_hops sizes the grid.
+ * ixtts_limiter: `lreqs_dev` int64 [n_reqs][IXTTS_LIMITER_REQ_COLS] = (first row, rows, start, extent, offset in out_dev, gain
+ *     index, W, offset of the window in tables_dev, mode (1: true), first partial slot), `ceilings_dev` fp64 [n_reqs] = c in sample
+ *     units, `tables_dev` fp64 = the taps, then per rate the window w[0 .. 2W], w[k] = 0.5 (1 - cos(2 pi (k + 1) / (2W + 2))) over
+ *     its sum; 1 <= W <= IXTTS_LIMITER_MAX_W.  y[n] = fp32(g x[n]) with g = gains_dev[gain index] (an index outside [0, n_gains):
+ *     1).  Detector p[n] = |y[n]|, in true mode the max with |z| at n - 3/4 .. n + 3/4; r[n] = min(1, c / p[n]), 1 where p = 0 and
+ *     outside [0, extent); m[n] = min over |k| <= W of r[n + k]; a[n] = 1 - sum_k w[k] (1 - m[n - W + k]) in fp64 (<= r[n]: every
+ *     m of the sum has n in its window); a32 = fp32(a), one ulp toward zero where that is above r[n]; out_dev[offset + n] =
+ *     a32 * y[n], one rounding, for n in [0, extent), gaps included.  One workgroup per tile of IXTTS_LIMITER_TILE samples
+ *     (max_tiles sizes the grid); tile t of a programme leaves partials_dev[2 (slot + t)] = the bits of its smallest a32 and
+ *     [.. + 1] = its samples with a32 < 1 (uint32; `partial_slots` pairs) for the host to reduce.  out_dev may be another part of
+ *     the buffer x_dev points into, disjoint from every row.  A programme its buffers cannot hold is left alone.
+ * ixtts_limiter_tile: IXTTS_LIMITER_TILE, for tests that aim at tile edges.
+ */
+#define IXTTS_TRUE_PEAK_TAPS 49
+#define IXTTS_LIMITER_TILE 1024
+#define IXTTS_LIMITER_MAX_W 240
+#define IXTTS_LIMITER_REQ_COLS 10
+int ixtts_limiter_tile(void);
+int ixtts_true_peak(const float* x_dev, long x_elems, const int64_t* rows_dev, int n_rows, const int64_t* reqs_dev, const int64_t* modes_dev, int n_reqs,
+                    long max_hops, const double* taps_dev, float* hop_peak_dev, long hops_elems, void* stream);
+int ixtts_limiter(const float* x_dev, long x_elems, const int64_t* rows_dev, int n_rows, const int64_t* lreqs_dev, const double* ceilings_dev, int n_reqs,
+                  long max_tiles, const double* tables_dev, long tables_elems, const float* gains_dev, int n_gains, float* out_dev, long out_elems,
+                  uint32_t* partials_dev, long partial_slots, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

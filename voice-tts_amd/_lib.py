@@ -58,6 +58,10 @@ LOUDNESS_COEF_COLS = 24  # IXTTS_LOUDNESS_COEF_COLS: shelf b0 b1 b2 a1 a2, high-
 LOUDNESS_MAX_HOP = 4800  # IXTTS_LOUDNESS_MAX_HOP
 LOUDNESS_CEILING_BOUND, LOUDNESS_NO_BLOCK = 1, 2  # flags of a record
 LOUDNESS_RECORD_BYTES = 24  # ixtts_loudness_record: f64 lufs, f32 gain, f32 peak, u32 flags, u32 blocks
+TRUE_PEAK_TAPS = 49  # IXTTS_TRUE_PEAK_TAPS
+LIMITER_TILE = 1024  # IXTTS_LIMITER_TILE: output samples per workgroup of the limiter (`limiter_tile()` asks the library)
+LIMITER_MAX_W = 240  # IXTTS_LIMITER_MAX_W: the look-around at 48 kHz
+LIMITER_REQ_COLS = 10  # IXTTS_LIMITER_REQ_COLS: (first row, rows, start, extent, out offset, gain index, W, window offset, mode, first partial slot)
 
 
 class QwenCfg(C.Structure):
@@ -185,6 +189,9 @@ SYMBOLS = {
     "ixtts_loudness_measure": (C.c_int, [_P, C.c_long, _P, C.c_int, _P, _P, C.c_int, C.c_long, _P, _P, C.c_long, _P]),
     "ixtts_loudness_gain": (C.c_int, [_P, _P, C.c_long, _P, _P, C.c_int, _P, _P, _P]),
     "ixtts_pcm_assemble_gain": (C.c_int, [_P, C.c_long, _P, C.c_long, _P, C.c_int, _P, C.c_int, C.c_int, _P]),
+    "ixtts_limiter_tile": (C.c_int, []),
+    "ixtts_true_peak": (C.c_int, [_P, C.c_long, _P, C.c_int, _P, _P, C.c_int, C.c_long, _P, _P, C.c_long, _P]),
+    "ixtts_limiter": (C.c_int, [_P, C.c_long, _P, C.c_int, _P, _P, C.c_int, C.c_long, _P, C.c_long, _P, C.c_int, _P, C.c_long, _P, C.c_long, _P]),
 }
 
 _lib = None
@@ -244,6 +251,11 @@ def max_batch_for(dtype):
 def resample_tile():
     """Output samples one workgroup of the resampler produces (a build constant of libixtts_hip.so)."""
     return int(lib().ixtts_resample_tile())
+
+
+def limiter_tile():
+    """Output samples one workgroup of the limiter produces (a build constant of libixtts_hip.so)."""
+    return int(lib().ixtts_limiter_tile())
 
 
 def current_stream_ptr():

@@ -831,6 +831,19 @@ class IndexTTS2:
                              "the whole programme, which a stream does not have")
         return _output.check_level(output_loudness, output_peak)
 
+    @staticmethod
+    def _output_limit(level, output_peak_mode, output_limiter, stream_return=False):
+        """`level`: what `_output_level` returned -> (level, None) when neither control is given, else (level, (peak_mode, limiter))
+        with the defaults filled in (`output.check_limit`: the limiter brings its own ceiling); ValueError for a value outside the
+        accepted ones, for "true" without anything that sets a ceiling, and for either control on a stream."""
+        if output_peak_mode is None and output_limiter is None:
+            return level, None
+        if stream_return:
+            raise ValueError("output_peak_mode / output_limiter cannot be combined with stream_return=True: the ceiling is held over "
+                             "the whole programme, which a stream does not have")
+        level, mode, limiter = _output.check_limit(output_peak_mode, output_limiter, level)
+        return level, (mode, limiter)
+
     last_duration = None  # the pace report of the last call: see `infer` / `infer_many`
 
     def _rate_control(self, speed, duration, stream_return=False):
@@ -874,7 +887,8 @@ class IndexTTS2:
     def infer(self, spk_audio_prompt, text, output_path, emo_audio_prompt=None, emo_alpha=1.0, emo_vector=None,
               use_emo_text=False, emo_text=None, use_random=False, interval_silence=200, verbose=False,
               max_text_tokens_per_segment=120, stream_return=False, more_segment_before=0, output_sample_rate=None,
-              output_encoding=None, output_loudness=None, output_peak=None, speed=None, duration=None, **generation_kwargs):
+              output_encoding=None, output_loudness=None, output_peak=None, speed=None, duration=None, output_peak_mode=None,
+              output_limiter=None, **generation_kwargs):
         """`output_sample_rate` (one of `output.SAMPLE_RATES`) / `output_encoding` (`pcm_s16le`, `mulaw`, `alaw`): the output stage on
         the device (output.py) takes the place of the host-side cat and int16 cast -- the `(sr, pcm)` return, the file at
         `output_path` and `last_timing["audio_length"]` follow the requested rate; pcm is uint8 for the G.711 encodings.  With
@@ -887,6 +901,13 @@ class IndexTTS2:
         the request through the output stage (22 050 Hz `pcm_s16le` when no format is asked) and is refused with
         `stream_return=True`.  Afterwards `last_loudness` is dict(measured_lufs | None, gain_db, peak_dbfs_in, target_met), or None
         when neither was given -- and then nothing changes anywhere.
+
+        `output_peak_mode` ("sample", the default, or "true": `output_peak` is then read in dBTP and held against the 4x-oversampled
+        true peak of BS.1770 Annex 2; it needs one of the other three controls) / `output_limiter` (a bool; True is a level control of
+        its own, with a ceiling of -1 when `output_peak` is not given): with the limiter the loudness gain does not give way, and a
+        look-ahead limiter on the device removes what exceeds the ceiling, sample by sample, so the ceiling no longer costs the
+        programme its target.  Both are refused with `stream_return=True`.  A call with either gets more keys in `last_loudness`:
+        peak_mode, limited, max_reduction_db, limited_fraction, delivered_lufs, delivered_peak_dbfs (`output.level_report_limit`).
 
         `speed` (speaking rate, a float in `s2mel.SPEED_RANGE` = [0.5, 2.0]): the length regulator stretches every segment's codes to
         `target_frames(n, speed)` mel frames -- tempo changes, pitch does not; the codes are those of any other speed.  `duration`
@@ -903,10 +924,14 @@ class IndexTTS2:
             self._output_format(output_sample_rate, output_encoding, stream_return)
         if output_loudness is not None or output_peak is not None:
             self._output_level(output_loudness, output_peak, stream_return)
+        if output_peak_mode is not None or output_limiter is not None:
+            self._output_limit(_output.check_level(output_loudness, output_peak), output_peak_mode, output_limiter, stream_return)
         gen = self.infer_generator(spk_audio_prompt, text, output_path, emo_audio_prompt, emo_alpha, emo_vector, use_emo_text,
                                    emo_text, use_random, interval_silence, verbose, max_text_tokens_per_segment, stream_return,
                                    more_segment_before, output_sample_rate=output_sample_rate, output_encoding=output_encoding,
                                    output_loudness=output_loudness, output_peak=output_peak,
+                                   **({} if output_peak_mode is None and output_limiter is None else
+                                      dict(output_peak_mode=output_peak_mode, output_limiter=output_limiter)),
                                    **({} if speed is None and duration is None else dict(speed=speed, duration=duration)), **generation_kwargs)
         if stream_return:
             return gen
@@ -917,7 +942,8 @@ class IndexTTS2:
 
     @torch.no_grad()
     def infer_many(self, requests, interval_silence=200, max_text_tokens_per_segment=120, decode_slots=8, output_sample_rate=None,
-                   output_encoding=None, output_loudness=None, output_peak=None, speed=None, duration=None, **generation_kwargs):
+                   output_encoding=None, output_loudness=None, output_peak=None, speed=None, duration=None, output_peak_mode=None,
+              output_limiter=None, **generation_kwargs):
         """Several `/tts` requests served TOGETHER (the worker's global lock, server.py:25,384, replaced by the
         decode scheduler): every request's segments share the decode slots -- the weights are read once per step for all of them
         -- and the post-decode stages run per segment as in `infer`, through the same helpers.  Each request is a dict with
@@ -952,6 +978,7 @@ class IndexTTS2:
         `output_loudness` / `output_peak` (see `infer`) hold for the call as well, a request may carry `loudness` / `peak` (they do
         not pin it either, and a bad value fails that request only); a request with either leaves through the output stage.
         `last_loudness` is then a list with one entry per request: the level report, or None where no control was asked.
+        `output_peak_mode` / `output_limiter` (see `infer`) likewise, with the request keys `peak_mode` / `limiter`.
 
         `speed` / `duration` (see `infer`) hold for the call; a request may carry its own `speed` or `duration` (then the call's pair
         does not apply to it; they do not pin it, and a bad value or a duration that cannot be met fails that request only).  The
@@ -990,6 +1017,8 @@ class IndexTTS2:
                        rq["encoding"] if rq.get("encoding") is not None else output_encoding)
                 level = self._output_level(rq["loudness"] if rq.get("loudness") is not None else output_loudness,
                                            rq["peak"] if rq.get("peak") is not None else output_peak)  # a bad value fails this request
+                level, limit = self._output_limit(level, rq["peak_mode"] if rq.get("peak_mode") is not None else output_peak_mode,
+                                                  rq["limiter"] if rq.get("limiter") is not None else output_limiter)
                 own = rq.get("speed") is not None or rq.get("duration") is not None  # the request's own pace, else the call's
                 pace = self._rate_control(rq.get("speed") if own else speed, rq.get("duration") if own else duration)  # a bad value fails this request
                 if fmt == (None, None) and level is None and pace[1] is None:
@@ -1009,7 +1038,7 @@ class IndexTTS2:
                 mine = [self._segment(cl, ids, eng, gr.max_mel_tokens, request=ri, index=si, stream=si if pinned else None, sampler=sampler,
                                       constraints=cons, processors=procs)
                         for si, ids in enumerate(segments)]
-                plans[ri] = dict(spk=spk, cl=cl, segments=segments, seed=gr.seed if pinned else None, fmt=fmt, level=level, pace=pace)
+                plans[ri] = dict(spk=spk, cl=cl, segments=segments, seed=gr.seed if pinned else None, fmt=fmt, level=level, limit=limit, pace=pace)
                 classes.setdefault(nb, []).extend(mine)  # only once the whole request is known to be well-formed
             except Exception as e:  # this request only
                 failed[ri] = e
@@ -1114,6 +1143,9 @@ class IndexTTS2:
                 kw = {} if all(t is None for t in totals) else dict(totals=totals)
                 if any(plans[ri]["level"] is not None for ri in mine):  # (a call without a level control makes the call it always made)
                     levels, reports = [plans[ri]["level"] or (None, None) for ri in mine], []
+                    if any(plans[ri]["limit"] is not None for ri in mine):  # (a call without the two makes the call it always made)
+                        limit = [plans[ri]["limit"] or (None, None) for ri in mine]
+                        kw = dict(kw, peak_mode=[lm[0] for lm in limit], limiter=[lm[1] for lm in limit])
                     res = _output.finish_pcm_many(*args, loudness=[lv[0] for lv in levels], peak=[lv[1] for lv in levels], reports=reports, **kw)
                     for ri, rep in zip(mine, reports):
                         self.last_loudness[ri] = rep
@@ -1160,11 +1192,13 @@ class IndexTTS2:
     def infer_generator(self, spk_audio_prompt, text, output_path, emo_audio_prompt=None, emo_alpha=1.0, emo_vector=None,
                         use_emo_text=False, emo_text=None, use_random=False, interval_silence=200, verbose=False,
                         max_text_tokens_per_segment=120, stream_return=False, quick_streaming_tokens=0, output_sample_rate=None,
-                        output_encoding=None, output_loudness=None, output_peak=None, speed=None, duration=None, **generation_kwargs):
+                        output_encoding=None, output_loudness=None, output_peak=None, speed=None, duration=None, output_peak_mode=None,
+              output_limiter=None, **generation_kwargs):
         logger.info("Starting inference...")
         start_time = time.perf_counter()
         # an output format or a level (see `infer`): the segments stay on the device and leave through `output.finish_pcm`
         level = self._output_level(output_loudness, output_peak, stream_return)
+        level, limit = self._output_limit(level, output_peak_mode, output_limiter, stream_return)
         self.last_loudness = None
         speed, duration = self._rate_control(speed, duration, stream_return)  # a pace (see `infer`); a duration leaves through the output stage too
         self.last_duration = None
@@ -1322,7 +1356,8 @@ class IndexTTS2:
             else:
                 reports = []
                 sampling_rate, pcm = _output.finish_pcm(wavs, output_sample_rate, output_encoding, interval_silence, loudness=level[0],
-                                                        peak=level[1], reports=reports, **kw)
+                                                        peak=level[1], reports=reports, **kw,
+                                                        **({} if limit is None else dict(peak_mode=limit[0], limiter=limit[1])))
                 self.last_loudness = reports[0]
                 logger.info(f"output level: {self.last_loudness}")
             wav_length = pcm.shape[0] / sampling_rate

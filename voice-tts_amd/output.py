@@ -9,6 +9,9 @@ the caller asked for, ON THE DEVICE (csrc/output.hip), and reaches the host in o
   k_weighting       the two biquads of ITU-R BS.1770 at a sample rate -- the ONE builder, for the measurement kernel and the tests
   measure_levels    K-weighted hop energies and sample peak of every programme of a call, then gating and gain: two launches
   pcm_assemble_gain `pcm_assemble` with a gain per row, read from the device
+  true_peak_taps    the 4x interpolator of the true peak (BS.1770 Annex 2), limiter_window: the limiter's smoothing window -- the ONE
+                    builder each, for the kernels of csrc/limiter.hip and the tests
+  true_peaks, limit the true peak of every hop in place of the sample peak; a look-ahead limiter under the ceiling: one launch each
   wav_bytes         the RIFF container of a result
 
 With nothing requested none of this runs: `infer` keeps its host-side cat and `.type(torch.int16)`.
@@ -275,6 +278,54 @@ def check_level(loudness=None, peak=None):
     return (None if loudness is None else float(loudness)), (DEFAULT_PEAK if peak is None else float(peak))
 
 
+PEAK_MODES = ("sample", "true")  # what the ceiling is held against: the sample peak, or the 4x-oversampled true peak (dBTP)
+LOUDNESS_TOLERANCE_LU = 0.5  # what EBU R128 grants a programme around its target
+_PARTIAL = np.dtype([("min_gain", "<f4"), ("count", "<u4")])  # what one tile of the limiter leaves
+
+
+def check_limit(peak_mode=None, limiter=None, level=None):
+    """`level`: what `check_level` returned.  -> (level, peak_mode, limiter) with the defaults filled in ("sample", False); the
+    limiter is a level control of its own, so with it a missing level becomes (None, -1 dBFS).  ValueError for a mode outside
+    `PEAK_MODES`, a limiter that is not a bool, and "true" without a loudness target, a ceiling or the limiter: there is no ceiling
+    for it to qualify."""
+    if peak_mode is not None and not (isinstance(peak_mode, str) and peak_mode in PEAK_MODES):
+        raise ValueError(f"output peak mode {peak_mode!r} is not one of {PEAK_MODES}")
+    if limiter is not None and not isinstance(limiter, (bool, np.bool_)):
+        raise ValueError(f"output limiter {limiter!r} is not a bool")
+    mode, limiter = "sample" if peak_mode is None else peak_mode, bool(limiter)
+    if limiter:
+        level = (None, DEFAULT_PEAK) if level is None else (level[0], DEFAULT_PEAK if level[1] is None else level[1])
+    if mode == "true" and level is None:
+        raise ValueError("output peak mode 'true' needs a ceiling to qualify: give a loudness target, a peak ceiling or the limiter")
+    return level, mode, limiter
+
+
+def ceiling(peak):
+    """A ceiling in dBFS / dBTP -> sample units."""
+    return 32768.0 * 10.0 ** (float(peak) / 20.0)
+
+
+def true_peak_taps():
+    """-> fp64 [49]: h[m] = sinc(m / 4) 0.5 (1 + cos(pi m / 24)), m = -24 .. 24 at index m + 24 -- the 4x interpolator of the true
+    peak (ITU-R BS.1770 Annex 2), a Hann-windowed sinc, the same at every rate.  The point n + k / 4 of a programme y is
+    z[4 n + k] = sum_j h[k - 4 j] y[n + j]; k = 0 is the sample itself."""
+    m = np.arange(-24, 25, dtype=np.float64)
+    return np.sinc(m / 4.0) * 0.5 * (1.0 + np.cos(np.pi * m / 24.0))
+
+
+def lookaround(fs):
+    """W: samples the limiter looks to either side (5 ms): 40 at 8 kHz, 110 at 22 050 Hz, 240 at 48 kHz."""
+    return (int(fs) + 100) // 200
+
+
+def limiter_window(fs):
+    """-> fp64 [2 W + 1]: the Hann window w[k] = 0.5 (1 - cos(2 pi (k + 1) / (2 W + 2))) over its sum -- what smooths the limiter's
+    gain reduction.  No entry is zero."""
+    W = lookaround(fs)
+    w = 0.5 * (1.0 - np.cos(2.0 * np.pi * (np.arange(2 * W + 1, dtype=np.float64) + 1.0) / (2 * W + 2)))
+    return w / w.sum()
+
+
 def hop_len(fs):
     """Samples of one hop (100 ms) of the gating blocks at `fs`: 1103 at 11 025 Hz."""
     return (int(fs) + 5) // 10
@@ -321,15 +372,58 @@ def level_report(record, loudness):
                 target_met=loudness is None or not (none or bound))
 
 
+def level_report_limit(record, loudness, peak_mode, limiter, extent=0, stats=None, delivered=None):
+    """`level_report` of a request that uses `peak_mode` / `limiter`, with the keys they add: peak_mode, limited, max_reduction_db,
+    limited_fraction, delivered_lufs | None, delivered_peak_dbfs (in the request's peak mode; so is peak_dbfs_in).  With the
+    limiter, `stats` = (smallest gain, samples with a gain below 1) of the programme's `extent` samples, `delivered` = the gating
+    kernel's record of the limited programme, and target_met says: an L existed and the delivered loudness is within
+    `LOUDNESS_TOLERANCE_LU` of the target.  Without it one gain was applied and nothing was measured twice: delivered = measured
+    plus the gain."""
+    rep = level_report(record, loudness)
+    dbfs = lambda p: 20.0 * math.log10(p / 32768.0) if p > 0 else float("-inf")  # noqa: E731
+    rep["peak_mode"] = peak_mode
+    if not limiter:
+        rep.update(limited=False, max_reduction_db=0.0, limited_fraction=0.0,
+                   delivered_lufs=None if rep["measured_lufs"] is None else rep["measured_lufs"] + rep["gain_db"],
+                   delivered_peak_dbfs=rep["peak_dbfs_in"] + rep["gain_db"])
+        return rep
+    smallest, count = float(stats[0]), int(stats[1])
+    lufs = None if delivered["flags"] & _lib.LOUDNESS_NO_BLOCK else float(delivered["lufs"])
+    rep.update(limited=count > 0, max_reduction_db=20.0 * math.log10(smallest) if 0.0 < smallest < 1.0 else 0.0,
+               limited_fraction=count / float(extent) if extent else 0.0, delivered_lufs=lufs, delivered_peak_dbfs=dbfs(float(delivered["peak"])))
+    rep["target_met"] = loudness is None or (rep["measured_lufs"] is not None and lufs is not None and abs(lufs - loudness) <= LOUDNESS_TOLERANCE_LU)
+    return rep
+
+
 class LevelPlan:
     """The tables of `measure_levels` for the programmes of a call: programme q = (rows [(src, n, dst)] with dst counted from the
     programme's start, ascending and disjoint; extent; sample rate; loudness target | None; ceiling | None).  Everything goes up in
-    ONE pinned copy; `rows`, `reqs`, `coefs`, `targets` are views of it."""
+    ONE pinned copy; `rows`, `reqs`, `coefs`, `targets` (and `lreqs`, `modes`, `ceilings`, `tables`) are views of it.
 
-    def __init__(self, programmes, device):
+    `limits` (one (peak_mode, limiter) per programme, see `check_limit`; None: nobody asked): a programme in true mode has the sample
+    peaks of its hops replaced by true peaks (`modes`).  A limited programme gets no ceiling in `targets` -- the gating kernel does
+    not give way -- and a row of the limiter's table `lreqs` (`_lib.LIMITER_REQ_COLS`); its ceiling defaults to `DEFAULT_PEAK`; the
+    limited programmes are written one after another, programme q at `lim_off[q]` of `lim_total` samples.  The interpolator and
+    one window per distinct rate ride in `tables`.  `limited_at` (where that region starts in the buffer the rows point into): every
+    limited programme is followed by a second one -- programmes n .. n + n2 of the tables: one row over its limited samples, no
+    target, no ceiling -- through which the same kernels measure what is delivered."""
+
+    def __init__(self, programmes, device, limits=None, limited_at=None):
+        programmes = [tuple(p) for p in programmes]
+        limits = [("sample", False)] * len(programmes) if limits is None else [(check_limit(m, bool(lim), (None, None))[1], bool(lim)) for m, lim in limits]
+        assert len(limits) == len(programmes)
+        self.limited = [q for q, (_, lim) in enumerate(limits) if lim]
+        self.lim_off, self.lim_total, second = {}, 0, []
+        for q in self.limited:
+            extent = int(programmes[q][1])
+            self.lim_off[q] = self.lim_total
+            if limited_at is not None:
+                second.append(([(int(limited_at) + self.lim_total, extent, 0)], extent, programmes[q][2], None, None))
+            self.lim_total += max(extent, 0)
+        modes = [int(m == "true") for m, _ in limits] + [int(limits[q][0] == "true") for q in self.limited][:len(second)]
         rows, reqs, coefs, targets, at, slot = [], [], [], [], 0, 0
         self.hops = []
-        for prog_rows, extent, rate, loudness, peak in programmes:
+        for k, (prog_rows, extent, rate, loudness, peak) in enumerate(programmes + second):
             H, extent = hop_len(rate), int(extent)
             if H > _lib.LOUDNESS_MAX_HOP:
                 raise ValueError(f"loudness: a hop of {H} samples ({rate} Hz) is more than the kernel's {_lib.LOUDNESS_MAX_HOP}")
@@ -343,43 +437,148 @@ class LevelPlan:
             rows += [(int(s), int(n), at + int(d)) for s, n, d in prog_rows]
             b_s, a_s, _, a_h = k_weighting(rate)
             coefs.append([b_s[0], b_s[1], b_s[2], a_s[1], a_s[2], a_h[1], a_h[2], 0.0] + [float(v) for v in chunk_transition(rate)[1].reshape(-1)])
-            targets.append([math.nan if loudness is None else loudness, math.nan if peak is None else peak])
+            held = peak is not None and not (k < len(programmes) and limits[k][1])  # (the limiter holds a limited programme's ceiling)
+            targets.append([math.nan if loudness is None else loudness, peak if held else math.nan])
             self.hops.append((slot, hops, extent // H))
             at, slot = at + extent, slot + hops
-        self.n, self.slots, self.max_hops, self.n_rows = len(reqs), slot, max([h for _, h, _ in self.hops], default=0), len(rows)
-        ints = np.array([v for r in rows for v in r] + [v for r in reqs for v in r], np.int64)
-        blob = torch.from_numpy(np.concatenate([ints, np.array([v for r in coefs + targets for v in r], np.float64).view(np.int64)]))
+        self.n, self.n2, self.slots, self.n_rows = len(programmes), len(second), slot, len(rows)
+        self.max_hops = max([h for _, h, _ in self.hops[:self.n]], default=0)
+        self.max_hops2 = max([h for _, h, _ in self.hops[self.n:]], default=0)
+        self.any_true, self.any_true2 = any(modes[:self.n]), any(modes[self.n:])
+        # the limiter's table, its ceilings, and the interpolator and the windows it and the true peak read
+        lreqs, ceilings, tables, w_at, self.tiles, pslot = [], [], [], {}, [], 0
+        if self.limited or self.any_true:
+            tables.append(true_peak_taps())
+        for q in self.limited:
+            rate, peak = programmes[q][2], programmes[q][4]
+            W = lookaround(rate)
+            if not 1 <= W <= _lib.LIMITER_MAX_W:
+                raise ValueError(f"limiter: a look-around of {W} samples ({rate} Hz) is outside the kernel's 1 .. {_lib.LIMITER_MAX_W}")
+            if rate not in w_at:
+                w_at[rate] = sum(t.size for t in tables)
+                tables.append(limiter_window(rate))
+            tiles = -(-reqs[q][3] // _lib.LIMITER_TILE)
+            lreqs.append(reqs[q][:4] + (self.lim_off[q], q, W, w_at[rate], modes[q], pslot))
+            ceilings.append(ceiling(DEFAULT_PEAK if peak is None else peak))
+            self.tiles.append((pslot, tiles))
+            pslot += tiles
+        self.partial_slots, self.max_tiles = pslot, max([t for _, t in self.tiles], default=0)
+        asked = limits != [("sample", False)] * len(limits)
+        if not asked:  # the tables of old, and nothing else
+            ints = np.array([v for r in rows for v in r] + [v for r in reqs for v in r], np.int64)
+            blob = torch.from_numpy(np.concatenate([ints, np.array([v for r in coefs + targets for v in r], np.float64).view(np.int64)]))
+            if torch.device(device).type == "cuda":
+                blob = blob.pin_memory()
+            blob = blob.to(device, non_blocking=True)
+            a, b = 3 * len(rows), 3 * len(rows) + _lib.LOUDNESS_REQ_COLS * self.n
+            c = b + _lib.LOUDNESS_COEF_COLS * self.n
+            self.rows, self.reqs, self.lreqs, self.modes = blob[:a], blob[a:b], None, None
+            self.coefs, self.targets, self.ceilings, self.tables = blob[b:c].view(torch.float64), blob[c:].view(torch.float64), None, None
+            return
+        ints = np.array([v for r in rows + reqs + lreqs for v in r] + modes, np.int64)
+        flts = np.concatenate([np.array([v for r in coefs + targets for v in r] + ceilings, np.float64)] + tables)
+        blob = torch.from_numpy(np.concatenate([ints, flts.view(np.int64)]))
         if torch.device(device).type == "cuda":
             blob = blob.pin_memory()
         blob = blob.to(device, non_blocking=True)
-        a, b = 3 * len(rows), 3 * len(rows) + _lib.LOUDNESS_REQ_COLS * self.n
-        c = b + _lib.LOUDNESS_COEF_COLS * self.n
-        self.rows, self.reqs = blob[:a], blob[a:b]
-        self.coefs, self.targets = blob[b:c].view(torch.float64), blob[c:].view(torch.float64)
+        cuts = np.cumsum([0, 3 * len(rows), _lib.LOUDNESS_REQ_COLS * len(reqs), _lib.LIMITER_REQ_COLS * len(lreqs), len(modes),
+                          _lib.LOUDNESS_COEF_COLS * len(reqs), 2 * len(reqs), len(ceilings), sum(t.size for t in tables)])
+        part = [blob[a:b] for a, b in zip(cuts[:-1].tolist(), cuts[1:].tolist())]
+        self.rows, self.reqs, self.lreqs, self.modes = part[:4]
+        self.coefs, self.targets, self.ceilings, self.tables = (p.view(torch.float64) for p in part[4:])
+
+
+def _level_buffers(plan, dev, records=None):
+    """-> (energy fp64 [slots | 1], hop_peak fp32 [..], records uint8, gains fp32 [n + n2 | 1]) for every programme of `plan`."""
+    n, k = max(plan.slots, 1), plan.n + plan.n2
+    work = torch.zeros(n + (n + 1) // 2, dtype=torch.float64, device=dev)  # (one fill: a hop the kernel skips reads as silence)
+    gains = torch.empty(max(k, 1), dtype=torch.float32, device=dev)
+    if records is None:
+        records = torch.empty(k * _RECORD.itemsize, dtype=torch.uint8, device=dev)
+    assert records.dtype == torch.uint8 and records.is_contiguous() and records.numel() >= k * _RECORD.itemsize and records.device == dev
+    return work[:n], work[n:].view(torch.float32), records, gains
+
+
+def _true_peak_launch(x, plan, lo, hi, max_hops, hop_peak):
+    P = C.c_void_p
+    modes = None if plan.modes is None else P(plan.modes.data_ptr() + 8 * lo)
+    _lib.check(_lib.lib().ixtts_true_peak(P(x.data_ptr()), x.numel(), P(plan.rows.data_ptr()), plan.n_rows, P(plan.reqs.data_ptr() + 8 * _lib.LOUDNESS_REQ_COLS * lo),
+                                          modes, hi - lo, max_hops, P(plan.tables.data_ptr()), P(hop_peak.data_ptr()), plan.slots,
+                                          _lib.current_stream_ptr()), "ixtts_true_peak")
+
+
+def _level_pass(x, plan, lo, hi, max_hops, true, energy, hop_peak, records, gains):
+    """Programmes lo .. hi of `plan`: measurement, true peaks over the sample peaks where asked, gating and gain."""
+    if hi <= lo:
+        return
+    L, P, s = _lib.lib(), C.c_void_p, _lib.current_stream_ptr()
+    reqs = plan.reqs.data_ptr() + 8 * _lib.LOUDNESS_REQ_COLS * lo
+    _lib.check(L.ixtts_loudness_measure(P(x.data_ptr()), x.numel(), P(plan.rows.data_ptr()), plan.n_rows, P(reqs),
+                                        P(plan.coefs.data_ptr() + 8 * _lib.LOUDNESS_COEF_COLS * lo), hi - lo, max_hops, P(energy.data_ptr()),
+                                        P(hop_peak.data_ptr()), plan.slots, s), "ixtts_loudness_measure")
+    if true:
+        _true_peak_launch(x, plan, lo, hi, max_hops, hop_peak)
+    _lib.check(L.ixtts_loudness_gain(P(energy.data_ptr()), P(hop_peak.data_ptr()), plan.slots, P(reqs), P(plan.targets.data_ptr() + 16 * lo), hi - lo,
+                                     P(records.data_ptr() + _RECORD.itemsize * lo), P(gains.data_ptr() + 4 * lo), s), "ixtts_loudness_gain")
 
 
 def measure_levels(x, plan, records=None):
     """TWO launches for every programme of `plan`: the K-weighted energy and the sample peak of every hop (fp64 recursion over the fp32
     samples of `x`, through the gaps), then gating, integrated loudness and gain per programme.  -> (energy fp64 [plan.slots],
     hop_peak fp32 [plan.slots], records uint8 [24 n] (`_RECORD`; `records`: write there), gains fp32 [n]), all on the device: the
-    gain reaches `pcm_assemble_gain` without visiting the host."""
+    gain reaches `pcm_assemble_gain` without visiting the host.  A plan with programmes in true mode: a third launch between the
+    two puts their true hop peaks in place of the sample peaks."""
     assert x.dtype == torch.float32 and x.is_contiguous()
-    dev = x.device
-    n = max(plan.slots, 1)
-    work = torch.zeros(n + (n + 1) // 2, dtype=torch.float64, device=dev)  # (one fill: a hop the kernel skips reads as silence)
-    energy, hop_peak = work[:n], work[n:].view(torch.float32)
-    gains = torch.empty(max(plan.n, 1), dtype=torch.float32, device=dev)
-    if records is None:
-        records = torch.empty(plan.n * _RECORD.itemsize, dtype=torch.uint8, device=dev)
-    assert records.dtype == torch.uint8 and records.is_contiguous() and records.numel() >= plan.n * _RECORD.itemsize and records.device == dev
+    energy, hop_peak, records, gains = _level_buffers(plan, x.device, records)
     if plan.n == 0:
         return energy[:0], hop_peak[:0], records, gains[:0]
-    L, P, s = _lib.lib(), C.c_void_p, _lib.current_stream_ptr()
-    _lib.check(L.ixtts_loudness_measure(P(x.data_ptr()), x.numel(), P(plan.rows.data_ptr()), plan.n_rows, P(plan.reqs.data_ptr()), P(plan.coefs.data_ptr()),
-                                        plan.n, plan.max_hops, P(energy.data_ptr()), P(hop_peak.data_ptr()), plan.slots, s), "ixtts_loudness_measure")
-    _lib.check(L.ixtts_loudness_gain(P(energy.data_ptr()), P(hop_peak.data_ptr()), plan.slots, P(plan.reqs.data_ptr()), P(plan.targets.data_ptr()), plan.n,
-                                     P(records.data_ptr()), P(gains.data_ptr()), s), "ixtts_loudness_gain")
-    return energy[:plan.slots], hop_peak[:plan.slots], records, gains
+    _level_pass(x, plan, 0, plan.n, plan.max_hops, plan.any_true, energy, hop_peak, records, gains)
+    return energy[:plan.slots], hop_peak[:plan.slots], records, gains[:plan.n + plan.n2]
+
+
+def true_peaks(x, plan):
+    """ONE launch: -> fp32 [plan.slots] on the device, the 4x-oversampled true peak of every hop (`true_peak_taps`) of the plan's
+    programmes in true mode (`limits=` of `LevelPlan`), and 0 in every other slot."""
+    assert x.dtype == torch.float32 and x.is_contiguous()
+    hop_peak = torch.zeros(max(plan.slots, 1), dtype=torch.float32, device=x.device)
+    if plan.n and plan.max_hops:
+        if plan.tables is None:
+            raise ValueError("true_peaks: the plan carries no interpolator (build it with limits=)")
+        _true_peak_launch(x, plan, 0, plan.n, plan.max_hops, hop_peak)
+    return hop_peak[:plan.slots]
+
+
+def _limiter_launch(x, plan, gains, out, partials):
+    P = C.c_void_p
+    assert out.dtype == torch.float32 and out.is_contiguous() and out.numel() >= plan.lim_total and out.device == x.device
+    assert partials.dtype == torch.uint8 and partials.is_contiguous() and partials.numel() >= plan.partial_slots * _PARTIAL.itemsize
+    assert partials.data_ptr() % 4 == 0 and partials.device == x.device
+    if not plan.limited or plan.max_tiles == 0:
+        return
+    _lib.check(_lib.lib().ixtts_limiter(P(x.data_ptr()), x.numel(), P(plan.rows.data_ptr()), plan.n_rows, P(plan.lreqs.data_ptr()), P(plan.ceilings.data_ptr()),
+                                        len(plan.limited), plan.max_tiles, P(plan.tables.data_ptr()), plan.tables.numel(),
+                                        None if gains is None else P(gains.data_ptr()), 0 if gains is None else gains.numel(), P(out.data_ptr()),
+                                        out.numel(), P(partials.data_ptr()), plan.partial_slots, _lib.current_stream_ptr()), "ixtts_limiter")
+
+
+def limiter_stats(partials, plan):
+    """What the limiter's tiles left (uint8 tensor or array of `_PARTIAL`) -> one (smallest gain fp32, samples with a gain below 1)
+    per limited programme of `plan`, reduced in tile order; (1.0, 0) for a programme without samples."""
+    raw = partials.cpu().numpy() if isinstance(partials, torch.Tensor) else np.asarray(partials)
+    tiles = np.frombuffer(raw[:plan.partial_slots * _PARTIAL.itemsize].tobytes(), dtype=_PARTIAL)
+    return [(np.float32(tiles["min_gain"][s:s + t].min()) if t else np.float32(1.0), int(tiles["count"][s:s + t].sum(dtype=np.int64))) for s, t in plan.tiles]
+
+
+def limit(x, plan, gains=None):
+    """ONE launch: every limited programme of `plan`, levelled by its entry of `gains` (fp32 on the device, indexed by programme;
+    None: 1) and held under its ceiling by the look-ahead limiter -> (fp32 [plan.lim_total] on the device,
+    programme q at `plan.lim_off[q]`, gaps and tail included; `limiter_stats` of the launch)."""
+    assert x.dtype == torch.float32 and x.is_contiguous()
+    assert gains is None or (gains.dtype == torch.float32 and gains.is_contiguous() and gains.device == x.device)
+    out = torch.empty(max(plan.lim_total, 1), dtype=torch.float32, device=x.device)
+    partials = torch.empty(max(plan.partial_slots, 1) * _PARTIAL.itemsize, dtype=torch.uint8, device=x.device)
+    _limiter_launch(x, plan, gains, out, partials)
+    return out[:plan.lim_total], limiter_stats(partials, plan)
 
 
 def read_records(records, n):
@@ -411,7 +610,8 @@ def pcm_assemble_gain(x, rows, total, encoding, gains, out=None):
     return out
 
 
-def finish_pcm_many(wav_lists, sample_rates, encodings, interval_silence=200, loudness=None, peak=None, reports=None, totals=None):
+def finish_pcm_many(wav_lists, sample_rates, encodings, interval_silence=200, loudness=None, peak=None, reports=None, totals=None, peak_mode=None,
+                    limiter=None):
     """The segments of several requests (each a list of fp32 [1, n_i] device tensors at 22 050 Hz, +-32767) -> one
     `(sr, ndarray [N, 1])` per request, int16 or uint8 (None for a request without segments): segment, `int(sr * interval_silence /
     1000)` samples of silence, segment ...  One resample launch per distinct target rate, one assemble launch per distinct
@@ -425,9 +625,19 @@ def finish_pcm_many(wav_lists, sample_rates, encodings, interval_silence=200, lo
     produces the bytes it produces without these arguments.
 
     `totals` (one entry per request, None: not asked): the request delivers exactly this many samples -- what follows its last
-    segment holds the encoding's code for zero, and a measured programme extends over it.  ValueError when the segments are longer."""
+    segment holds the encoding's code for zero, and a measured programme extends over it.  ValueError when the segments are longer.
+
+    `peak_mode` / `limiter` (one entry per request, None: not asked; see `check_limit`).  "true": the ceiling is held against the
+    4x-oversampled true peak (`true_peaks`, one launch between the measurement and the gating).  A limited programme gets the gain
+    of its loudness target without give-way and is then held under its ceiling sample by sample (`limit`, one launch, into a third
+    region of the arena, the programme contiguous with its gaps); the same kernels then measure the limited programme, for what the
+    report says is delivered; it is converted as ONE row of that region without a gain.  Its second record and the limiter's
+    per-tile numbers ride behind the first records: still one copy.  A request with either control gets the report of
+    `level_report_limit`; every other request the bytes and the report it gets without these arguments."""
     fmts = [check_format(sr, enc) for sr, enc in zip(sample_rates, encodings)]
     levels = [check_level(lo, pk) for lo, pk in zip(loudness or [None] * len(fmts), peak or [None] * len(fmts))]
+    limits = [check_limit(m, lim, lv) for m, lim, lv in zip(peak_mode or [None] * len(fmts), limiter or [None] * len(fmts), levels)]
+    levels, limits = [lm[0] for lm in limits], [lm[1:] for lm in limits]
     if reports is not None:
         reports[:] = [None] * len(wav_lists)
     live = [i for i, w in enumerate(wav_lists) if w]
@@ -437,8 +647,13 @@ def finish_pcm_many(wav_lists, sample_rates, encodings, interval_silence=200, lo
     segs = [[w.to(device, torch.float32).reshape(-1) for w in wav_lists[i]] for i in live]
     n_in = sum(s.numel() for ws in segs for s in ws)
     n_rs = sum(resampled_len(s.numel(), MODEL_RATE, fmts[i][0]) for i, ws in zip(live, segs) for s in ws if fmts[i][0] != MODEL_RATE)
-    # one fp32 arena: every segment as it left the vocoder, then every resampled segment
-    arena = torch.empty(n_in + n_rs, dtype=torch.float32, device=device)
+    n_lim = 0  # samples of the limited programmes: what they deliver, gaps and tail included
+    for i, ws in zip(live, segs):
+        if limits[i][1]:
+            n = sum(resampled_len(s.numel(), MODEL_RATE, fmts[i][0]) for s in ws) + (len(ws) - 1) * gap_len(fmts[i][0], interval_silence)
+            n_lim += n if totals is None or totals[i] is None else max(n, int(totals[i]))
+    # one fp32 arena: every segment as it left the vocoder, then every resampled segment, then every limited programme
+    arena = torch.empty(n_in + n_rs + n_lim, dtype=torch.float32, device=device)
     torch.cat([s for ws in segs for s in ws], out=arena[:n_in])
     src, pos, at = {}, 0, 0  # (request, segment) -> (offset in the arena, samples) of what gets converted
     by_rate = {}
@@ -454,7 +669,7 @@ def finish_pcm_many(wav_lists, sample_rates, encodings, interval_silence=200, lo
                 at += m
             pos += n
     for rate, rows in by_rate.items():
-        Resampler(rate, device).resample_into(arena[:n_in], arena[n_in:], rows)
+        Resampler(rate, device).resample_into(arena[:n_in], arena[n_in:n_in + n_rs], rows)
     # one byte buffer for the call: per encoding one region (16-byte aligned), a request after a request, no gap between requests
     by_enc, where, nbytes = {}, {}, 0
     for enc in ENCODINGS:
@@ -490,24 +705,47 @@ def finish_pcm_many(wav_lists, sample_rates, encodings, interval_silence=200, lo
             if totals is not None and totals[i] is not None:
                 at = max(at, int(totals[i]))  # the trailing silence is part of what is delivered
             progs.append((mine, at, fmts[i][0], levels[i][0], levels[i][1]))
-        plan = LevelPlan(progs, device)
-        rec_off, nbytes = nbytes, nbytes + plan.n * _RECORD.itemsize
+        new = any(limits[i] != ("sample", False) for i in asked)  # (nobody asks for a mode or the limiter: the plan of old)
+        plan = LevelPlan(progs, device, [limits[i] for i in asked], n_in + n_rs) if new else LevelPlan(progs, device)
+        assert plan.lim_total == n_lim
+        rec_off, nbytes = nbytes, nbytes + (plan.n + plan.n2) * _RECORD.itemsize
+        part_off, nbytes = nbytes, nbytes + plan.partial_slots * _PARTIAL.itemsize
     buf = torch.empty(nbytes, dtype=torch.uint8, device=device)
     if asked:
-        gains = measure_levels(arena, plan, records=buf[rec_off:])[3]
+        energy, hop_peak, records, gains = _level_buffers(plan, device, buf[rec_off:part_off])
+        _level_pass(arena, plan, 0, plan.n, plan.max_hops, plan.any_true, energy, hop_peak, records, gains)
+        if plan.limited:
+            _limiter_launch(arena, plan, gains, arena[n_in + n_rs:], buf[part_off:])
+            _level_pass(arena, plan, plan.n, plan.n + plan.n2, plan.max_hops2, plan.any_true2, energy, hop_peak, records, gains)
     for enc, (rows, total, off) in by_enc.items():
         width = 2 if enc == "pcm_s16le" else 1
         region = buf[off:off + total * width]
         region = region.view(torch.int16) if width == 2 else region
         if any(fmts[i][1] == enc for i in asked):
-            index = [asked.index(i) if i in asked else -1 for i in live if fmts[i][1] == enc for _ in wav_lists[i]]
-            pcm_assemble_gain(arena, [r + (g,) for r, g in zip(rows, index)], total, enc, gains, out=region)
+            rows4, k = [], 0
+            for i in live:
+                if fmts[i][1] != enc:
+                    continue
+                mine, k = rows[k:k + len(wav_lists[i])], k + len(wav_lists[i])
+                q = asked.index(i) if i in asked else -1
+                if q >= 0 and q in plan.lim_off:  # ONE row: the limited programme as the limiter wrote it
+                    rows4.append((n_in + n_rs + plan.lim_off[q], where[i][2], where[i][1], -1))
+                else:
+                    rows4 += [r + (q,) for r in mine]
+            pcm_assemble_gain(arena, rows4, total, enc, gains, out=region)
         else:
             pcm_assemble(arena, rows, total, enc, out=region)
     host = buf.cpu().numpy()  # the one copy (it waits for the stream)
     if asked and reports is not None:
-        for i, rec in zip(asked, read_records(host[rec_off:], plan.n)):
-            reports[i] = level_report(rec, levels[i][0])
+        recs = read_records(host[rec_off:], plan.n + plan.n2)
+        stats = dict(zip(plan.limited, limiter_stats(host[part_off:], plan)))
+        for q, i in enumerate(asked):
+            if limits[i] == ("sample", False):
+                reports[i] = level_report(recs[q], levels[i][0])
+            elif q in stats:
+                reports[i] = level_report_limit(recs[q], levels[i][0], limits[i][0], True, where[i][2], stats[q], recs[plan.n + plan.limited.index(q)])
+            else:
+                reports[i] = level_report_limit(recs[q], levels[i][0], limits[i][0], False)
     out = [None] * len(wav_lists)
     for i in live:
         enc, start, n = where[i]
@@ -520,9 +758,13 @@ def finish_pcm_many(wav_lists, sample_rates, encodings, interval_silence=200, lo
     return out
 
 
-def finish_pcm(wavs, sample_rate=None, encoding=None, interval_silence=200, loudness=None, peak=None, reports=None, total=None):
+def finish_pcm(wavs, sample_rate=None, encoding=None, interval_silence=200, loudness=None, peak=None, reports=None, total=None, peak_mode=None,
+               limiter=None):
     """One request's segments -> `(sr, ndarray [N, 1])`, int16 (`pcm_s16le`) or uint8 (`mulaw`, `alaw`); sr = the requested rate, or
     22050.  See `finish_pcm_many`."""
+    if peak_mode is not None or limiter is not None:
+        return finish_pcm_many([list(wavs)], [sample_rate], [encoding], interval_silence, [loudness], [peak], reports,
+                               totals=None if total is None else [total], peak_mode=[peak_mode], limiter=[limiter])[0]
     if total is not None:
         return finish_pcm_many([list(wavs)], [sample_rate], [encoding], interval_silence, [loudness], [peak], reports, totals=[total])[0]
     if loudness is None and peak is None:

@@ -2,7 +2,7 @@
 
 Same endpoints, models, priorities, error codes and CLI as the reference:
   POST /tts   TTSRequest{text, spk_audio (URL | hex > 100 chars), emo_audio?, emotion? (str | {str: float in [0,1]}), emo_alpha in [0,1] = 1.0,
-                         sample_rate?, encoding?, loudness?, peak?, speed?, duration?}   (the last six are this build's: the output stage of output.py,
+                         sample_rate?, encoding?, loudness?, peak?, peak_mode?, limiter?, speed?, duration?}   (the last eight are this build's: the output stage of output.py,
                          the speaking rate in [0.5, 2.0] and the target duration in seconds; 422 outside their sets / ranges, for speed together with
                          duration, and for a duration the rate range cannot reach -- its detail carries natural_s, min_s, max_s)
               -> TTSResponse{audio_hex, audio_length, inference_time, rtf, text}                       (server.py:183-235,320-440)
@@ -30,7 +30,7 @@ from typing import Dict, Optional, Union
 
 from fastapi import FastAPI, HTTPException
 from fastapi.middleware.cors import CORSMiddleware
-from pydantic import BaseModel, Field, field_validator, model_validator
+from pydantic import BaseModel, Field, StrictBool, field_validator, model_validator
 
 from .emotion import create_emotion_vector
 
@@ -87,6 +87,8 @@ class TTSRequest(BaseModel):
 
     loudness: Optional[float] = Field(None, description="target integrated loudness in LUFS (ITU-R BS.1770-4), -50 .. -5; default: the level of the synthesis")
     peak: Optional[float] = Field(None, description="sample-peak ceiling in dBFS, -20 .. 0; default -1 beside `loudness`")
+    peak_mode: Optional[str] = Field(None, description="what `peak` is held against: sample (default) or true (dBTP, the 4x-oversampled peak of BS.1770 Annex 2)")
+    limiter: Optional[StrictBool] = Field(None, description="hold the ceiling with a look-ahead limiter, so that it does not cost `loudness` its target; default false")
 
     speed: Optional[float] = Field(None, description="speaking rate, 0.5 .. 2.0 (tempo changes, pitch does not); default: the natural pace")
     duration: Optional[float] = Field(None, description="seconds the whole delivered audio lasts (trailing silence fills the rest); not together with `speed`")
@@ -120,6 +122,20 @@ class TTSRequest(BaseModel):
 
         check_level(**{info.field_name: v})  # ValueError naming the range -> 422
         return v
+
+    @field_validator("peak_mode", "limiter")
+    @classmethod
+    def _output_limit(cls, v, info):
+        from .output import check_limit
+
+        check_limit(**{info.field_name: v}, level=(None, None))  # ValueError naming the accepted values -> 422
+        return v
+
+    @model_validator(mode="after")
+    def _a_ceiling_for_the_mode(self):
+        if self.peak_mode == "true" and self.loudness is None and self.peak is None and not self.limiter:
+            raise ValueError("peak_mode 'true' needs a ceiling to qualify: give loudness, peak or limiter")
+        return self
 
     @field_validator("sample_rate", "encoding")
     @classmethod
@@ -363,8 +379,9 @@ def create_app(model_factory=default_model_factory):
             # the output format goes on only when the request sets it: a model without the keywords keeps working
             fmt_kw = {k: v for k, v in (("output_sample_rate", request.sample_rate), ("output_encoding", request.encoding),
                                         ("output_loudness", request.loudness), ("output_peak", request.peak), ("speed", request.speed),
-                                        ("duration", request.duration)) if v is not None}
-            leveled = request.loudness is not None or request.peak is not None
+                                        ("duration", request.duration), ("output_peak_mode", request.peak_mode),
+                                        ("output_limiter", request.limiter)) if v is not None}
+            leveled = request.loudness is not None or request.peak is not None or request.peak_mode is not None or request.limiter is not None
             start = time.time()
             if state["batcher"] is not None:  # opt-in: queued requests decode together (IXTTS_BATCH_SLOTS)
                 import io
@@ -373,7 +390,8 @@ def create_app(model_factory=default_model_factory):
                                                    emo_alpha=request.emo_alpha if emo_audio_data else 1.0, emo_vector=emo_vector,
                                                    **{k: v for k, v in (("sample_rate", request.sample_rate), ("encoding", request.encoding),
                                                                         ("loudness", request.loudness), ("peak", request.peak), ("speed", request.speed),
-                                                                        ("duration", request.duration)) if v is not None})).result()
+                                                                        ("duration", request.duration), ("peak_mode", request.peak_mode),
+                                                                        ("limiter", request.limiter)) if v is not None})).result()
                 if res is None:
                     raise RuntimeError("the text produced no speech segment")
                 sr, pcm = res

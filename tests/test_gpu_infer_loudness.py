@@ -107,14 +107,14 @@ def test_without_a_control_nothing_changes(tts, monkeypatch):
     from voice_tts_amd import output as O
 
     m, wav_a = tts
-    real = O.finish_pcm_many
+    real = O.finish
     entered = []
 
     def guard(*a, **kw):
         entered.append(1)
         return real(*a, **kw)
 
-    monkeypatch.setattr(O, "finish_pcm_many", guard)
+    monkeypatch.setattr(O, "finish", guard)
     sr0, pcm0 = _seeded(m, wav_a, TEXT, None, seed=5, **KW)
     assert not entered and m.last_loudness is None and sr0 == 22050 and pcm0.dtype == np.int16  # the host path, as ever
     # a ceiling of 0 dBFS can never bind: the request goes through the device stage with a gain of exactly 1 and gives the same samples
@@ -134,13 +134,13 @@ def test_infer_many_levels_each_request_on_its_own(tts, monkeypatch):
     P = dict(spk_audio_prompt=wav_a, text=TEXT, generation={"seed": 5})
     A = dict(P, loudness=-23.0)
     seen = []
-    real = O.finish_pcm_many
+    real, finish = O.finish_pcm_many, O.finish
 
-    def spy(wav_lists, *a, **kw):
-        seen.append(([[w.clone() for w in ws] for ws in wav_lists], a, kw))
-        return real(wav_lists, *a, **kw)
+    def spy(wav_lists, specs, interval_silence=200):
+        seen.append(([[w.clone() for w in ws] for ws in wav_lists], list(specs), interval_silence))
+        return finish(wav_lists, specs, interval_silence)
 
-    monkeypatch.setattr(O, "finish_pcm_many", spy)
+    monkeypatch.setattr(O, "finish", spy)
     alone = m.infer_many([A], decode_slots=8, **KW)
     rep = m.last_loudness
     assert isinstance(alone[0], tuple) and alone[0][0] == 22050 and len(rep) == 1 and rep[0]["measured_lufs"] is not None
@@ -150,9 +150,9 @@ def test_infer_many_levels_each_request_on_its_own(tts, monkeypatch):
     assert isinstance(outs[3], ValueError) and all(isinstance(outs[k], tuple) for k in (0, 1, 2, 4)), outs  # the bad value fails alone
     assert outs[1][0] == 22050 and np.array_equal(outs[1][1], alone[0][1]) and reps[1] == rep[0]  # alone and in the batch: the same bytes
     assert reps[0] is None and reps[3] is None and reps[4] is None and reps[2] is not None and outs[2][1].dtype == np.uint8
-    # the request that asks for a rate and no level: its bytes on the parent's path, `finish_pcm_many` without the new arguments
-    lists, a, kw = seen[-1]
-    assert len(seen) == 2 and set(kw) == {"loudness", "peak", "reports"} and kw["loudness"] == [None, -23.0, -16.0]
+    # the request that asks for a rate and no level: its spec asks for the rate alone, its bytes are those of the list form without a level
+    lists, specs, _ = seen[-1]
+    assert len(seen) == 2 and [s.loudness for s in specs] == [None, -23.0, -16.0] and specs[0] == O.OutputSpec.of(sample_rate=16000)
     parent = real([lists[0]], [16000], [None], 200)[0]
     assert outs[0][0] == parent[0] == 16000 and np.array_equal(outs[0][1], parent[1])
     # a call-wide target holds for every request that does not bring its own
@@ -161,6 +161,6 @@ def test_infer_many_levels_each_request_on_its_own(tts, monkeypatch):
     assert all(isinstance(o, tuple) for o in outs) and abs(a["measured_lufs"] - b["measured_lufs"]) < 1e-9
     if a["target_met"] and b["target_met"]:
         assert abs((a["gain_db"] - b["gain_db"]) - 10.0) < 1e-3
-    # and a call without any level makes the call it always made
+    # and a call without any level asks for the rate alone
     m.infer_many([dict(P, sample_rate=16000)], decode_slots=8, **KW)
-    assert seen[-1][2] == {} and m.last_loudness == [None]
+    assert seen[-1][1] == [O.OutputSpec.of(sample_rate=16000)] and m.last_loudness == [None]

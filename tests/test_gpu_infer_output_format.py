@@ -44,13 +44,13 @@ def test_infer_many_serves_a_pinned_request_in_three_formats(tts, monkeypatch):
     P = dict(spk_audio_prompt=wav_a, text=TEXT, generation={"seed": 5})
     reqs = [P, dict(P, sample_rate=16000), dict(P, sample_rate=8000, encoding="mulaw")]
     seen = []
-    real = O.finish_pcm_many
+    real, finish = O.finish_pcm_many, O.finish
 
-    def spy(wav_lists, rates, encodings, interval_silence=200):
-        seen.append(([[w.clone() for w in ws] for ws in wav_lists], list(rates), list(encodings), interval_silence))
-        return real(wav_lists, rates, encodings, interval_silence)
+    def spy(wav_lists, specs, interval_silence=200):
+        seen.append(([[w.clone() for w in ws] for ws in wav_lists], list(specs), interval_silence))
+        return finish(wav_lists, specs, interval_silence)
 
-    monkeypatch.setattr(O, "finish_pcm_many", spy)
+    monkeypatch.setattr(O, "finish", spy)
     outs = m.infer_many(reqs, decode_slots=8, **KW)
     assert all(isinstance(o, tuple) for o in outs), outs
     assert len(seen) == 1
@@ -59,8 +59,9 @@ def test_infer_many_serves_a_pinned_request_in_three_formats(tts, monkeypatch):
     assert len(seen) == 1  # a call that asks for nothing never enters the output stage
     # the plain request: what the call without the other two gives -- existing behaviour is untouched
     assert outs[0][0] == alone[0][0] == 22050 and outs[0][1].dtype == np.int16 and np.array_equal(outs[0][1], alone[0][1])
-    lists, rates, encs, interval = seen[0]
-    assert rates == [16000, 8000] and encs == [None, "mulaw"] and interval == 200
+    lists, specs, interval = seen[0]
+    assert specs == [O.OutputSpec.of(sample_rate=16000), O.OutputSpec.of(sample_rate=8000, encoding="mulaw")] and interval == 200
+    rates, encs = [16000, 8000], [None, "mulaw"]
     assert abs(audio - sum(o[1].shape[0] / o[0] for o in outs)) < 1e-9
     for ws, sr, enc, (got_sr, got) in zip(lists, rates, encs, outs[1:]):
         assert len(ws) >= 2 and all(w.dtype == torch.float32 and w.is_cuda and w.shape[0] == 1 for w in ws)

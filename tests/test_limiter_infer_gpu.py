@@ -59,21 +59,21 @@ def test_the_limiter_delivers_the_target_the_ceiling_used_to_cost(tts, monkeypat
 
     m, wav_a = tts
     seen = []
-    real = O.finish_pcm_many
+    real = O.finish
 
-    def spy(*a, **kw):
-        seen.append(kw)
-        return real(*a, **kw)
+    def spy(wav_lists, specs, interval_silence=200):
+        seen.append(list(specs))
+        return real(wav_lists, specs, interval_silence)
 
-    monkeypatch.setattr(O, "finish_pcm_many", spy)
+    monkeypatch.setattr(O, "finish", spy)
     kw = dict(output_sample_rate=8000, output_loudness=-16.0, seed=5, **KW)
     sr0, pcm0 = _seeded(m, wav_a, TEXT, None, **kw)
     old = m.last_loudness
-    assert set(old) == OLD_KEYS and old["target_met"] is False and "peak_mode" not in seen[-1] and "limiter" not in seen[-1]  # as it is today
+    assert set(old) == OLD_KEYS and old["target_met"] is False and seen[-1][0].limits == ("sample", False)  # as it is today
     assert abs(int(np.abs(pcm0.astype(np.int32)).max()) - CEILING) <= 1.0
     sr, pcm = _seeded(m, wav_a, TEXT, None, output_limiter=True, **kw)
     rep = m.last_loudness
-    assert seen[-1]["limiter"] == [True] and seen[-1]["peak_mode"] == ["sample"]
+    assert len(seen[-1]) == 1 and seen[-1][0].limits == ("sample", True)
     got = LR.loudness(pcm[:, 0].astype(np.float64), sr)
     print(f"without the limiter: {old}\nwith it: {rep}\ndelivered {got:.4f} LUFS, peak {np.abs(pcm.astype(np.int32)).max()} (ceiling {CEILING:.1f})")
     assert sr == sr0 == 8000 and pcm.dtype == np.int16 and pcm.shape == pcm0.shape and set(rep) == NEW_KEYS
@@ -114,19 +114,19 @@ def test_infer_many_takes_the_keys_and_a_bad_value_fails_alone(tts, monkeypatch)
     A = dict(P, sample_rate=8000, loudness=-16.0, limiter=True)
     B = dict(P, sample_rate=8000, loudness=-16.0, peak=-1.0, peak_mode="true")
     seen = []
-    real = O.finish_pcm_many
+    real, finish = O.finish_pcm_many, O.finish
 
-    def spy(wav_lists, *a, **kw):
-        seen.append(([[w.clone() for w in ws] for ws in wav_lists], a, kw))
-        return real(wav_lists, *a, **kw)
+    def spy(wav_lists, specs, interval_silence=200):
+        seen.append(([[w.clone() for w in ws] for ws in wav_lists], list(specs), interval_silence))
+        return finish(wav_lists, specs, interval_silence)
 
-    monkeypatch.setattr(O, "finish_pcm_many", spy)
+    monkeypatch.setattr(O, "finish", spy)
     outs = m.infer_many([A, B, dict(A, limiter="yes"), dict(P, sample_rate=8000, loudness=-16.0)], decode_slots=8, **KW)
     reps = m.last_loudness
     assert isinstance(outs[2], ValueError) and "limiter" in str(outs[2]) and all(isinstance(outs[k], tuple) for k in (0, 1, 3)), outs
     assert set(reps[0]) == NEW_KEYS and set(reps[1]) == NEW_KEYS and reps[2] is None and set(reps[3]) == OLD_KEYS
-    lists, a, kw = seen[-1]
-    assert len(seen) == 1 and kw["limiter"] == [True, False, None] and kw["peak_mode"] == ["sample", "true", None]
+    lists, specs, _ = seen[-1]
+    assert len(seen) == 1 and [s.limits for s in specs] == [("sample", True), ("true", False), ("sample", False)]
     # what `infer` does with such segments: `finish_pcm` under the keywords it passes
     for k, extra in ((0, dict(limiter=True, peak_mode="sample")), (1, dict(peak=-1.0, limiter=False, peak_mode="true"))):
         own = []

@@ -104,91 +104,62 @@ __device__ __forceinline__ unsigned int pcm_zero() {
 
 // Output sample i of [0, total): the row whose [dst, dst + n) holds it (rows ascending in dst, disjoint), else the code for silence.
 // A thread owns four consecutive samples and stores them as one word (u8) or two (s16); `out` is 8-byte aligned.
-template <int ENC>
+// GAIN: rows of four columns (src, n, dst, gain index) instead of three: a sample of a row whose index lies in [0, n_gains) is the
+// conversion of the fp32 product gain * x, rounded once; any other index converts x as it is.
+template <int ENC, bool GAIN>
 __global__ __launch_bounds__(256) void pcm_assemble_kernel(const float* __restrict__ x, long x_elems, void* __restrict__ out, long total,
-                                                           const long long* __restrict__ rows, int n_rows) {
+                                                           const long long* __restrict__ rows, int n_rows, const float* __restrict__ gains,
+                                                           int n_gains) {
+  constexpr int COLS = GAIN ? 4 : 3;
   const long i0 = ((long)blockIdx.x * 256 + threadIdx.x) * 4;
   if (i0 >= total) return;
   // the last row with dst <= i0 (-1: none)
   int lo = -1, hi = n_rows - 1;
   while (lo < hi) {
     const int mid = (lo + hi + 1) >> 1;
-    if (rows[3 * mid + 2] <= (long long)i0) lo = mid;
+    if (rows[COLS * mid + 2] <= (long long)i0) lo = mid;
     else hi = mid - 1;
   }
   int r = lo;
-  long long src = 0, n = 0, dst = 0;
-  if (r >= 0) { src = rows[3 * r]; n = rows[3 * r + 1]; dst = rows[3 * r + 2]; }
+  long long src = 0, n = 0, dst = 0, gi = -1;
+  if (r >= 0) {
+    src = rows[COLS * r]; n = rows[COLS * r + 1]; dst = rows[COLS * r + 2];
+    if constexpr (GAIN) gi = rows[COLS * r + 3];
+  }
+  bool scaled = false;
+  float g = 1.0f;
+  if constexpr (GAIN) {
+    scaled = gi >= 0 && gi < n_gains;
+    g = scaled ? gains[gi] : 1.0f;
+  }
   unsigned int c[4];
   // all four in one row, 16-byte aligned in the input: one load
   const long long s0 = src + (i0 - dst);
-  const bool quad = r >= 0 && i0 + 3 - dst < n && src >= 0 && s0 + 3 < x_elems && ((uintptr_t)(x + s0) & 15) == 0 && (r + 1 >= n_rows || rows[3 * (r + 1) + 2] > i0 + 3);
+  const bool quad = r >= 0 && i0 + 3 - dst < n && src >= 0 && s0 + 3 < x_elems && ((uintptr_t)(x + s0) & 15) == 0 && (r + 1 >= n_rows || rows[COLS * (r + 1) + 2] > i0 + 3);
   if (quad) {
-    const float4 v = *(const float4*)(x + s0);
+    float4 v = *(const float4*)(x + s0);
+    if constexpr (GAIN) {
+      if (scaled) { v.x = __fmul_rn(g, v.x); v.y = __fmul_rn(g, v.y); v.z = __fmul_rn(g, v.z); v.w = __fmul_rn(g, v.w); }
+    }
     c[0] = pcm_code<ENC>(v.x); c[1] = pcm_code<ENC>(v.y); c[2] = pcm_code<ENC>(v.z); c[3] = pcm_code<ENC>(v.w);
   }
 #pragma unroll
   for (int e = 0; e < 4 && !quad; ++e) {
     const long long i = i0 + e;
     // step to the next row once i reaches its dst (rows of n = 0 are stepped over)
-    while (r + 1 < n_rows && rows[3 * (r + 1) + 2] <= i) {
+    while (r + 1 < n_rows && rows[COLS * (r + 1) + 2] <= i) {
       ++r;
-      src = rows[3 * r]; n = rows[3 * r + 1]; dst = rows[3 * r + 2];
+      src = rows[COLS * r]; n = rows[COLS * r + 1]; dst = rows[COLS * r + 2];
+      if constexpr (GAIN) {
+        gi = rows[COLS * r + 3];
+        scaled = gi >= 0 && gi < n_gains;
+        g = scaled ? gains[gi] : 1.0f;
+      }
     }
     const long long s = src + (i - dst);
     const bool in = r >= 0 && i - dst < n && src >= 0 && s < x_elems;  // (a source outside the input reads as silence)
-    c[e] = in ? pcm_code<ENC>(x[s]) : pcm_zero<ENC>();
-  }
-  if (i0 + 4 <= total) {
-    if (ENC == IXTTS_PCM_S16LE) *(uint2*)((unsigned short*)out + i0) = make_uint2(c[0] | (c[1] << 16), c[2] | (c[3] << 16));
-    else *(unsigned int*)((unsigned char*)out + i0) = c[0] | (c[1] << 8) | (c[2] << 16) | (c[3] << 24);
-  } else {
-    for (int e = 0; e < 4 && i0 + e < total; ++e) {
-      if (ENC == IXTTS_PCM_S16LE) ((unsigned short*)out)[i0 + e] = (unsigned short)c[e];
-      else ((unsigned char*)out)[i0 + e] = (unsigned char)c[e];
-    }
-  }
-}
-
-// `pcm_assemble_kernel` over rows of four columns (src, n, dst, gain index): a sample of a row whose index lies in [0, n_gains) is
-// the conversion of the fp32 product gain * x, rounded once; any other index converts x as it is.
-template <int ENC>
-__global__ __launch_bounds__(256) void pcm_assemble_gain_kernel(const float* __restrict__ x, long x_elems, void* __restrict__ out, long total,
-                                                                const long long* __restrict__ rows, int n_rows, const float* __restrict__ gains,
-                                                                int n_gains) {
-  const long i0 = ((long)blockIdx.x * 256 + threadIdx.x) * 4;
-  if (i0 >= total) return;
-  int lo = -1, hi = n_rows - 1;
-  while (lo < hi) {
-    const int mid = (lo + hi + 1) >> 1;
-    if (rows[4 * mid + 2] <= (long long)i0) lo = mid;
-    else hi = mid - 1;
-  }
-  int r = lo;
-  long long src = 0, n = 0, dst = 0, gi = -1;
-  if (r >= 0) { src = rows[4 * r]; n = rows[4 * r + 1]; dst = rows[4 * r + 2]; gi = rows[4 * r + 3]; }
-  bool scaled = gi >= 0 && gi < n_gains;
-  float g = scaled ? gains[gi] : 1.0f;
-  unsigned int c[4];
-  const long long s0 = src + (i0 - dst);
-  const bool quad = r >= 0 && i0 + 3 - dst < n && src >= 0 && s0 + 3 < x_elems && ((uintptr_t)(x + s0) & 15) == 0 && (r + 1 >= n_rows || rows[4 * (r + 1) + 2] > i0 + 3);
-  if (quad) {
-    float4 v = *(const float4*)(x + s0);
-    if (scaled) { v.x = __fmul_rn(g, v.x); v.y = __fmul_rn(g, v.y); v.z = __fmul_rn(g, v.z); v.w = __fmul_rn(g, v.w); }
-    c[0] = pcm_code<ENC>(v.x); c[1] = pcm_code<ENC>(v.y); c[2] = pcm_code<ENC>(v.z); c[3] = pcm_code<ENC>(v.w);
-  }
-#pragma unroll
-  for (int e = 0; e < 4 && !quad; ++e) {
-    const long long i = i0 + e;
-    while (r + 1 < n_rows && rows[4 * (r + 1) + 2] <= i) {
-      ++r;
-      src = rows[4 * r]; n = rows[4 * r + 1]; dst = rows[4 * r + 2]; gi = rows[4 * r + 3];
-      scaled = gi >= 0 && gi < n_gains;
-      g = scaled ? gains[gi] : 1.0f;
-    }
-    const long long s = src + (i - dst);
-    const bool in = r >= 0 && i - dst < n && src >= 0 && s < x_elems;
-    c[e] = in ? pcm_code<ENC>(scaled ? __fmul_rn(g, x[s]) : x[s]) : pcm_zero<ENC>();
+    if constexpr (GAIN) c[e] = in ? pcm_code<ENC>(scaled ? __fmul_rn(g, x[s]) : x[s]) : pcm_zero<ENC>();
+    else c[e] = in ? pcm_code<ENC>(x[s]) : pcm_zero<ENC>();
   }
   if (i0 + 4 <= total) {
     if (ENC == IXTTS_PCM_S16LE) *(uint2*)((unsigned short*)out + i0) = make_uint2(c[0] | (c[1] << 16), c[2] | (c[3] << 16));
@@ -404,42 +375,37 @@ extern "C" int ixtts_resample_varlen_f32(const float* x_dev, long x_elems, float
   return IXTTS_OK;
 }
 
-extern "C" int ixtts_pcm_assemble(const float* x_dev, long x_elems, void* out_dev, long total, const int64_t* rows_dev, int n_rows, int encoding,
-                                  void* stream) {
-  IX_ARG(out_dev && rows_dev && (x_dev || x_elems == 0), "pcm_assemble: null pointer");
-  IX_ARG(n_rows >= 0 && total >= 0 && x_elems >= 0, "pcm_assemble: bad shape n_rows=%d total=%ld x_elems=%ld", n_rows, total, x_elems);
-  IX_ARG(encoding == IXTTS_PCM_S16LE || encoding == IXTTS_PCM_MULAW || encoding == IXTTS_PCM_ALAW, "pcm_assemble: unknown encoding %d", encoding);
-  IX_ARG(((uintptr_t)out_dev & 7) == 0, "pcm_assemble: the output buffer must be 8-byte aligned");
+// the checks and the launch of both assemble entries; `who` names the entry in the messages
+template <bool GAIN>
+static int pcm_assemble_host(const char* who, const float* x_dev, long x_elems, void* out_dev, long total, const int64_t* rows_dev, int n_rows,
+                             const float* gains_dev, int n_gains, int encoding, void* stream) {
+  IX_ARG(out_dev && rows_dev && (x_dev || x_elems == 0) && (gains_dev || n_gains == 0), "%s: null pointer", who);
+  if constexpr (GAIN) {
+    IX_ARG(n_rows >= 0 && total >= 0 && x_elems >= 0 && n_gains >= 0, "%s: bad shape n_rows=%d total=%ld x_elems=%ld n_gains=%d", who, n_rows, total,
+           x_elems, n_gains);
+  } else {
+    IX_ARG(n_rows >= 0 && total >= 0 && x_elems >= 0, "%s: bad shape n_rows=%d total=%ld x_elems=%ld", who, n_rows, total, x_elems);
+  }
+  IX_ARG(encoding == IXTTS_PCM_S16LE || encoding == IXTTS_PCM_MULAW || encoding == IXTTS_PCM_ALAW, "%s: unknown encoding %d", who, encoding);
+  IX_ARG(((uintptr_t)out_dev & 7) == 0, "%s: the output buffer must be 8-byte aligned", who);
   if (total == 0) return IXTTS_OK;
-  const dim3 grid((unsigned)((total + 1023) / 1024));
-  const hipStream_t s = (hipStream_t)stream;
-  const long long* rows = (const long long*)rows_dev;
-  if (encoding == IXTTS_PCM_S16LE) hipLaunchKernelGGL(pcm_assemble_kernel<IXTTS_PCM_S16LE>, grid, dim3(256), 0, s, x_dev, x_elems, out_dev, total, rows, n_rows);
-  else if (encoding == IXTTS_PCM_MULAW) hipLaunchKernelGGL(pcm_assemble_kernel<IXTTS_PCM_MULAW>, grid, dim3(256), 0, s, x_dev, x_elems, out_dev, total, rows, n_rows);
-  else hipLaunchKernelGGL(pcm_assemble_kernel<IXTTS_PCM_ALAW>, grid, dim3(256), 0, s, x_dev, x_elems, out_dev, total, rows, n_rows);
+  auto* kernel = encoding == IXTTS_PCM_S16LE ? pcm_assemble_kernel<IXTTS_PCM_S16LE, GAIN>
+               : encoding == IXTTS_PCM_MULAW ? pcm_assemble_kernel<IXTTS_PCM_MULAW, GAIN>
+                                             : pcm_assemble_kernel<IXTTS_PCM_ALAW, GAIN>;
+  hipLaunchKernelGGL(kernel, dim3((unsigned)((total + 1023) / 1024)), dim3(256), 0, (hipStream_t)stream, x_dev, x_elems, out_dev, total,
+                     (const long long*)rows_dev, n_rows, gains_dev, n_gains);
   IX_HIP(hipGetLastError());
   return IXTTS_OK;
 }
 
+extern "C" int ixtts_pcm_assemble(const float* x_dev, long x_elems, void* out_dev, long total, const int64_t* rows_dev, int n_rows, int encoding,
+                                  void* stream) {
+  return pcm_assemble_host<false>("pcm_assemble", x_dev, x_elems, out_dev, total, rows_dev, n_rows, nullptr, 0, encoding, stream);
+}
+
 extern "C" int ixtts_pcm_assemble_gain(const float* x_dev, long x_elems, void* out_dev, long total, const int64_t* rows_dev, int n_rows,
                                        const float* gains_dev, int n_gains, int encoding, void* stream) {
-  IX_ARG(out_dev && rows_dev && (x_dev || x_elems == 0) && (gains_dev || n_gains == 0), "pcm_assemble_gain: null pointer");
-  IX_ARG(n_rows >= 0 && total >= 0 && x_elems >= 0 && n_gains >= 0, "pcm_assemble_gain: bad shape n_rows=%d total=%ld x_elems=%ld n_gains=%d", n_rows, total,
-         x_elems, n_gains);
-  IX_ARG(encoding == IXTTS_PCM_S16LE || encoding == IXTTS_PCM_MULAW || encoding == IXTTS_PCM_ALAW, "pcm_assemble_gain: unknown encoding %d", encoding);
-  IX_ARG(((uintptr_t)out_dev & 7) == 0, "pcm_assemble_gain: the output buffer must be 8-byte aligned");
-  if (total == 0) return IXTTS_OK;
-  const dim3 grid((unsigned)((total + 1023) / 1024));
-  const hipStream_t s = (hipStream_t)stream;
-  const long long* rows = (const long long*)rows_dev;
-  if (encoding == IXTTS_PCM_S16LE)
-    hipLaunchKernelGGL(pcm_assemble_gain_kernel<IXTTS_PCM_S16LE>, grid, dim3(256), 0, s, x_dev, x_elems, out_dev, total, rows, n_rows, gains_dev, n_gains);
-  else if (encoding == IXTTS_PCM_MULAW)
-    hipLaunchKernelGGL(pcm_assemble_gain_kernel<IXTTS_PCM_MULAW>, grid, dim3(256), 0, s, x_dev, x_elems, out_dev, total, rows, n_rows, gains_dev, n_gains);
-  else
-    hipLaunchKernelGGL(pcm_assemble_gain_kernel<IXTTS_PCM_ALAW>, grid, dim3(256), 0, s, x_dev, x_elems, out_dev, total, rows, n_rows, gains_dev, n_gains);
-  IX_HIP(hipGetLastError());
-  return IXTTS_OK;
+  return pcm_assemble_host<true>("pcm_assemble_gain", x_dev, x_elems, out_dev, total, rows_dev, n_rows, gains_dev, n_gains, encoding, stream);
 }
 
 extern "C" int ixtts_loudness_measure(const float* x_dev, long x_elems, const int64_t* rows_dev, int n_rows, const int64_t* reqs_dev, const double* coefs_dev,

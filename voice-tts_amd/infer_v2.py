@@ -27,7 +27,7 @@ import torch
 
 from .bigvgan import BigVGAN
 from .gpt_engine import GptEngine, generation_constraints, generation_processors, resolve_gpt_dtype, resolve_min_length
-from . import output as _output  # (through the module: a test may wrap `finish_pcm_many`)
+from . import output as _output  # (through the module: a test may wrap `finish`)
 from .pipeline import conds_latent, decode_segment, latent_prefix, prepare_gpt_inputs, vocode, vocode_many
 from .s2mel import check_speed, target_frames
 from .weights import BIGVGAN_CFG, GPT_CFG, load_bigvgan_checkpoint, load_gpt_checkpoint
@@ -811,38 +811,15 @@ class IndexTTS2:
                 mels.append(self._stage("s2mel", None)(latent, codes, lens, spk))
         return mels
 
-    @staticmethod
-    def _output_format(output_sample_rate, output_encoding, stream_return=False):
-        """-> (rate, encoding) of a call that asks for an output format; ValueError for a value outside `output.SAMPLE_RATES` /
-        `output.ENCODINGS`, and for an encoding on a stream (its segments are fp32 tensors)."""
-        if stream_return and output_encoding is not None:
-            raise ValueError("output_encoding cannot be combined with stream_return=True: the stream yields fp32 segments "
-                             "(output_sample_rate alone resamples them)")
-        return _output.check_format(output_sample_rate, output_encoding)
-
     last_loudness = None  # the level report of the last call: see `infer` / `infer_many`
 
     @staticmethod
-    def _output_level(output_loudness, output_peak, stream_return=False):
-        """-> None, or (loudness | None, peak) of a call that asks for a level (`output.check_level`); ValueError for a value outside the
-        ranges, and for either control on a stream: it has no whole programme to measure."""
-        if stream_return and (output_loudness is not None or output_peak is not None):
-            raise ValueError("output_loudness / output_peak cannot be combined with stream_return=True: the level is measured over "
-                             "the whole programme, which a stream does not have")
-        return _output.check_level(output_loudness, output_peak)
-
-    @staticmethod
-    def _output_limit(level, output_peak_mode, output_limiter, stream_return=False):
-        """`level`: what `_output_level` returned -> (level, None) when neither control is given, else (level, (peak_mode, limiter))
-        with the defaults filled in (`output.check_limit`: the limiter brings its own ceiling); ValueError for a value outside the
-        accepted ones, for "true" without anything that sets a ceiling, and for either control on a stream."""
-        if output_peak_mode is None and output_limiter is None:
-            return level, None
-        if stream_return:
-            raise ValueError("output_peak_mode / output_limiter cannot be combined with stream_return=True: the ceiling is held over "
-                             "the whole programme, which a stream does not have")
-        level, mode, limiter = _output.check_limit(output_peak_mode, output_limiter, level)
-        return level, (mode, limiter)
+    def _output_spec(output_sample_rate=None, output_encoding=None, output_loudness=None, output_peak=None, output_peak_mode=None,
+                     output_limiter=None, duration=None, stream_return=False):
+        """-> what the call asks of the output stage (`output.OutputSpec.of`), None: nothing, the host path; ValueError for a value
+        outside the accepted ones, and for an encoding, a level or a limit on a stream."""
+        return _output.OutputSpec.of(output_sample_rate, output_encoding, output_loudness, output_peak, output_peak_mode, output_limiter,
+                                     duration=duration is not None, stream=stream_return)
 
     last_duration = None  # the pace report of the last call: see `infer` / `infer_many`
 
@@ -920,19 +897,13 @@ class IndexTTS2:
         or None when neither was given -- and then nothing changes anywhere."""
         if speed is not None or duration is not None:
             self._rate_control(speed, duration, stream_return)
-        if output_sample_rate is not None or output_encoding is not None:  # refused here, not at the generator's first step
-            self._output_format(output_sample_rate, output_encoding, stream_return)
-        if output_loudness is not None or output_peak is not None:
-            self._output_level(output_loudness, output_peak, stream_return)
-        if output_peak_mode is not None or output_limiter is not None:
-            self._output_limit(_output.check_level(output_loudness, output_peak), output_peak_mode, output_limiter, stream_return)
+        # refused here, not at the generator's first step
+        self._output_spec(output_sample_rate, output_encoding, output_loudness, output_peak, output_peak_mode, output_limiter, duration, stream_return)
         gen = self.infer_generator(spk_audio_prompt, text, output_path, emo_audio_prompt, emo_alpha, emo_vector, use_emo_text,
                                    emo_text, use_random, interval_silence, verbose, max_text_tokens_per_segment, stream_return,
                                    more_segment_before, output_sample_rate=output_sample_rate, output_encoding=output_encoding,
-                                   output_loudness=output_loudness, output_peak=output_peak,
-                                   **({} if output_peak_mode is None and output_limiter is None else
-                                      dict(output_peak_mode=output_peak_mode, output_limiter=output_limiter)),
-                                   **({} if speed is None and duration is None else dict(speed=speed, duration=duration)), **generation_kwargs)
+                                   output_loudness=output_loudness, output_peak=output_peak, speed=speed, duration=duration,
+                                   output_peak_mode=output_peak_mode, output_limiter=output_limiter, **generation_kwargs)
         if stream_return:
             return gen
         try:
@@ -1001,6 +972,8 @@ class IndexTTS2:
         plans = [None] * len(requests)
         failed = {}
         text_emo = self._emo_text_vectors(requests, failed)
+        call_wide = dict(output_sample_rate=output_sample_rate, output_encoding=output_encoding, output_loudness=output_loudness,
+                         output_peak=output_peak, output_peak_mode=output_peak_mode, output_limiter=output_limiter)
         for ri, rq in enumerate(requests):
             if ri in failed:
                 continue
@@ -1012,19 +985,11 @@ class IndexTTS2:
                 spk, emo_cond = self._encode_prompts(spk_prompt, emo_prompt)
                 cl = self._conds_latent(spk, emo_cond, emo_is_spk, emo_alpha, emo_vector, rq.get("use_random", False))
                 segments = self._segments_of(rq["text"], max_text_tokens_per_segment)
-                # the output format: the request's own keys, else the call's; None = the host path of old
-                fmt = (rq["sample_rate"] if rq.get("sample_rate") is not None else output_sample_rate,
-                       rq["encoding"] if rq.get("encoding") is not None else output_encoding)
-                level = self._output_level(rq["loudness"] if rq.get("loudness") is not None else output_loudness,
-                                           rq["peak"] if rq.get("peak") is not None else output_peak)  # a bad value fails this request
-                level, limit = self._output_limit(level, rq["peak_mode"] if rq.get("peak_mode") is not None else output_peak_mode,
-                                                  rq["limiter"] if rq.get("limiter") is not None else output_limiter)
                 own = rq.get("speed") is not None or rq.get("duration") is not None  # the request's own pace, else the call's
                 pace = self._rate_control(rq.get("speed") if own else speed, rq.get("duration") if own else duration)  # a bad value fails this request
-                if fmt == (None, None) and level is None and pace[1] is None:
-                    fmt = None
-                else:
-                    self._output_format(*fmt)  # a value outside the accepted sets fails this request
+                # what the request asks of the output stage: its own keys, else the call's; None = the host path (a bad value fails this request)
+                spec = self._output_spec(**{kw: rq[key] if rq.get(key) is not None else call_wide[kw] for key, kw in _output.OUTPUT_KEYS},
+                                         duration=pace[1])
                 gr, pinned, cons = self._request_generation(rq, generation_kwargs, g)
                 procs = self._generation_processors({**generation_kwargs, **(rq.get("generation") or {})})
                 nb = gr.num_beams
@@ -1038,7 +1003,7 @@ class IndexTTS2:
                 mine = [self._segment(cl, ids, eng, gr.max_mel_tokens, request=ri, index=si, stream=si if pinned else None, sampler=sampler,
                                       constraints=cons, processors=procs)
                         for si, ids in enumerate(segments)]
-                plans[ri] = dict(spk=spk, cl=cl, segments=segments, seed=gr.seed if pinned else None, fmt=fmt, level=level, limit=limit, pace=pace)
+                plans[ri] = dict(spk=spk, cl=cl, segments=segments, seed=gr.seed if pinned else None, spec=spec, pace=pace)
                 classes.setdefault(nb, []).extend(mine)  # only once the whole request is known to be well-formed
             except Exception as e:  # this request only
                 failed[ri] = e
@@ -1090,7 +1055,7 @@ class IndexTTS2:
                 pin = plan["seed"] is not None and self.s2mel is not None
                 plan["frames"] = None
                 if plan["pace"] != (None, None):  # the frame counts under the request's speed, or fitted to its duration (which may refuse)
-                    plan["rate"] = _output.check_format(*plan["fmt"])[0] if plan["fmt"] is not None else 22050
+                    plan["rate"] = plan["spec"].rate if plan["spec"] is not None else 22050
                     plan["natural"], plan["frames"], plan["total"] = self._paced_frames(plan["items"], *plan["pace"], plan["rate"], interval_silence)
                     plan["noises"] = [self._pinned_noise(it, plan["seed"], si, fr) if pin else None
                                       for si, it, fr in zip(kept, plan["items"], plan["frames"])]
@@ -1132,27 +1097,18 @@ class IndexTTS2:
         pcm = iter(vocode_many(self.bigvgan, [mel for ri in live for mel in plans[ri]["mels"]]))
         for ri in live:
             plans[ri]["pcm"] = [next(pcm) for _ in plans[ri]["mels"]]
-        # the requests that asked for a sample rate or an encoding: through the output stage on the device, all of them together
+        # the requests that ask something of the output stage: through it on the device, all of them together
         formatted = {}
         self.last_loudness = [None] * len(requests)
-        mine = [ri for ri in live if plans[ri]["fmt"] is not None and not any(isinstance(w, Exception) for w in plans[ri]["pcm"])]
+        mine = [ri for ri in live if plans[ri]["spec"] is not None and not any(isinstance(w, Exception) for w in plans[ri]["pcm"])]
         if mine:
             try:
-                args = ([plans[ri]["pcm"] for ri in mine], [plans[ri]["fmt"][0] for ri in mine], [plans[ri]["fmt"][1] for ri in mine], interval_silence)
-                totals = [plans[ri].get("total") for ri in mine]  # the sample counts of the requests with a duration
-                kw = {} if all(t is None for t in totals) else dict(totals=totals)
-                if any(plans[ri]["level"] is not None for ri in mine):  # (a call without a level control makes the call it always made)
-                    levels, reports = [plans[ri]["level"] or (None, None) for ri in mine], []
-                    if any(plans[ri]["limit"] is not None for ri in mine):  # (a call without the two makes the call it always made)
-                        limit = [plans[ri]["limit"] or (None, None) for ri in mine]
-                        kw = dict(kw, peak_mode=[lm[0] for lm in limit], limiter=[lm[1] for lm in limit])
-                    res = _output.finish_pcm_many(*args, loudness=[lv[0] for lv in levels], peak=[lv[1] for lv in levels], reports=reports, **kw)
-                    for ri, rep in zip(mine, reports):
-                        self.last_loudness[ri] = rep
-                        if rep is not None:
-                            logger.info(f"infer_many: request {ri} level: {rep}")
-                else:
-                    res = _output.finish_pcm_many(*args, **kw)
+                specs = [plans[ri]["spec"]._replace(total=plans[ri].get("total")) for ri in mine]  # (the sample count of a fitted duration)
+                res, reports = _output.finish([plans[ri]["pcm"] for ri in mine], specs, interval_silence)
+                for ri, rep in zip(mine, reports):
+                    self.last_loudness[ri] = rep
+                    if rep is not None:
+                        logger.info(f"infer_many: request {ri} level: {rep}")
                 formatted = dict(zip(mine, res))
             except Exception as e:
                 formatted = {ri: e for ri in mine}
@@ -1196,16 +1152,13 @@ class IndexTTS2:
               output_limiter=None, **generation_kwargs):
         logger.info("Starting inference...")
         start_time = time.perf_counter()
-        # an output format or a level (see `infer`): the segments stay on the device and leave through `output.finish_pcm`
-        level = self._output_level(output_loudness, output_peak, stream_return)
-        level, limit = self._output_limit(level, output_peak_mode, output_limiter, stream_return)
-        self.last_loudness = None
         speed, duration = self._rate_control(speed, duration, stream_return)  # a pace (see `infer`); a duration leaves through the output stage too
         self.last_duration = None
         paced = []  # (natural, asked) frame counts per segment, for `last_duration`
-        fmt = output_sample_rate is not None or output_encoding is not None or level is not None or duration is not None
-        if fmt:
-            out_rate, out_enc = self._output_format(output_sample_rate, output_encoding, stream_return)
+        # an output format, a level or a duration (see `infer`): the segments stay on the device and leave through `output.finish`
+        spec = self._output_spec(output_sample_rate, output_encoding, output_loudness, output_peak, output_peak_mode, output_limiter, duration,
+                                 stream_return)
+        self.last_loudness = None
         self._prompt_stages()
         gpt_gen_time = gpt_forward_time = s2mel_time = bigvgan_time = 0.0
         if use_emo_text:
@@ -1250,7 +1203,7 @@ class IndexTTS2:
         # after segment, as the reference); streaming keeps the per-segment order for its first-chunk latency
         pack_solve = not stream_return and len(segments) > 1 and self.s2mel is not None and s2mel_batching()
         packed = [] if pack_solve or duration is not None else None  # (a duration is fitted once every segment's codes are known)
-        wavs = []
+        wavs, total = [], None  # (total: the samples a fitted duration delivers)
         has_warned = False
         silence = None
         # the segments were decoded up front, so every segment's codes are known: IXTTS_LATENT_BATCH=1 runs ONE `latent_many` for all of
@@ -1312,12 +1265,12 @@ class IndexTTS2:
             wav = vocode(self.bigvgan, mel)
             torch.cuda.synchronize(self.device)
             bigvgan_time += time.perf_counter() - m0
-            if fmt:
+            if spec is not None:
                 wavs.append(wav)
                 if stream_return:  # the resampled, clamped fp32 row, and silence of the new length
-                    yield (wav if out_rate == sampling_rate else _output.Resampler(out_rate, wav.device).forward_many([wav])[0]).cpu()
+                    yield (wav if spec.rate == sampling_rate else _output.Resampler(spec.rate, wav.device).forward_many([wav])[0]).cpu()
                     if silence is None:
-                        silence = torch.zeros(wav.size(0), _output.gap_len(out_rate, interval_silence))
+                        silence = torch.zeros(wav.size(0), _output.gap_len(spec.rate, interval_silence))
                     yield silence
                 continue
             wavs.append(wav.cpu())
@@ -1328,11 +1281,10 @@ class IndexTTS2:
                 yield silence
         if packed:
             m0 = time.perf_counter()
-            total = None
             if speed is None and duration is None:
                 mels = self._mels(packed, spk, packed=True)
             else:
-                natural, frames, total = self._paced_frames(packed, speed, duration, out_rate if fmt else sampling_rate, interval_silence)
+                natural, frames, total = self._paced_frames(packed, speed, duration, spec.rate if spec is not None else sampling_rate, interval_silence)
                 paced = list(zip(natural, frames))
                 mels = self._mels(packed, spk, packed=pack_solve, frames=frames)
             torch.cuda.synchronize(self.device)
@@ -1342,23 +1294,16 @@ class IndexTTS2:
             for w in vocode_many(self.bigvgan, mels):  # one batched pass (IXTTS_BV_BATCH=0: mel after mel)
                 if isinstance(w, Exception):
                     raise w
-                wavs.append(w if fmt else w.cpu())  # (.cpu() waits for the vocoder)
-            if fmt:
+                wavs.append(w if spec is not None else w.cpu())  # (.cpu() waits for the vocoder)
+            if spec is not None:
                 torch.cuda.synchronize(self.device)
             bigvgan_time += time.perf_counter() - m0
         end_time = time.perf_counter()
         if not wavs:
             return
-        if fmt:
-            kw = {} if duration is None else dict(total=total)  # (without a duration: the call it always made)
-            if level is None:
-                sampling_rate, pcm = _output.finish_pcm(wavs, output_sample_rate, output_encoding, interval_silence, **kw)
-            else:
-                reports = []
-                sampling_rate, pcm = _output.finish_pcm(wavs, output_sample_rate, output_encoding, interval_silence, loudness=level[0],
-                                                        peak=level[1], reports=reports, **kw,
-                                                        **({} if limit is None else dict(peak_mode=limit[0], limiter=limit[1])))
-                self.last_loudness = reports[0]
+        if spec is not None:
+            ((sampling_rate, pcm),), (self.last_loudness,) = _output.finish([wavs], [spec._replace(total=total)], interval_silence)
+            if self.last_loudness is not None:
                 logger.info(f"output level: {self.last_loudness}")
             wav_length = pcm.shape[0] / sampling_rate
             end_time = time.perf_counter()  # (the output stage is part of the request)
@@ -1379,14 +1324,14 @@ class IndexTTS2:
         logger.info(f"RTF: {(end_time - start_time) / wav_length:.4f}")
         self.last_timing = dict(gpt_gen_time=gpt_gen_time, gpt_forward_time=gpt_forward_time, s2mel_time=s2mel_time,
                                 bigvgan_time=bigvgan_time, total=end_time - start_time, audio_length=wav_length)
-        if fmt:
+        if spec is not None:
             if output_path:
                 if os.path.isfile(output_path):
                     os.remove(output_path)
                 if os.path.dirname(output_path) != "":
                     os.makedirs(os.path.dirname(output_path), exist_ok=True)
                 with open(output_path, "wb") as f:
-                    f.write(_output.wav_bytes(sampling_rate, pcm, out_enc))
+                    f.write(_output.wav_bytes(sampling_rate, pcm, spec.encoding))
             if not stream_return:
                 yield output_path if output_path else (sampling_rate, pcm)
             return

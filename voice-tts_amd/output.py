@@ -5,7 +5,9 @@ the caller asked for, ON THE DEVICE (csrc/output.hip), and reaches the host in o
                     CPU restatement used on the prompt side) and the device resampler both take their table from it
   Resampler         packed rows of unequal length -> the requested rate, one launch for all of them
   pcm_assemble      rows -> one buffer of int16 / G.711 bytes, the gaps (interval silence) holding the encoding's code for zero
-  finish_pcm(_many) the tail of `infer` / `infer_many`: resample, convert, lay out, copy to the host once
+  OutputSpec        what ONE request asks of the stage, resolved: rate, encoding, loudness, peak, peak mode, limiter, total
+  finish            the tail of `infer` / `infer_many`, the one entry: the segments and the spec of every request of a call ->
+                    resample, measure, limit, convert, lay out, copy to the host once; `finish_pcm(_many)` spell the specs as lists
   k_weighting       the two biquads of ITU-R BS.1770 at a sample rate -- the ONE builder, for the measurement kernel and the tests
   measure_levels    K-weighted hop energies and sample peak of every programme of a call, then gating and gain: two launches
   pcm_assemble_gain `pcm_assemble` with a gain per row, read from the device
@@ -21,6 +23,7 @@ import io
 import math
 import struct
 import wave
+from typing import NamedTuple, Optional
 
 import numpy as np
 import torch
@@ -156,28 +159,40 @@ class Resampler:
         return [t.reshape(1, -1) for t in y.split(outs)]
 
 
-def pcm_assemble(x, rows, total, encoding, out=None):
-    """ONE launch: `total` samples of `encoding` -- x[src : src + n] converted at [dst, dst + n) for every (src, n, dst) of `rows`
-    (ascending in dst, disjoint), the encoding's code for silence everywhere else.  -> int16 / uint8 [total] on x's device (`out`:
-    write into this tensor's first `total` elements instead)."""
+def _assemble(x, rows, total, encoding, gains, out):
+    """`pcm_assemble` (`gains` None: rows of three columns) and `pcm_assemble_gain` (four): validation, table, ONE launch."""
     if encoding not in ENCODINGS:
         raise ValueError(f"output encoding {encoding!r} is not one of {ENCODINGS}")
+    cols = 3 if gains is None else 4
     assert x.dtype == torch.float32 and x.is_contiguous()
-    rows = sorted(((int(s), int(n), int(d)) for s, n, d in rows), key=lambda r: (r[2], r[1]))
+    assert gains is None or (gains.dtype == torch.float32 and gains.is_contiguous() and gains.device == x.device)
+    rows = sorted((tuple(int(v) for v in r) for r in rows), key=lambda r: (r[2], r[1]))
     end = 0
-    for s, n, d in rows:
-        if s < 0 or n < 0 or d < end or s + n > x.numel() or d + n > total:
+    for r in rows:
+        s, n, d = r[:3]
+        if len(r) != cols or s < 0 or n < 0 or d < end or s + n > x.numel() or d + n > total:
             raise ValueError(f"assemble row (src={s}, n={n}, dst={d}) overlaps its neighbour or leaves its buffers ({x.numel()} in, {total} out)")
         end = d + n
     dtype = torch.int16 if encoding == "pcm_s16le" else torch.uint8
     if out is None:
         out = torch.empty(int(total), dtype=dtype, device=x.device)
     assert out.dtype == dtype and out.is_contiguous() and out.numel() >= total and out.device == x.device
-    table = _row_table(rows if rows else [(0, 0, 0)], x.device)
-    _lib.check(_lib.lib().ixtts_pcm_assemble(C.c_void_p(x.data_ptr()), x.numel(), C.c_void_p(out.data_ptr()), int(total),
-                                             C.c_void_p(table.data_ptr()), len(rows), _lib.PCM_ENCODINGS[encoding], _lib.current_stream_ptr()),
-               "ixtts_pcm_assemble")
+    table = _row_table(rows if rows else [(0, 0, 0, -1)[:cols]], x.device, cols)
+    P = C.c_void_p
+    head = (P(x.data_ptr()), x.numel(), P(out.data_ptr()), int(total), P(table.data_ptr()), len(rows))
+    tail = (_lib.PCM_ENCODINGS[encoding], _lib.current_stream_ptr())
+    if gains is None:
+        _lib.check(_lib.lib().ixtts_pcm_assemble(*head, *tail), "ixtts_pcm_assemble")
+    else:
+        _lib.check(_lib.lib().ixtts_pcm_assemble_gain(*head, P(gains.data_ptr()), gains.numel(), *tail), "ixtts_pcm_assemble_gain")
     return out
+
+
+def pcm_assemble(x, rows, total, encoding, out=None):
+    """ONE launch: `total` samples of `encoding` -- x[src : src + n] converted at [dst, dst + n) for every (src, n, dst) of `rows`
+    (ascending in dst, disjoint), the encoding's code for silence everywhere else.  -> int16 / uint8 [total] on x's device (`out`:
+    write into this tensor's first `total` elements instead)."""
+    return _assemble(x, rows, total, encoding, None, out)
 
 
 def gap_len(sample_rate, interval_silence=200):
@@ -300,6 +315,53 @@ def check_limit(peak_mode=None, limiter=None, level=None):
     return level, mode, limiter
 
 
+# request key <-> keyword of `infer*`, in the order of `OutputSpec.of`
+OUTPUT_KEYS = (("sample_rate", "output_sample_rate"), ("encoding", "output_encoding"), ("loudness", "output_loudness"), ("peak", "output_peak"),
+               ("peak_mode", "output_peak_mode"), ("limiter", "output_limiter"))
+
+
+class OutputSpec(NamedTuple):
+    """What one request asks of the stage, resolved: what `check_format`, `check_level` and `check_limit` return, in that order, and
+    `total`: the samples the request delivers when a duration was fitted (`_replace(total=...)`), else None."""
+    rate: int
+    encoding: str
+    loudness: Optional[float]
+    peak: Optional[float]
+    peak_mode: str
+    limiter: bool
+    total: Optional[int] = None
+
+    @classmethod
+    def of(cls, sample_rate=None, encoding=None, loudness=None, peak=None, peak_mode=None, limiter=None, duration=False, stream=False):
+        """-> the spec, or None when nothing is asked of the stage: no rate, no encoding, no `duration` (a request with one leaves
+        through the stage whatever else it asks) and no level once `check_limit` has spoken -- a mode of "sample" or a limiter of
+        False alone asks nothing.  ValueError for what the three checks refuse and, on a `stream` (which yields fp32 segments and has
+        no whole programme), for an encoding, a level or a limit; format, level, limit in that order."""
+        if stream and encoding is not None:
+            raise ValueError("output_encoding cannot be combined with stream_return=True: the stream yields fp32 segments "
+                             "(output_sample_rate alone resamples them)")
+        rate, enc = check_format(sample_rate, encoding)
+        if stream and (loudness is not None or peak is not None):
+            raise ValueError("output_loudness / output_peak cannot be combined with stream_return=True: the level is measured over "
+                             "the whole programme, which a stream does not have")
+        level = check_level(loudness, peak)
+        if stream and (peak_mode is not None or limiter is not None):
+            raise ValueError("output_peak_mode / output_limiter cannot be combined with stream_return=True: the ceiling is held over "
+                             "the whole programme, which a stream does not have")
+        level, mode, limiter = check_limit(peak_mode, limiter, level)
+        if sample_rate is None and encoding is None and not duration and level is None:
+            return None
+        return cls(rate, enc, *(level or (None, None)), mode, limiter)
+
+    @property
+    def leveled(self):
+        return self.loudness is not None or self.peak is not None
+
+    @property
+    def limits(self):
+        return self.peak_mode, self.limiter
+
+
 def ceiling(peak):
     """A ceiling in dBFS / dBTP -> sample units."""
     return 32768.0 * 10.0 ** (float(peak) / 20.0)
@@ -398,15 +460,16 @@ def level_report_limit(record, loudness, peak_mode, limiter, extent=0, stats=Non
 class LevelPlan:
     """The tables of `measure_levels` for the programmes of a call: programme q = (rows [(src, n, dst)] with dst counted from the
     programme's start, ascending and disjoint; extent; sample rate; loudness target | None; ceiling | None).  Everything goes up in
-    ONE pinned copy; `rows`, `reqs`, `coefs`, `targets` (and `lreqs`, `modes`, `ceilings`, `tables`) are views of it.
+    ONE pinned copy; `rows`, `reqs`, `lreqs`, `modes`, `coefs`, `targets`, `ceilings`, `tables` are views of it, in that order.
 
-    `limits` (one (peak_mode, limiter) per programme, see `check_limit`; None: nobody asked): a programme in true mode has the sample
-    peaks of its hops replaced by true peaks (`modes`).  A limited programme gets no ceiling in `targets` -- the gating kernel does
-    not give way -- and a row of the limiter's table `lreqs` (`_lib.LIMITER_REQ_COLS`); its ceiling defaults to `DEFAULT_PEAK`; the
-    limited programmes are written one after another, programme q at `lim_off[q]` of `lim_total` samples.  The interpolator and
-    one window per distinct rate ride in `tables`.  `limited_at` (where that region starts in the buffer the rows point into): every
-    limited programme is followed by a second one -- programmes n .. n + n2 of the tables: one row over its limited samples, no
-    target, no ceiling -- through which the same kernels measure what is delivered."""
+    `limits` (one (peak_mode, limiter) per programme, see `check_limit`; None: ("sample", False) for every one, which leaves `lreqs`,
+    `ceilings` and `tables` empty): a programme in true mode has the sample peaks of its hops replaced by true peaks (`modes`).  A
+    limited programme gets no ceiling in `targets` -- the gating kernel does not give way -- and a row of the limiter's table
+    `lreqs` (`_lib.LIMITER_REQ_COLS`); its ceiling defaults to `DEFAULT_PEAK`; the limited programmes are written one after another,
+    programme q at `lim_off[q]` of `lim_total` samples.  The interpolator and one window per distinct rate ride in `tables`.
+    `limited_at` (where that region starts in the buffer the rows point into): every limited programme is followed by a second one
+    -- programmes n .. n + n2 of the tables: one row over its limited samples, no target, no ceiling -- through which the same
+    kernels measure what is delivered."""
 
     def __init__(self, programmes, device, limits=None, limited_at=None):
         programmes = [tuple(p) for p in programmes]
@@ -463,18 +526,6 @@ class LevelPlan:
             self.tiles.append((pslot, tiles))
             pslot += tiles
         self.partial_slots, self.max_tiles = pslot, max([t for _, t in self.tiles], default=0)
-        asked = limits != [("sample", False)] * len(limits)
-        if not asked:  # the tables of old, and nothing else
-            ints = np.array([v for r in rows for v in r] + [v for r in reqs for v in r], np.int64)
-            blob = torch.from_numpy(np.concatenate([ints, np.array([v for r in coefs + targets for v in r], np.float64).view(np.int64)]))
-            if torch.device(device).type == "cuda":
-                blob = blob.pin_memory()
-            blob = blob.to(device, non_blocking=True)
-            a, b = 3 * len(rows), 3 * len(rows) + _lib.LOUDNESS_REQ_COLS * self.n
-            c = b + _lib.LOUDNESS_COEF_COLS * self.n
-            self.rows, self.reqs, self.lreqs, self.modes = blob[:a], blob[a:b], None, None
-            self.coefs, self.targets, self.ceilings, self.tables = blob[b:c].view(torch.float64), blob[c:].view(torch.float64), None, None
-            return
         ints = np.array([v for r in rows + reqs + lreqs for v in r] + modes, np.int64)
         flts = np.concatenate([np.array([v for r in coefs + targets for v in r] + ceilings, np.float64)] + tables)
         blob = torch.from_numpy(np.concatenate([ints, flts.view(np.int64)]))
@@ -501,9 +552,8 @@ def _level_buffers(plan, dev, records=None):
 
 def _true_peak_launch(x, plan, lo, hi, max_hops, hop_peak):
     P = C.c_void_p
-    modes = None if plan.modes is None else P(plan.modes.data_ptr() + 8 * lo)
     _lib.check(_lib.lib().ixtts_true_peak(P(x.data_ptr()), x.numel(), P(plan.rows.data_ptr()), plan.n_rows, P(plan.reqs.data_ptr() + 8 * _lib.LOUDNESS_REQ_COLS * lo),
-                                          modes, hi - lo, max_hops, P(plan.tables.data_ptr()), P(hop_peak.data_ptr()), plan.slots,
+                                          P(plan.modes.data_ptr() + 8 * lo), hi - lo, max_hops, P(plan.tables.data_ptr()), P(hop_peak.data_ptr()), plan.slots,
                                           _lib.current_stream_ptr()), "ixtts_true_peak")
 
 
@@ -542,7 +592,7 @@ def true_peaks(x, plan):
     assert x.dtype == torch.float32 and x.is_contiguous()
     hop_peak = torch.zeros(max(plan.slots, 1), dtype=torch.float32, device=x.device)
     if plan.n and plan.max_hops:
-        if plan.tables is None:
+        if plan.tables.numel() == 0:
             raise ValueError("true_peaks: the plan carries no interpolator (build it with limits=)")
         _true_peak_launch(x, plan, 0, plan.n, plan.max_hops, hop_peak)
     return hop_peak[:plan.slots]
@@ -590,123 +640,92 @@ def read_records(records, n):
 def pcm_assemble_gain(x, rows, total, encoding, gains, out=None):
     """`pcm_assemble` over rows (src, n, dst, index): a sample of a row with 0 <= index < len(gains) is the conversion of the fp32
     product gains[index] * x (one rounding; `gains`: fp32 on the device), any other index converts x as `pcm_assemble` does."""
-    if encoding not in ENCODINGS:
-        raise ValueError(f"output encoding {encoding!r} is not one of {ENCODINGS}")
-    assert x.dtype == torch.float32 and x.is_contiguous() and gains.dtype == torch.float32 and gains.is_contiguous() and gains.device == x.device
-    rows = sorted(((int(s), int(n), int(d), int(g)) for s, n, d, g in rows), key=lambda r: (r[2], r[1]))
-    end = 0
-    for s, n, d, _ in rows:
-        if s < 0 or n < 0 or d < end or s + n > x.numel() or d + n > total:
-            raise ValueError(f"assemble row (src={s}, n={n}, dst={d}) overlaps its neighbour or leaves its buffers ({x.numel()} in, {total} out)")
-        end = d + n
-    dtype = torch.int16 if encoding == "pcm_s16le" else torch.uint8
-    if out is None:
-        out = torch.empty(int(total), dtype=dtype, device=x.device)
-    assert out.dtype == dtype and out.is_contiguous() and out.numel() >= total and out.device == x.device
-    table = _row_table(rows if rows else [(0, 0, 0, -1)], x.device, 4)
-    _lib.check(_lib.lib().ixtts_pcm_assemble_gain(C.c_void_p(x.data_ptr()), x.numel(), C.c_void_p(out.data_ptr()), int(total), C.c_void_p(table.data_ptr()),
-                                                  len(rows), C.c_void_p(gains.data_ptr()), gains.numel(), _lib.PCM_ENCODINGS[encoding],
-                                                  _lib.current_stream_ptr()), "ixtts_pcm_assemble_gain")
-    return out
+    return _assemble(x, rows, total, encoding, gains, out)
 
 
-def finish_pcm_many(wav_lists, sample_rates, encodings, interval_silence=200, loudness=None, peak=None, reports=None, totals=None, peak_mode=None,
-                    limiter=None):
-    """The segments of several requests (each a list of fp32 [1, n_i] device tensors at 22 050 Hz, +-32767) -> one
-    `(sr, ndarray [N, 1])` per request, int16 or uint8 (None for a request without segments): segment, `int(sr * interval_silence /
-    1000)` samples of silence, segment ...  One resample launch per distinct target rate, one assemble launch per distinct
-    encoding, then ONE copy to the host; the host waits for nothing before that copy.  A request's bytes depend on its own
-    segments, rate and encoding alone.
+def _programme(src, lens, gap, total, request):
+    """What one request delivers -> (rows [(src, n, dst)], extent): segment k, `lens[k]` samples at `src[k]` of the arena, goes to dst,
+    counted from the programme's start, with `gap` samples of silence between two segments; `extent` is what is delivered: `total`
+    where one is given (silence fills the tail; ValueError when the segments and gaps are longer)."""
+    rows, end = [], 0
+    for k, (s, n) in enumerate(zip(src, lens)):
+        end += gap if k else 0
+        rows.append((s, n, end))
+        end += n
+    if total is not None:
+        if int(total) < end:
+            raise ValueError(f"request {request}: {end} samples of segments and gaps do not fit a total of {int(total)}")
+        end = int(total)
+    return rows, end
 
-    `loudness` / `peak` (one entry per request, None: not asked; see `check_level`): the request's programme -- what it delivers, at
-    its rate, gaps included -- is measured after the resample launches (`measure_levels`), and its samples are converted from the
-    fp32 product gain * x; the records ride behind the PCM in the same buffer, so there is still one copy and no wait before it.
-    `reports`: a list that receives one `level_report` per request (None where no control was asked).  A request without a control
-    produces the bytes it produces without these arguments.
 
-    `totals` (one entry per request, None: not asked): the request delivers exactly this many samples -- what follows its last
-    segment holds the encoding's code for zero, and a measured programme extends over it.  ValueError when the segments are longer.
+def finish(wav_lists, specs, interval_silence=200):
+    """The segments of several requests (each a list of fp32 [1, n_i] device tensors at 22 050 Hz, +-32767) and one `OutputSpec` per
+    request -> (results, reports): one `(sr, ndarray [N, 1])` per request, int16 or uint8 (None for a request without segments):
+    segment, `int(sr * interval_silence / 1000)` samples of silence, segment ..., and one level report per request (None where no
+    level was asked).  One resample launch per distinct target rate, one assemble launch per distinct encoding, then ONE copy to the
+    host; the host waits for nothing before that copy.  A request's bytes and report depend on its own segments and spec alone.
 
-    `peak_mode` / `limiter` (one entry per request, None: not asked; see `check_limit`).  "true": the ceiling is held against the
-    4x-oversampled true peak (`true_peaks`, one launch between the measurement and the gating).  A limited programme gets the gain
-    of its loudness target without give-way and is then held under its ceiling sample by sample (`limit`, one launch, into a third
-    region of the arena, the programme contiguous with its gaps); the same kernels then measure the limited programme, for what the
-    report says is delivered; it is converted as ONE row of that region without a gain.  Its second record and the limiter's
-    per-tile numbers ride behind the first records: still one copy.  A request with either control gets the report of
-    `level_report_limit`; every other request the bytes and the report it gets without these arguments."""
-    fmts = [check_format(sr, enc) for sr, enc in zip(sample_rates, encodings)]
-    levels = [check_level(lo, pk) for lo, pk in zip(loudness or [None] * len(fmts), peak or [None] * len(fmts))]
-    limits = [check_limit(m, lim, lv) for m, lim, lv in zip(peak_mode or [None] * len(fmts), limiter or [None] * len(fmts), levels)]
-    levels, limits = [lm[0] for lm in limits], [lm[1:] for lm in limits]
-    if reports is not None:
-        reports[:] = [None] * len(wav_lists)
+    A spec with a level (`loudness` / `peak`, see `check_level`): the request's programme -- what it delivers, at its rate, gaps
+    included -- is measured after the resample launches (`measure_levels`), and its samples are converted from the fp32 product
+    gain * x; the records ride behind the PCM in the same buffer, so there is still one copy and no wait before it.  Its report is
+    `level_report`.
+
+    `total`: the request delivers exactly this many samples -- what follows its last segment holds the encoding's code for zero,
+    and a measured programme extends over it.  ValueError, before any device work, when the segments are longer.
+
+    `peak_mode` / `limiter` (see `check_limit`).  "true": the ceiling is held against the 4x-oversampled true peak (`true_peaks`,
+    one launch between the measurement and the gating).  A limited programme gets the gain of its loudness target without give-way
+    and is then held under its ceiling sample by sample (`limit`, one launch, into a third region of the arena, the programme
+    contiguous with its gaps); the same kernels then measure the limited programme, for what the report says is delivered; it is
+    converted as ONE row of that region without a gain.  Its second record and the limiter's per-tile numbers ride behind the first
+    records: still one copy.  A spec whose `limits` are not ("sample", False) gets the report of `level_report_limit`."""
+    results, reports = [None] * len(wav_lists), [None] * len(wav_lists)
     live = [i for i, w in enumerate(wav_lists) if w]
     if not live:
-        return [None] * len(wav_lists)
+        return results, reports
     device = wav_lists[live[0]][0].device
-    segs = [[w.to(device, torch.float32).reshape(-1) for w in wav_lists[i]] for i in live]
-    n_in = sum(s.numel() for ws in segs for s in ws)
-    n_rs = sum(resampled_len(s.numel(), MODEL_RATE, fmts[i][0]) for i, ws in zip(live, segs) for s in ws if fmts[i][0] != MODEL_RATE)
-    n_lim = 0  # samples of the limited programmes: what they deliver, gaps and tail included
-    for i, ws in zip(live, segs):
-        if limits[i][1]:
-            n = sum(resampled_len(s.numel(), MODEL_RATE, fmts[i][0]) for s in ws) + (len(ws) - 1) * gap_len(fmts[i][0], interval_silence)
-            n_lim += n if totals is None or totals[i] is None else max(n, int(totals[i]))
-    # one fp32 arena: every segment as it left the vocoder, then every resampled segment, then every limited programme
-    arena = torch.empty(n_in + n_rs + n_lim, dtype=torch.float32, device=device)
-    torch.cat([s for ws in segs for s in ws], out=arena[:n_in])
-    src, pos, at = {}, 0, 0  # (request, segment) -> (offset in the arena, samples) of what gets converted
-    by_rate = {}
-    for i, ws in zip(live, segs):
-        for k, s in enumerate(ws):
-            n = s.numel()
-            if fmts[i][0] == MODEL_RATE:
-                src[i, k] = (pos, n)
+    segs = {i: [w.to(device, torch.float32).reshape(-1) for w in wav_lists[i]] for i in live}
+    n_in = sum(s.numel() for i in live for s in segs[i])
+    # one fp32 arena: every segment as it left the vocoder, then every resampled segment, then every limited programme; a request's
+    # programme reads its segments where they get converted from
+    progs, by_rate, pos, n_rs = {}, {}, 0, 0
+    for i in live:
+        rate, src, lens = specs[i].rate, [], []
+        for s in segs[i]:
+            n = m = s.numel()
+            if rate == MODEL_RATE:
+                src.append(pos)
             else:
-                m = resampled_len(n, MODEL_RATE, fmts[i][0])
-                by_rate.setdefault(fmts[i][0], []).append((pos, n, at))
-                src[i, k] = (n_in + at, m)
-                at += m
+                m = resampled_len(n, MODEL_RATE, rate)
+                by_rate.setdefault(rate, []).append((pos, n, n_rs))
+                src.append(n_in + n_rs)
+                n_rs += m
+            lens.append(m)
             pos += n
+        progs[i] = _programme(src, lens, gap_len(rate, interval_silence), specs[i].total, i)
+    n_lim = sum(progs[i][1] for i in live if specs[i].limiter)
+    arena = torch.empty(n_in + n_rs + n_lim, dtype=torch.float32, device=device)
+    torch.cat([s for i in live for s in segs[i]], out=arena[:n_in])
     for rate, rows in by_rate.items():
         Resampler(rate, device).resample_into(arena[:n_in], arena[n_in:n_in + n_rs], rows)
     # one byte buffer for the call: per encoding one region (16-byte aligned), a request after a request, no gap between requests
-    by_enc, where, nbytes = {}, {}, 0
+    regions, where, nbytes = {}, {}, 0  # encoding -> (samples, byte offset); request -> its first sample in the region
     for enc in ENCODINGS:
-        mine = [i for i in live if fmts[i][1] == enc]
+        mine = [i for i in live if specs[i].encoding == enc]
         if not mine:
             continue
-        rows, total = [], 0
+        total = 0
         for i in mine:
-            start, gap = total, gap_len(fmts[i][0], interval_silence)
-            for k in range(len(wav_lists[i])):
-                total += gap if k else 0
-                rows.append((src[i, k][0], src[i, k][1], total))
-                total += src[i, k][1]
-            if totals is not None and totals[i] is not None:
-                if int(totals[i]) < total - start:
-                    raise ValueError(f"request {i}: {total - start} samples of segments and gaps do not fit a total of {int(totals[i])}")
-                total = start + int(totals[i])
-            where[i] = (enc, start, total - start)
-        width = 2 if enc == "pcm_s16le" else 1
-        by_enc[enc] = (rows, total, nbytes)
-        nbytes = (nbytes + total * width + 15) // 16 * 16
-    # the requests with a level control: programme q of the plan; their records go behind the PCM
-    asked = [i for i in live if levels[i] is not None]
+            where[i], total = total, total + progs[i][1]
+        regions[enc] = (total, nbytes)
+        nbytes = (nbytes + total * (2 if enc == "pcm_s16le" else 1) + 15) // 16 * 16
+    # the requests with a level: programme q of the plan; their records, then the limiter's partials, go behind the PCM
+    asked = [i for i in live if specs[i].leveled]
     plan = gains = None
     if asked:
-        progs = []
-        for i in asked:
-            at, gap, mine = 0, gap_len(fmts[i][0], interval_silence), []
-            for k in range(len(wav_lists[i])):
-                at += gap if k else 0
-                mine.append((src[i, k][0], src[i, k][1], at))
-                at += src[i, k][1]
-            if totals is not None and totals[i] is not None:
-                at = max(at, int(totals[i]))  # the trailing silence is part of what is delivered
-            progs.append((mine, at, fmts[i][0], levels[i][0], levels[i][1]))
-        new = any(limits[i] != ("sample", False) for i in asked)  # (nobody asks for a mode or the limiter: the plan of old)
-        plan = LevelPlan(progs, device, [limits[i] for i in asked], n_in + n_rs) if new else LevelPlan(progs, device)
+        plan = LevelPlan([progs[i] + (specs[i].rate, specs[i].loudness, specs[i].peak) for i in asked], device, [specs[i].limits for i in asked],
+                         n_in + n_rs)
         assert plan.lim_total == n_lim
         rec_off, nbytes = nbytes, nbytes + (plan.n + plan.n2) * _RECORD.itemsize
         part_off, nbytes = nbytes, nbytes + plan.partial_slots * _PARTIAL.itemsize
@@ -717,59 +736,64 @@ def finish_pcm_many(wav_lists, sample_rates, encodings, interval_silence=200, lo
         if plan.limited:
             _limiter_launch(arena, plan, gains, arena[n_in + n_rs:], buf[part_off:])
             _level_pass(arena, plan, plan.n, plan.n + plan.n2, plan.max_hops2, plan.any_true2, energy, hop_peak, records, gains)
-    for enc, (rows, total, off) in by_enc.items():
-        width = 2 if enc == "pcm_s16le" else 1
-        region = buf[off:off + total * width]
-        region = region.view(torch.int16) if width == 2 else region
-        if any(fmts[i][1] == enc for i in asked):
-            rows4, k = [], 0
-            for i in live:
-                if fmts[i][1] != enc:
-                    continue
-                mine, k = rows[k:k + len(wav_lists[i])], k + len(wav_lists[i])
-                q = asked.index(i) if i in asked else -1
-                if q >= 0 and q in plan.lim_off:  # ONE row: the limited programme as the limiter wrote it
-                    rows4.append((n_in + n_rs + plan.lim_off[q], where[i][2], where[i][1], -1))
-                else:
-                    rows4 += [r + (q,) for r in mine]
-            pcm_assemble_gain(arena, rows4, total, enc, gains, out=region)
-        else:
-            pcm_assemble(arena, rows, total, enc, out=region)
+    index = {i: q for q, i in enumerate(asked)}
+    for enc, (total, off) in regions.items():
+        region = buf[off:off + total * (2 if enc == "pcm_s16le" else 1)]
+        region = region.view(torch.int16) if enc == "pcm_s16le" else region
+        rows = []
+        for i in live:
+            if specs[i].encoding != enc:
+                continue
+            q = index.get(i, -1)
+            if plan is not None and q in plan.lim_off:  # ONE row: the limited programme as the limiter wrote it
+                rows.append((n_in + n_rs + plan.lim_off[q], progs[i][1], where[i], -1))
+            else:
+                rows += [(s, n, where[i] + d, q) for s, n, d in progs[i][0]]
+        if any(specs[i].encoding == enc for i in asked):
+            pcm_assemble_gain(arena, rows, total, enc, gains, out=region)
+        else:  # (nobody in this encoding has a gain: the three-column kernel)
+            pcm_assemble(arena, [r[:3] for r in rows], total, enc, out=region)
     host = buf.cpu().numpy()  # the one copy (it waits for the stream)
-    if asked and reports is not None:
+    if asked:
         recs = read_records(host[rec_off:], plan.n + plan.n2)
         stats = dict(zip(plan.limited, limiter_stats(host[part_off:], plan)))
         for q, i in enumerate(asked):
-            if limits[i] == ("sample", False):
-                reports[i] = level_report(recs[q], levels[i][0])
+            sp = specs[i]
+            if sp.limits == ("sample", False):
+                reports[i] = level_report(recs[q], sp.loudness)
             elif q in stats:
-                reports[i] = level_report_limit(recs[q], levels[i][0], limits[i][0], True, where[i][2], stats[q], recs[plan.n + plan.limited.index(q)])
+                reports[i] = level_report_limit(recs[q], sp.loudness, sp.peak_mode, True, progs[i][1], stats[q], recs[plan.n + plan.limited.index(q)])
             else:
-                reports[i] = level_report_limit(recs[q], levels[i][0], limits[i][0], False)
-    out = [None] * len(wav_lists)
+                reports[i] = level_report_limit(recs[q], sp.loudness, sp.peak_mode, False)
     for i in live:
-        enc, start, n = where[i]
-        off = by_enc[enc][2]
-        if enc == "pcm_s16le":
-            pcm = host[off:off + by_enc[enc][1] * 2].view(np.int16)[start:start + n]
+        total, off = regions[specs[i].encoding]
+        if specs[i].encoding == "pcm_s16le":
+            pcm = host[off:off + total * 2].view(np.int16)[where[i]:where[i] + progs[i][1]]
         else:
-            pcm = host[off + start:off + start + n]
-        out[i] = (fmts[i][0], pcm.copy().reshape(-1, 1))
-    return out
+            pcm = host[off + where[i]:off + where[i] + progs[i][1]]
+        results[i] = (specs[i].rate, pcm.copy().reshape(-1, 1))
+    return results, reports
+
+
+def finish_pcm_many(wav_lists, sample_rates, encodings, interval_silence=200, loudness=None, peak=None, reports=None, totals=None, peak_mode=None,
+                    limiter=None):
+    """`finish` with the specs spelt as parallel lists (one entry per request, None: not asked; a list left out: nobody asked):
+    what `OutputSpec.of` takes, and `totals`.  Every request goes through the stage, 22 050 Hz `pcm_s16le` where it asks for nothing.
+    -> the results; `reports`: a list that receives the reports."""
+    absent = [None] * len(sample_rates)
+    specs = [OutputSpec.of(*asks, duration=True)._replace(total=total) for *asks, total in
+             zip(sample_rates, encodings, loudness or absent, peak or absent, peak_mode or absent, limiter or absent, totals or absent)]
+    results, levels = finish(wav_lists, specs, interval_silence)
+    if reports is not None:
+        reports[:] = levels
+    return results
 
 
 def finish_pcm(wavs, sample_rate=None, encoding=None, interval_silence=200, loudness=None, peak=None, reports=None, total=None, peak_mode=None,
                limiter=None):
     """One request's segments -> `(sr, ndarray [N, 1])`, int16 (`pcm_s16le`) or uint8 (`mulaw`, `alaw`); sr = the requested rate, or
     22050.  See `finish_pcm_many`."""
-    if peak_mode is not None or limiter is not None:
-        return finish_pcm_many([list(wavs)], [sample_rate], [encoding], interval_silence, [loudness], [peak], reports,
-                               totals=None if total is None else [total], peak_mode=[peak_mode], limiter=[limiter])[0]
-    if total is not None:
-        return finish_pcm_many([list(wavs)], [sample_rate], [encoding], interval_silence, [loudness], [peak], reports, totals=[total])[0]
-    if loudness is None and peak is None:
-        return finish_pcm_many([list(wavs)], [sample_rate], [encoding], interval_silence)[0]
-    return finish_pcm_many([list(wavs)], [sample_rate], [encoding], interval_silence, [loudness], [peak], reports)[0]
+    return finish_pcm_many([list(wavs)], [sample_rate], [encoding], interval_silence, [loudness], [peak], reports, [total], [peak_mode], [limiter])[0]
 
 
 def wav_bytes(sr, pcm, encoding=None):

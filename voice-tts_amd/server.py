@@ -131,6 +131,11 @@ class TTSRequest(BaseModel):
         check_limit(**{info.field_name: v}, level=(None, None))  # ValueError naming the accepted values -> 422
         return v
 
+    @property
+    def leveled(self):
+        """The request names a level control: its reply logs the level report."""
+        return self.loudness is not None or self.peak is not None or self.peak_mode is not None or self.limiter is not None
+
     @model_validator(mode="after")
     def _a_ceiling_for_the_mode(self):
         if self.peak_mode == "true" and self.loudness is None and self.peak is None and not self.limiter:
@@ -377,21 +382,18 @@ def create_app(model_factory=default_model_factory):
                 else:
                     emo_vector = create_emotion_vector(request.emotion)
             # the output format goes on only when the request sets it: a model without the keywords keeps working
-            fmt_kw = {k: v for k, v in (("output_sample_rate", request.sample_rate), ("output_encoding", request.encoding),
-                                        ("output_loudness", request.loudness), ("output_peak", request.peak), ("speed", request.speed),
-                                        ("duration", request.duration), ("output_peak_mode", request.peak_mode),
-                                        ("output_limiter", request.limiter)) if v is not None}
-            leveled = request.loudness is not None or request.peak is not None or request.peak_mode is not None or request.limiter is not None
+            from .output import OUTPUT_KEYS
+
+            keys = OUTPUT_KEYS + (("speed", "speed"), ("duration", "duration"))  # request key, keyword of `infer`
+            fmt_kw = {kw: getattr(request, key) for key, kw in keys if getattr(request, key) is not None}
+            leveled = request.leveled
             start = time.time()
             if state["batcher"] is not None:  # opt-in: queued requests decode together (IXTTS_BATCH_SLOTS)
                 import io
 
                 res = state["batcher"].submit(dict(spk_audio_prompt=spk_audio_data, text=request.text, emo_audio_prompt=emo_audio_data if emo_audio_data else None,
                                                    emo_alpha=request.emo_alpha if emo_audio_data else 1.0, emo_vector=emo_vector,
-                                                   **{k: v for k, v in (("sample_rate", request.sample_rate), ("encoding", request.encoding),
-                                                                        ("loudness", request.loudness), ("peak", request.peak), ("speed", request.speed),
-                                                                        ("duration", request.duration), ("peak_mode", request.peak_mode),
-                                                                        ("limiter", request.limiter)) if v is not None})).result()
+                                                   **{key: getattr(request, key) for key, _ in keys if getattr(request, key) is not None})).result()
                 if res is None:
                     raise RuntimeError("the text produced no speech segment")
                 sr, pcm = res
